@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- PETs clustered / s and sweep wall-clock on MI355X for the cDBSCAN hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Workload (default): BASELINE.json configs[3] -- the synthetic genome of SURVEY.md 8d, 200 M cis PETs over the
 23 hg38 chromosomes, Hi-C mode `-m 3` = eps [5000, 7500, 10000] x minPts [50, 40, 30, 20]
@@ -71,7 +71,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-with-labels", action="store_true", help="skip the label-inclusive sweep (labels + tables on the host every run)")
     ap.add_argument("--proxy-ranks", default="2,4,8", help="single-GPU scaling proxy: time every rank's LPT share of N alone, for each N of the list (0 = off)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed sweeps, write what the last one returned as DIR/<name>.npy (see dump_outputs; one process only)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs needs a single process (--gpus 1)")
+    return args
 
 
 def free_port():
@@ -283,7 +290,7 @@ def main(argv=None):
             ncand = sum(len(t) for t in tabs)
         else:
             ncand = sum(len(v["boxes"]) for v in dataI.values())
-        return cut, steps, ncand
+        return cut, steps, ncand, dataI, cuts
 
     first_sweep_s = None
     for w in range(args.warmup):
@@ -300,8 +307,10 @@ def main(argv=None):
     t0 = time.perf_counter()
     pets = 0
     for k in range(args.steps):
-        cut, steps, ncand = one_sweep(False)
+        cut, steps, ncand, dataI, cuts = one_sweep(False)
         pets += sum(s["n_in"] for s in steps)          # genome-wide (all-reduced inside runSweepFast)
+        if k + 1 < args.steps:
+            dataI = None                                # freed before the next sweep, whose tables re-use its warm host pages
     sync_all()
     elapsed = time.perf_counter() - t0
     if comm is not None:
@@ -310,6 +319,9 @@ def main(argv=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device=tdev if on_gpu else None)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fs, dataI, cut, cuts, steps)
+    dataI = None
 
     line = None
     if rank == 0:
@@ -397,6 +409,43 @@ def main(argv=None):
     os.close(saved_stdout)
     if rank == 0:
         print(json.dumps(line), flush=True)
+
+
+DUMP_MAX_BOX_ROWS = 1500000                             # 5 float64 columns: 60 MB, under the 64 MB of a dump
+
+
+def dump_outputs(outdir, fs, dataI, cut, cuts, steps, max_rows=DUMP_MAX_BOX_ROWS):
+    """What the last timed sweep returned to its caller (pipe.runSweepFast), as float64 .npy files in `outdir` -- for comparing
+    two builds output for output (the inputs are seeded: the same arguments give the same genome):
+      candidate_boxes.npy   [chromosome, minX, maxX, minY, maxY] per candidate loop, rows sorted; above `max_rows` rows a fixed
+                            sample of them (seed 0, row order kept).  chromosome = position in `fs` (chr1 .. chrX of
+                            cloops_amd.synth.chrom_sizes on one process)
+      candidate_counts.npy  candidate loops per chromosome, over ALL rows
+      candidate_sums.npy    per chromosome, the column sums of minX, maxX, minY, maxY over ALL rows (exact: far below 2^53)
+      sweep_steps.npy       per run [eps, minPts, cut_in, n_inter, n_self, n_in, cut_out] (cut_out NaN when the run set none)
+      cuts.npy              the chain of cuts runSweepFast returned; final_cut.npy the cut it ended on
+    Coordinates are below 2^31, so float64 holds every value exactly."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    by_f = {v["f"]: v["boxes"] for v in dataI.values()}
+    tabs = [np.asarray(by_f.get(f, np.zeros((0, 4), np.int32)), dtype=np.int64).reshape(-1, 4) for f in fs]
+    rows = np.concatenate([np.concatenate([np.full((len(t), 1), i, np.int64), t], 1) for i, t in enumerate(tabs)]) if tabs else np.zeros((0, 5), np.int64)
+    rows = rows[np.lexsort(rows.T[::-1])]
+    if len(rows) > max_rows:
+        rows = rows[np.sort(np.random.default_rng(0).choice(len(rows), max_rows, replace=False))]
+    out = {
+        "candidate_boxes": rows,
+        "candidate_counts": np.asarray([len(t) for t in tabs]),
+        "candidate_sums": np.asarray([t.sum(axis=0) for t in tabs]).reshape(-1, 4),
+        "sweep_steps": np.asarray([[st["eps"], st["minPts"], st["cut_in"], st["n_inter"], st["n_self"], st["n_in"],
+                                    st["cut_out"] if st.get("cut_out") is not None else np.nan] for st in steps], dtype=np.float64).reshape(-1, 7),
+        "cuts": np.asarray(cuts),
+        "final_cut": np.asarray([cut]),
+    }
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    sys.stderr.write("bench.py: outputs of the last timed sweep in %s (%d candidate loops, %d rows stored)\n"
+                     % (outdir, int(sum(len(t) for t in tabs)), len(rows)))
 
 
 def _human(n):

@@ -217,3 +217,25 @@ def ref_saturation_namespace():
     exec(compile(ast.Module(body=body, type_ignores=[]), "jd2saturation:functions", "exec"), ns)
     _cache["saturation"] = ns
     return ns
+
+
+def ref_io_namespace():
+    """The reference's PET class, parseRawBedpe2 (cLoops/io.py:132-189) and parseRawBedpe, sliced out of the py2-only io.py
+    with the two py2 -> py3 semantic patches `/ 2` -> `// 2` and "rb" -> "rt", exec'd in memory.  Used to MAKE golden
+    vectors only (tests/golden/make_golden_reference_checks.py)."""
+    import gzip
+    if "io" in _cache:
+        return _cache["io"]
+    with open(os.path.join(REF_ROOT, "cLoops", "io.py")) as fh:
+        lines = fh.read().split("\n")
+
+    def block(start_pat):
+        s = [i for i, l in enumerate(lines) if l.startswith(start_pat)][0]
+        e = [i for i, l in enumerate(lines) if i > s and (l.startswith("def ") or l.startswith("class "))][0]
+        return "\n".join(lines[s:e])
+    src = block("class PET") + "\n" + block("def parseRawBedpe2") + "\n" + block("def parseRawBedpe(")
+    src = src.replace(") / 2", ") // 2").replace('"rb"', '"rt"')
+    ns = {"gzip": gzip, "os": os, "cFlush": lambda *a: None}
+    exec(compile(src, "io.py:slice", "exec"), ns)
+    _cache["io"] = ns
+    return ns

@@ -9,14 +9,14 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(gpus):
+def _bench(gpus, extra=()):
     env = dict(os.environ)
     env["CLOOPS_BENCH_PRELOAD"] = "bench_cpu_hook"
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), ROOT, env.get("PYTHONPATH", "")])
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "gloo",
-                          "--n-total", "400000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary"],
+                          "--n-total", "400000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary"] + list(extra),
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.strip()]
@@ -36,6 +36,53 @@ def test_bench_gpus_2_spawns_two_ranks_and_matches_single_process():
     assert two["config"]["final_cut"] == one["config"]["final_cut"]
     assert two["config"]["candidate_loops"] == one["config"]["candidate_loops"]
     assert two["config"]["pets_entering_dbscan_per_sweep"] == one["config"]["pets_entering_dbscan_per_sweep"]
+
+
+def test_bench_dump_outputs_are_reproducible_and_match_the_json_line(tmp_path):
+    """--dump-outputs: float64 .npy files of what the last timed sweep returned, identical from run to run with the same
+    arguments, consistent with the JSON line; --steps sets the number of timed sweeps"""
+    import numpy as np
+    dirs = [str(tmp_path / ("d%d" % k)) for k in range(2)]
+    runs = [_bench(1, ["--dump-outputs", d, "--steps", str(k + 1)]) for k, d in enumerate(dirs)]
+    assert [j["steps"] for j in runs] == [1, 2]
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "candidate_boxes.npy" in names
+    total = 0
+    for name in names:
+        a, b = (np.load(os.path.join(d, name)) for d in dirs)
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), name
+        total += os.path.getsize(os.path.join(dirs[0], name))
+    assert total <= 64 << 20
+    one = runs[0]
+    boxes = np.load(os.path.join(dirs[0], "candidate_boxes.npy"))
+    counts = np.load(os.path.join(dirs[0], "candidate_counts.npy"))
+    assert boxes.shape == (one["config"]["candidate_loops"], 5) and counts.sum() == one["config"]["candidate_loops"] and len(counts) == 23
+    assert np.array_equal(np.load(os.path.join(dirs[0], "candidate_sums.npy")),
+                          np.stack([boxes[boxes[:, 0] == i, 1:].sum(0) for i in range(23)]))
+    st = np.load(os.path.join(dirs[0], "sweep_steps.npy"))
+    assert st.shape == (12, 7) and st[:, 5].sum() == one["config"]["pets_entering_dbscan_per_sweep"]
+    assert [None if np.isnan(c) else int(c) for c in st[:, 6]] == one["config"]["cuts"]
+    assert int(np.load(os.path.join(dirs[0], "final_cut.npy"))[0]) == one["config"]["final_cut"]
+
+
+def test_bench_dump_outputs_samples_a_large_table(tmp_path):
+    """above the row budget the box table is a fixed sample of the sorted rows; counts and sums still cover every row"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    tabs = [np.sort(rng.integers(0, 10 ** 6, (n, 4)), axis=1).astype(np.int32) for n in (700, 0, 500)]
+    dataI = {("c%d" % i, "c%d" % i): {"f": "f%d" % i, "boxes": t} for i, t in enumerate(tabs) if len(t)}
+    steps = [{"eps": 5, "minPts": 3, "cut_in": 0, "n_inter": 2, "n_self": 1, "n_in": 9, "cut_out": 7}]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ["f0", "f1", "f2"], dataI, 7, [0, 7], steps, max_rows=300)
+    a, b = (np.load(str(tmp_path / d / "candidate_boxes.npy")) for d in ("a", "b"))
+    assert a.shape == (300, 5) and np.array_equal(a, b)
+    full = np.concatenate([np.concatenate([np.full((len(t), 1), i), t], 1) for i, t in enumerate(tabs)])
+    assert len(set(map(tuple, a)) - set(map(tuple, full.astype(np.float64)))) == 0
+    assert np.array_equal(a, a[np.lexsort(a.T[::-1])])
+    assert np.load(str(tmp_path / "a" / "candidate_counts.npy")).tolist() == [700, 0, 500]
+    assert np.array_equal(np.load(str(tmp_path / "a" / "candidate_sums.npy")), np.stack([t.astype(np.int64).sum(0) for t in tabs]))
 
 
 def _preflight_world2(children, timeout):

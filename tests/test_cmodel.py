@@ -24,23 +24,21 @@ def cpu_backend(monkeypatch):
     pipe.CACHE.clear()
 
 
-@pytest.mark.skipif(not __import__("refload").available(), reason="reference checkout not present")
 def test_table_equals_reference_functions(tmp_path):
-    """cross-check against the reference's OWN getIntSig / markIntSig (imported from /root/reference through
-    tests/refload.py, py2 -> py3 patched in memory): same table, cell by cell"""
-    import refload
-    ns = refload.ref_cmodel_namespace()
+    """cross-check against the table the reference's OWN getIntSig / markIntSig produced (py2 -> py3 patched in memory by
+    tests/refload.py; stored as tests/golden/chr21_cmodel_table.json by tests/golden/make_golden_reference_checks.py):
+    same table, cell by cell"""
+    want = G.cmodel_table()
     z, meta = pipe_checks.pipe_golden()
     X, Y = G.chr21_xy()
     mat = np.stack([np.arange(len(X)), X, Y], 1).astype(np.int64)
     f = os.path.join(str(tmp_path), "chr21-chr21.jd")
     joblib.dump(mat, f)
     recs = [["chr21", int(a), int(b), "chr21", int(c), int(d)] for a, b, c, d in z["v2_filtered"][:150]]
-    want = ns["markIntSig"](ns["getIntSig"](f, [list(r) for r in recs], [5], 0))
     got = cModel.markIntSig(cModel.getIntSig(f, recs, [5], 0))
-    assert list(got.index) == list(want.index) and list(got.columns) == list(want.columns)
-    for col in want.columns:
-        assert got[col].tolist() == want[col].tolist(), col
+    assert list(got.index) == want["index"] and list(got.columns) == want["columns"]
+    for col in want["columns"]:
+        assert got[col].tolist() == want["data"][col], col
 
 
 @pytest.mark.parametrize("variant", ["v2", "v1"])

@@ -6,10 +6,14 @@ import numpy as np
 import pytest
 
 import golden_util as G
-import refload
 from cloops_amd import io as cio
 
-BEDPE = os.path.join(refload.REF_ROOT, "examples", "GSM1872886_GM12878_CTCF_ChIA-PET_chr21_hg38.bedpe.gz")
+
+@pytest.fixture(scope="module")
+def example(tmp_path_factory):
+    """the reference's bundled example BEDPE, rebuilt from the stored columns (golden_util.write_example_bedpe)"""
+    return G.write_example_bedpe(tmp_path_factory.mktemp("example"))
+
 
 LINES = [
     "chr1\t100\t201\tchr1\t5000\t5100\tid1\t1\t+\t-",        # mid 150 (floor of 150.5), 5050
@@ -47,9 +51,8 @@ def test_jd_round_trip(tmp_path):
     assert mat.shape == (2, 3)
 
 
-@pytest.mark.skipif(not os.path.exists(BEDPE), reason="reference example data not present")
-def test_example_bedpe_matches_golden_input():
-    mats, n_lines, n_cis = cio.parse_bedpe([BEDPE])
+def test_example_bedpe_matches_golden_input(example):
+    mats, n_lines, n_cis = cio.parse_bedpe([example])
     X, Y = G.chr21_xy()
     assert list(mats.keys()) == ["chr21"] and n_cis == 99674
     assert np.array_equal(mats["chr21"][:, 1], X) and np.array_equal(mats["chr21"][:, 2], Y)
@@ -57,76 +60,36 @@ def test_example_bedpe_matches_golden_input():
     assert (int(X.min()), int(X.max()), int(Y.min()), int(Y.max())) == (m["xmin"], m["xmax"], m["ymin"], m["ymax"])
 
 
-@pytest.mark.skipif(not refload.available(), reason="reference checkout not present")
-def test_against_reference_parser_with_py2_semantics(tmp_path):
+def test_against_reference_parser_with_py2_semantics(example):
     """The reference's own PET class + parseRawBedpe2 (sliced out of the py2-only io.py, with the
-    two py2->py3 semantic patches `/ 2` -> `// 2` and "rb" -> "rt") on the example file."""
-    with open(os.path.join(refload.REF_ROOT, "cLoops", "io.py")) as fh:
-        lines = fh.read().split("\n")
-
-    def block(start_pat):
-        s = [i for i, l in enumerate(lines) if l.startswith(start_pat)][0]
-        e = [i for i, l in enumerate(lines) if i > s and (l.startswith("def ") or l.startswith("class "))][0]
-        return "\n".join(lines[s:e])
-    src = block("class PET") + "\n" + block("def parseRawBedpe2")
-    src = src.replace(") / 2", ") // 2").replace('"rb"', '"rt"')
-
-    class L(object):
-        def info(self, *a):
-            pass
-    ns = {"gzip": gzip, "os": os, "cFlush": lambda *a: None}
-    exec(compile(src, "io.py:slice", "exec"), ns)
-    out = tmp_path / "ref"
-    out.mkdir()
-    cfs = ns["parseRawBedpe2"]([BEDPE], str(out), [], 0, L())
-    assert len(cfs) == 1
-    ref = np.loadtxt(cfs[0], dtype=np.int64)
-    mats, _, _ = cio.parse_bedpe([BEDPE])
-    assert np.array_equal(ref, mats["chr21"])
+    two py2->py3 semantic patches `/ 2` -> `// 2` and "rb" -> "rt") on the example file: its output
+    is stored as a digest in tests/golden/reference_checks.npz (tests/golden/make_golden_reference_checks.py)."""
+    mats, _, _ = cio.parse_bedpe([example])
+    assert G.digest(mats["chr21"]) == str(G.reference_checks()["parse2_sha1"])
 
 
-@pytest.mark.skipif(not refload.available(), reason="reference checkout not present")
-def test_auto_eps_path_against_the_reference(tmp_path):
+def test_auto_eps_path_against_the_reference(example, tmp_path):
     """`eps = 0` (cLoops/pipe.py:231-239): the reference's parseRawBedpe (duplicate removal, distances of the PETs mapped to
     different strands; sliced out of the py2-only io.py with the same two py2 -> py3 patches as above) and its own
-    estFragSize (ests.py:23-33) on the example file, against cloops_amd.io.parseRawBedpe / cloops_amd.ests.estFragSize."""
+    estFragSize (ests.py:23-33) on the example file, against cloops_amd.io.parseRawBedpe / cloops_amd.ests.estFragSize.
+    What the reference returned is stored in tests/golden/reference_checks.npz."""
     import joblib
     from cloops_amd import ests
-    with open(os.path.join(refload.REF_ROOT, "cLoops", "io.py")) as fh:
-        lines = fh.read().split("\n")
-
-    def block(start_pat):
-        s = [i for i, l in enumerate(lines) if l.startswith(start_pat)][0]
-        e = [i for i, l in enumerate(lines) if i > s and (l.startswith("def ") or l.startswith("class "))][0]
-        return "\n".join(lines[s:e])
-    src = block("class PET") + "\n" + block("def parseRawBedpe(")
-    src = src.replace(") / 2", ") // 2").replace('"rb"', '"rt"')
-
-    class L(object):
-        def info(self, *a):
-            pass
-    ns = {"gzip": gzip, "os": os, "cFlush": lambda *a: None}
-    exec(compile(src, "io.py:slice", "exec"), ns)
+    z = G.reference_checks()
     # the example file, and a file with duplicated PETs (the example holds none): the first 3000 lines followed by the
     # first 1000 again
-    dup = str(tmp_path / "dup.bedpe")
-    with gzip.open(BEDPE, "rt") as fh:
-        head = [next(fh) for _ in range(3000)]
-    with open(dup, "w") as fh:
-        fh.writelines(head + head[:1000])
-    for k, f in enumerate((BEDPE, dup)):
-        out = tmp_path / ("ref%d" % k)
-        out.mkdir()
-        cfs, ds = ns["parseRawBedpe"]([f], str(out), [], 0, L())
-        ref = np.loadtxt(cfs[0], dtype=np.int64)
+    dup = G.write_dup(tmp_path, example)
+    for k, f in enumerate((example, dup)):
         mine = tmp_path / ("mine%d" % k)
         mine.mkdir()
         cfs2, ds2 = cio.parseRawBedpe([f], str(mine), [], 0)
-        assert len(cfs) == len(cfs2) == 1
-        assert np.array_equal(ref, joblib.load(cfs2[0]))
-        assert ds == ds2 and len(ds) > 100 and len(ds) < len(ref)
-        want = refload.ref_ests().estFragSize(ds)
+        assert len(cfs2) == 1
+        rows = joblib.load(cfs2[0])
+        assert G.digest(rows) == str(z["raw%d_sha1" % k]) and len(rows) == int(z["raw%d_rows" % k])
+        n = int(z["raw%d_ds_len" % k])
+        assert G.digest(ds2) == str(z["raw%d_ds_sha1" % k]) and len(ds2) == n and n > 100 and n < len(rows)
+        want = int(z["raw%d_fragsize" % k])
         assert ests.estFragSize(ds2) == want and want > 0
         if k == 1:
             mats, _, _ = cio.parse_bedpe([f])
-            assert len(ref) < len(mats["chr21"])            # the duplicate filter really dropped PETs
+            assert len(rows) < len(mats["chr21"])            # the duplicate filter really dropped PETs

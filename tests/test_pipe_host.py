@@ -6,7 +6,7 @@ import pytest
 
 import fake_backend
 import pipe_checks
-import refload
+import golden_util as G
 from cloops_amd import api, pipe
 
 
@@ -45,15 +45,15 @@ def test_filter_uses_floor_division():
     assert len(out[("c", "c")]["records"]) == 0
 
 
-@pytest.mark.skipif(not refload.available(), reason="reference checkout not present")
 def test_ests_matches_reference_function():
+    """estIntSelCutFrag == what the reference's own (cLoops/ests.py:36-61) returned on the same 20 draws
+    (tests/golden/reference_checks.npz)"""
     from cloops_amd.ests import estIntSelCutFrag
-    ref = refload.ref_ests().estIntSelCutFrag
-    rng = np.random.default_rng(3)
-    for _ in range(20):
-        di = np.exp(rng.normal(10, 1.5, 3000)).astype(np.int64).astype(float)
-        ds = np.exp(rng.normal(6, 1.0, 5000)).astype(np.int64).astype(float)
-        assert estIntSelCutFrag(di, ds) == ref(di, ds)
+    z = G.reference_checks()
+    draws = G.ests_draws()
+    assert G.digest(np.concatenate([np.concatenate([di, ds]) for di, ds in draws])) == str(z["ests_in_sha1"]), "draws drifted"
+    for (di, ds), want in zip(draws, z["ests_out"]):
+        assert estIntSelCutFrag(di, ds) == tuple(int(v) for v in want)
 
 
 def test_combine_steps_equals_sequential_combine_twice():
