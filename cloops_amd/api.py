@@ -448,6 +448,16 @@ class Chromosome(object):
                                            out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(npets)))
         return out, int(npets.value)
 
+    def quant_counts(self, windows, cut=0):
+        """K11: directed interval counts for quantifyLoops / deLoops.  windows: int32 [R, 44] as for sig_counts ->
+        (int32 [R, 123] counts: ra, rb, then |{X in A_k} & {Y in B_l}| at 2 + 11 k + l; N)  (cl_quant_counts)."""
+        w = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1, 44)
+        out = np.zeros((len(w), 123), dtype=np.int32)
+        npets = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_quant_counts(self._h, int(cut), len(w), w.ctypes.data_as(ctypes.c_void_p),
+                                             out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(npets)))
+        return out, int(npets.value)
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

@@ -301,3 +301,24 @@ __global__ void __launch_bounds__(256)
 k7_reduce_parts(const K7Part* __restrict__ parts, int nparts, K7Part* out, const int* __restrict__ bcount , int nb,
                 long long* totals, const volatile unsigned long long* dev_step , int step_words,
                 unsigned long long* __restrict__ host_step, const int* __restrict__ dev_hdr, int* __restrict__ host_hdr);
+
+// K8's X-sorted and Y-sorted PET tables (k_sweep.hip), shared with K11 (k_quant.hip): entry = (coordinate + 2^30) << 32 |
+// (other coordinate + 2^30), the PETs that fail the cut sorted to the end as ~0
+#define SIG_W 11                       // window 0 = the anchor itself, 1..10 = cModel.getNearbyPairRegions
+struct SigWin { int lo[2 * SIG_W]; int hi[2 * SIG_W]; };      // [0..10] = A windows, [11..21] = B windows
+
+// first index with (key >> 32) >= v   /   > v   in a sorted u64 table of m valid entries
+__device__ __forceinline__ int k8_lb(const u64* __restrict__ t, int m, long long v)
+{
+    const u64 target = v <= -(1ll << 30) ? 0ull : ((u64)(u32)(v + (1 << 30)) << 32);
+    int lo = 0, hi = m;
+    while (lo < hi) { int mid = (lo + hi) >> 1; if (t[mid] < target) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int k8_ub(const u64* __restrict__ t, int m, long long v)
+{
+    return k8_lb(t, m, v + 1);
+}
+// builds the tables of (chromosome, cut) unless the handle holds them already (c->sig_tx / sig_ty; c->sig_m[0] on the device = the
+// number of valid entries); enqueued on c->stream, c->n > 0
+int sig_tables(cl_chrom* c, int cut);

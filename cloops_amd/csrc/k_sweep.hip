@@ -403,7 +403,6 @@ k_cand_emit(int N, const unsigned char* __restrict__ keep, const int4* __restric
 // are two contiguous slices of the X-sorted and Y-sorted PET tables; every PET gets an 11-bit
 // membership mask per side and bumps the counters in LDS.  Pure integer work; the p-values stay on
 // the host (scipy), fed with exactly the reference's counts.
-#define SIG_W 11                       // window 0 = the anchor itself, 1..10 = cModel.getNearbyPairRegions
 #define SIG_OUT (2 * SIG_W + 1 + SIG_W * SIG_W)
 
 __global__ void k8_split(const int* __restrict__ X, const int* __restrict__ Y, int n, int cut,
@@ -418,20 +417,7 @@ __global__ void k8_split(const int* __restrict__ X, const int* __restrict__ Y, i
     ky[r] = valid ? (((u64)(u32)(y + (1 << 30)) << 32) | (u32)(x + (1 << 30))) : ~0ull;
 }
 
-// first index with (key >> 32) >= v   /   > v   in a sorted u64 table of m valid entries
-__device__ __forceinline__ int k8_lb(const u64* __restrict__ t, int m, long long v)
-{
-    const u64 target = v <= -(1ll << 30) ? 0ull : ((u64)(u32)(v + (1 << 30)) << 32);
-    int lo = 0, hi = m;
-    while (lo < hi) { int mid = (lo + hi) >> 1; if (t[mid] < target) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-__device__ __forceinline__ int k8_ub(const u64* __restrict__ t, int m, long long v)
-{
-    return k8_lb(t, m, v + 1);
-}
-
-struct SigWin { int lo[2 * SIG_W]; int hi[2 * SIG_W]; };      // [0..10] = A windows, [11..21] = B windows
+// k8_lb / k8_ub and SigWin: cl_chrom.h (K11 reads the same tables)
 
 __global__ void __launch_bounds__(TPB)
 k8_counts(const u64* __restrict__ tx, const u64* __restrict__ ty, const int* __restrict__ d_m, int nrec,
@@ -741,6 +727,31 @@ static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out)
 }
 
 // ---- K8 host entry point ------------------------------------------------------------------------
+int sig_tables(cl_chrom* c, int cut)
+{
+    if (c->sig_ready && c->sig_cut == cut) return CL_OK;
+    const int n = (int)c->n;
+    int rc;
+    // X-sorted and Y-sorted tables of the PETs that pass parseJd(f, cut); built once per (chromosome, cut)
+    if ((rc = c->sig_tx.ensure((size_t)n * 8)) || (rc = c->sig_ty.ensure((size_t)n * 8)) ||
+        (rc = c->sig_tmp.ensure((size_t)n * 8)) || (rc = c->sig_m.ensure(64))) return rc;
+    LAUNCH(k8_split, n, c->d_x, c->d_y, n, cut, c->sig_tmp.as<u64>(), c->sig_ty.as<u64>());
+    size_t bytes = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (size_t)n, 0, 64, c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query", hipGetErrorString(e));
+    if ((rc = c->sig_sorttmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
+    bytes = c->sig_sorttmp.bytes;
+    e = rocprim::radix_sort_keys(c->sig_sorttmp.p, bytes, c->sig_tmp.as<u64>(), c->sig_tx.as<u64>(), (size_t)n, 0, 64, c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(X)", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(c->sig_tmp.p, c->sig_ty.p, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+    bytes = c->sig_sorttmp.bytes;
+    e = rocprim::radix_sort_keys(c->sig_sorttmp.p, bytes, c->sig_tmp.as<u64>(), c->sig_ty.as<u64>(), (size_t)n, 0, 64, c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(Y)", hipGetErrorString(e));
+    hipLaunchKernelGGL(k8_count_valid, dim3(1), dim3(64), 0, c->stream, c->sig_tx.as<u64>(), n, c->sig_m.as<int>());
+    c->sig_ready = true; c->sig_cut = cut;
+    return CL_OK;
+}
+
 extern "C" int cl_sig_counts(cl_chrom* c, int32_t cut, int32_t n_records, const int32_t* windows, int32_t* out,
                              int64_t* n_pets)
 {
@@ -750,27 +761,8 @@ extern "C" int cl_sig_counts(cl_chrom* c, int32_t cut, int32_t n_records, const 
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_sig_counts: asynchronous runs still in flight");
     if (c->n == 0) { if (n_records) memset(out, 0, (size_t)n_records * SIG_OUT * 4); return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
-    const int n = (int)c->n;
     int rc;
-    if (!c->sig_ready || c->sig_cut != cut) {
-        // X-sorted and Y-sorted tables of the PETs that pass parseJd(f, cut); built once per (chromosome, cut)
-        if ((rc = c->sig_tx.ensure((size_t)n * 8)) || (rc = c->sig_ty.ensure((size_t)n * 8)) ||
-            (rc = c->sig_tmp.ensure((size_t)n * 8)) || (rc = c->sig_m.ensure(64))) return rc;
-        LAUNCH(k8_split, n, c->d_x, c->d_y, n, cut, c->sig_tmp.as<u64>(), c->sig_ty.as<u64>());
-        size_t bytes = 0;
-        hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (size_t)n, 0, 64, c->stream);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query", hipGetErrorString(e));
-        if ((rc = c->sig_sorttmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-        bytes = c->sig_sorttmp.bytes;
-        e = rocprim::radix_sort_keys(c->sig_sorttmp.p, bytes, c->sig_tmp.as<u64>(), c->sig_tx.as<u64>(), (size_t)n, 0, 64, c->stream);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(X)", hipGetErrorString(e));
-        HIP_TRY(hipMemcpyAsync(c->sig_tmp.p, c->sig_ty.p, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
-        bytes = c->sig_sorttmp.bytes;
-        e = rocprim::radix_sort_keys(c->sig_sorttmp.p, bytes, c->sig_tmp.as<u64>(), c->sig_ty.as<u64>(), (size_t)n, 0, 64, c->stream);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(Y)", hipGetErrorString(e));
-        hipLaunchKernelGGL(k8_count_valid, dim3(1), dim3(64), 0, c->stream, c->sig_tx.as<u64>(), n, c->sig_m.as<int>());
-        c->sig_ready = true; c->sig_cut = cut;
-    }
+    if ((rc = sig_tables(c, cut))) return rc;
     int hm = 0;
     HIP_TRY(hipMemcpyAsync(&hm, c->sig_m.p, 4, hipMemcpyDeviceToHost, c->stream));
     if (n_records > 0) {

@@ -209,6 +209,19 @@ int cl_dist_bin_hist(cl_chrom* c, int32_t cut, uint32_t lo, uint32_t hi, int shi
  */
 int cl_sig_counts(cl_chrom* c, int32_t cut, int32_t n_records, const int32_t* windows, int32_t* out, int64_t* n_pets);
 
+/*
+ * Interval counts for re-quantifying loops on a dataset (scripts/quantifyLoops.py:124-134) and for differential
+ * loops (scripts/deLoops): getPETsforRegions (cLoops/cModel.py:60-80) over the same 11 A and 11 B windows as
+ * cl_sig_counts, same `windows` layout (n_records x 44 int32: lo[22] then hi[22], A0..A10 then B0..B10), but the
+ * DIRECTED pair counts.  `out`: n_records x 123 int32:
+ *   [0]   ra = |S(A_0)|   with S(W) = {PETs with X in W} | {PETs with Y in W}
+ *   [1]   rb = |S(B_0)|
+ *   [2 + 11*k + l]  |{X in A_k} & {Y in B_l}|                                     ([2] = rab)
+ * `cut` > 0 restricts the PETs to Y-X >= cut like parseJd(f, cut) (cLoops/io.py:213-216); *n_pets = number of
+ * PETs in the model (N of getGenomeCoverage, cModel.py:45-57).  Reads the sorted tables cl_sig_counts builds.
+ */
+int cl_quant_counts(cl_chrom* c, int32_t cut, int32_t n_records, const int32_t* windows, int32_t* out, int64_t* n_pets);
+
 /* Device pointer to the labels of the last run (n int32, row aligned) -- lets the caller
  * keep results on the GPU (e.g. to hand them to RCCL) without a host round trip.  NULL if the run did not
  * produce row-aligned labels (see cl_set_device_labels). */
