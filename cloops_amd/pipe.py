@@ -25,7 +25,7 @@ from . import api
 from . import _roctx
 from .cDBSCAN2 import cDBSCAN as DBSCAN          # pipe.py:42  (production variant)
 from .dist import lpt_assign
-from .ests import estIntSelCutFrag, estIntSelCutFrag_from_stats
+from .ests import estIntSelCutFrag, estIntSelCutFrag_bounded
 
 #: clustering variant used by singleDBSCAN; "block" mirrors the alternative import at pipe.py:43
 DBSCAN_VARIANT = "v2"
@@ -607,7 +607,8 @@ def _lib_logbins():
     from ._lib import DIST_LOGBINS
     return DIST_LOGBINS
 
-#: |2**cut - nearest integer| below which runSweepFast re-derives the cut from the distance lists (ests.py:57 truncates)
+#: |2**cut - nearest integer| below which runSweepFast re-derives the cut from the distance lists (ests.py:57 truncates) even
+#: when the error bound of ests.estIntSelCutFrag_bounded would settle it (a floor under that bound)
 CUT_RECHECK_MARGIN = 1e-6
 
 
@@ -798,10 +799,6 @@ def _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gs
                 if tot["n_all"][0] > 0 and tot["n_all"][1] > 0:      # pipe.py:256-259
                     if tot["n_pos"][0] == 0 or tot["n_pos"][1] == 0:
                         raise ValueError("cannot convert float NaN to integer")      # what int(2 ** nan) raises in ests.py:57
-                    # sum log2|d| and the sum of squared deviations from the group mean, from sum x and sum x^2 (x = log2|d| - xshift)
-                    sumlog = [float(gf[0]) + xshift * tot["n_pos"][0], float(gf[1]) + xshift * tot["n_pos"][1]]
-                    sq = [float(gf[2]) - float(gf[0]) ** 2 / tot["n_pos"][0], float(gf[3]) - float(gf[1]) ** 2 / tot["n_pos"][1]]
-                    tot["sumlog"] = sumlog
                     n1 = tot["n_pos"][1]
                     med = _select_kth(used, cut, loghist, sorted({(n1 - 1) // 2, n1 // 2}), allsum, pool,
                                       fine=(fine_lo, fine) if fine_lo >= 1 else None)
@@ -809,14 +806,23 @@ def _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gs
                     # from step to step): lower edge of the log bin 1024 below it, so that the ranks below it are known
                     from .ests import logbin, logbin_range
                     fine_lo = logbin_range(logbin(max(1, med[0] - 1024)))[0]
-                    cut_2, frags, margin = estIntSelCutFrag_from_stats(tot["n_pos"], tot["sumlog"], sq, (med[0], med[-1]), with_margin=True)
-                    if margin < CUT_RECHECK_MARGIN and allsum is None:
-                        # 2**cut sits on an integer boundary within the rounding noise of the reduction order: settle
-                        # it the reference's way, from the distance lists with numpy's own sums (rare; one extra run
-                        # per chromosome with labels on the host)
-                        parts = [_cluster_arrays(r, ep, m, step_cut, variant) for r in used]
-                        cut_2, frags = estIntSelCutFrag(np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts]))
-                        st["cut_rechecked"] = True
+                    # the cut from sum x and sum x^2 (x = log2|d| - xshift), with the range that the reduction's rounding
+                    # leaves for the reference's int(2 ** cut) (ests.estIntSelCutFrag_bounded)
+                    cut_2, frags, (rc_lo, rc_hi), margin = estIntSelCutFrag_bounded(tot["n_all"], tot["n_pos"], gf[0:2], gf[2:4], xshift,
+                                                                                    (med[0], med[-1]), n_parts=int(g[3]))
+                    if rc_lo != rc_hi or margin < CUT_RECHECK_MARGIN:
+                        if allsum is None:
+                            # 2**cut may sit on either side of an integer within the error of the statistics: settle it the
+                            # reference's way, from the distance lists with numpy's own sums (rare -- a group of (nearly) equal
+                            # distances, or 2**cut within ~1e-6 of an integer; one extra run per chromosome with labels on the host)
+                            parts = [_cluster_arrays(r, ep, m, step_cut, variant) for r in used]
+                            cut_2, frags = estIntSelCutFrag(np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts]))
+                            st["cut_rechecked"] = True
+                        else:
+                            # several ranks: the lists are spread over them -- keep the statistics' cut, inside the bound
+                            st["cut_range"] = (int(rc_lo), int(rc_hi))
+                            if log and rc_lo != rc_hi:
+                                log("WARNING: the distance statistics of eps=%s,minPts=%s bound the cutoff only to [%s, %s]" % (ep, m, rc_lo, rc_hi))
                     if log:
                         log("Estimated inter-ligation and self-ligation distance cutoff as %s for eps=%s,minPts=%s" % (cut_2, ep, m))
                     if forced_cuts is not None and forced_cuts[this_step] is not None:
