@@ -4,6 +4,7 @@ This is what the reference-shaped wrappers (cDBSCAN.py, cDBSCAN2.py, blockDBSCAN
 pipe.py) and bench.py are built on.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -457,6 +458,22 @@ class Chromosome(object):
         _lib.check(self._lib.cl_quant_counts(self._h, int(cut), len(w), w.ctypes.data_as(ctypes.c_void_p),
                                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(npets)))
         return out, int(npets.value)
+
+    def contact_hist(self, bin_size, cut=0):
+        """K12: histogram of the cell counts of the upper contact matrix (scripts/jd2fingerprint:32-50) of the PETs with
+        Y - X >= cut (cut > 0) at `bin_size` -> (values int64 ascending, mult int64, n_kept, min_c): mult[k] cells hold values[k]
+        PETs each; min_c is None when no PET passes the cut  (cl_contact_hist)."""
+        if int(bin_size) < 1:
+            raise ValueError("bin_size must be >= 1, got %s" % bin_size)
+        cap = math.isqrt(2 * self.n) + 2                               # D (D + 1) / 2 <= kept PETs <= n
+        values = np.zeros(cap, dtype=np.int64)
+        mult = np.zeros(cap, dtype=np.int64)
+        nd, ncells, nkept, minc = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        _lib.check(self._lib.cl_contact_hist(self._h, int(cut), int(bin_size), cap, values.ctypes.data_as(ctypes.c_void_p),
+                                             mult.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nd), ctypes.byref(ncells),
+                                             ctypes.byref(nkept), ctypes.byref(minc)))
+        d = int(nd.value)
+        return values[:d].copy(), mult[:d].copy(), int(nkept.value), (int(minc.value) if nkept.value else None)
 
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)

@@ -222,6 +222,22 @@ int cl_sig_counts(cl_chrom* c, int32_t cut, int32_t n_records, const int32_t* wi
  */
 int cl_quant_counts(cl_chrom* c, int32_t cut, int32_t n_records, const int32_t* windows, int32_t* out, int64_t* n_pets);
 
+/*
+ * Histogram of the cell counts of the upper contact matrix (scripts/jd2fingerprint:32-50, jd2contactMatrixUpper):
+ * the PETs with Y-X >= cut (cut > 0; parseJd(jd, cut), cLoops/io.py:213-216) fall into the cells
+ * ((X - minC) / bin_size, (Y - minC) / bin_size), integer division, minC = the minimum of both coordinate
+ * columns of those PETs.  Returns the distinct cell counts in ascending order, `values[k]`, with the number of
+ * cells holding that many PETs, `mult[k]`, k < *n_distinct.  The distinct counts D satisfy D (D + 1) / 2 <= *n_kept.
+ * *n_cells = number of non-empty cells (sum of mult), *n_kept = PETs that pass the cut, *min_c = minC
+ * (n_cells / n_kept / min_c may be NULL).  No PET passing the cut: *n_kept = *n_distinct = 0 and CL_OK (the
+ * script's np.min raises there: the caller decides).  Errors: CL_ERR_ARG for a NULL handle or n_distinct,
+ * bin_size < 1, cap < 0, cap > 0 with NULL values / mult, runs in flight, or cap < D (then *n_distinct = D and
+ * nothing is written to values / mult).  Uses scratch of its own, freed before returning; leaves the handle's
+ * layouts, count cache and K8 tables untouched.
+ */
+int cl_contact_hist(cl_chrom* c, int32_t cut, int32_t bin_size, int64_t cap, int64_t* values, int64_t* mult,
+                    int64_t* n_distinct, int64_t* n_cells, int64_t* n_kept, int32_t* min_c);
+
 /* Device pointer to the labels of the last run (n int32, row aligned) -- lets the caller
  * keep results on the GPU (e.g. to hand them to RCCL) without a host round trip.  NULL if the run did not
  * produce row-aligned labels (see cl_set_device_labels). */
