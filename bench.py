@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- PETs clustered / s and sweep wall-clock on MI355X for the cDBSCAN hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (default): BASELINE.json configs[3] -- the synthetic genome of SURVEY.md 8d, 200 M cis PETs over the
 23 hg38 chromosomes, Hi-C mode `-m 3` = eps [5000, 7500, 10000] x minPts [50, 40, 30, 20]
@@ -17,9 +17,9 @@ layout: the sorted order does not depend on minPts, and a cut only removes a PRE
 runs of an eps work on that one layout by index -- nothing is copied), one region query per eps plus the cut band of
 every later run, and components, borders, cluster table and distance statistics for every run.  What a timed sweep
 re-uses from the warm-up is the q index and the fine layout (they depend on the rows only): a real pipe() sweeps a
-dataset once (cLoops/pipe.py:247-275), so the same sweep with every derived order dropped first (cl_chrom_drop_indexes;
-allocations kept) is reported as top-level `cold_sweep_s`, the first sweep of the process (allocations too) as
-`first_sweep_s`, and the sweep that lands labels + tables on the host every run (SURVEY.md 8d(1)'s end point) as
+dataset once (cLoops/pipe.py:247-275), so the first sweep of the process (allocations too) is reported as `first_sweep_s`,
+and with --full the same sweep with every derived order dropped first (cl_chrom_drop_indexes; allocations kept) as
+top-level `cold_sweep_s` and the sweep that lands labels + tables on the host every run (SURVEY.md 8d(1)'s end point) as
 top-level `with_labels_sweep_s`.
 
 With N > 1 (`--gpus N` spawns N ranks through torch.distributed.run -- only the launcher -- when not already launched by
@@ -29,13 +29,16 @@ the final candidate tables are gathered once per sweep -- the path's only exchan
 libcloops_comm.so (cloops_amd/comm.py; no PyTorch in the GPU processes).  Total work is fixed (the same 200 M PETs):
 "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs:
+synthesis and upload, the warm-up and timed sweeps, --dump-outputs.  Everything else takes runs of its own and comes with
+--full (refined by --no-cpu-baseline, --full-cpu-baseline, --no-secondary, --no-with-labels, --proxy-ranks):
   "roofline"      K2 region-query kernel on chr1 (16.4 M PETs) at the sweep's own 12 (eps, minPts, cut) settings, timed
                   with HIP events on the library's stream right after the timed sweeps, chr1 ALONE on the GPU: inside a
                   sweep the kernels of the 23 chromosomes overlap on the device, so an event bracket there measures
                   contention, not the kernel (that figure is kept as `in_sweep_avg_launch_ms`)
   "secondary_5M"  BASELINE.json configs[1] (5 M PETs, one chromosome, eps 2000, minPts 5), the round-1 headline
   "cpu_baseline"  the CPU oracle (C port of cDBSCAN2) on this box's host cores, one process per chromosome
+and "cold_sweep_s", "with_labels", "scaling_proxy", "secondary_chr21_cli" (see their functions below).
 """
 import argparse
 import ctypes
@@ -46,6 +49,7 @@ import socket
 import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -55,6 +59,7 @@ CFG = 3                                                 # seed family of cloops_
 VARIANT = "v2"
 HBM_PEAK_GBS = 8000.0                                   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 N_5M, CHR1_LEN, EPS_5M, MINPTS_5M = 5000000, 248956422, 2000, 5
+SYNTH_THREADS = 8                                       # synthesis threads per node, shared by its ranks (~5 GB of host memory at peak)
 
 
 def parse_args(argv=None):
@@ -64,6 +69,9 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--n-total", type=float, default=N_TOTAL, help="PETs of the synthetic genome (tests use less)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: CPU ranks (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures or checks: the K2 roofline, the cold, label-inclusive and "
+                         "scaling-proxy sweeps, the secondary figures and the CPU baseline (the options below refine it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--full-cpu-baseline", action="store_true",
                     help="time the sequential oracle over the WHOLE sweep (12 runs x 23 chromosomes, one process per chromosome: about a minute on "
@@ -76,6 +84,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.full_cpu_baseline and not args.full:
+        ap.error("--full-cpu-baseline needs --full")
     if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         ap.error("--dump-outputs needs a single process (--gpus 1)")
     return args
@@ -242,11 +252,11 @@ def main(argv=None):
     mine = sorted(lpt_assign([n for _, _, n in sizes], world)[rank])
     device = local_rank if (use_dist and on_gpu) else 0
     t_gen = time.perf_counter()
-    fs = []
-    for ci in mine:
-        name, length, n = sizes[ci]
-        X, Y = synth_chrom(n, length, 1000 * CFG + ci)
-        fs.append(pipe.CACHE.put_arrays("%s-%s" % (name, name), X, Y, device=device))
+    # every chromosome has a seed of its own, so they are drawn side by side (numpy's generators and ufuncs release the GIL) and
+    # made resident one by one in chromosome order, exactly as a loop would make them
+    with ThreadPoolExecutor(max(1, SYNTH_THREADS // world)) as ex:
+        drawn = ex.map(lambda ci: synth_chrom(sizes[ci][2], sizes[ci][1], 1000 * CFG + ci), mine)
+        fs = [pipe.CACHE.put_arrays("%s-%s" % (sizes[ci][0], sizes[ci][0]), X, Y, device=device) for ci, (X, Y) in zip(mine, drawn)]
     t_gen = time.perf_counter() - t_gen
     # the per-run exchange of the chained cut is ONE vector of ~48 KB of statistics per step: over RCCL through a pinned
     # staging buffer (a ring over xGMI, tens of microseconds; CLOOPS_BENCH_STATS=gloo keeps it on the host over a gloo group:
@@ -263,7 +273,7 @@ def main(argv=None):
         allsum = make_allsum(device=None, group=stats_group)
     eps_list, minpts_list = MODE3
 
-    # K2 is timed inside a sweep on the largest local chromosome (chr1 on rank 0): HIP events on the library's stream -- in the
+    # --full: K2 is timed inside a sweep on the largest local chromosome (chr1 on rank 0): HIP events on the library's stream -- in the
     # last WARM-UP sweep only: the event records between the kernels of that stream cost the sweep ~7 % (0.214 -> 0.230 s), so
     # the timed sweeps run without them (the roofline figure comes from the solo replay behind the timed region anyway)
     probe_f = max(fs, key=lambda f: len(pipe.CACHE.get(f))) if fs else None
@@ -294,7 +304,7 @@ def main(argv=None):
 
     first_sweep_s = None
     for w in range(args.warmup):
-        probing = w == args.warmup - 1 and probe_f is not None and rank == 0
+        probing = args.full and w == args.warmup - 1 and probe_f is not None and rank == 0
         if probing:
             pipe.CACHE.get(probe_f).chrom.set_profiling(True)
         t0 = time.perf_counter()
@@ -350,7 +360,7 @@ def main(argv=None):
                        "parallelism": "23 chromosomes LPT-sharded over %d GPU(s)" % world,
                        "synthesis_s_rank0": round(t_gen, 2)},
         }
-        if probe_f is not None and on_gpu:
+        if args.full and probe_f is not None and on_gpu:
             # replay the sweep's 12 runs IN THE SWEEP'S ORDER on the probe chromosome alone (3 passes): the kernels without
             # neighbours on the device, with the region query re-used inside every eps exactly as a sweep re-uses it, then
             # the same passes with the re-use switched off (every run its own full region query)
@@ -361,7 +371,7 @@ def main(argv=None):
                 line["roofline"]["in_sweep_avg_launch_ms"] = sum(max(t[3]["ms_region"] - t[3]["ms_bracket"], 1e-6) for t in k2_log) / len(k2_log)
                 line["roofline"]["in_sweep_source"] = "HIP events around K2 on chr1's stream during the last warm-up sweep (same work as a timed one; the event records between the kernels cost a sweep ~7 %, so the timed sweeps run without them)"
     # single-GPU legs behind the timed region: the one-dataset sweep, the label-inclusive form of the same sweep, the scaling proxy
-    if rank == 0 and world == 1 and on_gpu:
+    if args.full and rank == 0 and world == 1 and on_gpu:
         # a dataset's ONLY sweep: every handle forgets its q index, fine layout, last layout and cached counts (allocations stay)
         cold = []
         for _ in range(2):
@@ -384,7 +394,7 @@ def main(argv=None):
             line["scaling_proxy"] = prox[top]
             line["scaling_proxy"]["by_ranks"] = {str(n): {k: v.get(k) for k in ("makespan_s", "sum_over_steps_of_slowest_rank_s", "predicted_sweep_s", "predicted_speedup", "lpt_balance")} for n, v in prox.items()}
     # the secondary single-eps figure and the CPU baseline: rank 0, single GPU only
-    if rank == 0 and world == 1 and on_gpu:
+    if args.full and rank == 0 and world == 1 and on_gpu:
         pipe.CACHE.clear()
         if not args.no_secondary:
             line["secondary_5M"] = secondary_5m(api, synth_chrom)

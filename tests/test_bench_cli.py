@@ -119,3 +119,14 @@ def test_preflight_all_ranks_take_the_same_decision(monkeypatch):
     monkeypatch.setenv("TORCHELASTIC_RUN_ID", "pf-c")
     c = _preflight_world2([hang, ok], 2.0)
     assert c[0][0] is False and c[1][0] is False and c[0] == c[1] and "rank 0: no answer" in c[0][1], c
+
+
+def test_full_is_off_by_default_and_full_cpu_baseline_needs_it():
+    """a plain run measures the headline only; what takes runs of its own comes with --full, which --full-cpu-baseline refines"""
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full", "--full-cpu-baseline"]).full_cpu_baseline is True
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--full-cpu-baseline"])

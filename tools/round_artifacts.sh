@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/round
 mkdir -p $O $R/gpurun_out/prof
 cd $R
-timeout 400 python bench.py > $O/bench_final.json 2> $O/bench_final.err
+timeout 400 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
 timeout 600 bash tools/profile_bench.sh > $R/gpurun_out/prof/profile_bench.log 2>&1
 export TMPDIR=/tmp
 ( cd /tmp && rm -rf /tmp/pst && timeout 200 rocprofv3 --kernel-trace --output-format csv -d /tmp/pst -o t -- python $R/tools/one_chrom_steps.py 0 > /dev/null 2>&1; python $R/tools/per_run_trace.py /tmp/pst k7_reduce_parts > $O/per_step_trace.txt 2>&1 )
