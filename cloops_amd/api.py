@@ -475,6 +475,21 @@ class Chromosome(object):
         d = int(nd.value)
         return values[:d].copy(), mult[:d].copy(), int(nkept.value), (int(minc.value) if nkept.value else None)
 
+    def anchor_mask(self, starts, ends):
+        """K13: the rows with X or Y inside one of the closed intervals [starts[k], ends[k]] (scripts/jd2cleanWashuPETs.py:200-227;
+        any order, overlaps allowed) -> (mask uint64 [ceil(n / 64)], n_merged, n_kept): n_merged = intervals after merging the
+        overlapping or touching ones, n_kept = set rows; rows_of_mask(mask) gives the rows  (cl_anchor_mask)."""
+        s = np.ascontiguousarray(starts, dtype=np.int64).ravel()
+        e = np.ascontiguousarray(ends, dtype=np.int64).ravel()
+        if len(s) != len(e):
+            raise ValueError("starts and ends differ in length (%d, %d)" % (len(s), len(e)))
+        nw = (self.n + 63) // 64
+        mask = np.zeros(max(nw, 1), dtype=np.uint64)
+        nm, nk = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_anchor_mask(self._h, len(s), s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p),
+                                            mask.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nm), ctypes.byref(nk)))
+        return mask[:nw], int(nm.value), int(nk.value)
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

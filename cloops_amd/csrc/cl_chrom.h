@@ -208,6 +208,7 @@ struct cl_chrom {
     DevBuf k7_cls, k7_parts;          // K7: class per cluster id, per-workgroup partials
     DevBuf sig_tx, sig_ty, sig_tmp, sig_sorttmp, sig_m, sig_win, sig_out;   // K8: sorted PET tables, windows, counts
     DevBuf fp_small, fp_keys, fp_sorted, fp_tmp, fp_pairs;       // K12 (k_fingerprint.hip): scratch of one call, freed when it returns
+    DevBuf an_s, an_e, an_dir, an_mask, an_wsum;                 // K13 (k_anchor.hip): anchors, directory, row mask, workgroup totals; kept between calls
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;

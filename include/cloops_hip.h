@@ -238,6 +238,20 @@ int cl_quant_counts(cl_chrom* c, int32_t cut, int32_t n_records, const int32_t* 
 int cl_contact_hist(cl_chrom* c, int32_t cut, int32_t bin_size, int64_t cap, int64_t* values, int64_t* mult,
                     int64_t* n_distinct, int64_t* n_cells, int64_t* n_kept, int32_t* min_c);
 
+/*
+ * The PETs with an end inside a loop anchor (scripts/jd2cleanWashuPETs.py:162-227, getAnchors + getAnchorPETs): the n_iv
+ * closed intervals [starts[k], ends[k]] (any order, overlaps and duplicates allowed) are merged on the host until none
+ * overlap or share an endpoint (mergeAllAnchors, :162-180, at its fixed point: [1,5] and [5,9] merge, [1,5] and [6,9]
+ * do not), and `mask`, (n + 63) / 64 words, gets bit r % 64 of word r / 64 set iff X[r] or Y[r] lies in a merged
+ * interval (the closed searchsorted pair of :214-222); bits past n are 0.  *n_merged = number of merged intervals
+ * (the "merged anchors" of the script's log line), *n_kept = number of set rows.  n_iv == 0: a zero mask, zero
+ * counts, CL_OK.  Errors: CL_ERR_ARG for a NULL handle, NULL mask / n_merged / n_kept, n_iv < 0, NULL starts / ends
+ * with n_iv > 0, any starts[k] > ends[k], or runs in flight.  Uses scratch of its own that stays with the handle;
+ * leaves the handle's layouts, count cache and K8 tables untouched.
+ */
+int cl_anchor_mask(cl_chrom* c, int64_t n_iv, const int64_t* starts, const int64_t* ends,
+                   uint64_t* mask, int64_t* n_merged, int64_t* n_kept);
+
 /* Device pointer to the labels of the last run (n int32, row aligned) -- lets the caller
  * keep results on the GPU (e.g. to hand them to RCCL) without a host round trip.  NULL if the run did not
  * produce row-aligned labels (see cl_set_device_labels). */
