@@ -490,6 +490,102 @@ class Chromosome(object):
                                             mask.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nm), ctypes.byref(nk)))
         return mask[:nw], int(nm.value), int(nk.value)
 
+    TRACK_KINDS = {"washu": 0, "juice": 1}         # CL_TRACK_WASHU, CL_TRACK_JUICE
+    TRACK_NAME_MAX = 64                            # CL_TRACK_NAME_MAX
+    TRACK_BUDGET = 64 << 20                        # default bytes per rendered chunk
+
+    def track_build(self, kind, cut, ext, ids, chr_a, chr_b):
+        """K14: the browser-track lines of this chromosome's PETs (cLoops/io.py jd2washU / jd2hic, parseJd's cut) made on the device
+        and kept for track_chunks / track_render.  kind "washu" (two lines per PET, sorted by start, end, row, side) or "juice"
+        (one line per PET, row order); ids: the .jd's first column (int64 [n]) or None for the row numbers -> (records, bytes of
+        the whole text)  (cl_track_build)"""
+        if kind not in self.TRACK_KINDS:
+            raise ValueError("unknown track kind %r (washu or juice)" % (kind,))
+        ptr = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
+            if len(ids) != self.n:
+                raise ValueError("ids: %d entries for %d rows" % (len(ids), self.n))
+            ptr = ids.ctypes.data_as(ctypes.c_void_p)
+        nr, nb = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_track_build(self._h, self.TRACK_KINDS[kind], int(cut), int(ext), ptr, chr_a.encode(), chr_b.encode(),
+                                            ctypes.byref(nr), ctypes.byref(nb)))
+        return int(nr.value), int(nb.value)
+
+    def track_chunks(self, budget=TRACK_BUDGET):
+        """the built track split into chunks of at most `budget` bytes, none splitting a line -> (record bounds, byte bounds), int64
+        [chunks + 1]: chunk k is records rec[k] .. rec[k + 1] - 1, bytes byt[k] .. byt[k + 1] - 1 of the text  (cl_track_chunks)"""
+        nc = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_track_chunks(self._h, int(budget), 0, None, None, ctypes.byref(nc)))
+        rec = np.zeros(nc.value + 1, dtype=np.int64)
+        byt = np.zeros(nc.value + 1, dtype=np.int64)
+        _lib.check(self._lib.cl_track_chunks(self._h, int(budget), len(rec), rec.ctypes.data_as(ctypes.c_void_p),
+                                             byt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nc)))
+        self._track_bounds = (rec, byt)
+        return rec, byt
+
+    def track_render(self, chunk, out=None):
+        """the text of chunk `chunk` of the last track_chunks -> bytes; with `out` (a writable buffer: bytearray, numpy uint8, or
+        a (pointer, capacity) pair of page-locked memory) it is written there and its length returned  (cl_track_render)"""
+        nb = ctypes.c_int64(0)
+        if out is None:
+            buf = np.empty(self._track_cap(chunk), dtype=np.uint8)
+            _lib.check(self._lib.cl_track_render(self._h, int(chunk), buf.ctypes.data_as(ctypes.c_void_p), len(buf), ctypes.byref(nb)))
+            return buf[:nb.value].tobytes()
+        if isinstance(out, tuple):
+            ptr, cap = out
+        else:
+            a = np.frombuffer(out, dtype=np.uint8)
+            ptr, cap = a.ctypes.data, len(a)
+        _lib.check(self._lib.cl_track_render(self._h, int(chunk), ctypes.c_void_p(ptr), int(cap), ctypes.byref(nb)))
+        return int(nb.value)
+
+    def _track_cap(self, chunk):
+        rec, byt = getattr(self, "_track_bounds", ([0], [0]))
+        if not 0 <= chunk < len(rec) - 1:
+            return 1                               # the library reports the index
+        return max(1, int(byt[chunk + 1] - byt[chunk]))
+
+    def track_free(self):
+        """releases the device scratch of track_build  (cl_track_free)"""
+        _lib.check(self._lib.cl_track_free(self._h))
+
+    def track_iter(self, budget=TRACK_BUDGET):
+        """the chunks of the built track in order, as memoryviews of two page-locked buffers: chunk k + 1 is rendered and copied
+        to the host (by a helper thread; the library call releases the GIL) while the caller consumes chunk k.  A view is valid
+        until the next one is requested."""
+        rec, byt = self.track_chunks(budget)
+        K = len(rec) - 1
+        if K == 0:
+            return
+        size = int(np.max(np.diff(byt)))
+        bufs = []
+        pool = None
+        fut = None
+        try:
+            for _ in range(2):
+                p = self._lib.cl_host_alloc(size)
+                if not p:
+                    raise MemoryError("cl_host_alloc(%d) failed" % size)
+                bufs.append(p)
+            from concurrent.futures import ThreadPoolExecutor
+            pool = ThreadPoolExecutor(1)
+            fut = pool.submit(self.track_render, 0, (bufs[0], size))
+            for k in range(K):
+                nb = fut.result()
+                fut = pool.submit(self.track_render, k + 1, (bufs[(k + 1) & 1], size)) if k + 1 < K else None
+                yield memoryview((ctypes.c_char * nb).from_address(bufs[k & 1])).cast("B")
+        finally:
+            if fut is not None:
+                try:
+                    fut.result()
+                except Exception:
+                    pass
+            if pool is not None:
+                pool.shutdown()
+            for p in bufs:
+                self._lib.cl_host_free(ctypes.c_void_p(p))
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

@@ -209,6 +209,15 @@ struct cl_chrom {
     DevBuf sig_tx, sig_ty, sig_tmp, sig_sorttmp, sig_m, sig_win, sig_out;   // K8: sorted PET tables, windows, counts
     DevBuf fp_small, fp_keys, fp_sorted, fp_tmp, fp_pairs;       // K12 (k_fingerprint.hip): scratch of one call, freed when it returns
     DevBuf an_s, an_e, an_dir, an_mask, an_wsum;                 // K13 (k_anchor.hip): anchors, directory, row mask, workgroup totals; kept between calls
+    // K14 (k_track.hip): tile counts / offsets, kept rows, keys, line lengths / ends, ids, names, chunk bounds, render output;
+    // kept from cl_track_build to the next build or cl_track_free
+    DevBuf tk_tcnt, tk_toff, tk_row, tk_keys, tk_sorted, tk_len, tk_end, tk_tmp, tk_ids, tk_names, tk_bnd, tk_out;
+    struct TrackState {
+        bool built = false, ids = false;
+        int kind = 0, la = 0, lb = 0, gbits = 0;
+        long long cut = 0, ext = 0, R = 0, total = 0;                // records, bytes of the whole text
+        std::vector<long long> crec, cbyte;                          // the last cl_track_chunks: record / byte bounds
+    } tk;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;

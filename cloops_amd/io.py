@@ -141,3 +141,7 @@ def parseJd(f, cut=0):
     """cLoops/io.py:206-217."""
     from .pipe import parseJd as _p
     return _p(f, cut)
+
+
+# cLoops/io.py:220-348, the browser-track converters (cloops_amd.tracks)
+from .tracks import jd2hic, jd2washU, loops2juice, loops2washU  # noqa: E402,F401

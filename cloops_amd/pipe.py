@@ -929,7 +929,7 @@ def runSweep(fs, eps, minPts, cut=0, cpu=1, max_cut=False, log=None):
 
 
 # ---------------------------------------------------------------------------------------
-# the whole flow of cLoops/pipe.py:206-295 (minus the viewer converters and plots, SURVEY 2 #9,#11)
+# the whole flow of cLoops/pipe.py:206-295 (minus the plots)
 # ---------------------------------------------------------------------------------------
 MODES = {1: ([500, 1000, 2000], [5], 0), 2: ([1000, 2000, 5000], [5], 0),
          3: ([5000, 7500, 10000], [50, 40, 30, 20], 1), 4: ([2500, 5000, 7500, 10000], [30, 20], 1)}   # pipe.py:329-344
@@ -940,9 +940,9 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
-    Differences to the reference, all outside the hot path: no washU / juicebox conversion and no
-    plots (`washU`, `juice`, `plot` are accepted and ignored).  `eps == 0` estimates eps from the distances of the
-    PETs mapped to different strands (io.py:62-129, ests.py:23-33)."""
+    Differences to the reference, all outside the hot path: no plots (`plot` is accepted and ignored).  `washU` /
+    `juice` write `<fout>_loops_washU.txt` / `<fout>_loops_juicebox.txt` after `<fout>.loop` (pipe.py:288-292, cloops_amd.tracks).
+    `eps == 0` estimates eps from the distances of the PETs mapped to different strands (io.py:62-129, ests.py:23-33)."""
     import shutil
     from . import io as cio
     from . import cModel
@@ -968,6 +968,12 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     if e:
         shutil.rmtree(fout)
         return
+    if washU:                                                 # pipe.py:288-292
+        from .tracks import loops2washU
+        loops2washU(fout + ".loop", fout + "_loops_washU.txt")
+    if juice:
+        from .tracks import loops2juice
+        loops2juice(fout + ".loop", fout + "_loops_juicebox.txt")
     if tmp == False:                                          # noqa: E712  (pipe.py:294)
         shutil.rmtree(fout)
     return steps
@@ -975,7 +981,7 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
 
 def main(argv=None):
     """`python -m cloops_amd -f a.bedpe.gz -o out -m 1` -- the flags of cLoops/utils.py:73-204 that
-    drive the hot path (same names; -w / -j / -plot are accepted and ignored)."""
+    drive the hot path (same names; -w / -j write the loop tracks, -plot is accepted and ignored)."""
     import argparse
     ap = argparse.ArgumentParser(prog="cloops_amd")
     ap.add_argument("-f", dest="fnIn", required=True)

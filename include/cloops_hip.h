@@ -252,6 +252,43 @@ int cl_contact_hist(cl_chrom* c, int32_t cut, int32_t bin_size, int64_t cap, int
 int cl_anchor_mask(cl_chrom* c, int64_t n_iv, const int64_t* starts, const int64_t* ends,
                    uint64_t* mask, int64_t* n_merged, int64_t* n_kept);
 
+/*
+ * Browser-track text of the PETs (K14): the lines cLoops/io.py:292-348 writes per PET, made on the device in chunks.
+ *
+ * cl_track_build -- jd2washU / jd2hic's loop over parseJd(f, cut) (io.py:206-217, :301-318, :336-342).  Rows with
+ * cut > 0 and Y - X < cut are dropped.  kind CL_TRACK_WASHU: two records per kept row, side 0 anchored at p = X, side 1
+ * at p = Y, each line `own\tstart\tend\tpartner:pstart-pend,1\tid\t.\n` with start = max(0, p - ext), end = p + ext
+ * (the partner's interval the same way from the other end; int64 arithmetic that wraps as numpy's does), own / partner
+ * = name_a / name_b for side 0 and the other way round for side 1; the records are in the order (start, end, row,
+ * side) -- the order `bedtools sort` gives up to its unordered ties.  kind CL_TRACK_JUICE: one record per kept row in
+ * row order, `0\tname_a\tX\t0\t1\tname_b\tY\t1\n`.  ids: n host int64 (the .jd's first column) or NULL for the row
+ * numbers.  -> *n_records, *n_bytes of the whole text.  Errors: CL_ERR_ARG for a NULL handle or NULL outputs / names,
+ * an unknown kind, cut < 0, a name longer than CL_TRACK_NAME_MAX bytes, or runs in flight.  The scratch it keeps
+ * (device memory of its own: the kept rows, the sorted keys, the line offsets) lives until the next build,
+ * cl_track_free or cl_chrom_destroy; the handle's layouts, count cache and K8 tables stay untouched.
+ *
+ * cl_track_chunks -- splits the built text into chunks of at most `budget` bytes, never inside a line: chunk k is
+ * records [rec_bounds[k], rec_bounds[k + 1]), bytes [byte_bounds[k], byte_bounds[k + 1]) of the text; *n_chunks
+ * chunks, none empty (0 for an empty track).  rec_bounds and byte_bounds both NULL: only *n_chunks; else both hold
+ * cap >= *n_chunks + 1 entries.  The chunks are kept for cl_track_render until the next call.  Errors: CL_ERR_ARG for
+ * no built track, budget below the longest line the template allows (2 * CL_TRACK_NAME_MAX + 111 bytes covers every
+ * template), cap too small, or runs in flight.
+ *
+ * cl_track_render -- the text of chunk `chunk` into host memory `out` (cap >= its bytes; page-locked memory from
+ * cl_host_alloc copies fastest); *n_bytes = its length.  Errors: CL_ERR_ARG for no chunks, an index out of range, cap
+ * too small, or runs in flight.
+ *
+ * cl_track_free -- releases the scratch of cl_track_build.
+ */
+#define CL_TRACK_WASHU 0
+#define CL_TRACK_JUICE 1
+#define CL_TRACK_NAME_MAX 64
+int cl_track_build(cl_chrom* c, int32_t kind, int64_t cut, int64_t ext, const int64_t* ids, const char* name_a,
+                   const char* name_b, int64_t* n_records, int64_t* n_bytes);
+int cl_track_chunks(cl_chrom* c, int64_t budget, int64_t cap, int64_t* rec_bounds, int64_t* byte_bounds, int64_t* n_chunks);
+int cl_track_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n_bytes);
+int cl_track_free(cl_chrom* c);
+
 /* Device pointer to the labels of the last run (n int32, row aligned) -- lets the caller
  * keep results on the GPU (e.g. to hand them to RCCL) without a host round trip.  NULL if the run did not
  * produce row-aligned labels (see cl_set_device_labels). */
