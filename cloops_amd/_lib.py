@@ -18,6 +18,7 @@ CL_ERR_DOMAIN = -4
 CL_ERR_GRID = -5
 CL_ERR_NODEVICE = -6
 CL_ERR_HASH = -7
+CL_ERR_PARSE = -8
 
 VARIANT_CDBSCAN1 = 1
 VARIANT_CDBSCAN2 = 2
@@ -28,7 +29,7 @@ SYMBOLS = [
     "cl_last_error", "cl_device_count", "cl_chrom_create", "cl_chrom_destroy", "cl_chrom_size",
     "cl_cluster", "cl_get_boxes", "cl_neighbor_counts", "cl_labels_device", "cl_set_profiling",
     "cl_get_timing", "cl_version", "cl_host_alloc", "cl_host_free", "cl_cluster_async", "cl_wait", "cl_boxes_host",
-    "cl_dist_summary", "cl_dist_bin_hist", "cl_last_n_in", "cl_sig_counts", "cl_quant_counts", "cl_contact_hist", "cl_anchor_mask", "cl_track_build", "cl_track_chunks", "cl_track_render", "cl_track_free", "cl_cluster_weighted",
+    "cl_dist_summary", "cl_dist_bin_hist", "cl_last_n_in", "cl_sig_counts", "cl_quant_counts", "cl_contact_hist", "cl_anchor_mask", "cl_track_build", "cl_track_chunks", "cl_track_render", "cl_track_free", "cl_conv_create", "cl_conv_feed", "cl_conv_render", "cl_conv_error", "cl_conv_timing", "cl_conv_destroy", "cl_cluster_weighted",
     "cl_set_layout_reuse", "cl_set_sort_index", "cl_set_device_labels", "cl_set_table_export", "cl_cand_reset", "cl_cand_append", "cl_cand_finish", "cl_cluster_step_async", "cl_step_result",
     "cl_set_count_reuse", "cl_set_count_floor", "cl_set_count_thresholds", "cl_set_eps_list", "cl_chrom_set_stream", "cl_last_region_mode", "cl_debug_arena_overcommit", "cl_chrom_subsample", "cl_stream_create", "cl_stream_destroy", "cl_set_traversal", "cl_cand_finish_device", "cl_cluster_pairs_async", "cl_cluster_rowmask_async", "cl_last_n_labelled", "cl_set_pairs_defer", "cl_pairs_sync", "cl_sweep_plan", "cl_chrom_drop_indexes",
 ]
@@ -150,6 +151,18 @@ def load():
     lib.cl_track_render.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, i64p]
     lib.cl_track_free.restype = ctypes.c_int
     lib.cl_track_free.argtypes = [vp]
+    lib.cl_conv_create.restype = ctypes.c_int
+    lib.cl_conv_create.argtypes = [ctypes.c_int, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(vp)]
+    lib.cl_conv_feed.restype = ctypes.c_int
+    lib.cl_conv_feed.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, i64p, i64p, i64p]
+    lib.cl_conv_render.restype = ctypes.c_int
+    lib.cl_conv_render.argtypes = [vp, vp, ctypes.c_int64, i64p]
+    lib.cl_conv_error.restype = ctypes.c_int
+    lib.cl_conv_error.argtypes = [vp, i64p, ctypes.POINTER(ctypes.c_int32)]
+    lib.cl_conv_timing.restype = ctypes.c_int
+    lib.cl_conv_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.cl_conv_destroy.restype = ctypes.c_int
+    lib.cl_conv_destroy.argtypes = [vp]
     lib.cl_last_n_in.restype = ctypes.c_int64
     lib.cl_last_n_in.argtypes = [vp]
     lib.cl_get_boxes.restype = ctypes.c_int

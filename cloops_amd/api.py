@@ -590,3 +590,59 @@ class Chromosome(object):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+
+class Converter(object):
+    """K15: a pairs-to-BEDPE converter on the device (cl_conv of include/cloops_hip.h), shaped like Chromosome.track_*: feed a chunk of
+    complete lines, render their BEDPE text.  fmt "hicpro" (scripts/hicpropairs2bedpe) or "juicer" (scripts/juicerLong2bedpe.py)."""
+    FORMATS = {"hicpro": 0, "juicer": 1}           # CL_CONV_HICPRO, CL_CONV_JUICER
+    KINDS = {1: "fewer than 7 fields", 2: "not an integer", 3: "integer outside int64", 4: "line longer than the chunk budget"}
+    BUDGET = 64 << 20                              # default bytes per chunk
+
+    def __init__(self, fmt, ext, budget=BUDGET, device=0, stream=None):
+        if fmt not in self.FORMATS:
+            raise ValueError("unknown pairs format %r (hicpro or juicer)" % (fmt,))
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p()
+        self.fmt, self.ext, self.budget = fmt, int(ext), int(budget)
+        _lib.check(self._lib.cl_conv_create(int(device), ctypes.c_void_p(stream), self.FORMATS[fmt], self.ext, self.budget,
+                                            ctypes.byref(self._h)))
+
+    def feed(self, ptr, n, last):
+        """the complete lines of the n bytes at host address `ptr` (all of them with `last`) -> (bytes consumed, lines converted,
+        bytes of their text, error): error None, or (line number counted over this handle's feeds, reason) of the first line the
+        reference would raise on -- the lines in front of it are converted  (cl_conv_feed, cl_conv_error)"""
+        used, nl, nb = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = self._lib.cl_conv_feed(self._h, ctypes.c_void_p(ptr), int(n), int(bool(last)), ctypes.byref(used), ctypes.byref(nl),
+                                    ctypes.byref(nb))
+        err = None
+        if rc == _lib.CL_ERR_PARSE:
+            line, kind = ctypes.c_int64(0), ctypes.c_int32(0)
+            _lib.check(self._lib.cl_conv_error(self._h, ctypes.byref(line), ctypes.byref(kind)))
+            err = (int(line.value), self.KINDS.get(int(kind.value), "error %d" % kind.value))
+        else:
+            _lib.check(rc)
+        return int(used.value), int(nl.value), int(nb.value), err
+
+    def render(self, ptr, cap):
+        """the text of the last feed's lines into `cap` bytes of host memory at `ptr` -> its length  (cl_conv_render)"""
+        nb = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_conv_render(self._h, ctypes.c_void_p(ptr), int(cap), ctypes.byref(nb)))
+        return int(nb.value)
+
+    def timing(self):
+        """device ms of the last feed and render: h2d, feed kernels, render kernel, d2h  (cl_conv_timing)"""
+        ms = (ctypes.c_float * 4)()
+        _lib.check(self._lib.cl_conv_timing(self._h, ms))
+        return {"h2d": ms[0], "feed": ms[1], "render": ms[2], "d2h": ms[3]}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.cl_conv_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                               # noqa: BLE001
+            pass

@@ -1,0 +1,570 @@
+// k_convert.hip -- K15: the pairs-to-BEDPE converters of the reference (scripts/hicpropairs2bedpe, scripts/juicerLong2bedpe.py) on
+// the device: a line index over raw bytes, a field tokenizer with exact integer parsing, and a lane-per-line renderer -- kernels and
+// the C entry points of the cl_conv handle.
+#include "cl_chrom.h"
+#include "cl_text.h"
+
+// ==========================================================================================
+// K15: one chunk of complete lines per cl_conv_feed, its text made by cl_conv_render
+// ==========================================================================================
+// The reference reads one line at a time in Python, splits it, parses two integers and writes one BEDPE line.  Here the host hands
+// over a chunk of complete lines (page-locked, up to the handle's byte budget) and the device does the rest, in four steps:
+//   k15_count / k15_lines   the line index: 16 KiB tiles of input bytes read with 16-byte loads, '\n' found by an exact SWAR byte
+//                           compare and counted by popcount; a count per tile, an exclusive scan of the counts, an ordered write
+//                           of every line's end (the position of its '\n')
+//   k15_parse<FMT>          256 lines per workgroup, one per lane: the tile's bytes staged in LDS with 16-byte loads (a tile wider
+//                           than the LDS reads global memory instead), each lane walks its own line 8 bytes per read, splits it as
+//                           the script does (up to field 6), parses the two positions and writes one record and its output
+//                           length; the first bad line: a wave minimum, a workgroup minimum, one atomicMin per workgroup
+//   inclusive scan          the int64 running sum of the lengths: line j occupies [end[j - 1], end[j]) of the chunk's text
+//   k15_render<FMT>         K14's LDS tile: one lane per line assembles its text in LDS, the workgroup writes its span with
+//                           16-byte stores; copied fields are read from the chunk, still in HBM (a span wider than the LDS is
+//                           written straight to global memory)
+// The reading rules are Python 2's on bytes: lines end at '\n' only, whitespace is ASCII \t \n \v \f \r and space,
+// an integer is optional whitespace, an optional sign, ASCII digits, optional whitespace, and must fit int64 with +-ext applied.
+#define K15_U 4                                  // 16-byte words per thread of an index tile
+#define K15_TILE (TPB * K15_U * 16)              // bytes per index tile: 16 KiB
+#define K15_T 256                                // lines per parse / render workgroup (one per lane)
+#define K15_LDS (40 * 1024)                      // bytes of a staged input or output tile: 4 workgroups per CU
+#define K15_PAD 64                               // device bytes past a chunk (16-byte loads of its last word, the added '\n')
+
+struct K15Rec {                                  // one parsed line
+    u32 off[5], len[5];                          // copied fields (chunk offsets): hicpro f0 f1 f3 f4 f6; juicer f1 f5
+    long long v[4];                              // the four printed integers
+    u32 flags;                                   // juicer: bit 0 / 1 = field 0 / 4 is "0"; a bad line: its error kind << 8
+    u32 pad;
+};
+
+// bit b: byte b of the 16 is '\n'; bytes at or past `left` do not count
+__device__ __forceinline__ u32 k15_nlmask(uint4 v, long long left)
+{
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+    u32 m = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const u32 x = w[i] ^ 0x0a0a0a0au;
+        const u32 t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);    // 0x80 in exactly the bytes of x that are zero
+        m |= (((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u)) << (4 * i);
+    }
+    return left >= 16 ? m : (left <= 0 ? 0u : m & ((1u << left) - 1u));
+}
+
+__global__ void __launch_bounds__(TPB)
+k15_count(const uint4* __restrict__ in, long long n, u32* __restrict__ tcnt)
+{
+    __shared__ int wc[TPB / 64];
+    const long long t0 = (long long)blockIdx.x * K15_TILE;
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < K15_U; ++u) {
+        const long long pos = t0 + ((long long)u * TPB + threadIdx.x) * 16;
+        if (pos < n) cnt += __popc(k15_nlmask(in[pos >> 4], n - pos));
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) tcnt[blockIdx.x] = (u32)(wc[0] + wc[1] + wc[2] + wc[3]);
+}
+
+// the ends of the lines of every tile at toff[tile] onwards, in byte order (only the first lmax of the chunk are kept)
+__global__ void __launch_bounds__(TPB)
+k15_lines(const uint4* __restrict__ in, long long n, const u32* __restrict__ toff, long long lmax, u32* __restrict__ ends)
+{
+    __shared__ u32 ws[K15_U][TPB / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long t0 = (long long)blockIdx.x * K15_TILE;
+    u32 m[K15_U];
+    int inc[K15_U];
+#pragma unroll
+    for (int u = 0; u < K15_U; ++u) {
+        const long long pos = t0 + ((long long)u * TPB + threadIdx.x) * 16;
+        m[u] = pos < n ? k15_nlmask(in[pos >> 4], n - pos) : 0u;
+        int s = __popc(m[u]);
+        for (int o = 1; o < 64; o <<= 1) {                            // inclusive scan over the wave
+            const int t = __shfl_up(s, o);
+            if (lane >= o) s += t;
+        }
+        inc[u] = s;
+        if (lane == 63) ws[u][w] = (u32)s;
+    }
+    __syncthreads();
+    u32 base = toff[blockIdx.x];
+#pragma unroll
+    for (int u = 0; u < K15_U; ++u) {
+        u32 k = base + (u32)(inc[u] - __popc(m[u]));
+        for (int v = 0; v < w; ++v) k += ws[u][v];
+        const long long pos = t0 + ((long long)u * TPB + threadIdx.x) * 16;
+        u32 mm = m[u];
+        while (mm) {
+            const int b = __builtin_ctz(mm);
+            mm &= mm - 1;
+            if ((long long)k < lmax) ends[k] = (u32)(pos + b);
+            ++k;
+        }
+        for (int v = 0; v < TPB / 64; ++v) base += ws[u][v];
+    }
+}
+
+// bytes of the chunk, one aligned 8-byte word per read: from the chunk in global memory (a0 = 0) or from the tile staged in LDS
+// (chunk byte a0, a multiple of 16, at LDS byte 0)
+struct K15Rd {
+    const u64* g;
+    long long a0, wi;
+    u64 w;
+    __device__ __forceinline__ u32 at(long long q)
+    {
+        const long long i = (q - a0) >> 3;
+        if (i != wi) { wi = i; w = g[i]; }
+        return (u32)(w >> ((q & 7) << 3)) & 0xffu;
+    }
+};
+
+__device__ __forceinline__ bool k15_ws(u32 c) { return c == 32u || (c >= 9u && c <= 13u); }
+
+// Python 2's int() of the bytes [s, e), bounded to int64 -> 0 and v, or the error kind
+__device__ __forceinline__ int k15_int(K15Rd& rd, long long s, long long e, long long& v)
+{
+    while (s < e && k15_ws(rd.at(s))) ++s;
+    while (e > s && k15_ws(rd.at(e - 1))) --e;
+    bool neg = false;
+    if (s < e) {
+        const u32 c = rd.at(s);
+        if (c == '+' || c == '-') { neg = c == '-'; ++s; }
+    }
+    if (s >= e) return CL_CONV_E_INT;
+    const u64 lim = neg ? (1ull << 63) : (1ull << 63) - 1;
+    u64 m = 0;
+    bool over = false;
+    for (; s < e; ++s) {
+        const u32 d = rd.at(s) - (u32)'0';
+        if (d > 9) return CL_CONV_E_INT;                              // ValueError before any overflow
+        if (m > (lim - d) / 10) over = true;
+        else m = m * 10 + d;
+    }
+    if (over) return CL_CONV_E_RANGE;
+    v = neg ? (long long)(0ull - m) : (long long)m;
+    return 0;
+}
+
+// scripts/hicpropairs2bedpe:15-34: line.strip().split('\t'); A from f1, f2, f3 and B from f4, f5, f6; f0 . f3 f6 copied
+__device__ __forceinline__ int k15_hicpro(K15Rd& rd, long long s, long long e, long long ext, K15Rec& r, long long& olen)
+{
+    while (e > s && k15_ws(rd.at(e - 1))) --e;
+    while (s < e && k15_ws(rd.at(s))) ++s;
+    long long fs[7], fe[7];
+    long long q = s;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        if (k > 0) { ok = ok && q < e; ++q; }                        // the '\t' that ended field k - 1
+        fs[k] = q;
+        if (ok)
+            while (q < e && rd.at(q) != '\t') ++q;
+        fe[k] = q;
+    }
+    if (!ok) return CL_CONV_E_FIELDS;
+    long long p1 = 0, p2 = 0;
+    int bad = k15_int(rd, fs[2], fe[2], p1);
+    if (!bad) bad = k15_int(rd, fs[5], fe[5], p2);
+    if (bad) return bad;
+    const bool plus1 = fe[3] - fs[3] == 1 && rd.at(fs[3]) == '+';
+    const bool plus2 = fe[6] - fs[6] == 1 && rd.at(fs[6]) == '+';
+    long long a1 = p1, a2 = p1, b1 = p2, b2 = p2;
+    bool ovf = plus1 ? __builtin_add_overflow(p1, ext, &a2) : __builtin_sub_overflow(p1, ext, &a1);
+    ovf |= plus2 ? __builtin_add_overflow(p2, ext, &b2) : __builtin_sub_overflow(p2, ext, &b1);
+    if (ovf) return CL_CONV_E_RANGE;
+    r.off[0] = (u32)fs[0]; r.len[0] = (u32)(fe[0] - fs[0]);
+    r.off[1] = (u32)fs[1]; r.len[1] = (u32)(fe[1] - fs[1]);
+    r.off[2] = (u32)fs[3]; r.len[2] = (u32)(fe[3] - fs[3]);
+    r.off[3] = (u32)fs[4]; r.len[3] = (u32)(fe[4] - fs[4]);
+    r.off[4] = (u32)fs[6]; r.len[4] = (u32)(fe[6] - fs[6]);
+    r.v[0] = a1; r.v[1] = a2; r.v[2] = b1; r.v[3] = b2;
+    r.flags = 0;
+    olen = (long long)r.len[0] + r.len[1] + r.len[2] + r.len[3] + r.len[4] + cl_width(a1) + cl_width(a2) + cl_width(b1) + cl_width(b2) + 11;
+    return 0;
+}
+
+// scripts/juicerLong2bedpe.py:12-31: line.split(); f1 max(0, p1 - ext) p1 + ext f5 max(0, p2 - ext) p2 + ext . . s1 s2
+__device__ __forceinline__ int k15_juicer(K15Rd& rd, long long s, long long e, long long ext, K15Rec& r, long long& olen)
+{
+    long long fs[7], fe[7];
+    long long q = s;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        if (ok)
+            while (q < e && k15_ws(rd.at(q))) ++q;
+        ok = ok && q < e;
+        fs[k] = q;
+        if (ok)
+            while (q < e && !k15_ws(rd.at(q))) ++q;
+        fe[k] = q;
+    }
+    if (!ok) return CL_CONV_E_FIELDS;
+    long long p1 = 0, p2 = 0;
+    int bad = k15_int(rd, fs[2], fe[2], p1);
+    if (!bad) bad = k15_int(rd, fs[6], fe[6], p2);
+    if (bad) return bad;
+    long long lo1, hi1, lo2, hi2;
+    const int ovf = (int)__builtin_sub_overflow(p1, ext, &lo1) | (int)__builtin_add_overflow(p1, ext, &hi1) |
+                    (int)__builtin_sub_overflow(p2, ext, &lo2) | (int)__builtin_add_overflow(p2, ext, &hi2);
+    if (ovf) return CL_CONV_E_RANGE;
+    r.v[0] = lo1 > 0 ? lo1 : 0; r.v[1] = hi1;
+    r.v[2] = lo2 > 0 ? lo2 : 0; r.v[3] = hi2;
+    const bool z1 = fe[0] - fs[0] == 1 && rd.at(fs[0]) == '0';
+    const bool z2 = fe[4] - fs[4] == 1 && rd.at(fs[4]) == '0';
+    r.flags = (z1 ? 1u : 0u) | (z2 ? 2u : 0u);
+    r.off[0] = (u32)fs[1]; r.len[0] = (u32)(fe[1] - fs[1]);
+    r.off[1] = (u32)fs[5]; r.len[1] = (u32)(fe[5] - fs[5]);
+    r.off[2] = r.off[3] = r.off[4] = 0;
+    r.len[2] = r.len[3] = r.len[4] = 0;
+    olen = (long long)r.len[0] + r.len[1] + cl_width(r.v[0]) + cl_width(r.v[1]) + cl_width(r.v[2]) + cl_width(r.v[3]) + 14;
+    return 0;
+}
+
+template <int FMT>
+__device__ __forceinline__ int k15_line(K15Rd& rd, long long s, long long e, long long ext, K15Rec& r, long long& olen)
+{
+    return FMT == CL_CONV_HICPRO ? k15_hicpro(rd, s, e, ext, r, olen) : k15_juicer(rd, s, e, ext, r, olen);
+}
+
+// lines [256 b, 256 b + 256) of the chunk -> their records and output lengths (0 for a bad line); the first bad line -> *err
+template <int FMT>
+__global__ void __launch_bounds__(K15_T)
+k15_parse(const uint4* __restrict__ in, const u32* __restrict__ ends, long long L, long long ext, K15Rec* __restrict__ rec,
+          long long* __restrict__ len, int* __restrict__ err)
+{
+    extern __shared__ uint4 k15_lds[];
+    __shared__ int wmin[K15_T / 64];
+    const long long q0 = (long long)blockIdx.x * K15_T;
+    const long long q1 = q0 + K15_T < L ? q0 + K15_T : L;
+    const long long a0 = (q0 > 0 ? (long long)ends[q0 - 1] + 1 : 0) & ~15ll;
+    const long long a1 = ((long long)ends[q1 - 1] + 1 + 15) & ~15ll;        // the tile's bytes, its last '\n' included
+    const bool fits = a1 - a0 <= K15_LDS;
+    if (fits)
+        for (long long i = threadIdx.x; i < (a1 - a0) >> 4; i += K15_T) k15_lds[i] = in[(a0 >> 4) + i];
+    __syncthreads();
+    const long long j = q0 + threadIdx.x;
+    int bad = INT_MAX;
+    if (j < q1) {
+        const long long s = j > 0 ? (long long)ends[j - 1] + 1 : 0, e = ends[j];
+        K15Rec r = {};
+        long long olen = 0;
+        int kind;
+        if (fits) {
+            K15Rd rd{(const u64*)k15_lds, a0, -1, 0};
+            kind = k15_line<FMT>(rd, s, e, ext, r, olen);
+        } else {
+            K15Rd rd{(const u64*)in, 0, -1, 0};
+            kind = k15_line<FMT>(rd, s, e, ext, r, olen);
+        }
+        if (kind) { r.flags = (u32)kind << 8; olen = 0; bad = (int)j; }
+        rec[j] = r;
+        len[j] = olen;
+    }
+    bad = dpp_reduce_wave(bad, OpMin());
+    if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int m = min(min(wmin[0], wmin[1]), min(wmin[2], wmin[3]));
+        if (m != INT_MAX) atomicMin(err, m);
+    }
+}
+
+__device__ __forceinline__ int k15_copy(char* d, int p, K15Rd& rd, u32 off, u32 n)
+{
+    for (u32 k = 0; k < n; ++k) d[p + k] = (char)rd.at((long long)off + k);
+    return p + (int)n;
+}
+
+// the text of one record at d[p ..]
+template <int FMT>
+__device__ __forceinline__ void k15_emit(char* d, int p, const uint4* in, const K15Rec& r)
+{
+    K15Rd rd{(const u64*)in, 0, -1, 0};
+    if (FMT == CL_CONV_HICPRO) {                                       // A0 A1 A2 B0 B1 B2 f0 . f3 f6
+        p = k15_copy(d, p, rd, r.off[1], r.len[1]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[0]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[1]); d[p++] = '\t';
+        p = k15_copy(d, p, rd, r.off[3], r.len[3]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[2]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[3]); d[p++] = '\t';
+        p = k15_copy(d, p, rd, r.off[0], r.len[0]); d[p++] = '\t'; d[p++] = '.'; d[p++] = '\t';
+        p = k15_copy(d, p, rd, r.off[2], r.len[2]); d[p++] = '\t';
+        p = k15_copy(d, p, rd, r.off[4], r.len[4]); d[p++] = '\n';
+    } else {                                                           // f1 lo1 hi1 f5 lo2 hi2 . . s1 s2
+        p = k15_copy(d, p, rd, r.off[0], r.len[0]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[0]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[1]); d[p++] = '\t';
+        p = k15_copy(d, p, rd, r.off[1], r.len[1]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[2]); d[p++] = '\t';
+        p = cl_put(d, p, r.v[3]); d[p++] = '\t';
+        d[p++] = '.'; d[p++] = '\t'; d[p++] = '.'; d[p++] = '\t';
+        d[p++] = (r.flags & 1u) ? '+' : '-'; d[p++] = '\t';
+        d[p++] = (r.flags & 2u) ? '+' : '-'; d[p++] = '\n';
+    }
+}
+
+// lines [0, R) of the chunk -> out[0 .. end[R - 1]); 256 lines per workgroup, staged in LDS when their span fits
+template <int FMT>
+__global__ void __launch_bounds__(K15_T)
+k15_render(const uint4* __restrict__ in, const K15Rec* __restrict__ rec, const long long* __restrict__ end, long long R,
+           char* __restrict__ out)
+{
+    extern __shared__ uint4 k15_lds[];
+    char* buf = (char*)k15_lds;
+    const long long q0 = (long long)blockIdx.x * K15_T;
+    const long long q1 = q0 + K15_T < R ? q0 + K15_T : R;
+    const long long g0 = q0 > 0 ? end[q0 - 1] : 0, g1 = end[q1 - 1];   // the tile's span in out
+    const long long a0 = g0 & ~15ll;                                    // LDS byte i <-> out byte a0 + i
+    const bool fits = g1 - a0 <= K15_LDS;
+    const long long j = q0 + threadIdx.x;
+    if (j < q1) {
+        const long long p0 = j > 0 ? end[j - 1] : 0;
+        const K15Rec r = rec[j];
+        if (fits) k15_emit<FMT>(buf, (int)(p0 - a0), in, r);
+        else k15_emit<FMT>(out + p0, 0, in, r);
+    }
+    if (!fits) return;                                                  // uniform over the workgroup
+    __syncthreads();
+    // the span [g0, g1) as 16-byte words of out: whole words with one store each, the two edge words byte by byte
+    const long long w0 = g0 >> 4, w1 = (g1 + 15) >> 4;
+    for (long long w = w0 + threadIdx.x; w < w1; w += blockDim.x) {
+        const long long b = w << 4;
+        if (b >= g0 && b + 16 <= g1) {
+            *(uint4*)(out + b) = k15_lds[(b - a0) >> 4];
+        } else {
+            const long long s = b > g0 ? b : g0, e = b + 16 < g1 ? b + 16 : g1;
+            for (long long i = s; i < e; ++i) out[i] = buf[i - a0];
+        }
+    }
+}
+
+// ---- K15 host side ------------------------------------------------------------------------------
+struct cl_conv {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int fmt = 0;
+    long long ext = 0, budget = 0, lmax = 0;
+    DevBuf in, tcnt, toff, ends, rec, len, end, tmp, err, out;
+    long long lines = 0;                          // lines of every feed so far: cl_conv_error's line numbers
+    bool fed = false;                             // the last feed's lines can be rendered
+    long long R = 0, nbytes = 0;                  // ... how many, and the bytes of their text
+    long long err_line = 0;
+    int err_kind = 0;
+    hipEvent_t ev[6] = {};                        // feed: copy start / copy end / kernels end; render: start / kernel end / copy end
+    float ms_h2d = 0, ms_feed = 0, ms_render = 0, ms_d2h = 0;
+};
+
+static void conv_free(cl_conv* c)
+{
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (DevBuf* b : {&c->in, &c->tcnt, &c->toff, &c->ends, &c->rec, &c->len, &c->end, &c->tmp, &c->err, &c->out}) b->release();
+    for (hipEvent_t& e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+extern "C" int cl_conv_create(int device, void* stream, int32_t format, int64_t ext, int64_t budget, cl_conv** out)
+{
+    if (!out) return fail(CL_ERR_ARG, "cl_conv_create: out is null");
+    *out = nullptr;
+    if (format != CL_CONV_HICPRO && format != CL_CONV_JUICER) return fail(CL_ERR_ARG, "cl_conv_create: unknown format");
+    if (budget < 1 || budget > CL_CONV_BUDGET_MAX) return fail(CL_ERR_ARG, "cl_conv_create: budget outside 1 .. CL_CONV_BUDGET_MAX");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(CL_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(CL_ERR_ARG, "cl_conv_create: bad device index");
+    HIP_TRY(hipSetDevice(device));
+    cl_conv* c = new cl_conv();
+    c->device = device; c->fmt = format; c->ext = ext; c->budget = budget;
+    c->lmax = budget / 16 + K15_T;
+    int rc = CL_OK;
+    if (stream) c->stream = (hipStream_t)stream;
+    else if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(CL_ERR_HIP, "hipStreamCreate");
+    else c->own_stream = true;
+    for (int i = 0; rc == CL_OK && i < 6; ++i)
+        if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = fail(CL_ERR_HIP, "hipEventCreate");
+    if (rc == CL_OK) rc = c->err.ensure(16);
+    if (rc != CL_OK) { conv_free(c); return rc; }
+    *out = c;
+    return CL_OK;
+}
+
+template <typename T>
+static int conv_read(cl_conv* c, T* dst, const void* src)            // one value from device memory, synchronously
+{
+    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CL_OK;
+}
+
+static int conv_feed(cl_conv* c, const char* bytes, long long cut, long long* consumed, int* bad, long long* L_out)
+{
+    const bool virt = bytes[cut - 1] != '\n';                          // the input's last line, without its newline
+    const long long ne = cut + (virt ? 1 : 0);
+    const long long tiles = (ne + K15_TILE - 1) / K15_TILE;
+    int rc;
+    if ((rc = c->in.ensure((size_t)ne + K15_PAD)) || (rc = c->tcnt.ensure((size_t)(tiles + 1) * 4)) ||
+        (rc = c->toff.ensure((size_t)(tiles + 1) * 4)) || (rc = c->ends.ensure((size_t)c->lmax * 4)))
+        return rc;
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(hipMemcpyAsync(c->in.p, bytes, (size_t)cut, hipMemcpyHostToDevice, c->stream));
+    if (virt) HIP_TRY(hipMemsetAsync(c->in.as<char>() + cut, '\n', 1, c->stream));
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    HIP_TRY(hipMemsetAsync(c->tcnt.as<u32>() + tiles, 0, 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->err.p, 0x7f, 4, c->stream));          // no bad line: 0x7f7f7f7f, above any line index
+    hipLaunchKernelGGL(k15_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->tcnt.as<u32>());
+    HIP_TRY(hipGetLastError());
+    size_t bytes_tmp = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, bytes_tmp, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan size query", hipGetErrorString(e));
+    if ((rc = c->tmp.ensure(std::max<size_t>(bytes_tmp, 16)))) return rc;
+    bytes_tmp = c->tmp.bytes;
+    e = rocprim::exclusive_scan(c->tmp.p, bytes_tmp, c->tcnt.as<u32>(), c->toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(tiles)", hipGetErrorString(e));
+    hipLaunchKernelGGL(k15_lines, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->toff.as<u32>(), c->lmax,
+                       c->ends.as<u32>());
+    HIP_TRY(hipGetLastError());
+    u32 nl = 0;
+    if ((rc = conv_read(c, &nl, c->toff.as<u32>() + tiles))) return rc;
+    long long L = nl;
+    *consumed = cut;
+    if (L > c->lmax) {                                                  // the rest of the chunk waits for the next feed
+        L = c->lmax;
+        u32 last_end = 0;
+        if ((rc = conv_read(c, &last_end, c->ends.as<u32>() + (L - 1)))) return rc;
+        *consumed = (long long)last_end + 1;
+    }
+    if ((rc = c->rec.ensure((size_t)L * sizeof(K15Rec))) || (rc = c->len.ensure((size_t)L * 8)) || (rc = c->end.ensure((size_t)L * 8))) return rc;
+    const unsigned grid = (unsigned)((L + K15_T - 1) / K15_T);
+    if (c->fmt == CL_CONV_HICPRO)
+        hipLaunchKernelGGL(k15_parse<CL_CONV_HICPRO>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
+                           c->rec.as<K15Rec>(), c->len.as<long long>(), c->err.as<int>());
+    else
+        hipLaunchKernelGGL(k15_parse<CL_CONV_JUICER>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
+                           c->rec.as<K15Rec>(), c->len.as<long long>(), c->err.as<int>());
+    HIP_TRY(hipGetLastError());
+    bytes_tmp = 0;
+    e = rocprim::inclusive_scan(nullptr, bytes_tmp, (long long*)nullptr, (long long*)nullptr, (size_t)L, rocprim::plus<long long>(), c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan size query", hipGetErrorString(e));
+    if ((rc = c->tmp.ensure(std::max<size_t>(bytes_tmp, 16)))) return rc;
+    bytes_tmp = c->tmp.bytes;
+    e = rocprim::inclusive_scan(c->tmp.p, bytes_tmp, c->len.as<long long>(), c->end.as<long long>(), (size_t)L, rocprim::plus<long long>(), c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan(lines)", hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    if ((rc = conv_read(c, bad, c->err.p))) return rc;
+    *L_out = L;
+    return CL_OK;
+}
+
+extern "C" int cl_conv_feed(cl_conv* c, const char* bytes, int64_t n, int32_t last, int64_t* consumed, int64_t* n_lines, int64_t* n_bytes)
+{
+    if (!c) return fail(CL_ERR_ARG, "null converter handle");
+    if (consumed) *consumed = 0;
+    if (n_lines) *n_lines = 0;
+    if (n_bytes) *n_bytes = 0;
+    if (!consumed || !n_lines || !n_bytes || n < 0 || (n > 0 && !bytes)) return fail(CL_ERR_ARG, "cl_conv_feed: bad arguments");
+    if (n > c->budget) return fail(CL_ERR_ARG, "cl_conv_feed: more bytes than the handle's budget");
+    c->fed = false; c->R = 0; c->nbytes = 0; c->err_line = 0; c->err_kind = 0;
+    c->ms_h2d = c->ms_feed = c->ms_render = c->ms_d2h = 0;
+    long long cut = n;                                                  // complete lines only, unless the input ends here
+    if (!last) {
+        const void* nl = n > 0 ? memrchr(bytes, '\n', (size_t)n) : nullptr;
+        if (!nl) {
+            c->fed = true;                                              // nothing to render
+            if (n < c->budget) return CL_OK;                            // no complete line yet
+            c->err_line = c->lines + 1;
+            c->err_kind = CL_CONV_E_LONG;
+            return fail(CL_ERR_PARSE, "cl_conv_feed: a line longer than the chunk budget");
+        }
+        cut = (const char*)nl - bytes + 1;
+    }
+    if (cut == 0) { c->fed = true; return CL_OK; }
+    HIP_TRY(hipSetDevice(c->device));
+    long long used = 0, L = 0;
+    int bad = INT_MAX;
+    int rc = conv_feed(c, bytes, cut, &used, &bad, &L);
+    if (rc != CL_OK) {
+        (void)hipStreamSynchronize(c->stream);                          // no copy from `bytes` may still be pending
+        return rc;
+    }
+    const long long R = bad < L ? bad : L;
+    long long total = 0;
+    if (R > 0 && (rc = conv_read(c, &total, c->end.as<long long>() + (R - 1)))) return rc;
+    u32 flags = 0;
+    if (bad < L && (rc = conv_read(c, &flags, (const char*)c->rec.p + (size_t)bad * sizeof(K15Rec) + offsetof(K15Rec, flags)))) return rc;
+    (void)hipEventElapsedTime(&c->ms_h2d, c->ev[0], c->ev[1]);
+    (void)hipEventElapsedTime(&c->ms_feed, c->ev[1], c->ev[2]);
+    const long long first = c->lines;
+    c->lines += L;
+    c->fed = true;
+    c->R = R;
+    c->nbytes = total;
+    *consumed = used;
+    *n_lines = R;
+    *n_bytes = total;
+    if (bad < L) {
+        c->err_line = first + bad + 1;
+        c->err_kind = (int)(flags >> 8);
+        return fail(CL_ERR_PARSE, "cl_conv_feed: a line the reference's script would raise on (cl_conv_error)");
+    }
+    return CL_OK;
+}
+
+extern "C" int cl_conv_render(cl_conv* c, char* out, int64_t cap, int64_t* n_bytes)
+{
+    if (!c) return fail(CL_ERR_ARG, "null converter handle");
+    if (n_bytes) *n_bytes = 0;
+    if (!n_bytes || (!out && c->nbytes > 0)) return fail(CL_ERR_ARG, "cl_conv_render: bad arguments");
+    if (!c->fed) return fail(CL_ERR_ARG, "cl_conv_render: no feed to render");
+    if (cap < c->nbytes) return fail(CL_ERR_ARG, "cl_conv_render: capacity below the feed's bytes");
+    if (c->R == 0) return CL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->out.ensure((size_t)c->nbytes + 16))) return rc;
+    const unsigned grid = (unsigned)((c->R + K15_T - 1) / K15_T);
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+    if (c->fmt == CL_CONV_HICPRO)
+        hipLaunchKernelGGL(k15_render<CL_CONV_HICPRO>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),
+                           c->end.as<long long>(), c->R, c->out.as<char>());
+    else
+        hipLaunchKernelGGL(k15_render<CL_CONV_JUICER>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),
+                           c->end.as<long long>(), c->R, c->out.as<char>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[4], c->stream));
+    hipError_t e = hipMemcpyAsync(out, c->out.p, (size_t)c->nbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev[5], c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_conv_render: copy", hipGetErrorString(e != hipSuccess ? e : e2));
+    (void)hipEventElapsedTime(&c->ms_render, c->ev[3], c->ev[4]);
+    (void)hipEventElapsedTime(&c->ms_d2h, c->ev[4], c->ev[5]);
+    *n_bytes = c->nbytes;
+    return CL_OK;
+}
+
+extern "C" int cl_conv_error(cl_conv* c, int64_t* line, int32_t* kind)
+{
+    if (!c) return fail(CL_ERR_ARG, "null converter handle");
+    if (!line || !kind) return fail(CL_ERR_ARG, "cl_conv_error: bad arguments");
+    *line = c->err_line;
+    *kind = c->err_kind;
+    return CL_OK;
+}
+
+extern "C" int cl_conv_timing(cl_conv* c, float* ms)
+{
+    if (!c) return fail(CL_ERR_ARG, "null converter handle");
+    if (!ms) return fail(CL_ERR_ARG, "cl_conv_timing: bad arguments");
+    ms[0] = c->ms_h2d; ms[1] = c->ms_feed; ms[2] = c->ms_render; ms[3] = c->ms_d2h;
+    return CL_OK;
+}
+
+extern "C" int cl_conv_destroy(cl_conv* c)
+{
+    if (!c) return CL_OK;
+    conv_free(c);
+    return CL_OK;
+}

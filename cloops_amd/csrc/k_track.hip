@@ -1,6 +1,7 @@
 // k_track.hip -- K14: browser-track text of the PETs of a resident chromosome (cLoops/io.py jd2washU / jd2hic) rendered on the
 // device -- kernels and C entry points.
 #include "cl_chrom.h"
+#include "cl_text.h"
 
 // ==========================================================================================
 // K14: PET lines for the washU long-range track and for `juicer_tools pre` (cLoops/io.py:206-217, :292-348)
@@ -51,36 +52,6 @@ __device__ __forceinline__ int k14_lane_rank(u64 mask)                 // set bi
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
 }
 
-__device__ __forceinline__ u64 k14_mag(long long v) { return v < 0 ? 0ull - (u64)v : (u64)v; }
-
-__device__ __forceinline__ int k14_ndig(u64 m)                         // decimal digits of m (1 for 0)
-{
-    int d = 1;
-    u64 p = 10;
-#pragma unroll
-    for (int k = 1; k < 20; ++k) { d += m >= p ? 1 : 0; p = k < 19 ? p * 10 : p; }
-    return d;
-}
-
-__device__ __forceinline__ int k14_width(long long v) { return (v < 0 ? 1 : 0) + k14_ndig(k14_mag(v)); }
-
-// v in decimal at s[pos ..] -> the position after it
-__device__ __forceinline__ int k14_put(char* s, int pos, long long v)
-{
-    u64 m = k14_mag(v);
-    if (v < 0) s[pos++] = '-';
-    const int e = pos + k14_ndig(m);
-    int k = e - 1;
-    while (m >> 32) {                                                   // m / 10 by multiply-high (exact for every u64)
-        const u64 q = __umul64hi(m, 0xCCCCCCCCCCCCCCCDull) >> 3;
-        s[k--] = (char)('0' + (int)(m - q * 10));
-        m = q;
-    }
-    u32 w = (u32)m;
-    for (; k >= pos; --k) { s[k] = (char)('0' + (int)(w % 10)); w /= 10; }
-    return e;
-}
-
 __device__ __forceinline__ int k14_str(char* s, int pos, const char* t, int len)
 {
     for (int k = 0; k < len; ++k) s[pos + k] = t[k];
@@ -118,8 +89,8 @@ template <int KIND>
 __device__ __forceinline__ int k14_len(const K14Tpl& t, const K14F& f)
 {
     if (KIND == CL_TRACK_WASHU)                                       // a\ts\te\tb:ps-pe,1\tid\t.\n
-        return t.la + t.lb + 11 + k14_width(f.f0) + k14_width(f.f1) + k14_width(f.f2) + k14_width(f.f3) + k14_width(f.f4);
-    return t.la + t.lb + 12 + k14_width(f.f0) + k14_width(f.f1);       // 0\ta\tX\t0\t1\tb\tY\t1\n
+        return t.la + t.lb + 11 + cl_width(f.f0) + cl_width(f.f1) + cl_width(f.f2) + cl_width(f.f3) + cl_width(f.f4);
+    return t.la + t.lb + 12 + cl_width(f.f0) + cl_width(f.f1);       // 0\ta\tX\t0\t1\tb\tY\t1\n
 }
 
 __global__ void __launch_bounds__(TPB)
@@ -235,19 +206,19 @@ k14_render(K14Tpl t, long long r0, long long r1, long long b0, const long long* 
             const char* par = side ? nm : nm + K14_NAME_MAX;
             const int lo = side ? t.lb : t.la, lp = side ? t.la : t.lb;
             p = k14_str(buf, p, own, lo); buf[p++] = '\t';
-            p = k14_put(buf, p, f.f0); buf[p++] = '\t';
-            p = k14_put(buf, p, f.f1); buf[p++] = '\t';
+            p = cl_put(buf, p, f.f0); buf[p++] = '\t';
+            p = cl_put(buf, p, f.f1); buf[p++] = '\t';
             p = k14_str(buf, p, par, lp); buf[p++] = ':';
-            p = k14_put(buf, p, f.f2); buf[p++] = '-';
-            p = k14_put(buf, p, f.f3); buf[p++] = ','; buf[p++] = '1'; buf[p++] = '\t';
-            p = k14_put(buf, p, f.f4); buf[p++] = '\t'; buf[p++] = '.'; buf[p++] = '\n';
+            p = cl_put(buf, p, f.f2); buf[p++] = '-';
+            p = cl_put(buf, p, f.f3); buf[p++] = ','; buf[p++] = '1'; buf[p++] = '\t';
+            p = cl_put(buf, p, f.f4); buf[p++] = '\t'; buf[p++] = '.'; buf[p++] = '\n';
         } else {
             buf[p++] = '0'; buf[p++] = '\t';
             p = k14_str(buf, p, nm, t.la); buf[p++] = '\t';
-            p = k14_put(buf, p, f.f0);
+            p = cl_put(buf, p, f.f0);
             buf[p++] = '\t'; buf[p++] = '0'; buf[p++] = '\t'; buf[p++] = '1'; buf[p++] = '\t';
             p = k14_str(buf, p, nm + K14_NAME_MAX, t.lb); buf[p++] = '\t';
-            p = k14_put(buf, p, f.f1);
+            p = cl_put(buf, p, f.f1);
             buf[p++] = '\t'; buf[p++] = '1'; buf[p++] = '\n';
         }
     }

@@ -289,6 +289,58 @@ int cl_track_chunks(cl_chrom* c, int64_t budget, int64_t cap, int64_t* rec_bound
 int cl_track_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n_bytes);
 int cl_track_free(cl_chrom* c);
 
+/*
+ * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
+ * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
+ * chromosome: it is a handle of its own.
+ *
+ * cl_conv_create -- a converter on `device` for `format` (CL_CONV_HICPRO: HiC-Pro allValidPairs, fields split at '\t'
+ * after strip(), A = [f1, p1, p1 + ext] on "+" else [f1, p1 - ext, p1], B the same from f4 f5 f6, line
+ * `A B f0 . f3 f6`; CL_CONV_JUICER: Juicer "long" format, fields split at whitespace runs, line
+ * `f1 max(0, p1 - ext) p1 + ext f5 max(0, p2 - ext) p2 + ext . . s1 s2`, s = "+" where f0 / f4 is "0"), on `stream` (NULL:
+ * a stream of its own), taking chunks of at most `budget` bytes (1 .. CL_CONV_BUDGET_MAX).  Errors: CL_ERR_NODEVICE
+ * without a device (there is no CPU path); CL_ERR_ARG for a NULL out, an unknown format or a budget out of range.
+ *
+ * cl_conv_feed -- converts the complete lines of bytes[0 .. n) (n <= budget; page-locked memory from cl_host_alloc copies
+ * fastest): with last == 0 the bytes after the last '\n' are left over (*consumed stops there) and go in front of the
+ * next feed; with last != 0 the input ends here and its last line may lack the '\n'.  A feed may also stop early on very
+ * short lines (at most budget / 16 + 256 lines per feed): the caller feeds bytes[*consumed ..] again.  *n_lines /
+ * *n_bytes: the lines converted and the bytes of their text, for cl_conv_render.  Reading rules: lines end at '\n' only,
+ * whitespace is ASCII \t \n \v \f \r and space, an integer is an optional sign and ASCII digits with optional whitespace
+ * around it, and must fit int64 with +-ext applied.  CL_ERR_PARSE: a line the reference would raise on (fewer than 7
+ * fields, a bad integer, a blank line), a value out of int64, or (last == 0) n == budget bytes with no '\n'; the lines in
+ * front of it are converted and counted, cl_conv_error tells which line and why.  Errors: CL_ERR_ARG for NULL outputs,
+ * n < 0 or n > budget.
+ *
+ * cl_conv_render -- the text of the last feed's lines into host memory `out` (cap >= *n_bytes of that feed);
+ * *n_bytes = its length.  Errors: CL_ERR_ARG for no feed since creation, or cap too small.
+ *
+ * cl_conv_error -- the last feed's error: *line counts every line fed to this handle (1-based), *kind is one of
+ * CL_CONV_E_* (0: none).
+ *
+ * cl_conv_timing -- device times of the last feed and render, in ms: ms[0] copy to the device, ms[1] the feed's kernels
+ * (the index, parse and scan, with one read-back of the line count between them), ms[2] the render kernel, ms[3] the
+ * copy to the host.
+ *
+ * cl_conv_destroy -- waits for the handle's stream and frees the handle.
+ */
+typedef struct cl_conv cl_conv;
+#define CL_ERR_PARSE        -8   /* cl_conv_feed: a line the reference's script would raise on (cl_conv_error)   */
+#define CL_CONV_HICPRO       0
+#define CL_CONV_JUICER       1
+#define CL_CONV_E_FIELDS     1   /* fewer than 7 fields (a blank line included): the reference's IndexError      */
+#define CL_CONV_E_INT        2   /* a position that is not an integer: the reference's ValueError               */
+#define CL_CONV_E_RANGE      3   /* a position, or a position +- ext, outside int64                              */
+#define CL_CONV_E_LONG       4   /* a line longer than the chunk budget                                          */
+#define CL_CONV_BUDGET_MAX   (1LL << 30)
+int cl_conv_create(int device, void* stream, int32_t format, int64_t ext, int64_t budget, cl_conv** out);
+int cl_conv_feed(cl_conv* c, const char* bytes, int64_t n, int32_t last, int64_t* consumed, int64_t* n_lines,
+                 int64_t* n_bytes);
+int cl_conv_render(cl_conv* c, char* out, int64_t cap, int64_t* n_bytes);
+int cl_conv_error(cl_conv* c, int64_t* line, int32_t* kind);
+int cl_conv_timing(cl_conv* c, float* ms);
+int cl_conv_destroy(cl_conv* c);
+
 /* Device pointer to the labels of the last run (n int32, row aligned) -- lets the caller
  * keep results on the GPU (e.g. to hand them to RCCL) without a host round trip.  NULL if the run did not
  * produce row-aligned labels (see cl_set_device_labels). */
