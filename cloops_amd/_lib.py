@@ -30,6 +30,8 @@ SYMBOLS = [
     "cl_cluster", "cl_get_boxes", "cl_neighbor_counts", "cl_labels_device", "cl_set_profiling",
     "cl_get_timing", "cl_version", "cl_host_alloc", "cl_host_free", "cl_cluster_async", "cl_wait", "cl_boxes_host",
     "cl_dist_summary", "cl_dist_bin_hist", "cl_last_n_in", "cl_sig_counts", "cl_quant_counts", "cl_contact_hist", "cl_anchor_mask", "cl_track_build", "cl_track_chunks", "cl_track_render", "cl_track_free", "cl_conv_create", "cl_conv_feed", "cl_conv_render", "cl_conv_error", "cl_conv_timing", "cl_conv_destroy", "cl_cluster_weighted",
+    "cl_ingest_create", "cl_ingest_feed", "cl_ingest_names", "cl_ingest_commit", "cl_ingest_finish", "cl_ingest_rows", "cl_ingest_chrom_arrays",
+    "cl_ingest_distances", "cl_ingest_timing", "cl_ingest_destroy",
     "cl_set_layout_reuse", "cl_set_sort_index", "cl_set_device_labels", "cl_set_table_export", "cl_cand_reset", "cl_cand_append", "cl_cand_finish", "cl_cluster_step_async", "cl_step_result",
     "cl_set_count_reuse", "cl_set_count_floor", "cl_set_count_thresholds", "cl_set_eps_list", "cl_chrom_set_stream", "cl_last_region_mode", "cl_debug_arena_overcommit", "cl_chrom_subsample", "cl_stream_create", "cl_stream_destroy", "cl_set_traversal", "cl_cand_finish_device", "cl_cluster_pairs_async", "cl_cluster_rowmask_async", "cl_last_n_labelled", "cl_set_pairs_defer", "cl_pairs_sync", "cl_sweep_plan", "cl_chrom_drop_indexes",
 ]
@@ -46,6 +48,11 @@ class ClTiming(ctypes.Structure):
                 ("ms_d2h", ctypes.c_float), ("ms_total", ctypes.c_float), ("n_in", ctypes.c_int64),
                 ("n_strips", ctypes.c_int64), ("ms_bracket", ctypes.c_float), ("ms_band", ctypes.c_float),
                 ("n_queried", ctypes.c_int64)]
+
+
+class ClIngestName(ctypes.Structure):
+    _fields_ = [("hash", ctypes.c_uint64), ("first", ctypes.c_uint32), ("off", ctypes.c_uint32), ("len", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
 
 
 DIST_LOGBINS = 3840
@@ -163,6 +170,27 @@ def load():
     lib.cl_conv_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.cl_conv_destroy.restype = ctypes.c_int
     lib.cl_conv_destroy.argtypes = [vp]
+    lib.cl_ingest_create.restype = ctypes.c_int
+    lib.cl_ingest_create.argtypes = [ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(vp)]
+    lib.cl_ingest_feed.restype = ctypes.c_int
+    lib.cl_ingest_feed.argtypes = [vp, vp, ctypes.c_int64, i64p, i64p, i64p]
+    lib.cl_ingest_names.restype = ctypes.c_int
+    lib.cl_ingest_names.argtypes = [vp, vp, ctypes.c_int64, i64p]
+    lib.cl_ingest_commit.restype = ctypes.c_int
+    lib.cl_ingest_commit.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32,
+                                     vp, i32p]
+    lib.cl_ingest_finish.restype = ctypes.c_int
+    lib.cl_ingest_finish.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, i64p]
+    lib.cl_ingest_rows.restype = ctypes.c_int
+    lib.cl_ingest_rows.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int64]
+    lib.cl_ingest_chrom_arrays.restype = ctypes.c_int
+    lib.cl_ingest_chrom_arrays.argtypes = [vp, ctypes.c_int32, i64p, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.cl_ingest_distances.restype = ctypes.c_int
+    lib.cl_ingest_distances.argtypes = [vp, vp, ctypes.c_int64]
+    lib.cl_ingest_timing.restype = ctypes.c_int
+    lib.cl_ingest_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.cl_ingest_destroy.restype = ctypes.c_int
+    lib.cl_ingest_destroy.argtypes = [vp]
     lib.cl_last_n_in.restype = ctypes.c_int64
     lib.cl_last_n_in.argtypes = [vp]
     lib.cl_get_boxes.restype = ctypes.c_int

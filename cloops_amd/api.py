@@ -646,3 +646,96 @@ class Converter(object):
             self.close()
         except Exception:                                               # noqa: BLE001
             pass
+
+
+class Ingest(object):
+    """K16: a BEDPE reader on the device (cl_ingest of include/cloops_hip.h), shaped like Converter: feed a chunk of complete lines,
+    read its distinct chromosome names, commit the host's table for them; finish joins two handles and leaves every chromosome's
+    mid-points in HBM."""
+    TIMES = ("h2d", "index", "parse", "names", "commit", "finish")
+    BUDGET = 64 << 20                              # default bytes per chunk
+
+    def __init__(self, budget=BUDGET, cut=0, want_distances=False, device=0, stream=None):
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p()
+        self.device, self.budget = int(device), int(budget)
+        _lib.check(self._lib.cl_ingest_create(int(device), ctypes.c_void_p(stream), self.budget, int(cut), int(bool(want_distances)),
+                                              ctypes.byref(self._h)))
+
+    def feed(self, ptr, n):
+        """the n bytes of complete lines at host address `ptr` -> (lines, first exotic line or -1, distinct names or -1 for too
+        many)  (cl_ingest_feed)"""
+        nl, ex, nn = ctypes.c_int64(0), ctypes.c_int64(-1), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_ingest_feed(self._h, ctypes.c_void_p(ptr), int(n), ctypes.byref(nl), ctypes.byref(ex), ctypes.byref(nn)))
+        return int(nl.value), int(ex.value), int(nn.value)
+
+    def names(self, n):
+        """the last feed's distinct names -> [(hash, first line, offset, length)], by first line  (cl_ingest_names)"""
+        if n <= 0:
+            return []
+        arr = (_lib.ClIngestName * n)()
+        got = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_ingest_names(self._h, arr, n, ctypes.byref(got)))
+        return sorted(((int(e.hash), int(e.first), int(e.off), int(e.len)) for e in arr[:got.value]), key=lambda t: t[1])
+
+    def commit(self, chunk, line0, table, n_ids):
+        """the host's answer for the last feed: table = [(hash, id or -1, name bytes)] -> (PETs appended per id, status)
+        (cl_ingest_commit)"""
+        table = sorted(table)
+        nt = len(table)
+        hashes = np.array([t[0] for t in table], dtype=np.uint64)
+        ids = np.array([t[1] for t in table], dtype=np.int32)
+        lens = np.array([len(t[2]) for t in table], dtype=np.uint32)
+        offs = np.zeros(nt, dtype=np.uint32)
+        if nt:
+            offs[1:] = np.cumsum(lens[:-1])
+        blob = b"".join(t[2] for t in table)
+        counts = np.zeros(max(n_ids, 1), dtype=np.int64)
+        status = ctypes.c_int32(0)
+        vp = ctypes.c_void_p
+        _lib.check(self._lib.cl_ingest_commit(self._h, int(chunk), int(line0), hashes.ctypes.data_as(vp), ids.ctypes.data_as(vp),
+                                              offs.ctypes.data_as(vp), lens.ctypes.data_as(vp), nt, ctypes.c_char_p(blob), len(blob), int(n_ids),
+                                              counts.ctypes.data_as(vp), ctypes.byref(status)))
+        return counts[:n_ids], int(status.value)
+
+    def finish(self, other, n_ids, unique):
+        """-> (rows per id, number of distances)  (cl_ingest_finish)"""
+        rows = np.zeros(max(n_ids, 1), dtype=np.int64)
+        nd = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_ingest_finish(self._h, other._h if other is not None else None, int(n_ids), int(bool(unique)),
+                                              rows.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nd)))
+        return rows[:n_ids], int(nd.value)
+
+    def rows(self, cid, n):
+        """the int64 mid-points (cA, cB) of chromosome `cid`  (cl_ingest_rows)"""
+        a, b = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+        _lib.check(self._lib.cl_ingest_rows(self._h, int(cid), a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p), n))
+        return a, b
+
+    def chrom_arrays(self, cid):
+        """-> (n, device address of X, of Y): int32 arrays that live as long as this object  (cl_ingest_chrom_arrays)"""
+        n, x, y = ctypes.c_int64(0), ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(self._lib.cl_ingest_chrom_arrays(self._h, int(cid), ctypes.byref(n), ctypes.byref(x), ctypes.byref(y)))
+        return int(n.value), x.value, y.value
+
+    def distances(self, n):
+        out = np.empty(n, dtype=np.int64)
+        _lib.check(self._lib.cl_ingest_distances(self._h, out.ctypes.data_as(ctypes.c_void_p), n))
+        return out
+
+    def timing(self):
+        """device ms summed over this handle's calls  (cl_ingest_timing)"""
+        ms = (ctypes.c_float * len(self.TIMES))()
+        _lib.check(self._lib.cl_ingest_timing(self._h, ms))
+        return dict(zip(self.TIMES, ms))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.cl_ingest_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                               # noqa: BLE001
+            pass

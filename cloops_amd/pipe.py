@@ -12,6 +12,7 @@ What differs is where the work happens:
   * `runDBSCAN` spreads chromosomes over the visible GPUs (one host thread per GPU) instead
     of joblib worker processes (pipe.py:117).
 """
+import itertools
 import os
 import sys
 import threading
@@ -118,11 +119,15 @@ class _StreamPool(object):
 STREAMS = _StreamPool()
 
 
-def _make_chrom(X, Y, device):
-    """a resident chromosome on one of the device's shared streams (its close() also gives the stream's slot back) -> chromosome"""
+def _make_chrom(X, Y, device, make=None):
+    """a resident chromosome on one of the device's shared streams (its close() also gives the stream's slot back) -> chromosome.
+    `make(stream)` builds the handle from arrays that are on the device already (cloops_amd.ingest) instead of uploading X, Y"""
     stream, slot = STREAMS.pick(device, len(X))
     try:
-        ch = api.Chromosome(X, Y, device=device, stream=stream) if stream else api.Chromosome(X, Y, device=device)
+        if make is not None:
+            ch = make(stream)
+        else:
+            ch = api.Chromosome(X, Y, device=device, stream=stream) if stream else api.Chromosome(X, Y, device=device)
     except Exception:
         _StreamPool.release(slot, len(X))
         raise
@@ -222,12 +227,13 @@ class ChromCache(object):
                 return False
         return _Pinned()
 
-    def put_arrays(self, name, X, Y, device=0, ids=None):
+    def put_arrays(self, name, X, Y, device=0, ids=None, key=None):
         """Register an in-memory chromosome under the pseudo path 'mem://<chrA>-<chrB>' (no .jd
-        file, no disk): what a direct BEDPE -> HBM loader hands to the sweep."""
+        file, no disk): what a direct BEDPE -> HBM loader hands to the sweep.  `key`: the pair of chromosome names when `name`
+        does not spell it (a prefix, a '-' inside a name)."""
         f = "mem://" + name
         r = _Resident()
-        r.key = tuple(name.split("-")) if "-" in name else (name, name)
+        r.key = tuple(key) if key is not None else (tuple(name.split("-")) if "-" in name else (name, name))
         r.stamp, r.device = ("mem", len(X)), device
         r.lock = threading.Lock()
         r.sweep_lock = threading.Lock()
@@ -935,15 +941,41 @@ MODES = {1: ([500, 1000, 2000], [5], 0), 2: ([1000, 2000, 5000], [5], 0),
          3: ([5000, 7500, 10000], [50, 40, 30, 20], 1), 4: ([2500, 5000, 7500, 10000], [30, 20], 1)}   # pipe.py:329-344
 
 
+_PIPE_RUNS = itertools.count()
+
+
+def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp):
+    """the input through the GPU reader (cloops_amd.ingest.load_bedpe): -> ('mem://' names, distances or None); with `tmp` the
+    `.jd` files of the host reader are written from the host copies"""
+    from . import ingest
+    ds = [] if auto_eps else None
+    cfs = ingest.load_bedpe(fs, chroms, cut, unique=auto_eps, strand_distances=ds, prefix="pipe-%d-%d" % (os.getpid(), next(_PIPE_RUNS)))
+    if tmp:
+        import joblib
+        try:
+            for f in cfs:
+                r = CACHE.get(f)
+                joblib.dump(ingest.rows_matrix(r.X, r.Y), os.path.join(fout, "%s-%s.jd" % r.key))
+        except BaseException:
+            for f in cfs:
+                CACHE.drop(f)
+            raise
+    return cfs, ds
+
+
 def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0, cut=0, plot=0, max_cut=False,
-         log=None):
+         log=None, reader="gpu"):
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
     Differences to the reference, all outside the hot path: no plots (`plot` is accepted and ignored).  `washU` /
     `juice` write `<fout>_loops_washU.txt` / `<fout>_loops_juicebox.txt` after `<fout>.loop` (pipe.py:288-292, cloops_amd.tracks).
-    `eps == 0` estimates eps from the distances of the PETs mapped to different strands (io.py:62-129, ests.py:23-33)."""
+    `eps == 0` estimates eps from the distances of the PETs mapped to different strands (io.py:62-129, ests.py:23-33).
+    `reader`: "gpu" reads the BEDPE files on the device (K16, cloops_amd.ingest): the chromosomes go from the text to HBM
+    without `.jd` files, which are written only with `tmp`; "host" is cloops_amd.io's Python loop and its `.jd` files."""
     import shutil
+    if reader not in ("gpu", "host"):
+        raise ValueError("reader must be 'gpu' or 'host', got %r" % (reader,))
     from . import io as cio
     from . import cModel
     if chroms == "":
@@ -955,16 +987,26 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
             log("working directory %s exists, return." % fout)
         return
     os.mkdir(fout)
-    if eps == 0 or eps == [0]:                                # pipe.py:231-239: eps from the data
-        from .ests import estFragSize
-        cfs, ds = cio.parseRawBedpe(fs, fout, chroms, cut)
-        cfs = [cio.txt2jd(f) for f in cfs]
-        eps = [estFragSize(ds) * 2]
-    else:
-        cfs = [cio.txt2jd(f) for f in cio.parseRawBedpe2(fs, fout, chroms, cut)]
-    dataI, cut, cuts, steps = runSweepFast(cfs, eps, minPts, cut=cut, max_cut=max_cut, log=log)
-    records = {key: {"f": v["f"], "records": _records(key, v["boxes"])} for key, v in dataI.items()}
-    e = cModel.runStat(records, minPts, 0, cpu, fout, hic)    # pipe.py:284 passes cut = 0
+    auto_eps = eps == 0 or eps == [0]                         # pipe.py:231-239: eps from the data
+    mem = []
+    try:
+        if reader == "gpu":
+            cfs, ds = _read_gpu(fs, fout, chroms, cut, auto_eps, tmp)
+            mem = cfs
+        elif auto_eps:
+            cfs, ds = cio.parseRawBedpe(fs, fout, chroms, cut)
+            cfs = [cio.txt2jd(f) for f in cfs]
+        else:
+            cfs = [cio.txt2jd(f) for f in cio.parseRawBedpe2(fs, fout, chroms, cut)]
+        if auto_eps:
+            from .ests import estFragSize
+            eps = [estFragSize(ds) * 2]
+        dataI, cut, cuts, steps = runSweepFast(cfs, eps, minPts, cut=cut, max_cut=max_cut, log=log)
+        records = {key: {"f": v["f"], "records": _records(key, v["boxes"])} for key, v in dataI.items()}
+        e = cModel.runStat(records, minPts, 0, cpu, fout, hic)    # pipe.py:284 passes cut = 0
+    finally:
+        for f in mem:                                         # 'mem://' residents are never evicted by age
+            CACHE.drop(f)
     if e:
         shutil.rmtree(fout)
         return
@@ -998,6 +1040,7 @@ def main(argv=None):
     ap.add_argument("-cut", dest="cut", type=int, default=0)
     ap.add_argument("-plot", dest="plot", action="store_true")
     ap.add_argument("-max_cut", dest="max_cut", action="store_true")
+    ap.add_argument("-reader", dest="reader", default="gpu", choices=["host", "gpu"])
     op = ap.parse_args(argv)
     if op.mode == 0:                                          # pipe.py:306-327
         eps = sorted(int(x) for x in str(op.eps).split(","))
@@ -1010,5 +1053,5 @@ def main(argv=None):
         eps, minPts, hic = MODES[op.mode]
     sys.stderr.write("mode:%s\t eps:%s\t minPts:%s\t hic:%s\t\n" % (op.mode, eps, minPts, hic))
     pipe(op.fnIn.split(","), op.fnOut, eps, minPts, op.chroms, op.cpu, op.tmp, hic, op.washU, op.juice, op.cut,
-         op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"))
+         op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader)
     return 0

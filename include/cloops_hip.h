@@ -341,6 +341,77 @@ int cl_conv_error(cl_conv* c, int64_t* line, int32_t* kind);
 int cl_conv_timing(cl_conv* c, float* ms);
 int cl_conv_destroy(cl_conv* c);
 
+/*
+ * BEDPE input (K16): the per-line loops of cLoops/io.py:62-129 (parseRawBedpe) and :132-189 (parseRawBedpe2) with the PET
+ * rule of :30-59 (class PET), one chunk of BEDPE text at a time; the PETs stay on the device, grouped by chromosome in
+ * file order, ready for cl_chrom_create(..., on_device = 1).  The host reads (or inflates) the bytes and keeps the
+ * dictionary chromosome name -> id; it never touches a PET.  A handle works on one stream; two handles on two streams
+ * take the chunks in turn (chunk k on handle k % 2) and cl_ingest_finish joins them.
+ *
+ * Reading rules (cloops_amd/io.py:parse_bedpe under Python 3's text mode): a line ends at '\n', "\r\n" counts as '\n';
+ * fields split at '\t' only; a line is skipped when a field is exactly "*" and a field is exactly "-1" (io.py:84-85,
+ * :159-160), when it has fewer than 10 fields (:43, :47 read the strands), when field 1, 2, 4 or 5 is no integer (:87-93,
+ * :162-166), when fields 0 and 3 differ (:96, :168) or when cB - cA < cut for cut > 0 (:103-104, :174-175); the ends are
+ * swapped when startA + endA > startB + endB (:50-53); cA, cB are the floors of the half sums (:55-56).  An integer is
+ * [+-]?[0-9]+ with |value| < 2^62; a field of bytes 0x21 .. 0x7e without '_' that is not one makes the line skipped; any
+ * other numeric field, a byte >= 0x80, a '\r' not followed by '\n' or a chromosome name longer than 255 bytes makes the
+ * line EXOTIC: the device does not restate what Python's int() and text decoding do with it, the caller reads the files on the host.
+ *
+ * cl_ingest_create -- a reader on `device` and `stream` (NULL: a stream of its own) for chunks of at most `budget` bytes
+ * (1 .. CL_CONV_BUDGET_MAX), with the distance filter `cut` (io.py:103, :174); want_distances != 0 keeps what
+ * cl_ingest_distances needs (io.py:122-123).  Errors: CL_ERR_NODEVICE without a device (there is no CPU path); CL_ERR_ARG.
+ *
+ * cl_ingest_feed -- the loop bodies of io.py:80-105 / :155-176 for the n bytes of complete lines at `bytes` (n <= budget;
+ * only the last line may lack its '\n'; page-locked memory copies fastest): *n_lines = the lines of the chunk (blank ones
+ * count, io.py:82, :157), *first_exotic = the first exotic line of the chunk (0-based) or -1, *n_names = the distinct
+ * chromosome names of the kept lines, or -1 when they are more than 65536 (the caller reads the files on the host).
+ *
+ * cl_ingest_names -- the distinct names of the last feed, one entry each: the name's 64-bit hash, the first line it
+ * occurs on and where its bytes are in the chunk (any order; what is copied is sized by the names, not by the lines).
+ *
+ * cl_ingest_commit -- io.py:98-99 / :171-172 (the wanted chromosomes) and :106-121 / :177-185 (the PET appended to its
+ * chromosome): the host's table for the last feed -- `hashes` ascending, ids[k] the chromosome id (0 .. n_ids - 1) of
+ * hashes[k] or -1 to drop it, its name at names[name_off[k] .. + name_len[k]) -- is applied to every kept line and the
+ * PETs are appended to their chromosomes in line order; `chunk` orders the chunks of all handles, `line0` is the global
+ * number of the chunk's first line.  counts[id] = the PETs appended per chromosome.  *status: 0; 1 when a line's name
+ * differs from the dictionary's bytes under the same hash, 2 when a hash is missing from the table -- nothing is
+ * appended then (two names with one hash never merge).
+ *
+ * cl_ingest_finish -- ends the read on `c` and on `other` (the second handle or NULL; its chunks move to `c`): per
+ * chromosome id the chunks' PETs become one array each in file order; unique != 0 drops every PET whose (cA, cB)
+ * occurred earlier on its chromosome (io.py:113-116); n_rows[id] = the PETs left, *n_distances = the kept PETs whose
+ * strand fields differ (io.py:122-123).  After it only the calls below and cl_ingest_destroy are allowed on `c`, only
+ * cl_ingest_destroy on `other`.
+ *
+ * cl_ingest_rows -- the int64 mid-points of chromosome `id` into host arrays a, b of cap >= n_rows[id] values.
+ * cl_ingest_chrom_arrays -- *x, *y: int32 device arrays of *n mid-points for cl_chrom_create(..., on_device = 1); they
+ * live until cl_ingest_destroy.  CL_ERR_DOMAIN when a value is outside |v| < 2^29 (what cl_chrom_create requires).
+ * cl_ingest_distances -- cB - cA of the PETs counted by *n_distances, in global line order (io.py:122-123), into `out`.
+ *
+ * cl_ingest_timing -- device times summed over the handle's calls, in ms: ms[0] copies to the device, ms[1] the line
+ * index, ms[2] the parse kernel, ms[3] the names table, ms[4] commit (apply, sort, gather), ms[5] finish.
+ *
+ * cl_ingest_destroy -- waits for the handle's stream and frees the handle and every array it handed out.
+ */
+typedef struct cl_ingest cl_ingest;
+typedef struct cl_ingest_name {
+    uint64_t hash;
+    uint32_t first, off, len, pad;
+} cl_ingest_name;
+#define CL_INGEST_TIMES 6
+int cl_ingest_create(int device, void* stream, int64_t budget, int64_t cut, int32_t want_distances, cl_ingest** out);
+int cl_ingest_feed(cl_ingest* c, const char* bytes, int64_t n, int64_t* n_lines, int64_t* first_exotic, int64_t* n_names);
+int cl_ingest_names(cl_ingest* c, cl_ingest_name* out, int64_t cap, int64_t* n);
+int cl_ingest_commit(cl_ingest* c, int64_t chunk, int64_t line0, const uint64_t* hashes, const int32_t* ids,
+                     const uint32_t* name_off, const uint32_t* name_len, int32_t n_table, const char* names,
+                     int64_t names_bytes, int32_t n_ids, int64_t* counts, int32_t* status);
+int cl_ingest_finish(cl_ingest* c, cl_ingest* other, int32_t n_ids, int32_t unique, int64_t* n_rows, int64_t* n_distances);
+int cl_ingest_rows(cl_ingest* c, int32_t id, int64_t* a, int64_t* b, int64_t cap);
+int cl_ingest_chrom_arrays(cl_ingest* c, int32_t id, int64_t* n, void** x, void** y);
+int cl_ingest_distances(cl_ingest* c, int64_t* out, int64_t cap);
+int cl_ingest_timing(cl_ingest* c, float* ms);
+int cl_ingest_destroy(cl_ingest* c);
+
 /* Device pointer to the labels of the last run (n int32, row aligned) -- lets the caller
  * keep results on the GPU (e.g. to hand them to RCCL) without a host round trip.  NULL if the run did not
  * produce row-aligned labels (see cl_set_device_labels). */
