@@ -24,17 +24,14 @@ VARIANT_CDBSCAN1 = 1
 VARIANT_CDBSCAN2 = 2
 VARIANT_BLOCK = 3
 
-# every symbol include/cloops_hip.h declares (tests check the .so exports all of them)
-SYMBOLS = [
-    "cl_last_error", "cl_device_count", "cl_chrom_create", "cl_chrom_destroy", "cl_chrom_size",
-    "cl_cluster", "cl_get_boxes", "cl_neighbor_counts", "cl_labels_device", "cl_set_profiling",
-    "cl_get_timing", "cl_version", "cl_host_alloc", "cl_host_free", "cl_cluster_async", "cl_wait", "cl_boxes_host",
-    "cl_dist_summary", "cl_dist_bin_hist", "cl_last_n_in", "cl_sig_counts", "cl_quant_counts", "cl_contact_hist", "cl_anchor_mask", "cl_track_build", "cl_track_chunks", "cl_track_render", "cl_track_free", "cl_conv_create", "cl_conv_feed", "cl_conv_render", "cl_conv_error", "cl_conv_timing", "cl_conv_destroy", "cl_cluster_weighted",
-    "cl_ingest_create", "cl_ingest_feed", "cl_ingest_names", "cl_ingest_commit", "cl_ingest_finish", "cl_ingest_rows", "cl_ingest_chrom_arrays",
-    "cl_ingest_distances", "cl_ingest_timing", "cl_ingest_destroy",
-    "cl_set_layout_reuse", "cl_set_sort_index", "cl_set_device_labels", "cl_set_table_export", "cl_cand_reset", "cl_cand_append", "cl_cand_finish", "cl_cluster_step_async", "cl_step_result",
-    "cl_set_count_reuse", "cl_set_count_floor", "cl_set_count_thresholds", "cl_set_eps_list", "cl_chrom_set_stream", "cl_last_region_mode", "cl_debug_arena_overcommit", "cl_chrom_subsample", "cl_stream_create", "cl_stream_destroy", "cl_set_traversal", "cl_cand_finish_device", "cl_cluster_pairs_async", "cl_cluster_rowmask_async", "cl_last_n_labelled", "cl_set_pairs_defer", "cl_pairs_sync", "cl_sweep_plan", "cl_chrom_drop_indexes",
-]
+# the other integer #defines of include/cloops_hip.h that the host side restates: this is their one home (tests/test_abi.py
+# compares every one with the header)
+CL_TRACK_WASHU, CL_TRACK_JUICE = 0, 1
+CL_TRACK_NAME_MAX = 64
+CL_CONV_HICPRO, CL_CONV_JUICER = 0, 1
+CL_CONV_E_FIELDS, CL_CONV_E_INT, CL_CONV_E_RANGE, CL_CONV_E_LONG = 1, 2, 3, 4
+CL_INGEST_TIMES = 6
+DIST_LOGBINS = 3840          # CL_DIST_LOGBINS
 
 
 class ClBox(ctypes.Structure):
@@ -55,13 +52,101 @@ class ClIngestName(ctypes.Structure):
                 ("pad", ctypes.c_uint32)]
 
 
-DIST_LOGBINS = 3840
-
-
 class ClDsummary(ctypes.Structure):
     _fields_ = [("n_all", ctypes.c_int64 * 2), ("n_pos", ctypes.c_int64 * 2), ("sumx", ctypes.c_double * 2),
                 ("sumxx", ctypes.c_double * 2), ("xshift", ctypes.c_double), ("loghist", ctypes.c_uint64 * DIST_LOGBINS),
                 ("fine_lo", ctypes.c_int64), ("fine", ctypes.c_uint64 * 2048)]
+
+
+_int, _i32, _u32, _i64, _vp, _cp = ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p
+_i32p, _i64p, _u64p, _f32p, _vpp = (ctypes.POINTER(t) for t in (_i32, _i64, ctypes.c_uint64, ctypes.c_float, _vp))
+
+# The C ABI of include/cloops_hip.h, one line per function: name -> (restype, argtypes).  load() applies it once; tests/test_abi.py
+# checks every entry, the structs above and the constants against the header.
+PROTOTYPES = {
+    "cl_last_error": (_cp, []),
+    "cl_device_count": (_int, []),
+    "cl_version": (_int, []),
+    "cl_chrom_create": (_int, [_int, _vp, _vp, _vp, _i64, _int, _vpp]),
+    "cl_chrom_destroy": (None, [_vp]),
+    "cl_chrom_size": (_i64, [_vp]),
+    "cl_chrom_subsample": (_int, [_vp, _vp, _i64, _vpp]),
+    "cl_chrom_set_stream": (_int, [_vp, _vp]),
+    "cl_chrom_drop_indexes": (_int, [_vp]),
+    "cl_cluster": (_int, [_vp, _int, _i32, _i32, _i32, _vp, _i32p, _i32p]),
+    "cl_cluster_weighted": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32p, _i32p]),
+    "cl_cluster_async": (_int, [_vp, _int, _i32, _i32, _i32, _vp]),
+    "cl_cluster_pairs_async": (_int, [_vp, _int, _i32, _i32, _i32, _vp, _i64]),
+    "cl_cluster_rowmask_async": (_int, [_vp, _int, _i32, _i32, _i32, _vp, _i64]),
+    "cl_cluster_step_async": (_int, [_vp, _int, _i32, _i32, _i32, _i32, _i64]),
+    "cl_wait": (_int, [_vp, _i32p, _i32p]),
+    "cl_step_result": (_int, [_vp, _i64p, _i64p, ctypes.POINTER(ClDsummary)]),
+    "cl_set_pairs_defer": (None, [_vp, _int]),
+    "cl_pairs_sync": (_int, [_vp]),
+    "cl_last_n_labelled": (_i64, [_vp]),
+    "cl_last_n_in": (_i64, [_vp]),
+    "cl_last_region_mode": (_int, [_vp]),
+    "cl_get_boxes": (_int, [_vp, _vp]),
+    "cl_boxes_host": (_vp, [_vp]),
+    "cl_labels_device": (_vp, [_vp]),
+    "cl_neighbor_counts": (_int, [_vp, _i32, _i32, _vp]),
+    "cl_dist_summary": (_int, [_vp, _i32, ctypes.POINTER(ClDsummary)]),
+    "cl_dist_bin_hist": (_int, [_vp, _i32, _u32, _u32, _int, _u64p]),
+    "cl_sig_counts": (_int, [_vp, _i32, _i32, _vp, _vp, _i64p]),
+    "cl_quant_counts": (_int, [_vp, _i32, _i32, _vp, _vp, _i64p]),
+    "cl_contact_hist": (_int, [_vp, _i32, _i32, _i64, _vp, _vp, _i64p, _i64p, _i64p, _i32p]),
+    "cl_anchor_mask": (_int, [_vp, _i64, _vp, _vp, _vp, _i64p, _i64p]),
+    "cl_track_build": (_int, [_vp, _i32, _i64, _i64, _vp, _cp, _cp, _i64p, _i64p]),
+    "cl_track_chunks": (_int, [_vp, _i64, _i64, _vp, _vp, _i64p]),
+    "cl_track_render": (_int, [_vp, _i64, _vp, _i64, _i64p]),
+    "cl_track_free": (_int, [_vp]),
+    "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
+    "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
+    "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),
+    "cl_conv_error": (_int, [_vp, _i64p, _i32p]),
+    "cl_conv_timing": (_int, [_vp, _f32p]),
+    "cl_conv_destroy": (_int, [_vp]),
+    "cl_ingest_create": (_int, [_int, _vp, _i64, _i64, _i32, _vpp]),
+    "cl_ingest_feed": (_int, [_vp, _vp, _i64, _i64p, _i64p, _i64p]),
+    "cl_ingest_names": (_int, [_vp, _vp, _i64, _i64p]),
+    "cl_ingest_commit": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32p]),
+    "cl_ingest_finish": (_int, [_vp, _vp, _i32, _i32, _vp, _i64p]),
+    "cl_ingest_rows": (_int, [_vp, _i32, _vp, _vp, _i64]),
+    "cl_ingest_chrom_arrays": (_int, [_vp, _i32, _i64p, _vpp, _vpp]),
+    "cl_ingest_distances": (_int, [_vp, _vp, _i64]),
+    "cl_ingest_timing": (_int, [_vp, _f32p]),
+    "cl_ingest_destroy": (_int, [_vp]),
+    "cl_cand_reset": (_int, [_vp]),
+    "cl_cand_append": (_int, [_vp, _i32, _i64p, _i64p]),
+    "cl_cand_finish": (_int, [_vp, _i32, _vp, _i64, _i64p]),
+    "cl_cand_finish_device": (_int, [_vp, _i32, _vpp, _i64p]),
+    "cl_set_table_export": (None, [_vp, _int]),
+    "cl_set_device_labels": (None, [_vp, _int]),
+    "cl_set_profiling": (None, [_vp, _int]),
+    "cl_get_timing": (_int, [_vp, ctypes.POINTER(ClTiming)]),
+    "cl_sweep_plan": (_int, [_vp, _i32p, _i32, _i32p, _i32]),
+    "cl_set_layout_reuse": (None, [_vp, _int]),
+    "cl_set_sort_index": (None, [_vp, _int]),
+    "cl_set_count_reuse": (None, [_vp, _int]),
+    "cl_set_count_floor": (None, [_vp, _i32]),
+    "cl_set_count_thresholds": (None, [_vp, _i32p, _i32]),
+    "cl_set_eps_list": (None, [_vp, _i32p, _i32]),
+    "cl_set_traversal": (None, [_vp, _int]),
+    "cl_stream_create": (_vp, [_int]),
+    "cl_stream_destroy": (None, [_vp]),
+    "cl_host_alloc": (_vp, [_i64]),
+    "cl_host_free": (None, [_vp]),
+    "cl_debug_arena_overcommit": (None, [_i64]),
+}
+SYMBOLS = list(PROTOTYPES)
+
+
+def bind(lib, table):
+    """state the prototypes of `table` (name -> (restype, argtypes)) on a loaded library -> the library"""
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
 
 
 class CloopsHipError(RuntimeError):
@@ -87,159 +172,27 @@ def load():
         raise ImportError(
             "libcloops_hip.so is missing (%s). Build it with `python -m cloops_amd.build` "
             "(needs hipcc); there is no CPU fallback." % path)
-    lib = ctypes.CDLL(path)
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    vp = ctypes.c_void_p
-    lib.cl_last_error.restype = ctypes.c_char_p
-    lib.cl_last_error.argtypes = []
-    lib.cl_device_count.restype = ctypes.c_int
-    lib.cl_version.restype = ctypes.c_int
-    lib.cl_chrom_create.restype = ctypes.c_int
-    lib.cl_chrom_create.argtypes = [ctypes.c_int, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(vp)]
-    lib.cl_chrom_destroy.restype = None
-    lib.cl_chrom_destroy.argtypes = [vp]
-    lib.cl_chrom_size.restype = ctypes.c_int64
-    lib.cl_chrom_size.argtypes = [vp]
-    lib.cl_cluster.restype = ctypes.c_int
-    lib.cl_cluster.argtypes = [vp, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, i32p, i32p]
-    lib.cl_cluster_weighted.restype = ctypes.c_int
-    lib.cl_cluster_weighted.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, i32p, i32p]
-    lib.cl_cluster_async.restype = ctypes.c_int
-    lib.cl_cluster_async.argtypes = [vp, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp]
-    lib.cl_wait.restype = ctypes.c_int
-    lib.cl_wait.argtypes = [vp, i32p, i32p]
-    lib.cl_boxes_host.restype = vp
-    lib.cl_boxes_host.argtypes = [vp]
-    lib.cl_dist_summary.restype = ctypes.c_int
-    lib.cl_dist_summary.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ClDsummary)]
-    lib.cl_dist_bin_hist.restype = ctypes.c_int
-    lib.cl_dist_bin_hist.argtypes = [vp, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-    lib.cl_set_device_labels.restype = None
-    lib.cl_set_device_labels.argtypes = [vp, ctypes.c_int]
-    lib.cl_set_table_export.restype = None
-    lib.cl_set_table_export.argtypes = [vp, ctypes.c_int]
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    lib.cl_cand_reset.restype = ctypes.c_int
-    lib.cl_cand_reset.argtypes = [vp]
-    lib.cl_cand_append.restype = ctypes.c_int
-    lib.cl_cand_append.argtypes = [vp, ctypes.c_int32, i64p, i64p]
-    lib.cl_cluster_step_async.restype = ctypes.c_int
-    lib.cl_cluster_step_async.argtypes = [vp, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
-    lib.cl_step_result.restype = ctypes.c_int
-    lib.cl_step_result.argtypes = [vp, i64p, i64p, ctypes.POINTER(ClDsummary)]
-    lib.cl_cand_finish.restype = ctypes.c_int
-    lib.cl_cand_finish.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int64, i64p]
-    lib.cl_cluster_pairs_async.restype = ctypes.c_int
-    lib.cl_cluster_pairs_async.argtypes = [vp, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64]
-    lib.cl_cluster_rowmask_async.restype = ctypes.c_int
-    lib.cl_cluster_rowmask_async.argtypes = [vp, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64]
-    lib.cl_set_pairs_defer.restype = None
-    lib.cl_set_pairs_defer.argtypes = [vp, ctypes.c_int]
-    lib.cl_pairs_sync.restype = ctypes.c_int
-    lib.cl_pairs_sync.argtypes = [vp]
-    lib.cl_last_n_labelled.restype = ctypes.c_int64
-    lib.cl_last_n_labelled.argtypes = [vp]
-    lib.cl_cand_finish_device.restype = ctypes.c_int
-    lib.cl_cand_finish_device.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(vp), i64p]
-    lib.cl_sig_counts.restype = ctypes.c_int
-    lib.cl_sig_counts.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int64)]
-    lib.cl_quant_counts.restype = ctypes.c_int
-    lib.cl_quant_counts.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int64)]
-    lib.cl_contact_hist.restype = ctypes.c_int
-    lib.cl_contact_hist.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, i64p, i64p, i64p,
-                                    ctypes.POINTER(ctypes.c_int32)]
-    lib.cl_anchor_mask.restype = ctypes.c_int
-    lib.cl_anchor_mask.argtypes = [vp, ctypes.c_int64, vp, vp, vp, i64p, i64p]
-    lib.cl_track_build.restype = ctypes.c_int
-    lib.cl_track_build.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_char_p, ctypes.c_char_p, i64p, i64p]
-    lib.cl_track_chunks.restype = ctypes.c_int
-    lib.cl_track_chunks.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, i64p]
-    lib.cl_track_render.restype = ctypes.c_int
-    lib.cl_track_render.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, i64p]
-    lib.cl_track_free.restype = ctypes.c_int
-    lib.cl_track_free.argtypes = [vp]
-    lib.cl_conv_create.restype = ctypes.c_int
-    lib.cl_conv_create.argtypes = [ctypes.c_int, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(vp)]
-    lib.cl_conv_feed.restype = ctypes.c_int
-    lib.cl_conv_feed.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, i64p, i64p, i64p]
-    lib.cl_conv_render.restype = ctypes.c_int
-    lib.cl_conv_render.argtypes = [vp, vp, ctypes.c_int64, i64p]
-    lib.cl_conv_error.restype = ctypes.c_int
-    lib.cl_conv_error.argtypes = [vp, i64p, ctypes.POINTER(ctypes.c_int32)]
-    lib.cl_conv_timing.restype = ctypes.c_int
-    lib.cl_conv_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    lib.cl_conv_destroy.restype = ctypes.c_int
-    lib.cl_conv_destroy.argtypes = [vp]
-    lib.cl_ingest_create.restype = ctypes.c_int
-    lib.cl_ingest_create.argtypes = [ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(vp)]
-    lib.cl_ingest_feed.restype = ctypes.c_int
-    lib.cl_ingest_feed.argtypes = [vp, vp, ctypes.c_int64, i64p, i64p, i64p]
-    lib.cl_ingest_names.restype = ctypes.c_int
-    lib.cl_ingest_names.argtypes = [vp, vp, ctypes.c_int64, i64p]
-    lib.cl_ingest_commit.restype = ctypes.c_int
-    lib.cl_ingest_commit.argtypes = [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32,
-                                     vp, i32p]
-    lib.cl_ingest_finish.restype = ctypes.c_int
-    lib.cl_ingest_finish.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, i64p]
-    lib.cl_ingest_rows.restype = ctypes.c_int
-    lib.cl_ingest_rows.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int64]
-    lib.cl_ingest_chrom_arrays.restype = ctypes.c_int
-    lib.cl_ingest_chrom_arrays.argtypes = [vp, ctypes.c_int32, i64p, ctypes.POINTER(vp), ctypes.POINTER(vp)]
-    lib.cl_ingest_distances.restype = ctypes.c_int
-    lib.cl_ingest_distances.argtypes = [vp, vp, ctypes.c_int64]
-    lib.cl_ingest_timing.restype = ctypes.c_int
-    lib.cl_ingest_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    lib.cl_ingest_destroy.restype = ctypes.c_int
-    lib.cl_ingest_destroy.argtypes = [vp]
-    lib.cl_last_n_in.restype = ctypes.c_int64
-    lib.cl_last_n_in.argtypes = [vp]
-    lib.cl_get_boxes.restype = ctypes.c_int
-    lib.cl_get_boxes.argtypes = [vp, vp]
-    lib.cl_neighbor_counts.restype = ctypes.c_int
-    lib.cl_neighbor_counts.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp]
-    lib.cl_labels_device.restype = vp
-    lib.cl_labels_device.argtypes = [vp]
-    lib.cl_set_profiling.restype = None
-    lib.cl_set_profiling.argtypes = [vp, ctypes.c_int]
-    lib.cl_set_layout_reuse.restype = None
-    lib.cl_set_layout_reuse.argtypes = [vp, ctypes.c_int]
-    lib.cl_set_sort_index.restype = None
-    lib.cl_set_sort_index.argtypes = [vp, ctypes.c_int]
-    lib.cl_set_count_reuse.restype = None
-    lib.cl_set_count_reuse.argtypes = [vp, ctypes.c_int]
-    lib.cl_set_traversal.restype = None
-    lib.cl_set_traversal.argtypes = [vp, ctypes.c_int]
-    lib.cl_set_count_floor.restype = None
-    lib.cl_set_count_floor.argtypes = [vp, ctypes.c_int32]
-    lib.cl_chrom_set_stream.restype = ctypes.c_int
-    lib.cl_chrom_set_stream.argtypes = [vp, vp]
-    lib.cl_sweep_plan.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
-    lib.cl_chrom_drop_indexes.argtypes = [vp]
-    lib.cl_set_eps_list.restype = None
-    lib.cl_set_eps_list.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
-    lib.cl_set_count_thresholds.restype = None
-    lib.cl_set_count_thresholds.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
-    lib.cl_last_region_mode.restype = ctypes.c_int
-    lib.cl_last_region_mode.argtypes = [vp]
-    lib.cl_stream_create.restype = vp
-    lib.cl_stream_create.argtypes = [ctypes.c_int]
-    lib.cl_stream_destroy.restype = None
-    lib.cl_stream_destroy.argtypes = [vp]
-    lib.cl_chrom_subsample.restype = ctypes.c_int
-    lib.cl_chrom_subsample.argtypes = [vp, vp, ctypes.c_int64, ctypes.POINTER(vp)]
-    lib.cl_debug_arena_overcommit.restype = None
-    lib.cl_debug_arena_overcommit.argtypes = [ctypes.c_int64]
-    lib.cl_get_timing.restype = ctypes.c_int
-    lib.cl_get_timing.argtypes = [vp, ctypes.POINTER(ClTiming)]
-    lib.cl_host_alloc.restype = vp
-    lib.cl_host_alloc.argtypes = [ctypes.c_int64]
-    lib.cl_host_free.restype = None
-    lib.cl_host_free.argtypes = [vp]
-    _lib = lib
-    return lib
+    _lib = bind(ctypes.CDLL(path), PROTOTYPES)
+    return _lib
 
 
 def check(rc):
     if rc != CL_OK:
         msg = load().cl_last_error()
         raise CloopsHipError(rc, msg.decode() if msg else "")
+
+
+def host_alloc(nbytes):
+    """page-locked host memory of the library (its cl_host_alloc entry) -> address; the owner frees it with lib.cl_host_free"""
+    p = load().cl_host_alloc(int(nbytes))
+    if not p:
+        raise MemoryError("no page-locked host memory of %d bytes" % nbytes)
+    return p
+
+
+def stream_create(device):
+    """a HIP stream made by the library (its cl_stream_create entry) -> address; the owner ends it with lib.cl_stream_destroy"""
+    s = load().cl_stream_create(int(device))
+    if not s:
+        raise CloopsHipError(CL_ERR_HIP, (load().cl_last_error() or b"").decode())
+    return s

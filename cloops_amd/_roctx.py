@@ -3,6 +3,8 @@
 import ctypes
 import os
 
+from ._lib import bind
+
 _lib = None
 _tried = False
 
@@ -16,11 +18,7 @@ def _load():
         return None
     for name in ("libroctx64.so", "libroctx64.so.4", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libroctx64.so")):
         try:
-            lib = ctypes.CDLL(name)
-            lib.roctxRangePushA.argtypes = [ctypes.c_char_p]
-            lib.roctxRangePushA.restype = ctypes.c_int
-            lib.roctxRangePop.restype = ctypes.c_int
-            _lib = lib
+            _lib = bind(ctypes.CDLL(name), {"roctxRangePushA": (ctypes.c_int, [ctypes.c_char_p]), "roctxRangePop": (ctypes.c_int, [])})
             break
         except (OSError, AttributeError):
             continue

@@ -54,49 +54,59 @@ class ClusterResult(object):
         self.timing = timing
 
 
-class Chromosome(object):
+class _Handle(object):
+    """the lifetime of one library handle: _open() makes it, close() destroys it once (also when the object is collected)"""
+    _DESTROY = None                                # the entry that destroys the handle
+
+    def _open(self, create, *args):
+        """`create(*args, &handle)`: every cl_*_create entry takes its out-pointer last"""
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p()
+        _lib.check(getattr(self._lib, create)(*args, ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self._lib, self._DESTROY)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                               # noqa: BLE001
+            pass
+
+
+class Chromosome(_Handle):
     """One chromosome's PET coordinates resident in HBM (cl_chrom of include/cloops_hip.h)."""
+    _DESTROY = "cl_chrom_destroy"
 
     def __init__(self, X, Y, device=0, stream=None):
-        lib = _lib.load()
-        self._lib = lib
-        self._h = ctypes.c_void_p()
         X = _as_i32(X, "X")
         Y = _as_i32(Y, "Y")
         if X.shape != Y.shape:
             raise ValueError("X and Y differ in length")
-        self.n = int(X.shape[0])
+        self._create(X.shape[0], device, "cl_chrom_create", int(device), ctypes.c_void_p(stream), X.ctypes.data_as(ctypes.c_void_p),
+                     Y.ctypes.data_as(ctypes.c_void_p), int(X.shape[0]), 0)
+
+    def _create(self, n, device, create, *args):
+        """the one constructor step of all three ways to make a chromosome: the fields, the handle, the traversal override"""
+        self.n = int(n)
         self.device = device
-        self._init_state()
-        _lib.check(lib.cl_chrom_create(int(device), ctypes.c_void_p(stream), X.ctypes.data_as(ctypes.c_void_p),
-                                       Y.ctypes.data_as(ctypes.c_void_p), self.n, 0, ctypes.byref(self._h)))
-        self._after_create()
-
-    def _after_create(self):
-        if TRAVERSAL_OVERRIDE is not None:
-            self._lib.cl_set_traversal(self._h, int(TRAVERSAL_OVERRIDE))
-
-    def _init_state(self):
         self._profiling = False
-        self._pinned = [None, None]
-        self._pinned_arr = [None, None]
+        self._pins = {}                            # (kind, slot) -> (address, int32 view or None): every page-locked block this object owns
         self._inflight = []
         self._enq = 0
+        self._open(create, *args)
+        if TRAVERSAL_OVERRIDE is not None:
+            self._lib.cl_set_traversal(self._h, int(TRAVERSAL_OVERRIDE))
 
     @classmethod
     def from_device_pointers(cls, x_ptr, y_ptr, n, device=0, stream=None, keepalive=None):
         """Wrap int32 device arrays (e.g. torch tensors' data_ptr()) without copying."""
         self = cls.__new__(cls)
-        lib = _lib.load()
-        self._lib = lib
-        self._h = ctypes.c_void_p()
-        self.n = int(n)
-        self.device = device
         self._keepalive = keepalive
-        self._init_state()
-        _lib.check(lib.cl_chrom_create(int(device), ctypes.c_void_p(stream), ctypes.c_void_p(x_ptr),
-                                       ctypes.c_void_p(y_ptr), self.n, 1, ctypes.byref(self._h)))
-        self._after_create()
+        self._create(n, device, "cl_chrom_create", int(device), ctypes.c_void_p(stream), ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr),
+                     int(n), 1)
         return self
 
     def subsample(self, rows):
@@ -104,47 +114,28 @@ class Chromosome(object):
         scripts/jd2saturation:46-47), gathered on the device (cl_chrom_subsample)"""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         new = Chromosome.__new__(Chromosome)
-        new._lib = self._lib
-        new._h = ctypes.c_void_p()
-        new.n = int(rows.shape[0])
-        new.device = self.device
-        new._init_state()
-        _lib.check(self._lib.cl_chrom_subsample(self._h, rows.ctypes.data_as(ctypes.c_void_p), new.n, ctypes.byref(new._h)))
-        new._after_create()
+        new._create(rows.shape[0], self.device, "cl_chrom_subsample", self._h, rows.ctypes.data_as(ctypes.c_void_p), int(rows.shape[0]))
         return new
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.cl_chrom_destroy(self._h)
-            self._h = ctypes.c_void_p()
-        for k, p in enumerate(getattr(self, "_pinned", [])):
-            if p:
-                self._lib.cl_host_free(ctypes.c_void_p(p))
-                self._pinned[k] = None
-        for k, p in enumerate(getattr(self, "_pin_pairs", None) or []):
-            if p:
-                self._lib.cl_host_free(ctypes.c_void_p(p))
-                self._pin_pairs[k] = None
-        for k, p in enumerate(getattr(self, "_pin_mask", None) or []):
-            if p:
-                self._lib.cl_host_free(ctypes.c_void_p(p))
-                self._pin_mask[k] = None
+        _Handle.close(self)
+        pins, self._pins = getattr(self, "_pins", {}), {}
+        for p, _ in pins.values():
+            self._lib.cl_host_free(ctypes.c_void_p(p))
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _pin(self, kind, slot, nbytes, shape=None):
+        """the page-locked block `kind` of result slot `slot` (two per kind: a run takes slot `enq & 1`), made on first use
+        -> (address, int32 view of `shape` or None)"""
+        e = self._pins.get((kind, slot))
+        if e is None:
+            p = _lib.host_alloc(nbytes)
+            view = None if shape is None else np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_int32)), shape=shape)
+            e = self._pins[kind, slot] = (p, view)
+        return e
 
     def _pinned_labels(self, which=0):
         """Page-locked int32[n] result buffers owned by this object (two: one per result slot)."""
-        if self._pinned[which] is None:
-            p = self._lib.cl_host_alloc(max(4, self.n * 4))
-            if not p:
-                raise MemoryError("cl_host_alloc failed")
-            self._pinned[which] = p
-            self._pinned_arr[which] = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_int32)), shape=(self.n,))
-        return self._pinned_arr[which]
+        return self._pin("labels", which, max(4, self.n * 4), (self.n,))[1]
 
     def set_profiling(self, on=True):
         self._profiling = bool(on)
@@ -233,7 +224,7 @@ class Chromosome(object):
         _lib.check(self._lib.cl_chrom_drop_indexes(self._h))
 
     def set_traversal(self, level=4):
-        """how far a run works on its core / walker lists instead of LDS tiles over every PET: 0 .. 3 (default 3; results
+        """how far a run works on its core / walker lists instead of LDS tiles over every PET: 0 .. 4 (default 4; results
         identical at every level -- cl_set_traversal of include/cloops_hip.h)"""
         self._lib.cl_set_traversal(self._h, int(level))
 
@@ -296,16 +287,7 @@ class Chromosome(object):
         (row, label) pair per labelled PET in a page-locked buffer (cl_cluster_pairs_async); pair with wait_pairs()."""
         v = VARIANTS[variant]
         self.set_table_export(want_boxes)
-        which = self._enq & 1
-        if getattr(self, "_pin_pairs", None) is None:
-            self._pin_pairs, self._pin_pairs_arr = [None, None], [None, None]
-        if self._pin_pairs[which] is None:
-            p = self._lib.cl_host_alloc(max(8, self.n * 8))
-            if not p:
-                raise MemoryError("cl_host_alloc(%d) failed" % (self.n * 8))
-            self._pin_pairs[which] = p
-            self._pin_pairs_arr[which] = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_int32)), shape=(self.n, 2))
-        buf = self._pin_pairs_arr[which]
+        buf = self._pin("pairs", self._enq & 1, max(8, self.n * 8), (self.n, 2))[1]
         _lib.check(self._lib.cl_cluster_pairs_async(self._h, v, int(eps), int(minPts), int(cut), buf.ctypes.data_as(ctypes.c_void_p), self.n))
         self._inflight.append((buf, bool(want_boxes)))
         self._enq += 1
@@ -332,17 +314,7 @@ class Chromosome(object):
         the 8 bytes per clustered PET of cluster_pairs_async; pair with wait_rowmask()."""
         v = VARIANTS[variant]
         self.set_table_export(want_boxes)
-        which = self._enq & 1
-        if getattr(self, "_pin_mask", None) is None:
-            self._pin_mask = [None, None]
-        nw = (self.n + 63) // 64
-        nbytes = 8 * nw + 4 * max(self.n, 1)
-        if self._pin_mask[which] is None:
-            p = self._lib.cl_host_alloc(nbytes)
-            if not p:
-                raise MemoryError("cl_host_alloc(%d) failed" % nbytes)
-            self._pin_mask[which] = p
-        p = self._pin_mask[which]
+        p = self._pin("rowmask", self._enq & 1, 8 * ((self.n + 63) // 64) + 4 * max(self.n, 1))[0]
         _lib.check(self._lib.cl_cluster_rowmask_async(self._h, v, int(eps), int(minPts), int(cut), ctypes.c_void_p(p), max(self.n, 1)))
         self._inflight.append((p, bool(want_boxes)))
         self._enq += 1
@@ -490,8 +462,8 @@ class Chromosome(object):
                                             mask.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nm), ctypes.byref(nk)))
         return mask[:nw], int(nm.value), int(nk.value)
 
-    TRACK_KINDS = {"washu": 0, "juice": 1}         # CL_TRACK_WASHU, CL_TRACK_JUICE
-    TRACK_NAME_MAX = 64                            # CL_TRACK_NAME_MAX
+    TRACK_KINDS = {"washu": _lib.CL_TRACK_WASHU, "juice": _lib.CL_TRACK_JUICE}
+    TRACK_NAME_MAX = _lib.CL_TRACK_NAME_MAX
     TRACK_BUDGET = 64 << 20                        # default bytes per rendered chunk
 
     def track_build(self, kind, cut, ext, ids, chr_a, chr_b):
@@ -564,10 +536,7 @@ class Chromosome(object):
         fut = None
         try:
             for _ in range(2):
-                p = self._lib.cl_host_alloc(size)
-                if not p:
-                    raise MemoryError("cl_host_alloc(%d) failed" % size)
-                bufs.append(p)
+                bufs.append(_lib.host_alloc(size))
             from concurrent.futures import ThreadPoolExecutor
             pool = ThreadPoolExecutor(1)
             fut = pool.submit(self.track_render, 0, (bufs[0], size))
@@ -592,21 +561,20 @@ class Chromosome(object):
         return out
 
 
-class Converter(object):
+class Converter(_Handle):
     """K15: a pairs-to-BEDPE converter on the device (cl_conv of include/cloops_hip.h), shaped like Chromosome.track_*: feed a chunk of
     complete lines, render their BEDPE text.  fmt "hicpro" (scripts/hicpropairs2bedpe) or "juicer" (scripts/juicerLong2bedpe.py)."""
-    FORMATS = {"hicpro": 0, "juicer": 1}           # CL_CONV_HICPRO, CL_CONV_JUICER
-    KINDS = {1: "fewer than 7 fields", 2: "not an integer", 3: "integer outside int64", 4: "line longer than the chunk budget"}
+    FORMATS = {"hicpro": _lib.CL_CONV_HICPRO, "juicer": _lib.CL_CONV_JUICER}
+    KINDS = {_lib.CL_CONV_E_FIELDS: "fewer than 7 fields", _lib.CL_CONV_E_INT: "not an integer", _lib.CL_CONV_E_RANGE: "integer outside int64",
+             _lib.CL_CONV_E_LONG: "line longer than the chunk budget"}
     BUDGET = 64 << 20                              # default bytes per chunk
+    _DESTROY = "cl_conv_destroy"
 
     def __init__(self, fmt, ext, budget=BUDGET, device=0, stream=None):
         if fmt not in self.FORMATS:
             raise ValueError("unknown pairs format %r (hicpro or juicer)" % (fmt,))
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.fmt, self.ext, self.budget = fmt, int(ext), int(budget)
-        _lib.check(self._lib.cl_conv_create(int(device), ctypes.c_void_p(stream), self.FORMATS[fmt], self.ext, self.budget,
-                                            ctypes.byref(self._h)))
+        self._open("cl_conv_create", int(device), ctypes.c_void_p(stream), self.FORMATS[fmt], self.ext, self.budget)
 
     def feed(self, ptr, n, last):
         """the complete lines of the n bytes at host address `ptr` (all of them with `last`) -> (bytes consumed, lines converted,
@@ -636,31 +604,18 @@ class Converter(object):
         _lib.check(self._lib.cl_conv_timing(self._h, ms))
         return {"h2d": ms[0], "feed": ms[1], "render": ms[2], "d2h": ms[3]}
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.cl_conv_destroy(self._h)
-            self._h = ctypes.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                                               # noqa: BLE001
-            pass
-
-
-class Ingest(object):
+class Ingest(_Handle):
     """K16: a BEDPE reader on the device (cl_ingest of include/cloops_hip.h), shaped like Converter: feed a chunk of complete lines,
     read its distinct chromosome names, commit the host's table for them; finish joins two handles and leaves every chromosome's
     mid-points in HBM."""
-    TIMES = ("h2d", "index", "parse", "names", "commit", "finish")
+    TIMES = ("h2d", "index", "parse", "names", "commit", "finish")       # CL_INGEST_TIMES of them
     BUDGET = 64 << 20                              # default bytes per chunk
+    _DESTROY = "cl_ingest_destroy"
 
     def __init__(self, budget=BUDGET, cut=0, want_distances=False, device=0, stream=None):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.device, self.budget = int(device), int(budget)
-        _lib.check(self._lib.cl_ingest_create(int(device), ctypes.c_void_p(stream), self.budget, int(cut), int(bool(want_distances)),
-                                              ctypes.byref(self._h)))
+        self._open("cl_ingest_create", int(device), ctypes.c_void_p(stream), self.budget, int(cut), int(bool(want_distances)))
 
     def feed(self, ptr, n):
         """the n bytes of complete lines at host address `ptr` -> (lines, first exotic line or -1, distinct names or -1 for too
@@ -728,14 +683,3 @@ class Ingest(object):
         ms = (ctypes.c_float * len(self.TIMES))()
         _lib.check(self._lib.cl_ingest_timing(self._h, ms))
         return dict(zip(self.TIMES, ms))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.cl_ingest_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                                               # noqa: BLE001
-            pass

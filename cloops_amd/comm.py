@@ -17,11 +17,32 @@ import time
 
 import numpy as np
 
+from ._lib import bind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libcloops_comm.so")
-SYMBOLS = ("cl_comm_last_error", "cl_comm_rccl_version", "cl_comm_unique_id", "cl_comm_init", "cl_comm_destroy", "cl_comm_rank", "cl_comm_world",
-           "cl_comm_allreduce_f64", "cl_comm_allreduce_max_f64", "cl_comm_allgather_i32", "cl_comm_gather_i32", "cl_comm_barrier",
-           "cl_comm_host_alloc", "cl_comm_host_free", "cl_comm_gather_i32_pinned", "cl_comm_gather_device", "cl_comm_allreduce_f64_device")
+_int, _i32, _i64, _vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+# The C ABI of include/cloops_comm.h, one line per function: name -> (restype, argtypes); tests/test_abi.py checks it against the header.
+PROTOTYPES = {
+    "cl_comm_last_error": (ctypes.c_char_p, []),
+    "cl_comm_rccl_version": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "cl_comm_unique_id": (_int, [_vp]),
+    "cl_comm_init": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp)]),
+    "cl_comm_destroy": (None, [_vp]),
+    "cl_comm_rank": (_int, [_vp]),
+    "cl_comm_world": (_int, [_vp]),
+    "cl_comm_allreduce_f64": (_int, [_vp, _vp, _i64]),
+    "cl_comm_allreduce_max_f64": (_int, [_vp, _vp, _i64]),
+    "cl_comm_allgather_i32": (_int, [_vp, _vp, _i64, _vp]),
+    "cl_comm_gather_i32": (_int, [_vp, _vp, _i64, _int, _vp]),
+    "cl_comm_barrier": (_int, [_vp]),
+    "cl_comm_host_alloc": (_vp, [_i64]),
+    "cl_comm_host_free": (None, [_vp]),
+    "cl_comm_gather_i32_pinned": (_int, [_vp, _vp, _i64, _int, _vp]),
+    "cl_comm_gather_device": (_int, [_vp, _vp, _vp, _i32, _i32, _int, _vp, _i64, _vp]),
+    "cl_comm_allreduce_f64_device": (_int, [_vp, _vp, _i64, _vp]),
+}
+SYMBOLS = tuple(PROTOTYPES)
 ID_BYTES = 128
 ID_DIR = "/tmp"
 _lib = None
@@ -65,28 +86,7 @@ def load():
 def _declare(lib):
     """the prototypes of include/cloops_comm.h on a loaded library (tests load a build of cloops_comm.cpp against a host-memory
     test double of HIP / RCCL through this, tests/test_comm_fake_world.py)"""
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    lib.cl_comm_last_error.restype = ctypes.c_char_p
-    lib.cl_comm_rccl_version.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    lib.cl_comm_unique_id.argtypes = [vp]
-    lib.cl_comm_init.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
-    lib.cl_comm_destroy.argtypes = [vp]
-    lib.cl_comm_destroy.restype = None
-    lib.cl_comm_rank.argtypes = [vp]
-    lib.cl_comm_world.argtypes = [vp]
-    lib.cl_comm_allreduce_f64.argtypes = [vp, vp, i64]
-    lib.cl_comm_allreduce_max_f64.argtypes = [vp, vp, i64]
-    lib.cl_comm_allgather_i32.argtypes = [vp, vp, i64, vp]
-    lib.cl_comm_gather_i32.argtypes = [vp, vp, i64, ctypes.c_int, vp]
-    lib.cl_comm_barrier.argtypes = [vp]
-    lib.cl_comm_host_alloc.restype = vp
-    lib.cl_comm_host_alloc.argtypes = [i64]
-    lib.cl_comm_host_free.restype = None
-    lib.cl_comm_host_free.argtypes = [vp]
-    lib.cl_comm_gather_i32_pinned.argtypes = [vp, vp, i64, ctypes.c_int, vp]
-    lib.cl_comm_gather_device.argtypes = [vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, vp, i64, vp]
-    lib.cl_comm_allreduce_f64_device.argtypes = [vp, vp, i64, vp]
-    return lib
+    return bind(lib, PROTOTYPES)
 
 
 def _check(rc):

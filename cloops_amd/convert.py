@@ -32,6 +32,8 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from datetime import datetime
 
+from . import _lib
+
 BUDGET = 64 << 20            # bytes of input per chunk
 THREADS = 8                  # -p: gzip member pool
 MAX_THREADS = 16
@@ -39,29 +41,41 @@ MEMBER = 4 << 20             # bytes of text per gzip member
 _NL_WINDOW = 1 << 16
 
 
-class GpuSeam(object):
+class _DeviceSeam(object):
+    """what the seams on the device share (this one and cloops_amd.ingest's): two handles on two library streams, chunk k on handle
+    k % 2, and the page-locked blocks they own"""
+
+    def __init__(self, device, make):
+        """make(stream) -> the handle (api.Converter, api.Ingest) of that stream"""
+        self.lib = _lib.load()
+        self.handles, self.streams, self.pins = [], [], []
+        for _ in range(2):
+            self.streams.append(_lib.stream_create(device))
+            self.handles.append(make(self.streams[-1]))
+
+    def _pin(self, n):
+        self.pins.append(_lib.host_alloc(n))
+        return self.pins[-1]
+
+    def close(self):
+        for h in self.handles:
+            h.close()
+        for s in self.streams:
+            self.lib.cl_stream_destroy(ctypes.c_void_p(s))
+        for p in self.pins:
+            self.lib.cl_host_free(ctypes.c_void_p(p))
+        self.handles, self.streams, self.pins = [], [], []
+
+
+class GpuSeam(_DeviceSeam):
     """the per-chunk seam on the device: two K15 handles on two streams (chunk k on handle k % 2) and page-locked buffers.  The CPU
     tests put a brute-force seam with the same methods in its place (`make_seam`)."""
 
     def __init__(self, fmt, ext, budget, device=0):
-        from . import _lib, api
-        self.lib = _lib.load()
-        self.convs, self.streams, self.pins = [], [], []
+        from . import api
+        _DeviceSeam.__init__(self, device, lambda s: api.Converter(fmt, ext, budget, device, s))
         self.outs = [None, None]                  # per handle: (address, capacity) of its page-locked output buffer
         self.ms = collections.Counter()
-        for _ in range(2):
-            s = self.lib.cl_stream_create(int(device))
-            if not s:
-                raise _lib.CloopsHipError(_lib.CL_ERR_HIP, self.lib.cl_last_error().decode())
-            self.streams.append(s)
-            self.convs.append(api.Converter(fmt, ext, budget, device, s))
-
-    def _pin(self, n):
-        p = self.lib.cl_host_alloc(int(n))
-        if not p:
-            raise MemoryError("cl_host_alloc(%d) failed" % n)
-        self.pins.append(p)
-        return p
 
     def buffer(self, n):
         """a page-locked input buffer of n bytes (a ctypes array: writable, with the buffer protocol)"""
@@ -82,7 +96,7 @@ class GpuSeam(object):
         error): text a bytes-like object valid until chunk k + 2 is asked for; error None, or the reason the line after the
         converted ones is bad"""
         h = k & 1
-        cv = self.convs[h]
+        cv = self.handles[h]
         addr = ctypes.addressof(buf)
         parts, lines, done = [], 0, 0
         while True:
@@ -102,15 +116,6 @@ class GpuSeam(object):
         if err is None and done < n:
             raise RuntimeError("K15 left %d bytes of a chunk unconverted" % (n - done))
         return text, lines, None if err is None else err[1]
-
-    def close(self):
-        for cv in self.convs:
-            cv.close()
-        for s in self.streams:
-            self.lib.cl_stream_destroy(ctypes.c_void_p(s))
-        for p in self.pins:
-            self.lib.cl_host_free(ctypes.c_void_p(p))
-        self.convs, self.pins, self.streams = [], [], []
 
 
 def make_seam(fmt, ext, budget, device=0):

@@ -68,35 +68,25 @@ class _Keep(object):
             pass
 
 
-class GpuSeam(object):
+class GpuSeam(convert._DeviceSeam):
     """the per-chunk seam on the device: two K16 handles on two streams (chunk k on handle k % 2) and page-locked buffers.  The CPU
     tests put a brute-force seam with the same methods in its place (`make_seam`)."""
 
     def __init__(self, budget, cut, want_distances, device=0):
-        from . import _lib, api
-        self.lib = _lib.load()
+        from . import api
+        convert._DeviceSeam.__init__(self, device, lambda s: api.Ingest(budget, cut, want_distances, device, s))
         self.device = device
-        self.ings, self.streams, self.pins, self.bufs = [], [], [], []
+        self.bufs = []
         self.turn = 0
         self.keep = None
         self.ms_closed = collections.Counter()     # device ms of the handle that finish() closes
-        for _ in range(2):
-            s = self.lib.cl_stream_create(int(device))
-            if not s:
-                raise _lib.CloopsHipError(_lib.CL_ERR_HIP, self.lib.cl_last_error().decode())
-            self.streams.append(s)
-            self.ings.append(api.Ingest(budget, cut, want_distances, device, s))
 
     def buffer(self, n):
         """a page-locked input buffer of n bytes; the three of one reader are handed to the next file's reader again"""
         k = self.turn % 3
         self.turn += 1
         if k >= len(self.bufs):
-            p = self.lib.cl_host_alloc(int(n))
-            if not p:
-                raise MemoryError("cl_host_alloc(%d) failed" % n)
-            self.pins.append(p)
-            self.bufs.append((ctypes.c_char * n).from_address(p))
+            self.bufs.append((ctypes.c_char * n).from_address(self._pin(n)))
         return self.bufs[k]
 
     def chunk(self, k, buf, n, last):
@@ -107,26 +97,26 @@ class GpuSeam(object):
         mv = memoryview(buf).cast("B")
         if not last and mv[n - 1] != 10:
             return _Chunk(h, 0, [], n, True), 0, "a line longer than the chunk budget"
-        lines, exotic, nn = self.ings[h].feed(ctypes.addressof(buf), n)
+        lines, exotic, nn = self.handles[h].feed(ctypes.addressof(buf), n)
         if exotic >= 0:
             return _Chunk(h, lines, [], n, True), exotic, "a line the device does not read (Python's int() or text decoding decides)"
         if nn < 0:
             return _Chunk(h, lines, [], n, True), 0, "more than 65536 chromosome names in one chunk"
-        names = [(hs, first, bytes(mv[off:off + ln])) for hs, first, off, ln in self.ings[h].names(nn)]
+        names = [(hs, first, bytes(mv[off:off + ln])) for hs, first, off, ln in self.handles[h].names(nn)]
         return _Chunk(h, lines, names, n), lines, None
 
     def commit(self, chunk, k, line0, table, n_ids):
         """-> (PETs appended per id, status)"""
-        return self.ings[chunk.h].commit(k, line0, table, n_ids)
+        return self.handles[chunk.h].commit(k, line0, table, n_ids)
 
     def finish(self, n_ids, unique):
         """-> (rows per id, number of distances); the arrays live in `self.keep` from here on"""
-        out = self.ings[0].finish(self.ings[1], n_ids, unique)
-        self.ms_closed.update(self.ings[1].timing())
-        self.ings[1].close()
-        self.keep = _Keep(self.lib, self.ings[0], self.streams[0])
+        out = self.handles[0].finish(self.handles[1], n_ids, unique)
+        self.ms_closed.update(self.handles[1].timing())
+        self.handles[1].close()
+        self.keep = _Keep(self.lib, self.handles[0], self.streams[0])
         self.lib.cl_stream_destroy(ctypes.c_void_p(self.streams[1]))
-        self.ings, self.streams = [], []
+        self.handles, self.streams = [], []
         return out
 
     def rows(self, cid, n):
@@ -140,19 +130,14 @@ class GpuSeam(object):
 
     def timing(self):
         ms = collections.Counter(self.ms_closed)
-        for ing in self.ings + ([self.keep.ing] if self.keep is not None and self.keep.ing is not None else []):
+        for ing in self.handles + ([self.keep.ing] if self.keep is not None and self.keep.ing is not None else []):
             ms.update(ing.timing())
         return ms
 
     def close(self):
         """frees the handles, streams and buffers (not `keep` once somebody took it: see load_bedpe)"""
-        for ing in self.ings:
-            ing.close()
-        for s in self.streams:
-            self.lib.cl_stream_destroy(ctypes.c_void_p(s))
-        for p in self.pins:
-            self.lib.cl_host_free(ctypes.c_void_p(p))
-        self.ings, self.streams, self.pins, self.bufs = [], [], [], []
+        convert._DeviceSeam.close(self)
+        self.bufs = []
 
 
 def make_seam(budget, cut, want_distances, device=0):

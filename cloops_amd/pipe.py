@@ -60,7 +60,7 @@ SWEEP_STREAMS = 3
 
 
 class _StreamPool(object):
-    """per device: up to SWEEP_STREAMS library-made streams (cl_stream_create), handed out to the least loaded one; they
+    """per device: up to SWEEP_STREAMS library-made streams (_lib.stream_create), handed out to the least loaded one; they
     live as long as the process (handles may outlive the cache entry that made them)"""
 
     def __init__(self):
@@ -74,8 +74,9 @@ class _StreamPool(object):
         with self._lock:
             slots = self._by_dev.setdefault(device, [])
             if len(slots) < SWEEP_STREAMS:
-                ptr = _lib.load().cl_stream_create(int(device))
-                if not ptr:                               # (no such device: the handle's own creation reports it)
+                try:
+                    ptr = _lib.stream_create(device)
+                except _lib.CloopsHipError:               # (no such device: the handle's own creation reports it)
                     return None, None
                 slots.append([ptr, 0])
             slot = min(slots, key=lambda s: s[1])
