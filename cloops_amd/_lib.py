@@ -32,6 +32,7 @@ CL_CONV_HICPRO, CL_CONV_JUICER = 0, 1
 CL_CONV_E_FIELDS, CL_CONV_E_INT, CL_CONV_E_RANGE, CL_CONV_E_LONG = 1, 2, 3, 4
 CL_INGEST_TIMES = 6
 DIST_LOGBINS = 3840          # CL_DIST_LOGBINS
+CL_KDE_MAX_GRID = 1024
 
 
 class ClBox(ctypes.Structure):
@@ -60,6 +61,7 @@ class ClDsummary(ctypes.Structure):
 
 _int, _i32, _u32, _i64, _vp, _cp = ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p
 _i32p, _i64p, _u64p, _f32p, _vpp = (ctypes.POINTER(t) for t in (_i32, _i64, ctypes.c_uint64, ctypes.c_float, _vp))
+_f64, _f64p = ctypes.c_double, ctypes.POINTER(ctypes.c_double)
 
 # The C ABI of include/cloops_hip.h, one line per function: name -> (restype, argtypes).  load() applies it once; tests/test_abi.py
 # checks every entry, the structs above and the constants against the header.
@@ -92,6 +94,9 @@ PROTOTYPES = {
     "cl_neighbor_counts": (_int, [_vp, _i32, _i32, _vp]),
     "cl_dist_summary": (_int, [_vp, _i32, ctypes.POINTER(ClDsummary)]),
     "cl_dist_bin_hist": (_int, [_vp, _i32, _u32, _u32, _int, _u64p]),
+    "cl_dist_collect": (_int, [_vp, _i32, _i64p, _i64p, _i64p]),
+    "cl_dist_kde": (_int, [_vp, _int, _f64, _f64, _f64, _int, _f64p]),
+    "cl_kde_array": (_int, [_int, _vp, _i64, _f64, _f64, _f64, _int, _f64p]),
     "cl_sig_counts": (_int, [_vp, _i32, _i32, _vp, _vp, _i64p]),
     "cl_quant_counts": (_int, [_vp, _i32, _i32, _vp, _vp, _i64p]),
     "cl_contact_hist": (_int, [_vp, _i32, _i32, _i64, _vp, _vp, _i64p, _i64p, _i64p, _i32p]),

@@ -411,6 +411,22 @@ class Chromosome(_Handle):
                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out.astype(np.int64)
 
+    # ---- kernel density sums of log2|d| of the last completed run (K17; the curves of cPlots.plotIntSelCutFrag) ----
+    def dist_collect(self, cut=0):
+        """pack and sort the (|d|, weight) entries with |d| > 0 of both groups on the device (cl_dist_collect; same `cut` as
+        the run) -> dict(n_pos=[inter, self], dmin=[...], dmax=[...]); an empty group has n_pos 0 and dmin = dmax = 0"""
+        out = [(ctypes.c_int64 * 2)() for _ in range(3)]
+        _lib.check(self._lib.cl_dist_collect(self._h, int(cut), *out))
+        return {k: [int(a[0]), int(a[1])] for k, a in zip(("n_pos", "dmin", "dmax"), out)}
+
+    def dist_kde(self, group, lo, step, inv_h, gridsize):
+        """-> float64[gridsize]: S[j] = sum over the collected entries of `group` (0 = inter, 1 = self) of
+        weight * exp(-((log2|d| - (lo + j step)) inv_h)^2 / 2), unnormalised (cl_dist_kde); needs dist_collect() after the run"""
+        out = np.zeros(max(int(gridsize), 1), dtype=np.float64)
+        _lib.check(self._lib.cl_dist_kde(self._h, int(group), float(lo), float(step), float(inv_h), int(gridsize),
+                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
     def sig_counts(self, windows, cut=0):
         """K8: interval counts for the significance test.  windows: int32 [R, 44] (lo[22], hi[22];
         A0..A10 then B0..B10) -> (int32 [R, 144] counts, N)  (cl_sig_counts of include/cloops_hip.h)."""
@@ -559,6 +575,21 @@ class Chromosome(_Handle):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+
+def kde_array(d, lo, step, inv_h, gridsize, device=0):
+    """K17 over a plain array of integer distances, each of weight 1 (|d| is taken, zeros are dropped) -> float64[gridsize]:
+    S[j] = sum_i exp(-((log2|d_i| - (lo + j step)) inv_h)^2 / 2), unnormalised (cl_kde_array)"""
+    d = np.asarray(d)
+    if d.ndim != 1 or (d.size and d.dtype.kind not in "iu"):
+        raise TypeError("kde_array: a one-dimensional integer array required")
+    if d.size and (d.min() < -(2 ** 31 - 1) or d.max() > 2 ** 31 - 1):
+        raise _lib.CloopsHipError(_lib.CL_ERR_DOMAIN, "distances must satisfy |d| < 2^31")
+    d = np.ascontiguousarray(d, dtype=np.int32)
+    out = np.zeros(max(int(gridsize), 1), dtype=np.float64)
+    _lib.check(_lib.load().cl_kde_array(int(device), d.ctypes.data_as(ctypes.c_void_p), int(d.shape[0]), float(lo), float(step),
+                                        float(inv_h), int(gridsize), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out
 
 
 class Converter(_Handle):

@@ -206,6 +206,11 @@ struct cl_chrom {
     long long cand_n = 0, cand_cap = 0;
     DevBuf hdr;                       // device result headers, 16 ints per slot
     DevBuf k7_cls, k7_parts;          // K7: class per cluster id, per-workgroup partials
+    // K17 (k_sweep.hip): the (|d|, weight) entries of the two distance groups as cl_dist_collect appended them (group 0 from the
+    // front, group 1 from the back of ONE buffer of kde_cap entries) and sorted, counters, sort scratch, the evaluation's partials
+    DevBuf kde_ent, kde_sorted, kde_ctr, kde_tmp, kde_part;
+    int kde_run = -1;                 // `deq` at the cl_dist_collect that filled them (-1: none): valid while no further run completes
+    long long kde_cap = 0, kde_cnt[2] = {0, 0};
     DevBuf sig_tx, sig_ty, sig_tmp, sig_sorttmp, sig_m, sig_win, sig_out;   // K8: sorted PET tables, windows, counts
     DevBuf fp_small, fp_keys, fp_sorted, fp_tmp, fp_pairs;       // K12 (k_fingerprint.hip): scratch of one call, freed when it returns
     DevBuf an_s, an_e, an_dir, an_mask, an_wsum;                 // K13 (k_anchor.hip): anchors, directory, row mask, workgroup totals; kept between calls

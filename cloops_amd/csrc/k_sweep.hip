@@ -573,6 +573,232 @@ extern "C" int cl_dist_bin_hist(cl_chrom* c, int32_t cut, uint32_t lo, uint32_t 
     return CL_OK;
 }
 
+// ==========================================================================================
+// K17: Gaussian kernel density sums of log2|d| (cLoops/cPlots.py:42-75 plotIntSelCutFrag, called at pipe.py:261-267)
+// ==========================================================================================
+// The reference's picture of a step is sns.kdeplot over log2|d| of the `dis` and of the `dss` list: per group the double sum
+// S[j] = sum_i w_i exp(-((x_i - grid_j) / h)^2 / 2) over N distances and G grid points -- the one O(N G) part of the reference.
+// cl_dist_collect packs the (|d|, weight) entries of both groups of the last completed run (one k7_for_each pass: the short PETs of
+// one distance are ONE entry of weight dh[d]) and sorts each list; cl_dist_kde evaluates the UNNORMALISED sums of one group on a
+// grid (additive over chromosomes: the host adds them and normalises once); cl_kde_array runs the same kernel over a host array.
+#define K17_TILE 1024            // entries a workgroup stages in LDS at a time
+#define K17_MAXGRID 1024         // = CL_KDE_MAX_GRID
+#define K17_BLOCKS 1024          // most workgroups (= partial sum vectors) of one evaluation
+struct K17Ctr { unsigned long long n_pos[2]; unsigned cnt[2]; unsigned dmin[2]; unsigned dmax[2]; };
+
+// entries = |d| << 32 | weight.  Group 0 grows from ent[0] upwards, group 1 from ent[cap - 1] downwards: together they hold at
+// most one entry per PET of the run plus one per distance below the cut, which is what `cap` is sized for.  The append order
+// depends on the scheduling (one atomic per wave and group); the lists are sorted before anything is computed from them.
+__global__ void __launch_bounds__(TPB)
+k17_collect(K7Src s, int cut, const signed char* __restrict__ cls, u64* __restrict__ ent, unsigned cap, K17Ctr* __restrict__ ctr)
+{
+    unsigned long long np_[2] = {0ull, 0ull};
+    unsigned mn[2] = {~0u, ~0u}, mx[2] = {0u, 0u};
+    const int lane = threadIdx.x & 63;
+    k7_for_each(s, cut, cls, [&](int g, int ad, int w) {
+        if (ad <= 0) return;                                              // cPlots.py:50-51: d > 0 after np.abs
+        np_[g] += (unsigned long long)w;
+        mn[g] = min(mn[g], (unsigned)ad); mx[g] = max(mx[g], (unsigned)ad);
+        const u64 act = __ballot(1), ones = __ballot(g == 1);
+        const u64 mine = g == 1 ? ones : (act & ~ones);                   // the lanes that append to my list in this call
+        const int leader = __ffsll((unsigned long long)mine) - 1;
+        unsigned base = 0u;
+        if (lane == leader) base = atomicAdd(&ctr->cnt[g], (unsigned)__popcll(mine));
+        base = (unsigned)__shfl((int)base, leader);
+        const unsigned pos = base + (unsigned)__popcll(mine & ((1ull << lane) - 1ull));
+        if (pos < cap) ent[g == 1 ? cap - 1u - pos : pos] = ((u64)(unsigned)ad << 32) | (u64)(unsigned)w;
+    });
+    __shared__ unsigned long long s_n[2][TPB / 64];
+    __shared__ unsigned s_mn[2][TPB / 64], s_mx[2][TPB / 64];
+    for (int g = 0; g < 2; ++g)
+        for (int o = 32; o > 0; o >>= 1) {
+            np_[g] += __shfl_down(np_[g], o);
+            mn[g] = min(mn[g], (unsigned)__shfl_down((int)mn[g], o)); mx[g] = max(mx[g], (unsigned)__shfl_down((int)mx[g], o));
+        }
+    if (lane == 0)
+        for (int g = 0; g < 2; ++g) { s_n[g][threadIdx.x >> 6] = np_[g]; s_mn[g][threadIdx.x >> 6] = mn[g]; s_mx[g][threadIdx.x >> 6] = mx[g]; }
+    __syncthreads();
+    if (threadIdx.x < 2) {                                                // integer totals: exact in any order
+        const int g = threadIdx.x;
+        unsigned long long a = 0ull; unsigned lo = ~0u, hi = 0u;
+        for (int w = 0; w < TPB / 64; ++w) { a += s_n[g][w]; lo = min(lo, s_mn[g][w]); hi = max(hi, s_mx[g][w]); }
+        if (a) { atomicAdd(&ctr->n_pos[g], a); atomicMin(&ctr->dmin[g], lo); atomicMax(&ctr->dmax[g], hi); }
+    }
+}
+
+// S[j] of the entries [0, m) on grid_j = lo + j step, j < G <= NP * 256: workgroup b takes the tiles [b tiles_per, (b + 1) tiles_per)
+// (fixed ranges), stages a tile as (x = log2|d| in double, weight in double) and walks it with every lane reading the same LDS
+// address (a broadcast: no bank conflicts); thread t keeps the sums of the grid points t, t + 256, ... in registers and stores
+// them to row b of `parts`.  x - grid_j and its product with 1 / h are formed in double (in float32 the error of S reaches
+// 2e-4 at h = 0.05); only z, t = (-log2(e) / 2) z z and exp2(t) are float32; weight and accumulation are double again.
+// RAW: the entries are plain int32 distances of weight 1 (the kernel takes |d|; zeros weigh nothing).
+template <int NP, bool RAW>
+__global__ void __launch_bounds__(256)
+k17_kde(const u64* __restrict__ ent, const int* __restrict__ raw, long long m, int tiles_per, double lo, double step, double inv_h, int G,
+        double* __restrict__ parts)
+{
+    __shared__ double l_rcp[128], l_lg[128];
+    __shared__ double2 tile[K17_TILE];
+    const int tid = threadIdx.x;
+    if (tid < 128) { l_rcp[tid] = K7_RCP[tid]; l_lg[tid] = K7_LOG[tid]; }
+    double gj[NP], acc[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) { gj[p] = fma((double)(tid + 256 * p), step, lo); acc[p] = 0.0; }
+    const long long ntiles = (m + K17_TILE - 1) / K17_TILE;
+    const long long t0 = (long long)blockIdx.x * tiles_per, t1 = min(ntiles, t0 + (long long)tiles_per);
+    for (long long t = t0; t < t1; ++t) {
+        const long long base = t * K17_TILE;
+        const int cnt = (int)min((long long)K17_TILE, m - base);
+        __syncthreads();                                                  // the tables are in LDS / the tile before is used up
+        for (int k = tid; k < cnt; k += 256) {
+            unsigned ad, w;
+            if (RAW) { const int d = raw[base + k]; ad = d < 0 ? 0u - (unsigned)d : (unsigned)d; w = ad ? 1u : 0u; }
+            else { const u64 e = ent[base + k]; ad = (unsigned)(e >> 32); w = (unsigned)e; }
+            tile[k] = make_double2(ad ? k7_log2(ad, l_rcp, l_lg) : 0.0, (double)w);
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < cnt; ++k) {
+            const double2 xw = tile[k];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const float z = (float)((xw.x - gj[p]) * inv_h);
+                const float e = __builtin_amdgcn_exp2f((-0.72134752044448170f * z) * z);      // exp(-z z / 2)
+                acc[p] = fma(xw.y, (double)e, acc[p]);
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) { const int j = tid + 256 * p; if (j < G) parts[(size_t)blockIdx.x * G + j] = acc[p]; }
+}
+
+// the partial vectors added in workgroup order, one grid point per thread (fixed order: deterministic)
+__global__ void __launch_bounds__(256)
+k17_reduce(const double* __restrict__ parts, int nparts, int G, double* __restrict__ out)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= G) return;
+    double a = 0.0;
+    for (int b = 0; b < nparts; ++b) a += parts[(size_t)b * G + j];
+    out[j] = a;
+}
+
+static int k17_check_grid(const char* who, double lo, double step, double inv_h, int gridsize, const double* sums)
+{
+    if (!sums) return fail(CL_ERR_ARG, who, "sums is null");
+    if (gridsize < 2 || gridsize > K17_MAXGRID) return fail(CL_ERR_ARG, who, "gridsize must be 2 .. 1024");
+    if (!(lo - lo == 0.0) || !(step - step == 0.0) || !(inv_h > 0.0) || !(inv_h - inv_h == 0.0)) return fail(CL_ERR_ARG, who, "lo, step must be finite and inv_h positive");
+    return CL_OK;
+}
+
+// enqueues the evaluation of m > 0 entries on `stream` and copies the G sums to `sums` (host); the caller synchronises
+static int k17_evaluate(hipStream_t stream, DevBuf& part, const u64* ent, const int* raw, long long m, double lo, double step, double inv_h,
+                        int G, double* sums)
+{
+    const long long ntiles = (m + K17_TILE - 1) / K17_TILE;
+    const long long per = (ntiles + K17_BLOCKS - 1) / K17_BLOCKS;
+    if (per > INT_MAX) return fail(CL_ERR_GRID, "kernel density: too many entries");
+    const int nb = (int)((ntiles + per - 1) / per);
+    int rc;
+    if ((rc = part.ensure(((size_t)nb + 1) * G * sizeof(double)))) return rc;
+    double* parts = part.as<double>();
+    double* out = parts + (size_t)nb * G;
+    const int np = (G + 255) / 256;
+#define K17_GO(NP, RAW) hipLaunchKernelGGL((k17_kde<NP, RAW>), dim3(nb), dim3(256), 0, stream, ent, raw, m, (int)per, lo, step, inv_h, G, parts)
+    if (raw) { if (np == 1) K17_GO(1, true); else if (np == 2) K17_GO(2, true); else if (np == 3) K17_GO(3, true); else K17_GO(4, true); }
+    else { if (np == 1) K17_GO(1, false); else if (np == 2) K17_GO(2, false); else if (np == 3) K17_GO(3, false); else K17_GO(4, false); }
+#undef K17_GO
+    hipLaunchKernelGGL(k17_reduce, dim3(np), dim3(256), 0, stream, (const double*)parts, nb, G, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sums, out, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, stream));
+    return CL_OK;
+}
+
+extern "C" int cl_dist_collect(cl_chrom* c, int32_t cut, int64_t* n_pos, int64_t* dmin, int64_t* dmax)
+{
+    if (!n_pos || !dmin || !dmax) return fail(CL_ERR_ARG, "cl_dist_collect: null argument");
+    for (int g = 0; g < 2; ++g) { n_pos[g] = 0; dmin[g] = 0; dmax[g] = 0; }
+    if (c && c->n == 0) return CL_OK;
+    int rc = k7_prepare(c);
+    if (rc) return rc;
+    if (!c->slot[c->last_slot].sorted_src && !c->slot[c->last_slot].rows_valid) return fail(CL_ERR_ARG, "cl_dist_collect: the last run left no labels");
+    c->kde_run = -1;
+    // one entry per PET of the run at most, plus one per distance below the cut when those come from the distance histogram
+    const long long cap = c->n + 65536;
+    if (cap > (long long)UINT_MAX) return fail(CL_ERR_GRID, "cl_dist_collect: more than 2^32 entries");
+    if ((rc = c->kde_ent.ensure((size_t)cap * 8)) || (rc = c->kde_sorted.ensure((size_t)cap * 8)) || (rc = c->kde_ctr.ensure(sizeof(K17Ctr)))) return rc;
+    K17Ctr h{};
+    h.dmin[0] = h.dmin[1] = ~0u;
+    HIP_TRY(hipMemcpyAsync(c->kde_ctr.p, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k17_collect, dim3(K7_BLOCKS), dim3(TPB), 0, c->stream, k7_source(c, cut), (int)cut, c->k7_cls.as<signed char>(),
+                       c->kde_ent.as<u64>(), (unsigned)cap, c->kde_ctr.as<K17Ctr>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h, c->kde_ctr.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((long long)h.cnt[0] + (long long)h.cnt[1] > cap) return fail(CL_ERR_GRID, "internal: distance entry buffer overrun");
+    // each list sorted by (|d|, weight): equal keys are equal entries, so the sorted lists -- and every sum over them -- are the
+    // same whatever order the waves appended in
+    hipError_t e;
+    for (int g = 0; g < 2; ++g) {                                         // (the sort picks its algorithm by size: ask for both lists)
+        size_t need = 0;
+        e = rocprim::radix_sort_keys(nullptr, need, (u64*)nullptr, (u64*)nullptr, std::max<size_t>(h.cnt[g], 1), 0, 64, c->stream);
+        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query (kde)", hipGetErrorString(e));
+        if ((rc = c->kde_tmp.ensure(std::max<size_t>(need, 16)))) return rc;
+    }
+    for (int g = 0; g < 2; ++g) {
+        if (!h.cnt[g]) continue;
+        const size_t off = g ? (size_t)cap - h.cnt[g] : 0;
+        size_t bytes = c->kde_tmp.bytes;
+        e = rocprim::radix_sort_keys(c->kde_tmp.p, bytes, c->kde_ent.as<u64>() + off, c->kde_sorted.as<u64>() + off, (size_t)h.cnt[g], 0, 64, c->stream);
+        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(kde)", hipGetErrorString(e));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int g = 0; g < 2; ++g) {
+        c->kde_cnt[g] = h.cnt[g];
+        n_pos[g] = (int64_t)h.n_pos[g];
+        if (h.cnt[g]) { dmin[g] = h.dmin[g]; dmax[g] = h.dmax[g]; }
+    }
+    c->kde_cap = cap;
+    c->kde_run = c->deq;
+    return CL_OK;
+}
+
+extern "C" int cl_dist_kde(cl_chrom* c, int group, double lo, double step, double inv_h, int gridsize, double* sums)
+{
+    int rc = k17_check_grid("cl_dist_kde", lo, step, inv_h, gridsize, sums);
+    if (rc) return rc;
+    memset(sums, 0, (size_t)gridsize * sizeof(double));
+    if (group != 0 && group != 1) return fail(CL_ERR_ARG, "cl_dist_kde: group must be 0 (inter-ligation) or 1 (self-ligation)");
+    if (c && c->n == 0) return CL_OK;
+    if ((rc = k7_prepare(c))) return rc;
+    if (c->kde_run != c->deq) return fail(CL_ERR_ARG, "cl_dist_kde: call cl_dist_collect for the last completed run first");
+    const long long m = c->kde_cnt[group];
+    if (m == 0) return CL_OK;
+    const u64* ent = c->kde_sorted.as<u64>() + (group ? (size_t)(c->kde_cap - m) : 0);
+    if ((rc = k17_evaluate(c->stream, c->kde_part, ent, (const int*)nullptr, m, lo, step, inv_h, gridsize, sums))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CL_OK;
+}
+
+extern "C" int cl_kde_array(int device, const int32_t* d_host, int64_t n, double lo, double step, double inv_h, int gridsize, double* sums)
+{
+    int rc = k17_check_grid("cl_kde_array", lo, step, inv_h, gridsize, sums);
+    if (rc) return rc;
+    memset(sums, 0, (size_t)gridsize * sizeof(double));
+    if (n < 0 || (n > 0 && !d_host)) return fail(CL_ERR_ARG, "cl_kde_array: bad arguments");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(CL_ERR_NODEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(CL_ERR_ARG, "cl_kde_array: no such device");
+    if (n == 0) return CL_OK;
+    HIP_TRY(hipSetDevice(device));
+    struct Tmp { DevBuf d, part; ~Tmp() { d.release(); part.release(); } } tmp;
+    if ((rc = tmp.d.ensure((size_t)n * 4))) return rc;
+    HIP_TRY(hipMemcpy(tmp.d.p, d_host, (size_t)n * 4, hipMemcpyHostToDevice));
+    if ((rc = k17_evaluate((hipStream_t)nullptr, tmp.part, (const u64*)nullptr, tmp.d.as<int>(), (long long)n, lo, step, inv_h, gridsize, sums))) return rc;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)nullptr));
+    return CL_OK;
+}
+
 // ---- K10 host entry points -----------------------------------------------------------------------
 extern "C" int cl_cand_reset(cl_chrom* c)
 {

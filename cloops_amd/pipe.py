@@ -602,6 +602,54 @@ def _select_kth(chroms, cut, loghist, ranks, allsum=None, pool=None, fine=None):
     return out
 
 
+def _step_kde(chroms, cut, n_pos, sumx, sumxx, xshift, pool=None, gridsize=None):
+    """The density curves of cPlots.plotIntSelCutFrag for the step whose runs are the last completed ones on `chroms` (K17): per
+    chromosome one collect pass, the genome-wide extremes of |d| and Scott's bandwidth from the step's own sums (n_pos, sumx, sumxx
+    of log2|d| - xshift, both groups) give each group its grid, the unnormalised sums of all chromosomes are added and normalised
+    once.  -> {"grid": float64[2, G], "density": float64[2, G], "n": [n0, n1], "h": [h0, h1]}; a group without a density
+    (fewer than two PETs, or equal distances) has NaN rows."""
+    from . import plots
+    G = int(gridsize or plots.GRIDSIZE)
+
+    def collect(r):
+        with r.lock:
+            return r.chrom.dist_collect(cut)
+
+    cols = _pmap(pool, collect, chroms)
+    grid = np.full((2, G), np.nan)
+    dens = np.full((2, G), np.nan)
+    ns, hs = [], []
+    for g in (0, 1):
+        n = int(n_pos[g])
+        h = plots.scott_bandwidth(n, sumx[g], sumxx[g], xshift)
+        ns.append(n)
+        hs.append(float(h))
+        live = [(r, c) for r, c in zip(chroms, cols) if c["n_pos"][g] > 0]
+        if sum(c["n_pos"][g] for _, c in live) != n:
+            raise RuntimeError("distance entries of group %d: %d collected, %d in the step's statistics" % (g, sum(c["n_pos"][g] for _, c in live), n))
+        if not plots.drawable(n, h):
+            continue
+        lo, step = plots.support(min(c["dmin"][g] for _, c in live), max(c["dmax"][g] for _, c in live), h, G)
+
+        def kde(rc):
+            with rc[0].lock:
+                return rc[0].chrom.dist_kde(g, lo, step, 1.0 / h, G)
+
+        S = np.zeros(G)
+        for part in _pmap(pool, kde, live):                   # (file order: the sum does not depend on which finishes first)
+            S += part
+        grid[g] = plots.grid_points(lo, step, G)
+        dens[g] = plots.density(S, n, h)
+    return {"grid": grid, "density": dens, "n": ns, "h": hs}
+
+
+def _plot_step(kde, cut, prefix, log=None):
+    """`<prefix>.pdf` from a step's curves (cLoops/pipe.py:261-267)"""
+    from . import plots
+    curves = [(kde["grid"][g], kde["density"][g], kde["n"][g]) if np.isfinite(kde["density"][g][0]) else None for g in (0, 1)]
+    plots.plot_cut_curves(curves, cut, prefix, warn=log)
+
+
 SWEEP_THREADS = 8
 #: enqueue the chromosomes of a sweep step from the pool's threads instead of one after the other from the calling thread.
 #: Measured on the 200 M-PET mode-3 sweep: 0.212 s against 0.208 s -- the serial order (largest chromosome first) is worth more
@@ -625,7 +673,7 @@ class _DataI(dict):
 
 
 def runSweepFast(fs, eps, minPts, cut=0, max_cut=False, log=None, variant=None, allsum=None, probe=None, forced_cuts=None, finish_device=False,
-                 device_consumer=None):
+                 device_consumer=None, plot=None):
     """runSweep with the per-step statistics reduced on the GPUs: neither labels nor distance
     lists come back to the host -- per chromosome only the K-row cluster table, a few sums, and
     the 256-bin histograms of an exact radix select for the median (all additive over chromosomes
@@ -653,16 +701,27 @@ def runSweepFast(fs, eps, minPts, cut=0, max_cut=False, log=None, variant=None, 
     it returns is `dataI.gathered` (bench.py: the RCCL gather of the tables to the merging rank).  Without a consumer the caller
     must use the pointers before anything else touches these handles.
 
+    `plot` (optional): a file prefix switches the distance-cutoff pictures of cLoops/pipe.py:261-267 on: every step that estimates
+    a cut also gets st["kde"] = {"grid", "density": float64[2, G], "n", "h"} -- the Gaussian kernel densities of log2|d| of its
+    inter- and self-ligation PETs, summed on the GPUs (K17, cloops_amd.plots) -- st["plot_s"], the wall time of that, and the file
+    `<plot>_eps<ep>_minPts<m>_disCutoff.pdf`.  Nothing is re-clustered for it and the steps, cuts and candidates do not change;
+    with None (the default) not one extra call is made.  Not with `allsum`: the extremes of |d| are no sums (ValueError).
+
     returns (dataI {key: {"f": f, "boxes": int32[k,4]}} of the local chromosomes, cut, cuts, steps)."""
     variant = variant or DBSCAN_VARIANT
+    if plot is not None and allsum is not None:
+        raise ValueError("runSweepFast: plot needs the whole genome on one rank (it cannot be combined with allsum)")
     gsum = allsum if allsum is not None else (lambda a: a)
     devs = _devices()
     with CACHE.pinned(fs, devs) as res_all:
-        return _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gsum, probe, forced_cuts, finish_device, device_consumer)
+        return _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gsum, probe, forced_cuts, finish_device, device_consumer,
+                           plot)
 
 
 def _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gsum, probe=None, forced_cuts=None, finish_device=False,
-                device_consumer=None):
+                device_consumer=None, plot=None):
+    if plot is not None and allsum is not None:
+        raise ValueError("runSweepFast: plot needs the whole genome on one rank (it cannot be combined with allsum)")
     cuts = [cut]
     steps = []
     live = [(f, r) for f, r in zip(fs, res_all) if len(r)]
@@ -830,6 +889,13 @@ def _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gs
                             st["cut_range"] = (int(rc_lo), int(rc_hi))
                             if log and rc_lo != rc_hi:
                                 log("WARNING: the distance statistics of eps=%s,minPts=%s bound the cutoff only to [%s, %s]" % (ep, m, rc_lo, rc_hi))
+                    if plot is not None:
+                        # pipe.py:261-267: the picture of this step's two distance groups with the estimated cut drawn in; the
+                        # handles still hold the step's runs (a re-check above repeated them with the same parameters)
+                        t_plot0 = time.perf_counter()
+                        st["kde"] = _step_kde(used, step_cut, tot["n_pos"], gf[0:2], gf[2:4], xshift, pool)
+                        _plot_step(st["kde"], cut_2, "%s_eps%s_minPts%s_disCutoff" % (plot, ep, m), log)
+                        st["plot_s"] = time.perf_counter() - t_plot0
                     if log:
                         log("Estimated inter-ligation and self-ligation distance cutoff as %s for eps=%s,minPts=%s" % (cut_2, ep, m))
                     if forced_cuts is not None and forced_cuts[this_step] is not None:
@@ -936,7 +1002,7 @@ def runSweep(fs, eps, minPts, cut=0, cpu=1, max_cut=False, log=None):
 
 
 # ---------------------------------------------------------------------------------------
-# the whole flow of cLoops/pipe.py:206-295 (minus the plots)
+# the whole flow of cLoops/pipe.py:206-295
 # ---------------------------------------------------------------------------------------
 MODES = {1: ([500, 1000, 2000], [5], 0), 2: ([1000, 2000, 5000], [5], 0),
          3: ([5000, 7500, 10000], [50, 40, 30, 20], 1), 4: ([2500, 5000, 7500, 10000], [30, 20], 1)}   # pipe.py:329-344
@@ -969,7 +1035,8 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
-    Differences to the reference, all outside the hot path: no plots (`plot` is accepted and ignored).  `washU` /
+    `plot` writes `<fout>_eps<ep>_minPts<m>_disCutoff.pdf` for every step that estimates a cut (pipe.py:261-267; the densities
+    are summed on the GPU and are those of seaborn under Python 3, cloops_amd.plots / INTEGRATION.md).  `washU` /
     `juice` write `<fout>_loops_washU.txt` / `<fout>_loops_juicebox.txt` after `<fout>.loop` (pipe.py:288-292, cloops_amd.tracks).
     `eps == 0` estimates eps from the distances of the PETs mapped to different strands (io.py:62-129, ests.py:23-33).
     `reader`: "gpu" reads the BEDPE files on the device (K16, cloops_amd.ingest): the chromosomes go from the text to HBM
@@ -1002,7 +1069,7 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
         if auto_eps:
             from .ests import estFragSize
             eps = [estFragSize(ds) * 2]
-        dataI, cut, cuts, steps = runSweepFast(cfs, eps, minPts, cut=cut, max_cut=max_cut, log=log)
+        dataI, cut, cuts, steps = runSweepFast(cfs, eps, minPts, cut=cut, max_cut=max_cut, log=log, plot=fout if plot else None)
         records = {key: {"f": v["f"], "records": _records(key, v["boxes"])} for key, v in dataI.items()}
         e = cModel.runStat(records, minPts, 0, cpu, fout, hic)    # pipe.py:284 passes cut = 0
     finally:
@@ -1024,7 +1091,7 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
 
 def main(argv=None):
     """`python -m cloops_amd -f a.bedpe.gz -o out -m 1` -- the flags of cLoops/utils.py:73-204 that
-    drive the hot path (same names; -w / -j write the loop tracks, -plot is accepted and ignored)."""
+    drive the hot path (same names; -w / -j write the loop tracks, -plot the distance-cutoff picture of every sweep step)."""
     import argparse
     ap = argparse.ArgumentParser(prog="cloops_amd")
     ap.add_argument("-f", dest="fnIn", required=True)

@@ -196,6 +196,28 @@ int cl_dist_summary(cl_chrom* c, int32_t cut, cl_dsummary* out);
 int cl_dist_bin_hist(cl_chrom* c, int32_t cut, uint32_t lo, uint32_t hi, int shift, uint64_t* hist2048);
 
 /*
+ * Kernel density sums of log2|d| (kernel K17) -- the curves of cLoops/cPlots.py:42-75 (plotIntSelCutFrag: sns.kdeplot of
+ * log2|d| over d != 0 of `dis` and of `dss`), which cLoops/pipe.py:261-267 draws for every step under -plot.  Same groups and
+ * same `cut` as cl_dist_summary.
+ *   cl_dist_collect : ONE pass over the last completed run: the entries (|d|, weight) with |d| > 0 of both groups go to
+ *                     device lists the handle keeps (all PETs under the cut of one distance are one weighted entry), each
+ *                     list sorted, so that everything computed from it is the same from call to call.  n_pos[2] = PETs
+ *                     with d != 0 per group, dmin[2] / dmax[2] = smallest / largest |d| > 0 (0 for an empty group).
+ *   cl_dist_kde     : sums[j] = sum_i w_i exp(-((log2|d_i| - grid_j) inv_h)^2 / 2) over the collected entries of `group`,
+ *                     grid_j = lo + j step, 0 <= j < gridsize, 2 <= gridsize <= CL_KDE_MAX_GRID.  UNNORMALISED, hence
+ *                     additive over chromosomes: density = sum over chromosomes / (n h sqrt(2 pi)) with h = 1 / inv_h.
+ *                     The difference and its product with inv_h are formed in double, the exponential in float32, weight
+ *                     and sum in double: relative error below 4e-5.  Two calls on one run return identical arrays.
+ *                     Needs cl_dist_collect after the last completed run (CL_ERR_ARG otherwise).
+ *   cl_kde_array    : the same sums over a host array of n int32 distances, each of weight 1 (|d| is taken, zeros are
+ *                     dropped), without a chromosome handle: what cPlots.plotIntSelCutFrag(di, ds, ...) runs on.
+ */
+#define CL_KDE_MAX_GRID 1024
+int cl_dist_collect(cl_chrom* c, int32_t cut, int64_t* n_pos, int64_t* dmin, int64_t* dmax);
+int cl_dist_kde(cl_chrom* c, int group, double lo, double step, double inv_h, int gridsize, double* sums);
+int cl_kde_array(int device, const int32_t* d_host, int64_t n, double lo, double step, double inv_h, int gridsize, double* sums);
+
+/*
  * Interval counting for the significance test of candidate loops (cLoops/cModel.py:60-80,108-143):
  * for every record, 11 A windows (the anchor iva + the 10 shifted windows of getNearbyPairRegions,
  * cModel.py:83-105) and 11 B windows, each [lo, hi] inclusive.  `windows`: n_records x 44 int32 laid
