@@ -28,9 +28,10 @@ VARIANT_BLOCK = 3
 # compares every one with the header)
 CL_TRACK_WASHU, CL_TRACK_JUICE = 0, 1
 CL_TRACK_NAME_MAX = 64
-CL_CONV_HICPRO, CL_CONV_JUICER = 0, 1
+CL_CONV_HICPRO, CL_CONV_JUICER, CL_CONV_PAIRS = 0, 1, 2
 CL_CONV_E_FIELDS, CL_CONV_E_INT, CL_CONV_E_RANGE, CL_CONV_E_LONG = 1, 2, 3, 4
 CL_INGEST_TIMES = 6
+CL_INGEST_BEDPE, CL_INGEST_PAIRS = 0, 1
 DIST_LOGBINS = 3840          # CL_DIST_LOGBINS
 CL_KDE_MAX_GRID = 1024
 
@@ -112,7 +113,10 @@ PROTOTYPES = {
     "cl_conv_timing": (_int, [_vp, _f32p]),
     "cl_conv_destroy": (_int, [_vp]),
     "cl_ingest_create": (_int, [_int, _vp, _i64, _i64, _i32, _vpp]),
+    "cl_ingest_set_format": (_int, [_vp, _i32, _i64]),
     "cl_ingest_feed": (_int, [_vp, _vp, _i64, _i64p, _i64p, _i64p]),
+    "cl_ingest_error": (_int, [_vp, _i64p, _i32p]),
+    "cl_ingest_headers": (_int, [_vp, _i64p]),
     "cl_ingest_names": (_int, [_vp, _vp, _i64, _i64p]),
     "cl_ingest_commit": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i32p]),
     "cl_ingest_finish": (_int, [_vp, _vp, _i32, _i32, _vp, _i64p]),

@@ -594,18 +594,21 @@ def kde_array(d, lo, step, inv_h, gridsize, device=0):
 
 class Converter(_Handle):
     """K15: a pairs-to-BEDPE converter on the device (cl_conv of include/cloops_hip.h), shaped like Chromosome.track_*: feed a chunk of
-    complete lines, render their BEDPE text.  fmt "hicpro" (scripts/hicpropairs2bedpe) or "juicer" (scripts/juicerLong2bedpe.py)."""
-    FORMATS = {"hicpro": _lib.CL_CONV_HICPRO, "juicer": _lib.CL_CONV_JUICER}
+    complete lines, render their BEDPE text.  fmt "hicpro" (scripts/hicpropairs2bedpe), "juicer" (scripts/juicerLong2bedpe.py) or
+    "pairs" (4DN pairs: hicpro's rule on other columns, no script of the reference)."""
+    FORMATS = {"hicpro": _lib.CL_CONV_HICPRO, "juicer": _lib.CL_CONV_JUICER}      # the two scripts of the reference
+    OWN_FORMATS = {"pairs": _lib.CL_CONV_PAIRS}
     KINDS = {_lib.CL_CONV_E_FIELDS: "fewer than 7 fields", _lib.CL_CONV_E_INT: "not an integer", _lib.CL_CONV_E_RANGE: "integer outside int64",
              _lib.CL_CONV_E_LONG: "line longer than the chunk budget"}
     BUDGET = 64 << 20                              # default bytes per chunk
     _DESTROY = "cl_conv_destroy"
 
     def __init__(self, fmt, ext, budget=BUDGET, device=0, stream=None):
-        if fmt not in self.FORMATS:
-            raise ValueError("unknown pairs format %r (hicpro or juicer)" % (fmt,))
+        formats = dict(self.FORMATS, **self.OWN_FORMATS)
+        if fmt not in formats:
+            raise ValueError("unknown pairs format %r (hicpro, juicer or pairs)" % (fmt,))
         self.fmt, self.ext, self.budget = fmt, int(ext), int(budget)
-        self._open("cl_conv_create", int(device), ctypes.c_void_p(stream), self.FORMATS[fmt], self.ext, self.budget)
+        self._open("cl_conv_create", int(device), ctypes.c_void_p(stream), formats[fmt], self.ext, self.budget)
 
     def feed(self, ptr, n, last):
         """the complete lines of the n bytes at host address `ptr` (all of them with `last`) -> (bytes consumed, lines converted,
@@ -639,14 +642,23 @@ class Converter(_Handle):
 class Ingest(_Handle):
     """K16: a BEDPE reader on the device (cl_ingest of include/cloops_hip.h), shaped like Converter: feed a chunk of complete lines,
     read its distinct chromosome names, commit the host's table for them; finish joins two handles and leaves every chromosome's
-    mid-points in HBM."""
+    mid-points in HBM.  fmt "pairs" (K18) reads 4DN pairs text as the BEDPE that Converter("pairs", ext) makes of it."""
+    FORMATS = {"bedpe": _lib.CL_INGEST_BEDPE, "pairs": _lib.CL_INGEST_PAIRS}
     TIMES = ("h2d", "index", "parse", "names", "commit", "finish")       # CL_INGEST_TIMES of them
     BUDGET = 64 << 20                              # default bytes per chunk
     _DESTROY = "cl_ingest_destroy"
 
-    def __init__(self, budget=BUDGET, cut=0, want_distances=False, device=0, stream=None):
-        self.device, self.budget = int(device), int(budget)
+    def __init__(self, budget=BUDGET, cut=0, want_distances=False, device=0, stream=None, fmt="bedpe", ext=0):
+        if fmt not in self.FORMATS:
+            raise ValueError("unknown input format %r (bedpe or pairs)" % (fmt,))
+        self.device, self.budget, self.fmt, self.ext = int(device), int(budget), fmt, int(ext)
         self._open("cl_ingest_create", int(device), ctypes.c_void_p(stream), self.budget, int(cut), int(bool(want_distances)))
+        if fmt != "bedpe":
+            try:
+                _lib.check(self._lib.cl_ingest_set_format(self._h, self.FORMATS[fmt], self.ext))
+            except BaseException:
+                self.close()
+                raise
 
     def feed(self, ptr, n):
         """the n bytes of complete lines at host address `ptr` -> (lines, first exotic line or -1, distinct names or -1 for too
@@ -654,6 +666,21 @@ class Ingest(_Handle):
         nl, ex, nn = ctypes.c_int64(0), ctypes.c_int64(-1), ctypes.c_int64(0)
         _lib.check(self._lib.cl_ingest_feed(self._h, ctypes.c_void_p(ptr), int(n), ctypes.byref(nl), ctypes.byref(ex), ctypes.byref(nn)))
         return int(nl.value), int(ex.value), int(nn.value)
+
+    def error(self):
+        """pairs: the first line of the last feed the converter raises on -> (line in the feed, 1-based, headers counted; reason), or
+        None  (cl_ingest_error)"""
+        line, kind = ctypes.c_int64(0), ctypes.c_int32(0)
+        _lib.check(self._lib.cl_ingest_error(self._h, ctypes.byref(line), ctypes.byref(kind)))
+        if line.value == 0:
+            return None
+        return int(line.value), Converter.KINDS.get(int(kind.value), "error %d" % kind.value)
+
+    def headers(self):
+        """pairs: the header lines among the last feed's lines  (cl_ingest_headers)"""
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_ingest_headers(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def names(self, n):
         """the last feed's distinct names -> [(hash, first line, offset, length)], by first line  (cl_ingest_names)"""

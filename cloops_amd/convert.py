@@ -1,5 +1,6 @@
 """Pairs files to BEDPE: scripts/hicpropairs2bedpe (pairs2bedpe) and scripts/juicerLong2bedpe.py (long2bedpe), function for
-function, and both scripts as `python -m cloops_amd.convert hicpro|juicer`.
+function, and both scripts as `python -m cloops_amd.convert hicpro|juicer`; `python -m cloops_amd.convert pairs` converts 4DN
+pairs files (cloops_amd.pairs, which builds on the pipeline below).
 
 The reference reads one line at a time in Python.  Here a reader thread reads (or inflates) the input straight into page-locked
 buffers of a byte budget, cut after the last newline (the tail goes in front of the next chunk); kernel K15 indexes, parses and
@@ -273,7 +274,15 @@ def _threads(threads):
     return threads
 
 
-def _convert(fmt, fin, fout, ext, gz_in, gz_out, threads, budget, device, stats):
+def _tapped(write, tap):
+    def both(text):
+        tap(text)
+        write(text)
+    return both if tap is not None else write
+
+
+def _convert(fmt, fin, fout, ext, gz_in, gz_out, threads, budget, device, stats, tap=None):
+    """tap(text): sees every chunk's text before it is written (cloops_amd.pairs counts its lines)"""
     stats = stats if stats is not None else collections.Counter()
     seam = make_seam(fmt, ext, budget, device)
     try:
@@ -282,13 +291,13 @@ def _convert(fmt, fin, fout, ext, gz_in, gz_out, threads, budget, device, stats)
             if gz_out:
                 gzw = _GzWriter(fo, threads)
                 try:
-                    lines, nbytes, err, line = _run(src, seam, budget, gzw.write, stats)
+                    lines, nbytes, err, line = _run(src, seam, budget, _tapped(gzw.write, tap), stats)
                 finally:
                     t0 = time.perf_counter()
                     gzw.close()
                     stats["write"] += time.perf_counter() - t0
             else:
-                lines, nbytes, err, line = _run(src, seam, budget, fo.write, stats)
+                lines, nbytes, err, line = _run(src, seam, budget, _tapped(fo.write, tap), stats)
     finally:
         for key, v in getattr(seam, "ms", {}).items():
             stats["device_ms_" + key] += v
@@ -335,7 +344,7 @@ def bedpe_name(f, out_dir=None):
 
 def _help(argv):
     ap = argparse.ArgumentParser(prog="python -m cloops_amd.convert",
-                                 description="Convert pairs files to BEDPE for cLoops (scripts hicpropairs2bedpe / juicerLong2bedpe.py) on MI355X.")
+                                 description="Convert pairs files to BEDPE for cLoops (scripts hicpropairs2bedpe / juicerLong2bedpe.py, 4DN pairs) on MI355X.")
     sub = ap.add_subparsers(dest="cmd", required=True)
     h = sub.add_parser("hicpro", help="Convert hicpro allValidPairs file to bedpe format for cLoops")
     h.add_argument(dest="input", nargs="+", type=str,
@@ -350,8 +359,15 @@ def _help(argv):
     j = sub.add_parser("juicer", help="Convert Juicer long format file to bedpe format for cLoops")
     j.add_argument("-i", "--input", dest="fin", required=True, type=str, help="Input file name, required.")
     j.add_argument("-o", "--out", dest="fout", required=True, type=str, help="Output file name, required.")
+    q = sub.add_parser("pairs", help="Convert 4DN pairs files (.pairs, .pairs.gz) to bedpe format for cLoops")
+    q.add_argument(dest="input", nargs="+", type=str, help="4DN pairs files, plain or gzipped (with additional .gz suffix).")
+    q.add_argument("-o", "--out", dest="out", required=False, type=str,
+                   help="Output directory. If specified all converted bedpe file will be put inside this folder rather than the same folder of respective input file.")
+    q.add_argument("-ext", dest="ext", required=False, type=int, default=50, help="Extension from the position of each read, default is 50. ")
+    q.add_argument("-p", dest="threads", required=False, type=int, default=THREADS,
+                   help="Threads compressing the gzip output, 1 .. %d, default is %d." % (MAX_THREADS, THREADS))
     op = ap.parse_args(argv)
-    if op.cmd == "hicpro" and not 1 <= op.threads <= MAX_THREADS:
+    if op.cmd in ("hicpro", "pairs") and not 1 <= op.threads <= MAX_THREADS:
         ap.error("-p must be 1 .. %d" % MAX_THREADS)
     return op
 
@@ -361,15 +377,24 @@ def main(argv=None):
     start = datetime.now()
     op = _help(argv)
     try:
-        if op.cmd == "hicpro":
+        if op.cmd in ("hicpro", "pairs"):
             if op.out is not None:
                 if os.path.isfile(op.out):
                     sys.stderr.write("Error: file %s exists, unable to create output folder\n" % op.out)
                     return 1
                 if not os.path.isdir(op.out):
                     os.makedirs(op.out)
+        if op.cmd == "hicpro":
             for f in hicpro_inputs(op.input):
                 pairs2bedpe(f, bedpe_name(f, op.out), ext=op.ext, threads=op.threads)
+        elif op.cmd == "pairs":
+            from . import pairs
+            for f in op.input:
+                if not os.path.isfile(f):
+                    sys.stderr.write("Error: input file %s not exists!\n" % f)
+                    return 1
+            for f in op.input:
+                pairs.pairs2bedpe(f, pairs.bedpe_name(f, op.out), ext=op.ext, threads=op.threads)
         else:
             if not os.path.isfile(op.fin):
                 sys.stderr.write("Error: input file %s not exists!\n" % op.fin)

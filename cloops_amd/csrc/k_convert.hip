@@ -1,9 +1,10 @@
 // k_convert.hip -- K15: the pairs-to-BEDPE converters of the reference (scripts/hicpropairs2bedpe, scripts/juicerLong2bedpe.py) on
 // the device: a line index over raw bytes, a field tokenizer with exact integer parsing, and a lane-per-line renderer -- kernels and
-// the C entry points of the cl_conv handle.
+// the C entry points of the cl_conv handle.  CL_CONV_PAIRS (4DN pairs text, no script of the reference) is the HiC-Pro rule on
+// other columns, with '#' header lines.
 #include "cl_chrom.h"
 #include "cl_text.h"
-#include "cl_lines.h"
+#include "cl_pairs.h"
 
 // ==========================================================================================
 // K15: one chunk of complete lines per cl_conv_feed, its text made by cl_conv_render
@@ -25,76 +26,48 @@
 // an integer is optional whitespace, an optional sign, ASCII digits, optional whitespace, and must fit int64 with +-ext applied.
 #define K15_T 256                                // lines per parse / render workgroup (one per lane)
 #define K15_LDS (40 * 1024)                      // bytes of a staged input or output tile: 4 workgroups per CU
+#define K15_HEADER 4u                            // K15Rec.flags: a '#' line of a pairs file (a record of no text)
 
 struct K15Rec {                                  // one parsed line
-    u32 off[5], len[5];                          // copied fields (chunk offsets): hicpro f0 f1 f3 f4 f6; juicer f1 f5
+    u32 off[5], len[5];                          // copied fields (chunk offsets): hicpro f0 f1 f3 f4 f6; pairs f0 f1 f5 f3 f6; juicer f1 f5
     long long v[4];                              // the four printed integers
-    u32 flags;                                   // juicer: bit 0 / 1 = field 0 / 4 is "0"; a bad line: its error kind << 8
+    u32 flags;                                   // juicer: bit 0 / 1 = field 0 / 4 is "0"; pairs: K15_HEADER; a bad line: its error kind << 8
     u32 pad;
 };
 
-__device__ __forceinline__ bool k15_ws(u32 c) { return c == 32u || (c >= 9u && c <= 13u); }
-
-// Python 2's int() of the bytes [s, e), bounded to int64 -> 0 and v, or the error kind
-__device__ __forceinline__ int k15_int(K15Rd& rd, long long s, long long e, long long& v)
+// the copied fields and the output length of a tab-separated line whose ends are v: f0, chromosome A, strand A, chromosome B, strand B
+__device__ __forceinline__ void k15_tab_rec(const long long* fs, const long long* fe, int c1, int s1, int c2, int s2, const long long* v, K15Rec& r,
+                                            long long& olen)
 {
-    while (s < e && k15_ws(rd.at(s))) ++s;
-    while (e > s && k15_ws(rd.at(e - 1))) --e;
-    bool neg = false;
-    if (s < e) {
-        const u32 c = rd.at(s);
-        if (c == '+' || c == '-') { neg = c == '-'; ++s; }
-    }
-    if (s >= e) return CL_CONV_E_INT;
-    const u64 lim = neg ? (1ull << 63) : (1ull << 63) - 1;
-    u64 m = 0;
-    bool over = false;
-    for (; s < e; ++s) {
-        const u32 d = rd.at(s) - (u32)'0';
-        if (d > 9) return CL_CONV_E_INT;                              // ValueError before any overflow
-        if (m > (lim - d) / 10) over = true;
-        else m = m * 10 + d;
-    }
-    if (over) return CL_CONV_E_RANGE;
-    v = neg ? (long long)(0ull - m) : (long long)m;
-    return 0;
+    const int f[5] = {0, c1, s1, c2, s2};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { r.off[k] = (u32)fs[f[k]]; r.len[k] = (u32)(fe[f[k]] - fs[f[k]]); }
+    r.v[0] = v[0]; r.v[1] = v[1]; r.v[2] = v[2]; r.v[3] = v[3];
+    r.flags = 0;
+    olen = (long long)r.len[0] + r.len[1] + r.len[2] + r.len[3] + r.len[4] + cl_width(v[0]) + cl_width(v[1]) + cl_width(v[2]) + cl_width(v[3]) + 11;
 }
 
 // scripts/hicpropairs2bedpe:15-34: line.strip().split('\t'); A from f1, f2, f3 and B from f4, f5, f6; f0 . f3 f6 copied
 __device__ __forceinline__ int k15_hicpro(K15Rd& rd, long long s, long long e, long long ext, K15Rec& r, long long& olen)
 {
-    while (e > s && k15_ws(rd.at(e - 1))) --e;
-    while (s < e && k15_ws(rd.at(s))) ++s;
-    long long fs[7], fe[7];
-    long long q = s;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        if (k > 0) { ok = ok && q < e; ++q; }                        // the '\t' that ended field k - 1
-        fs[k] = q;
-        if (ok)
-            while (q < e && rd.at(q) != '\t') ++q;
-        fe[k] = q;
-    }
-    if (!ok) return CL_CONV_E_FIELDS;
-    long long p1 = 0, p2 = 0;
-    int bad = k15_int(rd, fs[2], fe[2], p1);
-    if (!bad) bad = k15_int(rd, fs[5], fe[5], p2);
+    long long fs[7], fe[7], v[4];
+    if (!k15_tabs7(rd, s, e, fs, fe)) return CL_CONV_E_FIELDS;
+    const int bad = k15_ends<2, 3, 5, 6>(rd, fs, fe, ext, v);
     if (bad) return bad;
-    const bool plus1 = fe[3] - fs[3] == 1 && rd.at(fs[3]) == '+';
-    const bool plus2 = fe[6] - fs[6] == 1 && rd.at(fs[6]) == '+';
-    long long a1 = p1, a2 = p1, b1 = p2, b2 = p2;
-    bool ovf = plus1 ? __builtin_add_overflow(p1, ext, &a2) : __builtin_sub_overflow(p1, ext, &a1);
-    ovf |= plus2 ? __builtin_add_overflow(p2, ext, &b2) : __builtin_sub_overflow(p2, ext, &b1);
-    if (ovf) return CL_CONV_E_RANGE;
-    r.off[0] = (u32)fs[0]; r.len[0] = (u32)(fe[0] - fs[0]);
-    r.off[1] = (u32)fs[1]; r.len[1] = (u32)(fe[1] - fs[1]);
-    r.off[2] = (u32)fs[3]; r.len[2] = (u32)(fe[3] - fs[3]);
-    r.off[3] = (u32)fs[4]; r.len[3] = (u32)(fe[4] - fs[4]);
-    r.off[4] = (u32)fs[6]; r.len[4] = (u32)(fe[6] - fs[6]);
-    r.v[0] = a1; r.v[1] = a2; r.v[2] = b1; r.v[3] = b2;
-    r.flags = 0;
-    olen = (long long)r.len[0] + r.len[1] + r.len[2] + r.len[3] + r.len[4] + cl_width(a1) + cl_width(a2) + cl_width(b1) + cl_width(b2) + 11;
+    k15_tab_rec(fs, fe, 1, 3, 4, 6, v, r, olen);
+    return 0;
+}
+
+// 4DN pairs (readID chr1 pos1 chr2 pos2 strand1 strand2): the rule above on f0 f1 f2 f5 f3 f4 f6; a line whose first byte is '#'
+// is a header line: no text
+__device__ __forceinline__ int k15_pairs(K15Rd& rd, long long s, long long e, long long ext, K15Rec& r, long long& olen)
+{
+    if (s < e && rd.at(s) == '#') { r.flags = K15_HEADER; olen = 0; return 0; }
+    long long fs[7], fe[7], v[4];
+    if (!k15_tabs7(rd, s, e, fs, fe)) return CL_CONV_E_FIELDS;
+    const int bad = k15_ends<2, 5, 4, 6>(rd, fs, fe, ext, v);
+    if (bad) return bad;
+    k15_tab_rec(fs, fe, 1, 5, 3, 6, v, r, olen);
     return 0;
 }
 
@@ -139,6 +112,7 @@ __device__ __forceinline__ int k15_juicer(K15Rd& rd, long long s, long long e, l
 template <int FMT>
 __device__ __forceinline__ int k15_line(K15Rd& rd, long long s, long long e, long long ext, K15Rec& r, long long& olen)
 {
+    if (FMT == CL_CONV_PAIRS) return k15_pairs(rd, s, e, ext, r, olen);
     return FMT == CL_CONV_HICPRO ? k15_hicpro(rd, s, e, ext, r, olen) : k15_juicer(rd, s, e, ext, r, olen);
 }
 
@@ -196,7 +170,8 @@ template <int FMT>
 __device__ __forceinline__ void k15_emit(char* d, int p, const uint4* in, const K15Rec& r)
 {
     K15Rd rd{(const u64*)in, 0, -1, 0};
-    if (FMT == CL_CONV_HICPRO) {                                       // A0 A1 A2 B0 B1 B2 f0 . f3 f6
+    if (FMT == CL_CONV_PAIRS && (r.flags & K15_HEADER)) return;
+    if (FMT != CL_CONV_JUICER) {                                       // A0 A1 A2 B0 B1 B2 f0 . sA sB (hicpro f3 f6, pairs f5 f6)
         p = k15_copy(d, p, rd, r.off[1], r.len[1]); d[p++] = '\t';
         p = cl_put(d, p, r.v[0]); d[p++] = '\t';
         p = cl_put(d, p, r.v[1]); d[p++] = '\t';
@@ -286,7 +261,7 @@ extern "C" int cl_conv_create(int device, void* stream, int32_t format, int64_t 
 {
     if (!out) return fail(CL_ERR_ARG, "cl_conv_create: out is null");
     *out = nullptr;
-    if (format != CL_CONV_HICPRO && format != CL_CONV_JUICER) return fail(CL_ERR_ARG, "cl_conv_create: unknown format");
+    if (format != CL_CONV_HICPRO && format != CL_CONV_JUICER && format != CL_CONV_PAIRS) return fail(CL_ERR_ARG, "cl_conv_create: unknown format");
     if (budget < 1 || budget > CL_CONV_BUDGET_MAX) return fail(CL_ERR_ARG, "cl_conv_create: budget outside 1 .. CL_CONV_BUDGET_MAX");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(CL_ERR_NODEVICE, "no HIP device visible");
@@ -356,6 +331,9 @@ static int conv_feed(cl_conv* c, const char* bytes, long long cut, long long* co
     const unsigned grid = (unsigned)((L + K15_T - 1) / K15_T);
     if (c->fmt == CL_CONV_HICPRO)
         hipLaunchKernelGGL(k15_parse<CL_CONV_HICPRO>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
+                           c->rec.as<K15Rec>(), c->len.as<long long>(), c->err.as<int>());
+    else if (c->fmt == CL_CONV_PAIRS)
+        hipLaunchKernelGGL(k15_parse<CL_CONV_PAIRS>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
                            c->rec.as<K15Rec>(), c->len.as<long long>(), c->err.as<int>());
     else
         hipLaunchKernelGGL(k15_parse<CL_CONV_JUICER>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
@@ -435,7 +413,7 @@ extern "C" int cl_conv_render(cl_conv* c, char* out, int64_t cap, int64_t* n_byt
     if (!n_bytes || (!out && c->nbytes > 0)) return fail(CL_ERR_ARG, "cl_conv_render: bad arguments");
     if (!c->fed) return fail(CL_ERR_ARG, "cl_conv_render: no feed to render");
     if (cap < c->nbytes) return fail(CL_ERR_ARG, "cl_conv_render: capacity below the feed's bytes");
-    if (c->R == 0) return CL_OK;
+    if (c->R == 0 || c->nbytes == 0) return CL_OK;                      // no lines, or header lines only
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = c->out.ensure((size_t)c->nbytes + 16))) return rc;
@@ -443,6 +421,9 @@ extern "C" int cl_conv_render(cl_conv* c, char* out, int64_t cap, int64_t* n_byt
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     if (c->fmt == CL_CONV_HICPRO)
         hipLaunchKernelGGL(k15_render<CL_CONV_HICPRO>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),
+                           c->end.as<long long>(), c->R, c->out.as<char>());
+    else if (c->fmt == CL_CONV_PAIRS)
+        hipLaunchKernelGGL(k15_render<CL_CONV_PAIRS>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),
                            c->end.as<long long>(), c->R, c->out.as<char>());
     else
         hipLaunchKernelGGL(k15_render<CL_CONV_JUICER>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),

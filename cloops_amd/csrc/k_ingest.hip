@@ -1,7 +1,8 @@
 // k_ingest.hip -- K16: the BEDPE reader of the reference (cLoops/io.py:62-189, parseRawBedpe / parseRawBedpe2, restated by
-// cloops_amd/io.py:parse_bedpe) on the device -- kernels and the C entry points of the cl_ingest handle.
+// cloops_amd/io.py:parse_bedpe) on the device -- kernels and the C entry points of the cl_ingest handle.  K18: the same reader fed
+// with 4DN pairs text (cl_ingest_set_format), every data line read as the BEDPE line K15 writes for it.
 #include "cl_chrom.h"
-#include "cl_lines.h"
+#include "cl_pairs.h"
 
 // ==========================================================================================
 // K16: one chunk of complete lines per cl_ingest_feed; its PETs appended by cl_ingest_commit; the chromosomes made by cl_ingest_finish
@@ -33,12 +34,13 @@
 #define K16_KEPT 1u
 #define K16_STRANDS 2u
 #define K16_EXOTIC 4u
+#define K16_HEADER 8u                            // pairs: a '#' line (no PET; it does not count in the lines of the read)
 
 struct K16Rec {                                  // one parsed line
     long long cA, cB;                            // the mid-points, left one first
     u64 hash;                                    // of the chromosome name (never 0)
     u32 off, len;                                // the name in the chunk
-    u32 flags, pad;
+    u32 flags, pad;                              // pairs, a line the converter raises on: its CL_CONV_E_* kind << 8
 };
 
 struct K16Name { u64 hash; u32 first, off, len, pad; };                // what the host reads per distinct name of a chunk
@@ -64,6 +66,13 @@ __device__ __forceinline__ int k16_int(K15Rd& rd, long long s, long long e, long
         return 0;
     }
     return plain ? 1 : 2;
+}
+
+// the last step of a name's hash (FNV-1a over its bytes before): never 0
+__device__ __forceinline__ u64 k16_hash_end(u64 h)
+{
+    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+    return h ? h : 1;
 }
 
 // one line [s, e) (e: its '\n') -> its record
@@ -110,8 +119,7 @@ __device__ __forceinline__ void k16_line(K15Rd& rd, long long s, long long e, lo
         star = star || (q - f0 == 1 && b0 == '*');
         minus1 = minus1 || (q - f0 == 2 && b0 == '-' && b1 == '1');
     }
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-    r.hash = h ? h : 1;
+    r.hash = k16_hash_end(h);
     r.off = (u32)fs[0];
     r.len = (u32)(fe[0] - fs[0]);
     r.cA = r.cB = 0;
@@ -145,13 +153,82 @@ __device__ __forceinline__ void k16_line(K15Rd& rd, long long s, long long e, lo
     r.flags = flags | (exotic ? K16_EXOTIC : 0u);
 }
 
-// lines [256 b, 256 b + 256) of the chunk -> their records; the first exotic line -> *err
+// K18: one line [s, e) of a 4DN pairs file -> the record k16_line makes of the BEDPE line that K15 (CL_CONV_PAIRS, `ext`) writes for
+// it, `A0 A1 A2 B0 B1 B2 f0 . f5 f6` -> 0, or the kind of the error the converter raises on it (the record is not kept then)
+__device__ __forceinline__ int k18_line(K15Rd& rd, long long s, long long e, long long cut, long long ext, K16Rec& r)
+{
+    r.cA = r.cB = 0;
+    r.hash = 1;
+    r.off = r.len = 0;
+    r.pad = 0;
+    if (s < e && rd.at(s) == '#') { r.flags = K16_HEADER; return 0; }
+    long long fs[7], fe[7], v[4];
+    int kind = k15_tabs7(rd, s, e, fs, fe) ? 0 : CL_CONV_E_FIELDS;
+    if (!kind) kind = k15_ends<2, 5, 4, 6>(rd, fs, fe, ext, v);
+    if (kind) { r.flags = (u32)kind << 8; return kind; }
+    bool exotic = false;                                                // what Python 3's text mode would change in the copied bytes
+    for (long long q = s, qe = e > s && rd.at(e - 1) == '\r' ? e - 1 : e; q < qe; ++q) {
+        const u32 c = rd.at(q);
+        exotic = exotic || c >= 0x80u || c == '\r';
+    }
+    const long long big = 1ll << 62;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) exotic = exotic || v[k] >= big || v[k] <= -big;
+    bool star = false, minus1 = v[0] == -1 || v[1] == -1 || v[2] == -1 || v[3] == -1;
+    const int copied[5] = {0, 1, 3, 5, 6};                              // the fields of the BEDPE line that are not integers
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const long long f0 = fs[copied[k]], n = fe[copied[k]] - f0;
+        star = star || (n == 1 && rd.at(f0) == '*');
+        minus1 = minus1 || (n == 2 && rd.at(f0) == '-' && rd.at(f0 + 1) == '1');
+    }
+    const long long nlen = fe[1] - fs[1];
+    bool keep = !(star && minus1) && fe[3] - fs[3] == nlen;
+    u64 h = 0xcbf29ce484222325ull;
+    for (long long i = 0; keep && i < nlen; ++i) {                      // chr1 == chr2, byte for byte
+        const u32 c = rd.at(fs[1] + i);
+        keep = c == rd.at(fs[3] + i);
+        h = (h ^ c) * 0x100000001b3ull;
+    }
+    u32 flags = 0;
+    if (keep) {
+        r.hash = k16_hash_end(h);
+        r.off = (u32)fs[1];
+        r.len = (u32)nlen;
+        if (nlen > K16_NAME_LEN) exotic = true;
+    }
+    if (keep && !exotic) {
+        long long sa = v[0] + v[1], sb = v[2] + v[3];                   // |v| < 2^62: no overflow
+        if (sa > sb) { const long long t = sa; sa = sb; sb = t; }
+        r.cA = sa >> 1;                                                 // floor, also below zero
+        r.cB = sb >> 1;
+        keep = !(cut > 0 && r.cB - r.cA < cut);
+    }
+    if (keep) {
+        bool diff = fe[5] - fs[5] != fe[6] - fs[6];
+        for (long long i = 0; !diff && i < fe[5] - fs[5]; ++i) diff = rd.at(fs[5] + i) != rd.at(fs[6] + i);
+        flags |= K16_KEPT | (diff ? K16_STRANDS : 0u);
+    }
+    r.flags = flags | (exotic ? K16_EXOTIC : 0u);
+    return 0;
+}
+
+template <int FMT>
+__device__ __forceinline__ void k16_any(K15Rd& rd, long long s, long long e, long long cut, long long ext, K16Rec& r)
+{
+    if (FMT == CL_INGEST_PAIRS) (void)k18_line(rd, s, e, cut, ext, r);
+    else k16_line(rd, s, e, cut, r);
+}
+
+// lines [256 b, 256 b + 256) of the chunk -> their records; the first exotic line -> err[0]; pairs: the first line the converter
+// raises on -> err[7], the header lines counted in err[10]
+template <int FMT>
 __global__ void __launch_bounds__(K16_T)
-k16_parse(const uint4* __restrict__ in, const u32* __restrict__ ends, long long L, long long cut, K16Rec* __restrict__ rec,
+k16_parse(const uint4* __restrict__ in, const u32* __restrict__ ends, long long L, long long cut, long long ext, K16Rec* __restrict__ rec,
           int* __restrict__ err)
 {
     extern __shared__ uint4 k16_lds[];
-    __shared__ int wmin[K16_T / 64];
+    __shared__ int wmin[2][K16_T / 64];
     const long long q0 = (long long)blockIdx.x * K16_T;
     const long long q1 = q0 + K16_T < L ? q0 + K16_T : L;
     const long long a0 = (q0 > 0 ? (long long)ends[q0 - 1] + 1 : 0) & ~15ll;
@@ -161,26 +238,38 @@ k16_parse(const uint4* __restrict__ in, const u32* __restrict__ ends, long long 
         for (long long i = threadIdx.x; i < (a1 - a0) >> 4; i += K16_T) k16_lds[i] = in[(a0 >> 4) + i];
     __syncthreads();
     const long long j = q0 + threadIdx.x;
-    int bad = INT_MAX;
+    int bad = INT_MAX, raised = INT_MAX;
+    bool header = false;
     if (j < q1) {
         const long long s = j > 0 ? (long long)ends[j - 1] + 1 : 0, e = ends[j];
         K16Rec r;
         if (fits) {
             K15Rd rd{(const u64*)k16_lds, a0, -1, 0};
-            k16_line(rd, s, e, cut, r);
+            k16_any<FMT>(rd, s, e, cut, ext, r);
         } else {
             K15Rd rd{(const u64*)in, 0, -1, 0};
-            k16_line(rd, s, e, cut, r);
+            k16_any<FMT>(rd, s, e, cut, ext, r);
+        }
+        if (FMT == CL_INGEST_PAIRS) {
+            if (r.flags >> 8) raised = (int)j;
+            header = (r.flags & K16_HEADER) != 0;
         }
         if (r.flags & K16_EXOTIC) bad = (int)j;
         rec[j] = r;
     }
     bad = dpp_reduce_wave(bad, OpMin());
-    if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = bad;
+    if (FMT == CL_INGEST_PAIRS) {
+        raised = dpp_reduce_wave(raised, OpMin());
+        const int nh = __popcll(__ballot(header));
+        if ((threadIdx.x & 63) == 0 && nh) atomicAdd(&err[10], nh);
+    }
+    if ((threadIdx.x & 63) == 0) { wmin[0][threadIdx.x >> 6] = bad; wmin[1][threadIdx.x >> 6] = raised; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int m = min(min(wmin[0], wmin[1]), min(wmin[2], wmin[3]));
+        const int m = min(min(wmin[0][0], wmin[0][1]), min(wmin[0][2], wmin[0][3]));
         if (m != INT_MAX) atomicMin(err, m);
+        const int m2 = min(min(wmin[1][0], wmin[1][1]), min(wmin[1][2], wmin[1][3]));
+        if (FMT == CL_INGEST_PAIRS && m2 != INT_MAX) atomicMin(&err[7], m2);
     }
 }
 
@@ -411,6 +500,11 @@ struct cl_ingest {
     bool own_stream = false;
     long long budget = 0, cut = 0;
     bool want_dist = false;
+    int fmt = CL_INGEST_BEDPE;                    // cl_ingest_set_format
+    long long ext = 0;
+    bool any_feed = false;
+    long long err_line = 0, headers = 0;          // of the last feed: cl_ingest_error, cl_ingest_headers
+    int err_kind = 0;
     DevBuf in, tcnt, toff, ends, rec, tmp, err, nkey, nfirst, nout, th, tid, tof, tln, blob, key, val, skey, sval, start;
     long long L = 0;                              // lines of the last feed
     bool fed = false;
@@ -492,7 +586,8 @@ static int ingest_scan_tmp(cl_ingest* c, size_t need)
     return c->tmp.ensure(std::max<size_t>(need, 16));
 }
 
-// err words: [0] first exotic line, [1] commit status, [2] wide keys, [3] xy domain; [4 .. 6] names counters; [8] distance count (u64)
+// err words: [0] first exotic line, [1] commit status, [2] wide keys, [3] xy domain; [4 .. 6] names counters; [7] pairs: the first
+// line the converter raises on; [8] distance count (u64); [10] pairs: header lines
 static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* L_out, int* bad, u32* ctr)
 {
     const bool virt = bytes[n - 1] != '\n';                             // the input's last line, without its newline
@@ -508,6 +603,7 @@ static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* 
     HIP_TRY(hipMemsetAsync(c->tcnt.as<u32>() + tiles, 0, 4, c->stream));
     HIP_TRY(hipMemsetAsync(c->err.p, 0, 64, c->stream));
     HIP_TRY(hipMemsetAsync(c->err.p, 0x7f, 4, c->stream));            // no exotic line: 0x7f7f7f7f, above any line index
+    HIP_TRY(hipMemsetAsync(c->err.as<u32>() + 7, 0x7f, 4, c->stream));
     hipLaunchKernelGGL(k15_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
     size_t bytes_tmp = 0;
@@ -524,8 +620,13 @@ static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* 
     hipLaunchKernelGGL(k15_lines, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->toff.as<u32>(), L, c->ends.as<u32>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    hipLaunchKernelGGL(k16_parse, dim3((unsigned)((L + K16_T - 1) / K16_T)), dim3(K16_T), K16_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L,
-                       c->cut, c->rec.as<K16Rec>(), c->err.as<int>());
+    const dim3 pgrid((unsigned)((L + K16_T - 1) / K16_T));
+    if (c->fmt == CL_INGEST_PAIRS)
+        hipLaunchKernelGGL(k16_parse<CL_INGEST_PAIRS>, pgrid, dim3(K16_T), K16_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->cut, c->ext,
+                           c->rec.as<K16Rec>(), c->err.as<int>());
+    else
+        hipLaunchKernelGGL(k16_parse<CL_INGEST_BEDPE>, pgrid, dim3(K16_T), K16_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->cut, c->ext,
+                           c->rec.as<K16Rec>(), c->err.as<int>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     HIP_TRY(hipMemsetAsync(c->nkey.p, 0, (size_t)K16_SLOTS * 8, c->stream));
@@ -537,9 +638,16 @@ static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* 
                        L, dctr, c->nout.as<K16Name>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[4], c->stream));
-    u32 words[8] = {};
-    if ((rc = ingest_read(c, words, c->err.p, 8))) return rc;
+    u32 words[12] = {};
+    if ((rc = ingest_read(c, words, c->err.p, 12))) return rc;
     *bad = (int)words[0];
+    c->headers = words[10];
+    if ((long long)words[7] < L) {                                      // pairs: a line the converter raises on
+        u32 flags = 0;
+        if ((rc = ingest_read(c, &flags, (const char*)c->rec.p + (size_t)words[7] * sizeof(K16Rec) + offsetof(K16Rec, flags)))) return rc;
+        c->err_line = (long long)words[7] + 1;
+        c->err_kind = (int)(flags >> 8);
+    }
     ctr[0] = words[4]; ctr[1] = words[5]; ctr[2] = words[6];
     *L_out = L;
     ingest_ms(c, K16_MS_H2D, 0, 1);
@@ -559,6 +667,7 @@ extern "C" int cl_ingest_feed(cl_ingest* c, const char* bytes, int64_t n, int64_
     if (n > c->budget) return fail(CL_ERR_ARG, "cl_ingest_feed: more bytes than the handle's budget");
     if (c->finished) return fail(CL_ERR_ARG, "cl_ingest_feed: the handle is finished");
     c->fed = false; c->L = 0; c->n_names = 0;
+    c->any_feed = true; c->err_line = 0; c->err_kind = 0; c->headers = 0;
     if (n == 0) { c->fed = true; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
     long long L = 0;
@@ -576,6 +685,33 @@ extern "C" int cl_ingest_feed(cl_ingest* c, const char* bytes, int64_t n, int64_
     if (ctr[1] || ctr[0] > K16_NAMES_MAX) { *n_names = -1; return CL_OK; }   // more distinct names than the table takes
     c->n_names = ctr[2];
     *n_names = ctr[2];
+    return CL_OK;
+}
+
+extern "C" int cl_ingest_set_format(cl_ingest* c, int32_t format, int64_t ext)
+{
+    if (!c) return fail(CL_ERR_ARG, "null ingest handle");
+    if (format != CL_INGEST_BEDPE && format != CL_INGEST_PAIRS) return fail(CL_ERR_ARG, "cl_ingest_set_format: unknown format");
+    if (c->any_feed) return fail(CL_ERR_ARG, "cl_ingest_set_format: allowed only before the first feed");
+    c->fmt = format;
+    c->ext = ext;
+    return CL_OK;
+}
+
+extern "C" int cl_ingest_error(cl_ingest* c, int64_t* line, int32_t* kind)
+{
+    if (!c) return fail(CL_ERR_ARG, "null ingest handle");
+    if (!line || !kind) return fail(CL_ERR_ARG, "cl_ingest_error: bad arguments");
+    *line = c->err_line;
+    *kind = c->err_kind;
+    return CL_OK;
+}
+
+extern "C" int cl_ingest_headers(cl_ingest* c, int64_t* n)
+{
+    if (!c) return fail(CL_ERR_ARG, "null ingest handle");
+    if (!n) return fail(CL_ERR_ARG, "cl_ingest_headers: bad arguments");
+    *n = c->headers;
     return CL_OK;
 }
 

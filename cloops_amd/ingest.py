@@ -35,11 +35,12 @@ MIN_BUFFER = 4096
 
 
 class _Chunk(object):
-    """what a seam hands back for one chunk: its handle, its lines and its distinct names [(hash, first line, name bytes)]"""
-    __slots__ = ("h", "lines", "names", "nbytes", "bad")
+    """what a seam hands back for one chunk: its handle, its lines and its distinct names [(hash, first line, name bytes)]; pairs:
+    how many of the lines are header lines"""
+    __slots__ = ("h", "lines", "names", "nbytes", "bad", "headers")
 
-    def __init__(self, h, lines, names, nbytes, bad=False):
-        self.h, self.lines, self.names, self.nbytes, self.bad = h, lines, names, nbytes, bad
+    def __init__(self, h, lines, names, nbytes, bad=False, headers=0):
+        self.h, self.lines, self.names, self.nbytes, self.bad, self.headers = h, lines, names, nbytes, bad, headers
 
     def __len__(self):
         return self.nbytes
@@ -47,6 +48,11 @@ class _Chunk(object):
 
 class Fallback(Exception):
     """the read goes to the host: (reason, file, line)"""
+
+
+class LineError(str):
+    """a seam's reason for a chunk that ends the read with ValueError("<file>:<line>: <reason>") and not with the host's reading:
+    a line of a pairs file the converter raises on"""
 
 
 class _Keep(object):
@@ -72,10 +78,10 @@ class GpuSeam(convert._DeviceSeam):
     """the per-chunk seam on the device: two K16 handles on two streams (chunk k on handle k % 2) and page-locked buffers.  The CPU
     tests put a brute-force seam with the same methods in its place (`make_seam`)."""
 
-    def __init__(self, budget, cut, want_distances, device=0):
+    def __init__(self, budget, cut, want_distances, device=0, fmt="bedpe", ext=0):
         from . import api
-        convert._DeviceSeam.__init__(self, device, lambda s: api.Ingest(budget, cut, want_distances, device, s))
-        self.device = device
+        convert._DeviceSeam.__init__(self, device, lambda s: api.Ingest(budget, cut, want_distances, device, s, fmt, ext))
+        self.device, self.fmt = device, fmt
         self.bufs = []
         self.turn = 0
         self.keep = None
@@ -98,12 +104,18 @@ class GpuSeam(convert._DeviceSeam):
         if not last and mv[n - 1] != 10:
             return _Chunk(h, 0, [], n, True), 0, "a line longer than the chunk budget"
         lines, exotic, nn = self.handles[h].feed(ctypes.addressof(buf), n)
+        headers = 0
+        if self.fmt == "pairs":
+            err = self.handles[h].error()
+            if err is not None and (exotic < 0 or err[0] - 1 < exotic):
+                return _Chunk(h, lines, [], n, True), err[0] - 1, LineError(err[1])
+            headers = self.handles[h].headers()
         if exotic >= 0:
             return _Chunk(h, lines, [], n, True), exotic, "a line the device does not read (Python's int() or text decoding decides)"
         if nn < 0:
             return _Chunk(h, lines, [], n, True), 0, "more than 65536 chromosome names in one chunk"
         names = [(hs, first, bytes(mv[off:off + ln])) for hs, first, off, ln in self.handles[h].names(nn)]
-        return _Chunk(h, lines, names, n), lines, None
+        return _Chunk(h, lines, names, n, False, headers), lines, None
 
     def commit(self, chunk, k, line0, table, n_ids):
         """-> (PETs appended per id, status)"""
@@ -140,8 +152,8 @@ class GpuSeam(convert._DeviceSeam):
         self.bufs = []
 
 
-def make_seam(budget, cut, want_distances, device=0):
-    return GpuSeam(budget, cut, want_distances, device)
+def make_seam(budget, cut, want_distances, device=0, fmt="bedpe", ext=0):
+    return GpuSeam(budget, cut, want_distances, device, fmt, ext)
 
 
 def rows_matrix(X, Y):
@@ -161,15 +173,15 @@ def _budget_for(fs, budget):
     return min(budget, max([MIN_BUFFER] + [os.path.getsize(f) + 1 for f in fs]))
 
 
-def _read(fs, cs, cut, unique, want_distances, device, budget, stats):
-    """the device read -> (seam after finish, chromosome names in key order, rows per id, number of distances, lines);
-    raises Fallback"""
+def _read(fs, cs, cut, unique, want_distances, device, budget, stats, fmt="bedpe", ext=0):
+    """the device read -> (seam after finish, chromosome names in key order, rows per id, number of distances, lines: for pairs the
+    data lines); raises Fallback, or for pairs the converter's ValueError"""
     budget = int(budget)
     wanted = set(c.encode() if isinstance(c, str) else bytes(c) for c in cs) if cs else set()
     eff = _budget_for(fs, budget) if budget == BUDGET else budget
-    seam = make_seam(eff, cut, want_distances, device)
+    seam = make_seam(eff, cut, want_distances, device) if fmt == "bedpe" else make_seam(eff, cut, want_distances, device, fmt, ext)
     ids, by_hash, order = {}, {}, []
-    state = {"line": 0, "chunk": 0, "file": None}
+    state = {"line": 0, "chunk": 0, "file": None, "headers": 0}
 
     def write(chunk):                                                   # in chunk order: the dictionary, then the commit
         if chunk.bad:                                                   # the read ends here: _read raises Fallback
@@ -192,6 +204,7 @@ def _read(fs, cs, cut, unique, want_distances, device, budget, stats):
             if status:
                 raise Fallback("two chromosome names under one hash", state["file"], state["line"] + 1)
         state["line"] += chunk.lines
+        state["headers"] += getattr(chunk, "headers", 0)
         state["chunk"] += 1
 
     try:
@@ -201,6 +214,8 @@ def _read(fs, cs, cut, unique, want_distances, device, budget, stats):
             src = gzip.open(f, "rb") if f.endswith(".gz") else open(f, "rb", buffering=0)
             with src:
                 lines, _, err, line = convert._run(src, seam, eff, write, stats)
+            if isinstance(err, LineError):
+                raise ValueError("%s:%d: %s" % (f, line, err))
             if err is not None:
                 raise Fallback(err, f, line0 + line)
         rows, n_dist = seam.finish(len(order), unique)
@@ -208,7 +223,7 @@ def _read(fs, cs, cut, unique, want_distances, device, budget, stats):
         _account(seam, stats)
         seam.close()
         raise
-    return seam, [n.decode("ascii") for n in order], rows, n_dist, state["line"]
+    return seam, [n.decode("ascii") for n in order], rows, n_dist, state["line"] - state["headers"]
 
 
 def _account(seam, stats):
@@ -232,22 +247,27 @@ def _say(logger, msg):
         sys.stderr.write(msg + "\n")
 
 
-def _fallback(e, stats, logger):
+def _fallback(e, stats, logger, what="BEDPE"):
     reason, f, line = e.args
     stats["fallback"] = (reason, f, line)
-    _say(logger, "BEDPE reader: %s:%d: %s; reading on the host" % (f, line, reason))
+    _say(logger, "%s reader: %s:%d: %s; reading on the host" % (what, f, line, reason))
 
 
 def parse_bedpe_gpu(fs, cs=(), cut=0, unique=False, strand_distances=None, device=0, budget=BUDGET, stats=None, logger=None):
     """cloops_amd.io.parse_bedpe on the device -> (dict chrom -> int64 [n, 3] rows [id, X, Y] in file order, n_lines, n_cis)"""
+    return _parse_gpu(fs, cs, cut, unique, strand_distances, device, budget, stats, logger)
+
+
+def _parse_gpu(fs, cs, cut, unique, strand_distances, device, budget, stats, logger, fmt="bedpe", ext=0, host=None):
+    """parse_bedpe_gpu for `fmt`; host(fs, cs, cut, unique, strand_distances) is what a Fallback runs (None: cloops_amd.io.parse_bedpe)"""
     user, stats = stats, _Stats()
     stats["fallback"] = None
     try:
-        seam, names, rows, n_dist, n_lines = _read(fs, cs, cut, unique, strand_distances is not None, device, budget, stats)
+        seam, names, rows, n_dist, n_lines = _read(fs, cs, cut, unique, strand_distances is not None, device, budget, stats, fmt, ext)
     except Fallback as e:
-        _fallback(e, stats, logger)
+        _fallback(e, stats, logger, "BEDPE" if fmt == "bedpe" else fmt)
         stats.publish(user)
-        return cio.parse_bedpe(fs, cs, cut, unique, strand_distances)
+        return (host or cio.parse_bedpe)(fs, cs, cut, unique, strand_distances)
     try:
         out = {}
         for cid, name in enumerate(names):
@@ -270,6 +290,11 @@ def load_bedpe(fs, cs=(), cut=0, unique=False, strand_distances=None, device=0, 
     sweep's shared streams (the ingest's arrays as keepalive) and registered in pipe.CACHE as 'mem://<prefix>/<chr>-<chr>' with
     host copies of X / Y -> the names, in the order of parse_bedpe's keys.  Coordinates outside |v| < 2^29 raise the CL_ERR_DOMAIN
     error of api.Chromosome.  A read that fell back to the host registers the host rows with CACHE.put_arrays."""
+    return _load(fs, cs, cut, unique, strand_distances, device, prefix, budget, stats, logger)
+
+
+def _load(fs, cs, cut, unique, strand_distances, device, prefix, budget, stats, logger, fmt="bedpe", ext=0, host=None):
+    """load_bedpe for `fmt`; `host` as in _parse_gpu"""
     from . import api, pipe
     user, stats = stats, _Stats()
     stats["fallback"] = None
@@ -278,10 +303,10 @@ def load_bedpe(fs, cs=(), cut=0, unique=False, strand_distances=None, device=0, 
         return "%s/%s-%s" % (prefix, name, name) if prefix else "%s-%s" % (name, name)
 
     try:
-        seam, names, rows, n_dist, n_lines = _read(fs, cs, cut, unique, strand_distances is not None, device, budget, stats)
+        seam, names, rows, n_dist, n_lines = _read(fs, cs, cut, unique, strand_distances is not None, device, budget, stats, fmt, ext)
     except Fallback as e:
-        _fallback(e, stats, logger)
-        mats, n_lines, n_cis = cio.parse_bedpe(fs, cs, cut, unique, strand_distances)
+        _fallback(e, stats, logger, "BEDPE" if fmt == "bedpe" else fmt)
+        mats, n_lines, n_cis = (host or cio.parse_bedpe)(fs, cs, cut, unique, strand_distances)
         stats["lines"], stats["cis"] = n_lines, n_cis
         stats.publish(user)
         return [pipe.CACHE.put_arrays(pseudo(c), m[:, 1], m[:, 2], device=device, key=(c, c)) for c, m in mats.items()]
@@ -311,13 +336,14 @@ def load_bedpe(fs, cs=(), cut=0, unique=False, strand_distances=None, device=0, 
     return out
 
 
-def _write_jd(fs, fout, cs, cut, unique, logger):
+def _write_jd(fs, fout, cs, cut, unique, logger, parse=None):
+    """parse: the reader (None: parse_bedpe_gpu; cloops_amd.pairs hands in its own)"""
     import joblib
     for f in fs:
         if logger is not None:
             logger.info("Parsing PETs from %s, requiring initial distance cutoff > %s" % (f, cut))
     ds = [] if unique else None
-    mats, i, j = parse_bedpe_gpu(fs, cs, cut, unique=unique, strand_distances=ds, logger=logger)
+    mats, i, j = (parse or parse_bedpe_gpu)(fs, cs, cut, unique=unique, strand_distances=ds, logger=logger)
     cfs = []
     for c, m in mats.items():
         cf = os.path.join(fout, "%s-%s" % (c, c) + ".jd")
@@ -340,8 +366,11 @@ def parseRawBedpe2(fs, fout, cs, cut, logger=None):
 
 def _help(argv):
     ap = argparse.ArgumentParser(prog="python -m cloops_amd.ingest",
-                                 description="Read BEDPE files on MI355X into a directory of per-chromosome .jd files (what `cloops_amd -s` leaves).")
-    ap.add_argument("-f", dest="fnIn", required=True, type=str, help="BEDPE file(s), plain or .gz, separated by commas.")
+                                 description="Read BEDPE or 4DN pairs files on MI355X into a directory of per-chromosome .jd files (what `cloops_amd -s` leaves).")
+    ap.add_argument("-f", dest="fnIn", required=True, type=str, help="BEDPE (or, with -fmt pairs, 4DN pairs) file(s), plain or .gz, separated by commas.")
+    ap.add_argument("-fmt", dest="fmt", required=False, default="bedpe", choices=["bedpe", "pairs"], help="Input format, default bedpe.")
+    ap.add_argument("-ext", dest="ext", required=False, default=50, type=int,
+                    help="-fmt pairs: extension from the position of each read, as `convert pairs -ext`; default 50.")
     ap.add_argument("-o", dest="fnOut", required=True, type=str, help="Output directory (created; must not exist).")
     ap.add_argument("-c", dest="chroms", required=False, default="", type=str, help="Chromosomes to keep, separated by commas; default all.")
     ap.add_argument("-cut", dest="cut", required=False, default=0, type=int, help="Initial distance cutoff, default 0.")
@@ -362,7 +391,15 @@ def main(argv=None):
         return 1
     os.makedirs(op.fnOut)
     cs = [c for c in op.chroms.split(",") if c]
-    cfs = parseRawBedpe2(fs, op.fnOut, cs, op.cut)
+    if op.fmt == "pairs":
+        from . import pairs
+        try:
+            cfs = pairs.parseRawPairs2(fs, op.fnOut, cs, op.cut, ext=op.ext)
+        except ValueError as e:
+            sys.stderr.write("Error: %s\n" % e)
+            return 1
+    else:
+        cfs = parseRawBedpe2(fs, op.fnOut, cs, op.cut)
     sys.stderr.write("%d chromosomes written to %s. Used time: %s Bye!\n" % (len(cfs), op.fnOut, datetime.now() - start))
     return 0
 

@@ -1011,12 +1011,17 @@ MODES = {1: ([500, 1000, 2000], [5], 0), 2: ([1000, 2000, 5000], [5], 0),
 _PIPE_RUNS = itertools.count()
 
 
-def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp):
-    """the input through the GPU reader (cloops_amd.ingest.load_bedpe): -> ('mem://' names, distances or None); with `tmp` the
-    `.jd` files of the host reader are written from the host copies"""
+def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp, fmt="bedpe", ext=50):
+    """the input through the GPU reader (cloops_amd.ingest.load_bedpe, for 4DN pairs cloops_amd.pairs.load_pairs): -> ('mem://'
+    names, distances or None); with `tmp` the `.jd` files of the host reader are written from the host copies"""
     from . import ingest
     ds = [] if auto_eps else None
-    cfs = ingest.load_bedpe(fs, chroms, cut, unique=auto_eps, strand_distances=ds, prefix="pipe-%d-%d" % (os.getpid(), next(_PIPE_RUNS)))
+    prefix = "pipe-%d-%d" % (os.getpid(), next(_PIPE_RUNS))
+    if fmt == "pairs":
+        from . import pairs
+        cfs = pairs.load_pairs(fs, chroms, cut, unique=auto_eps, strand_distances=ds, ext=ext, prefix=prefix)
+    else:
+        cfs = ingest.load_bedpe(fs, chroms, cut, unique=auto_eps, strand_distances=ds, prefix=prefix)
     if tmp:
         import joblib
         try:
@@ -1031,7 +1036,7 @@ def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp):
 
 
 def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0, cut=0, plot=0, max_cut=False,
-         log=None, reader="gpu"):
+         log=None, reader="gpu", fmt="auto", ext=50):
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
@@ -1040,10 +1045,17 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     `juice` write `<fout>_loops_washU.txt` / `<fout>_loops_juicebox.txt` after `<fout>.loop` (pipe.py:288-292, cloops_amd.tracks).
     `eps == 0` estimates eps from the distances of the PETs mapped to different strands (io.py:62-129, ests.py:23-33).
     `reader`: "gpu" reads the BEDPE files on the device (K16, cloops_amd.ingest): the chromosomes go from the text to HBM
-    without `.jd` files, which are written only with `tmp`; "host" is cloops_amd.io's Python loop and its `.jd` files."""
+    without `.jd` files, which are written only with `tmp`; "host" is cloops_amd.io's Python loop and its `.jd` files.
+    `fmt`: "bedpe", "pairs" (4DN pairs read with the extension `ext`, K18, cloops_amd.pairs) or "auto": pairs exactly when the
+    first file's first line starts with `## pairs format`."""
     import shutil
     if reader not in ("gpu", "host"):
         raise ValueError("reader must be 'gpu' or 'host', got %r" % (reader,))
+    if fmt not in ("auto", "bedpe", "pairs"):
+        raise ValueError("fmt must be 'auto', 'bedpe' or 'pairs', got %r" % (fmt,))
+    if fmt == "auto":
+        from . import pairs
+        fmt = pairs.sniff(fs[0]) if fs else "bedpe"
     from . import io as cio
     from . import cModel
     if chroms == "":
@@ -1059,8 +1071,14 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     mem = []
     try:
         if reader == "gpu":
-            cfs, ds = _read_gpu(fs, fout, chroms, cut, auto_eps, tmp)
+            cfs, ds = _read_gpu(fs, fout, chroms, cut, auto_eps, tmp, fmt, ext)
             mem = cfs
+        elif fmt == "pairs":
+            from . import pairs
+            if auto_eps:
+                cfs, ds = pairs.parseRawPairs(fs, fout, chroms, cut, ext=ext, reader="host")
+            else:
+                cfs = pairs.parseRawPairs2(fs, fout, chroms, cut, ext=ext, reader="host")
         elif auto_eps:
             cfs, ds = cio.parseRawBedpe(fs, fout, chroms, cut)
             cfs = [cio.txt2jd(f) for f in cfs]
@@ -1109,6 +1127,8 @@ def main(argv=None):
     ap.add_argument("-plot", dest="plot", action="store_true")
     ap.add_argument("-max_cut", dest="max_cut", action="store_true")
     ap.add_argument("-reader", dest="reader", default="gpu", choices=["host", "gpu"])
+    ap.add_argument("-fmt", dest="fmt", default="auto", choices=["auto", "bedpe", "pairs"])
+    ap.add_argument("-ext", dest="ext", type=int, default=50)
     op = ap.parse_args(argv)
     if op.mode == 0:                                          # pipe.py:306-327
         eps = sorted(int(x) for x in str(op.eps).split(","))
@@ -1121,5 +1141,5 @@ def main(argv=None):
         eps, minPts, hic = MODES[op.mode]
     sys.stderr.write("mode:%s\t eps:%s\t minPts:%s\t hic:%s\t\n" % (op.mode, eps, minPts, hic))
     pipe(op.fnIn.split(","), op.fnOut, eps, minPts, op.chroms, op.cpu, op.tmp, hic, op.washU, op.juice, op.cut,
-         op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader)
+         op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader, fmt=op.fmt, ext=op.ext)
     return 0

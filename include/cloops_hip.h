@@ -319,7 +319,10 @@ int cl_track_free(cl_chrom* c);
  * cl_conv_create -- a converter on `device` for `format` (CL_CONV_HICPRO: HiC-Pro allValidPairs, fields split at '\t'
  * after strip(), A = [f1, p1, p1 + ext] on "+" else [f1, p1 - ext, p1], B the same from f4 f5 f6, line
  * `A B f0 . f3 f6`; CL_CONV_JUICER: Juicer "long" format, fields split at whitespace runs, line
- * `f1 max(0, p1 - ext) p1 + ext f5 max(0, p2 - ext) p2 + ext . . s1 s2`, s = "+" where f0 / f4 is "0"), on `stream` (NULL:
+ * `f1 max(0, p1 - ext) p1 + ext f5 max(0, p2 - ext) p2 + ext . . s1 s2`, s = "+" where f0 / f4 is "0"; CL_CONV_PAIRS:
+ * 4DN pairs v1.0, `readID chr1 pos1 chr2 pos2 strand1 strand2`, which replaces reordering the columns to HiC-Pro's by hand:
+ * CL_CONV_HICPRO's rule on f0 f1 f2 f5 f3 f4 f6, line `A B f0 . f5 f6`; a line whose first byte is '#' is a header line: it
+ * is counted in *n_lines and in cl_conv_error's line numbers and has no text), on `stream` (NULL:
  * a stream of its own), taking chunks of at most `budget` bytes (1 .. CL_CONV_BUDGET_MAX).  Errors: CL_ERR_NODEVICE
  * without a device (there is no CPU path); CL_ERR_ARG for a NULL out, an unknown format or a budget out of range.
  *
@@ -350,6 +353,7 @@ typedef struct cl_conv cl_conv;
 #define CL_ERR_PARSE        -8   /* cl_conv_feed: a line the reference's script would raise on (cl_conv_error)   */
 #define CL_CONV_HICPRO       0
 #define CL_CONV_JUICER       1
+#define CL_CONV_PAIRS        2
 #define CL_CONV_E_FIELDS     1   /* fewer than 7 fields (a blank line included): the reference's IndexError      */
 #define CL_CONV_E_INT        2   /* a position that is not an integer: the reference's ValueError               */
 #define CL_CONV_E_RANGE      3   /* a position, or a position +- ext, outside int64                              */
@@ -382,6 +386,21 @@ int cl_conv_destroy(cl_conv* c);
  * cl_ingest_create -- a reader on `device` and `stream` (NULL: a stream of its own) for chunks of at most `budget` bytes
  * (1 .. CL_CONV_BUDGET_MAX), with the distance filter `cut` (io.py:103, :174); want_distances != 0 keeps what
  * cl_ingest_distances needs (io.py:122-123).  Errors: CL_ERR_NODEVICE without a device (there is no CPU path); CL_ERR_ARG.
+ *
+ * cl_ingest_set_format -- what the handle reads, allowed only before its first feed (CL_ERR_ARG after it, or for an unknown
+ * format): CL_INGEST_BEDPE (what cl_ingest_create leaves) or CL_INGEST_PAIRS, 4DN pairs text.  It replaces converting the
+ * file with cl_conv_* (CL_CONV_PAIRS, `ext`) and feeding the BEDPE text: every data line gives the record of the line the
+ * converter writes for it (`A0 A1 A2 B0 B1 B2 f0 . f5 f6`: the "*" / "-1" rule on these ten fields, a coordinate equal to
+ * -1 being a "-1" field; chr1 against chr2; strand1 against strand2; the swap, the floors and `cut` as above).  A line
+ * whose first byte is '#' is a header line: no PET.  A byte >= 0x80, a '\r' that is not the last byte before the '\n', a
+ * coordinate of 2^62 or more in magnitude or a chromosome name longer than 255 bytes makes a data line EXOTIC.
+ *
+ * cl_ingest_error -- CL_INGEST_PAIRS: the first line of the last feed on which the converter raises (cl_conv_error's
+ * counterpart; it replaces looking for that line with a converter run): *line counts the lines of that feed, header
+ * lines included (1-based; 0: none), *kind is its CL_CONV_E_* (0: none).  The caller stops the read there.
+ *
+ * cl_ingest_headers -- CL_INGEST_PAIRS: *n = the header lines among the last feed's *n_lines (it replaces counting the
+ * lines of the converted text: the lines of a read are its data lines).
  *
  * cl_ingest_feed -- the loop bodies of io.py:80-105 / :155-176 for the n bytes of complete lines at `bytes` (n <= budget;
  * only the last line may lack its '\n'; page-locked memory copies fastest): *n_lines = the lines of the chunk (blank ones
@@ -421,8 +440,13 @@ typedef struct cl_ingest_name {
     uint32_t first, off, len, pad;
 } cl_ingest_name;
 #define CL_INGEST_TIMES 6
+#define CL_INGEST_BEDPE 0
+#define CL_INGEST_PAIRS 1
 int cl_ingest_create(int device, void* stream, int64_t budget, int64_t cut, int32_t want_distances, cl_ingest** out);
+int cl_ingest_set_format(cl_ingest* c, int32_t format, int64_t ext);
 int cl_ingest_feed(cl_ingest* c, const char* bytes, int64_t n, int64_t* n_lines, int64_t* first_exotic, int64_t* n_names);
+int cl_ingest_error(cl_ingest* c, int64_t* line, int32_t* kind);
+int cl_ingest_headers(cl_ingest* c, int64_t* n);
 int cl_ingest_names(cl_ingest* c, cl_ingest_name* out, int64_t cap, int64_t* n);
 int cl_ingest_commit(cl_ingest* c, int64_t chunk, int64_t line0, const uint64_t* hashes, const int32_t* ids,
                      const uint32_t* name_off, const uint32_t* name_len, int32_t n_table, const char* names,
