@@ -235,6 +235,7 @@ struct cl_chrom {
     int last_slot = -1;
     int last_K = 0;                   // max_label + 1
     bool have_result = false;
+    long long refused_labelled = -1;  // labelled PETs of the run whose cl_wait was refused for capacity (pairs / row-mask form); -1: the last wait refused nothing
     // profiling
     bool profiling = false;
     cl_timing timing{};

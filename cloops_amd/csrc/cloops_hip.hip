@@ -3393,6 +3393,7 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
     }
     sl.pending = false;
     c->deq++;
+    c->refused_labelled = -1;
 #ifdef CLOOPS_DEVEL
     if (getenv("CLOOPS_DBG_COUNTERS")) {                 // developer build: the device counters of the run that has just completed
         int h[8] = {0};
@@ -3408,8 +3409,10 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
         const long long kp = sl.h_hdr[6];
         // the kernel clamps its stores at the capacity but keeps counting: a run that labelled more PETs than the caller's
         // buffer holds is an argument error, nothing is copied (the staging buffer holds `capacity` pairs, not kp)
-        if (kp > sl.pairs_host_cap)
+        if (kp > sl.pairs_host_cap) {
+            c->refused_labelled = kp;                    // (cl_last_n_labelled: the capacity the caller needs)
             return fail(CL_ERR_ARG, "cl_cluster_pairs_async: the run labelled more PETs than capacity_pairs (n always suffices)");
+        }
         if (kp > 0 && sl.h_hdr[1] == 0) {
             HIP_TRY(hipMemcpyAsync(dst, sl.pairs.p, (size_t)kp * 8, hipMemcpyDeviceToHost, c->aux_stream));
             // (cl_set_pairs_defer: the caller completes the copy with cl_pairs_sync -- a loop over many handles then has all their
@@ -3423,8 +3426,10 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
         void* dst = sl.mask_host;
         sl.mask_host = nullptr;
         const long long kp = sl.h_hdr[6];
-        if (kp > sl.mask_host_cap)
+        if (kp > sl.mask_host_cap) {
+            c->refused_labelled = kp;
             return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: the run labelled more PETs than capacity_labels (n always suffices)");
+        }
         if (sl.h_hdr[1] == 0) {
             const size_t nw = (size_t)((c->n + 63) / 64);
             HIP_TRY(hipMemcpyAsync(dst, sl.pairs.p, nw * 8 + (size_t)kp * 4, hipMemcpyDeviceToHost, c->aux_stream));
@@ -3562,8 +3567,10 @@ extern "C" int cl_pairs_sync(cl_chrom* c)
 }
 extern "C" int64_t cl_last_n_labelled(const cl_chrom* c)
 {
-    if (!c || !c->have_result || c->last_slot < 0) return -1;
-    return c->slot[c->last_slot].h_hdr[6];               // (may exceed the capacity of a run cl_wait refused with CL_ERR_ARG)
+    if (!c) return -1;
+    if (c->refused_labelled >= 0) return c->refused_labelled;            // the run cl_wait has just refused with CL_ERR_ARG: more than its capacity
+    if (!c->have_result || c->last_slot < 0) return -1;
+    return c->slot[c->last_slot].h_hdr[6];
 }
 
 extern "C" int cl_cluster_step_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, int32_t step, int64_t fine_lo)

@@ -485,6 +485,10 @@ int cl_cand_reset(cl_chrom* c);
  * otherwise). */
 int cl_cluster_pairs_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, int32_t* pinned_pairs_out,
                            int64_t capacity_pairs);
+/* cl_last_n_labelled: the labelled PETs of the last completed pairs / row-mask run: what cl_wait copied.  After a cl_wait that
+ * returned CL_ERR_ARG for capacity it is the number that run labelled -- the capacity the caller needs, larger than the one it gave --
+ * until the handle's next cl_wait or synchronous run completes; nothing else of the refused run is available (the results the
+ * other getters return stay those of the run completed before it).  -1: no handle, or no completed run. */
 int64_t cl_last_n_labelled(const cl_chrom* c);
 /* The same set -- the clustered points and their cluster ids, what cDBSCAN(mat, eps, minPts).labels holds (cDBSCAN2.py:186-191,
  * cDBSCAN.py:143-152) -- in its smallest form: ceil(n / 64) 64-bit mask words (bit r % 64 of word r / 64 set <=> input row r is

@@ -188,3 +188,53 @@ def test_rowmask_form_on_tiny_and_empty_results():
         assert np.array_equal(again.labels, want.labels)
     finally:
         ch.close()
+
+
+@pytest.mark.parametrize("form", ["pairs", "rowmask"])
+def test_refused_wait_tells_the_capacity_it_needs(form):
+    """a cl_wait refused for capacity (CL_ERR_ARG, nothing copied) leaves the number of PETs the run labelled in cl_last_n_labelled
+    -- larger than the capacity given, and what a second try needs -- until the handle's next run completes"""
+    if api.TRAVERSAL_OVERRIDE is not None and int(api.TRAVERSAL_OVERRIDE) < 3:
+        pytest.skip("the pairs and row-mask forms need the list form of a run (traversal level >= 3)")
+    import ctypes
+    from cloops_amd import _lib
+    rng = np.random.default_rng(5)
+    X = np.sort(rng.integers(1000, 3000, 40)).astype(np.int32)
+    Y = (X + rng.integers(100, 400, 40)).astype(np.int32)
+    ch = api.Chromosome(X, Y)
+    lib = _lib.load()
+    p = lib.cl_host_alloc(8 + 8 * 40)
+    try:
+        want = ch.cluster("v2", 500, 3, 0)
+        k = int((want.labels >= 0).sum())
+        assert k > 2
+        few = ch.cluster("v2", 100, 6, 0)                       # the run completed before the refused one labels another number
+        assert int((few.labels >= 0).sum()) != k
+        enqueue = lib.cl_cluster_pairs_async if form == "pairs" else lib.cl_cluster_rowmask_async
+        nc, ml = ctypes.c_int32(0), ctypes.c_int32(-1)
+        for cap in (1, k - 1):
+            _lib.check(enqueue(ch._h, api.VARIANTS["v2"], 500, 3, 0, ctypes.c_void_p(p), cap))
+            assert lib.cl_wait(ch._h, ctypes.byref(nc), ctypes.byref(ml)) == _lib.CL_ERR_ARG
+            assert int(lib.cl_last_n_labelled(ch._h)) == k
+        # that capacity is enough, and the count is then the completed run's
+        _lib.check(enqueue(ch._h, api.VARIANTS["v2"], 500, 3, 0, ctypes.c_void_p(p), k))
+        _lib.check(lib.cl_wait(ch._h, ctypes.byref(nc), ctypes.byref(ml)))
+        assert int(lib.cl_last_n_labelled(ch._h)) == k and nc.value == want.n_clusters
+        if form == "pairs":
+            pairs = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_int32)), shape=(k, 2))
+            got = np.full(len(X), -1, np.int32)
+            got[pairs[:, 0]] = pairs[:, 1]
+        else:
+            mask = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(1,))
+            labels = np.ctypeslib.as_array(ctypes.cast(p + 8, ctypes.POINTER(ctypes.c_int32)), shape=(k,))
+            got = np.full(len(X), -1, np.int32)
+            got[ch.rows_of_mask(mask)] = labels
+        assert np.array_equal(got, want.labels)
+        # a refused wait, then a plain run: the handle still works
+        _lib.check(enqueue(ch._h, api.VARIANTS["v2"], 500, 3, 0, ctypes.c_void_p(p), 1))
+        assert lib.cl_wait(ch._h, ctypes.byref(nc), ctypes.byref(ml)) == _lib.CL_ERR_ARG
+        again = ch.cluster("v2", 500, 3, 0)
+        assert np.array_equal(again.labels, want.labels)
+    finally:
+        lib.cl_host_free(ctypes.c_void_p(p))
+        ch.close()
