@@ -102,6 +102,7 @@ PROTOTYPES = {
     "cl_quant_counts": (_int, [_vp, _i32, _i32, _vp, _vp, _i64p]),
     "cl_contact_hist": (_int, [_vp, _i32, _i32, _i64, _vp, _vp, _i64p, _i64p, _i64p, _i32p]),
     "cl_anchor_mask": (_int, [_vp, _i64, _vp, _vp, _vp, _i64p, _i64p]),
+    "cl_agg_loops": (_int, [_vp, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64p]),
     "cl_track_build": (_int, [_vp, _i32, _i64, _i64, _vp, _cp, _cp, _i64p, _i64p]),
     "cl_track_chunks": (_int, [_vp, _i64, _i64, _vp, _vp, _i64p]),
     "cl_track_render": (_int, [_vp, _i64, _vp, _i64, _i64p]),

@@ -478,6 +478,34 @@ class Chromosome(_Handle):
                                             mask.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nm), ctypes.byref(nk)))
         return mask[:nw], int(nm.value), int(nk.value)
 
+    def agg_loops(self, cx, cy, res, w=10, corner=3, cut=0, want_stats=True, want_mats=False):
+        """K19: the PETs with Y - X >= cut (cut > 0) piled up around the loop centres (cx[k], cy[k]) in W x W bins of `res` bp,
+        W = 2 w + 1: a row falls into cell ((X - ox) // res, (Y - oy) // res) of loop k when both differences lie in [0, W res),
+        ox = cx - w res - res // 2, oy likewise -> (S int64 [W, W] = the sum of the loops' matrices, stats int32 [n, 6] (total,
+        centre, ll, ul, ur, lr: corner x corner sums) or None, mats int32 [n, W, W] or None, n_kept = rows passing the cut)
+        (cl_agg_loops of include/cloops_hip.h)."""
+        res, w, corner = int(res), int(w), int(corner)
+        if res < 1 or not 1 <= w <= 20 or not 1 <= corner <= w or (2 * w + 1) * res >= 1 << 29:
+            raise ValueError("agg_loops needs res >= 1, 1 <= w <= 20, 1 <= corner <= w and (2 w + 1) res < 2^29, got res=%s w=%s corner=%s"
+                             % (res, w, corner))
+        cx = np.ascontiguousarray(cx, dtype=np.int64).ravel()
+        cy = np.ascontiguousarray(cy, dtype=np.int64).ravel()
+        if len(cx) != len(cy):
+            raise ValueError("cx and cy differ in length (%d, %d)" % (len(cx), len(cy)))
+        lim = np.iinfo(np.int32)
+        if len(cx) and (min(cx.min(), cy.min()) < lim.min or max(cx.max(), cy.max()) > lim.max):
+            raise ValueError("loop centres must fit int32")
+        cx, cy = cx.astype(np.int32), cy.astype(np.int32)
+        n, W = len(cx), 2 * w + 1
+        S = np.zeros((W, W), dtype=np.int64)
+        stats = np.zeros((n, 6), dtype=np.int32) if want_stats else None
+        mats = np.zeros((n, W, W), dtype=np.int32) if want_mats else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        nkept = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_agg_loops(self._h, int(cut), res, w, corner, n, ptr(cx), ptr(cy), ptr(S), ptr(stats), ptr(mats),
+                                          ctypes.byref(nkept)))
+        return S, stats, mats, int(nkept.value)
+
     TRACK_KINDS = {"washu": _lib.CL_TRACK_WASHU, "juice": _lib.CL_TRACK_JUICE}
     TRACK_NAME_MAX = _lib.CL_TRACK_NAME_MAX
     TRACK_BUDGET = 64 << 20                        # default bytes per rendered chunk

@@ -214,6 +214,11 @@ struct cl_chrom {
     DevBuf sig_tx, sig_ty, sig_tmp, sig_sorttmp, sig_m, sig_win, sig_out;   // K8: sorted PET tables, windows, counts
     DevBuf fp_small, fp_keys, fp_sorted, fp_tmp, fp_pairs;       // K12 (k_fingerprint.hip): scratch of one call, freed when it returns
     DevBuf an_s, an_e, an_dir, an_mask, an_wsum;                 // K13 (k_anchor.hip): anchors, directory, row mask, workgroup totals; kept between calls
+    // K19 (k_agg.hip): the rows that pass ag_cut sorted by X (keys in / out, Y in / out, sort scratch, their number), the loop
+    // centres and their order by cx (keys in / out, numbers in / out, sort scratch), the sum, per-loop statistics and matrices; kept
+    // between calls
+    DevBuf ag_kin, ag_vin, ag_sx, ag_sy, ag_tmp, ag_m, ag_cx, ag_cy, ag_lkin, ag_lkout, ag_lvin, ag_order, ag_ltmp, ag_sum, ag_stats, ag_mats;
+    bool ag_ready = false; int ag_cut = 0, ag_kept = 0;          // the table is built for ag_cut and holds ag_kept rows
     // K14 (k_track.hip): tile counts / offsets, kept rows, keys, line lengths / ends, ids, names, chunk bounds, render output;
     // kept from cl_track_build to the next build or cl_track_free
     DevBuf tk_tcnt, tk_toff, tk_row, tk_keys, tk_sorted, tk_len, tk_end, tk_tmp, tk_ids, tk_names, tk_bnd, tk_out;

@@ -2137,6 +2137,8 @@ static void free_chrom(cl_chrom* c)
                       &c->ncore, &c->bsize, &c->owner, &c->state, &c->flag, &c->rankscan, &c->slot[0].labels, &c->slot[0].table, &c->slot[1].labels, &c->slot[1].table, &c->slot[0].slab, &c->slot[1].slab, &c->slot[0].d_step, &c->slot[1].d_step, &c->slot[0].pairs, &c->slot[1].pairs, &c->hdr, &c->k7_cls, &c->k7_parts, &c->sig_tx, &c->sig_ty, &c->sig_tmp, &c->sig_sorttmp, &c->sig_m, &c->sig_win, &c->sig_out,
                       &c->fp_small, &c->fp_keys, &c->fp_sorted, &c->fp_tmp, &c->fp_pairs,
                       &c->an_s, &c->an_e, &c->an_dir, &c->an_mask, &c->an_wsum,
+                      &c->ag_kin, &c->ag_vin, &c->ag_sx, &c->ag_sy, &c->ag_tmp, &c->ag_m, &c->ag_cx, &c->ag_cy, &c->ag_lkin, &c->ag_lkout, &c->ag_lvin,
+                      &c->ag_order, &c->ag_ltmp, &c->ag_sum, &c->ag_stats, &c->ag_mats,
                       &c->tk_tcnt, &c->tk_toff, &c->tk_row, &c->tk_keys, &c->tk_sorted, &c->tk_len, &c->tk_end, &c->tk_tmp, &c->tk_ids,
                       &c->tk_names, &c->tk_bnd, &c->tk_out,
                       &c->ulist, &c->lo, &c->hi, &c->recs, &c->counters, &c->chainflag, &c->chainhead, &c->usize, &c->b_cstart, &c->b_ckey, &c->b_nb, &c->b_cx, &c->b_cy, &c->tile_s0, &c->bq, &c->bsp, &c->brow, &c->bstrip, &c->btile, &c->sel_tmp, &c->cand_box, &c->cand_step, &c->cand_keep, &c->cand_out, &c->dhist,

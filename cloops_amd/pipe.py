@@ -1036,7 +1036,7 @@ def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp, fmt="bedpe", ext=50):
 
 
 def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0, cut=0, plot=0, max_cut=False,
-         log=None, reader="gpu", fmt="auto", ext=50):
+         log=None, reader="gpu", fmt="auto", ext=50, agg=0, agg_res=0):
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
@@ -1047,7 +1047,10 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     `reader`: "gpu" reads the BEDPE files on the device (K16, cloops_amd.ingest): the chromosomes go from the text to HBM
     without `.jd` files, which are written only with `tmp`; "host" is cloops_amd.io's Python loop and its `.jd` files.
     `fmt`: "bedpe", "pairs" (4DN pairs read with the extension `ext`, K18, cloops_amd.pairs) or "auto": pairs exactly when the
-    first file's first line starts with `## pairs format`."""
+    first file's first line starts with `## pairs format`.
+    `agg` writes `<fout>_agg.txt`, `<fout>_agg_loops.txt` and `<fout>_agg.json` after `<fout>.loop`: the aggregate pile-up of the PETs
+    around the significant loops just called (K19, cloops_amd.agg), from the chromosomes still resident, in bins of `agg_res` bp
+    (0: the largest eps of the run)."""
     import shutil
     if reader not in ("gpu", "host"):
         raise ValueError("reader must be 'gpu' or 'host', got %r" % (reader,))
@@ -1090,6 +1093,9 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
         dataI, cut, cuts, steps = runSweepFast(cfs, eps, minPts, cut=cut, max_cut=max_cut, log=log, plot=fout if plot else None)
         records = {key: {"f": v["f"], "records": _records(key, v["boxes"])} for key, v in dataI.items()}
         e = cModel.runStat(records, minPts, 0, cpu, fout, hic)    # pipe.py:284 passes cut = 0
+        if agg and not e:
+            from .agg import aggLoops
+            aggLoops(fout + ".loop", list(cfs), fout, res=int(agg_res) if agg_res else int(max(eps)))
     finally:
         for f in mem:                                         # 'mem://' residents are never evicted by age
             CACHE.drop(f)
@@ -1109,7 +1115,8 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
 
 def main(argv=None):
     """`python -m cloops_amd -f a.bedpe.gz -o out -m 1` -- the flags of cLoops/utils.py:73-204 that
-    drive the hot path (same names; -w / -j write the loop tracks, -plot the distance-cutoff picture of every sweep step)."""
+    drive the hot path (same names; -w / -j write the loop tracks, -plot the distance-cutoff picture of every sweep step, -agg the
+    aggregate pile-up around the called loops in bins of -res bp)."""
     import argparse
     ap = argparse.ArgumentParser(prog="cloops_amd")
     ap.add_argument("-f", dest="fnIn", required=True)
@@ -1129,6 +1136,8 @@ def main(argv=None):
     ap.add_argument("-reader", dest="reader", default="gpu", choices=["host", "gpu"])
     ap.add_argument("-fmt", dest="fmt", default="auto", choices=["auto", "bedpe", "pairs"])
     ap.add_argument("-ext", dest="ext", type=int, default=50)
+    ap.add_argument("-agg", dest="agg", action="store_true")
+    ap.add_argument("-res", dest="res", type=int, default=0)
     op = ap.parse_args(argv)
     if op.mode == 0:                                          # pipe.py:306-327
         eps = sorted(int(x) for x in str(op.eps).split(","))
@@ -1141,5 +1150,6 @@ def main(argv=None):
         eps, minPts, hic = MODES[op.mode]
     sys.stderr.write("mode:%s\t eps:%s\t minPts:%s\t hic:%s\t\n" % (op.mode, eps, minPts, hic))
     pipe(op.fnIn.split(","), op.fnOut, eps, minPts, op.chroms, op.cpu, op.tmp, hic, op.washU, op.juice, op.cut,
-         op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader, fmt=op.fmt, ext=op.ext)
+         op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader, fmt=op.fmt, ext=op.ext,
+         agg=op.agg, agg_res=op.res)
     return 0

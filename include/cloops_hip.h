@@ -275,6 +275,30 @@ int cl_anchor_mask(cl_chrom* c, int64_t n_iv, const int64_t* starts, const int64
                    uint64_t* mask, int64_t* n_merged, int64_t* n_kept);
 
 /*
+ * Aggregate pile-up of the PETs around loop centres (K19; the aggregate peak analysis of Rao et al. 2014 -- the reference
+ * has no counterpart).  The rows with Y - X >= cut take part (all rows for cut <= 0).  With W = 2 w + 1, the window of the
+ * loop with centre (cx, cy) starts at ox = cx - w res - res / 2, oy = cy - w res - res / 2 (res / 2 rounded down); a row belongs
+ * to it iff 0 <= X - ox < W res and 0 <= Y - oy < W res, and falls into cell i = (X - ox) / res (the X bin), j = (Y - oy) / res
+ * (the Y bin) of the loop's matrix M (no negative number is ever divided; duplicated rows count each time; a window may reach
+ * below 0 or beyond the last row: those cells are 0).
+ *   sum_out    W x W int64, row-major [i][j]: the sum of M over all loops
+ *   stats_out  NULL, or n_loops x 6 int32 in the caller's loop order: total = sum of M, centre = M[w][w], and the sums of the four
+ *              corner x corner blocks ll = M[W-corner.., ..corner) (nearest the diagonal), ul = M[..corner, ..corner),
+ *              ur = M[..corner, W-corner..), lr = M[W-corner.., W-corner..)
+ *   mats_out   NULL, or n_loops x W x W int32: every loop's M
+ *   n_kept     NULL, or the number of rows that pass the cut
+ * Every value is an integer count, so nothing depends on how the loops are scheduled.  Centres may lie anywhere in int32: they are
+ * CLAMPED to [-2^30, 2^30], which changes no count (every coordinate of a handle satisfies |v| < 2^29 and W res < 2^29, so the
+ * window of a centre at or beyond +-2^30 is as empty as that of its clamped twin) and keeps the window arithmetic inside 32 bits.
+ * n_loops == 0, a handle without rows, or a cut that removes every row: zero outputs and CL_OK.  Errors: CL_ERR_ARG for a NULL
+ * handle or sum_out, res < 1, w outside [1, 20], corner outside [1, w], W res >= 2^29, n_loops < 0, NULL cx / cy with
+ * n_loops > 0, or runs in flight.  Keeps the rows that pass `cut`, sorted by X, in scratch of its own that stays with the handle
+ * (rebuilt when another cut is asked for); leaves the handle's layouts, count cache and K8 tables untouched.
+ */
+int cl_agg_loops(cl_chrom* c, int32_t cut, int32_t res, int32_t w, int32_t corner, int64_t n_loops, const int32_t* cx,
+                 const int32_t* cy, int64_t* sum_out, int32_t* stats_out, int32_t* mats_out, int64_t* n_kept);
+
+/*
  * Browser-track text of the PETs (K14): the lines cLoops/io.py:292-348 writes per PET, made on the device in chunks.
  *
  * cl_track_build -- jd2washU / jd2hic's loop over parseJd(f, cut) (io.py:206-217, :301-318, :336-342).  Rows with
