@@ -107,6 +107,12 @@ PROTOTYPES = {
     "cl_track_chunks": (_int, [_vp, _i64, _i64, _vp, _vp, _i64p]),
     "cl_track_render": (_int, [_vp, _i64, _vp, _i64, _i64p]),
     "cl_track_free": (_int, [_vp]),
+    "cl_cov_build": (_int, [_vp, _i64, _i32, _i64, _i64, _i64p, ctypes.POINTER(_u32), _i64p, _i64p]),
+    "cl_cov_runs": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "cl_cov_text": (_int, [_vp, _cp, _i64, _i64, _i64p]),
+    "cl_cov_chunks": (_int, [_vp, _i64, _i64, _vp, _vp, _i64p]),
+    "cl_cov_render": (_int, [_vp, _i64, _vp, _i64, _i64p]),
+    "cl_cov_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

@@ -599,6 +599,111 @@ class Chromosome(_Handle):
             for p in bufs:
                 self._lib.cl_host_free(ctypes.c_void_p(p))
 
+    COVERAGE_SCALE_MAX = 1 << 30                   # largest scale numerator of coverage_text
+
+    def coverage_build(self, cut=0, ends=3, ext=75, res=0):
+        """K20: the coverage of the genome by this chromosome's PET ends, built on the device and kept for coverage_runs /
+        coverage_text.  Rows with Y - X >= cut (all for cut <= 0); ends: 1 = X, 2 = Y, 3 = both; an end point p stands for
+        [max(0, p - ext), p + ext) (res == 0) or for its bin [floor(p / res) res, ... + res) (res >= 1, ext ignored) ->
+        (n_runs, max_depth, n_ends, area): the maximal runs of constant depth > 0, the largest depth, the end points taken, the sum
+        of depth * length over the runs  (cl_cov_build)"""
+        res = int(res)
+        nr, md, ne, ar = ctypes.c_int64(0), ctypes.c_uint32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_cov_build(self._h, int(cut), int(ends), 0 if res > 0 else int(ext), res, ctypes.byref(nr), ctypes.byref(md),
+                                          ctypes.byref(ne), ctypes.byref(ar)))
+        self._cov_runs = int(nr.value)
+        self._cov_bounds = ([0], [0])
+        return int(nr.value), int(md.value), int(ne.value), int(ar.value)
+
+    def coverage_runs(self, first=0, count=None):
+        """runs [first, first + count) of the built coverage (all from `first` on by default) -> (start int32, end int32, depth
+        uint32)  (cl_cov_runs)"""
+        first = int(first)
+        count = max(0, getattr(self, "_cov_runs", 0) - first) if count is None else int(count)
+        n = max(0, count)
+        s, e, d = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint32)
+        _lib.check(self._lib.cl_cov_runs(self._h, first, count, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p),
+                                         d.ctypes.data_as(ctypes.c_void_p)))
+        return s, e, d
+
+    def coverage_text(self, name, scale=None):
+        """the bedGraph text of the built runs, one line `name\\tstart\\tend\\tvalue\\n` per run, laid out on the device -> its bytes.
+        scale None: value = the depth; scale (num, den): the fixed-point number (depth * num + den // 2) // den thousandths with
+        three decimals (counts per million: num = 10^9, den = the end points of every chromosome written)  (cl_cov_text)"""
+        num, den = (0, 0) if scale is None else (int(scale[0]), int(scale[1]))
+        if scale is not None and den < 1:
+            raise ValueError("coverage_text: the scale's denominator must be >= 1, got %s" % (den,))
+        nb = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_cov_text(self._h, name.encode(), num, den, ctypes.byref(nb)))
+        return int(nb.value)
+
+    def coverage_chunks(self, budget=TRACK_BUDGET):
+        """the coverage text split into chunks of at most `budget` bytes, none splitting a line -> (run bounds, byte bounds), int64
+        [chunks + 1]  (cl_cov_chunks)"""
+        nc = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_cov_chunks(self._h, int(budget), 0, None, None, ctypes.byref(nc)))
+        run = np.zeros(nc.value + 1, dtype=np.int64)
+        byt = np.zeros(nc.value + 1, dtype=np.int64)
+        _lib.check(self._lib.cl_cov_chunks(self._h, int(budget), len(run), run.ctypes.data_as(ctypes.c_void_p),
+                                           byt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nc)))
+        self._cov_bounds = (run, byt)
+        return run, byt
+
+    def coverage_render(self, chunk, out=None):
+        """the text of chunk `chunk` of the last coverage_chunks -> bytes; with `out` (a writable buffer or a (pointer, capacity)
+        pair of page-locked memory) it is written there and its length returned  (cl_cov_render)"""
+        nb = ctypes.c_int64(0)
+        if out is None:
+            run, byt = getattr(self, "_cov_bounds", ([0], [0]))
+            cap = max(1, int(byt[chunk + 1] - byt[chunk])) if 0 <= chunk < len(run) - 1 else 1     # (the library reports the index)
+            buf = np.empty(cap, dtype=np.uint8)
+            _lib.check(self._lib.cl_cov_render(self._h, int(chunk), buf.ctypes.data_as(ctypes.c_void_p), len(buf), ctypes.byref(nb)))
+            return buf[:nb.value].tobytes()
+        if isinstance(out, tuple):
+            ptr, cap = out
+        else:
+            a = np.frombuffer(out, dtype=np.uint8)
+            ptr, cap = a.ctypes.data, len(a)
+        _lib.check(self._lib.cl_cov_render(self._h, int(chunk), ctypes.c_void_p(ptr), int(cap), ctypes.byref(nb)))
+        return int(nb.value)
+
+    def coverage_free(self):
+        """releases the device scratch of coverage_build  (cl_cov_free)"""
+        _lib.check(self._lib.cl_cov_free(self._h))
+        self._cov_runs = 0
+
+    def coverage_iter(self, budget=TRACK_BUDGET):
+        """the chunks of the coverage text in order, as memoryviews of two page-locked buffers, like track_iter: chunk k + 1 is
+        rendered and copied while the caller consumes chunk k.  A view is valid until the next one is requested."""
+        run, byt = self.coverage_chunks(budget)
+        K = len(run) - 1
+        if K == 0:
+            return
+        size = int(np.max(np.diff(byt)))
+        bufs = []
+        pool = None
+        fut = None
+        try:
+            for _ in range(2):
+                bufs.append(_lib.host_alloc(size))
+            from concurrent.futures import ThreadPoolExecutor
+            pool = ThreadPoolExecutor(1)
+            fut = pool.submit(self.coverage_render, 0, (bufs[0], size))
+            for k in range(K):
+                nb = fut.result()
+                fut = pool.submit(self.coverage_render, k + 1, (bufs[(k + 1) & 1], size)) if k + 1 < K else None
+                yield memoryview((ctypes.c_char * nb).from_address(bufs[k & 1])).cast("B")
+        finally:
+            if fut is not None:
+                try:
+                    fut.result()
+                except Exception:
+                    pass
+            if pool is not None:
+                pool.shutdown()
+            for p in bufs:
+                self._lib.cl_host_free(ctypes.c_void_p(p))
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

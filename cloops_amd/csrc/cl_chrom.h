@@ -228,6 +228,17 @@ struct cl_chrom {
         long long cut = 0, ext = 0, R = 0, total = 0;                // records, bytes of the whole text
         std::vector<long long> crec, cbyte;                          // the last cl_track_chunks: record / byte bounds
     } tk;
+    // K20 (k_cover.hip): the sorted end-point keys (in / out, sort scratch), per candidate break point its depth after / before and
+    // its rank among the other side's candidates, the run-start flags and their scan, counters, the runs (start, end, depth), line
+    // lengths / ends, the name, chunk bounds, render output; kept from cl_cov_build to the next build, cl_cov_free or destruction
+    DevBuf cv_kin, cv_key, cv_tmp, cv_dcur, cv_dprev, cv_xr, cv_flag, cv_scan, cv_ctr, cv_start, cv_end, cv_depth, cv_len, cv_lend, cv_name,
+           cv_bnd, cv_out;
+    struct CovState {
+        bool built = false, text = false;
+        int la = 0;
+        long long R = 0, total = 0, num = 0, den = 0;                // runs; bytes of the whole text and its scale (cl_cov_text)
+        std::vector<long long> crun, cbyte;                          // the last cl_cov_chunks: run / byte bounds
+    } cv;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
@@ -308,6 +319,11 @@ int lists_emit_records(cl_chrom* c, const GridParams& g, int nm, const ListRun& 
 int lists_scatter_owner(cl_chrom* c, int nm, const ListRun& L);
 int lists_final(cl_chrom* c, const GridParams& g, int nm, const ListRun& L, bool rows, int* pair_count);
 int lists_rowmask(cl_chrom* c, int* total);
+
+// kernel of k_track.hip that K20 (k_cover.hip) launches too: the chunk bounds over the running sum of line lengths
+__global__ void __launch_bounds__(TPB)
+k14_bounds(const long long* __restrict__ end, long long R, long long step, long long K, long long* __restrict__ brec,
+           long long* __restrict__ bbyte);
 
 // kernels of k_sweep.hip that the step tail (finish_enqueue) launches
 __global__ void __launch_bounds__(256)

@@ -1036,7 +1036,7 @@ def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp, fmt="bedpe", ext=50):
 
 
 def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0, cut=0, plot=0, max_cut=False,
-         log=None, reader="gpu", fmt="auto", ext=50, agg=0, agg_res=0):
+         log=None, reader="gpu", fmt="auto", ext=50, agg=0, agg_res=0, bdg=0, bdg_ext=75):
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
@@ -1050,7 +1050,9 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     first file's first line starts with `## pairs format`.
     `agg` writes `<fout>_agg.txt`, `<fout>_agg_loops.txt` and `<fout>_agg.json` after `<fout>.loop`: the aggregate pile-up of the PETs
     around the significant loops just called (K19, cloops_amd.agg), from the chromosomes still resident, in bins of `agg_res` bp
-    (0: the largest eps of the run)."""
+    (0: the largest eps of the run).
+    `bdg` writes `<fout>.bedGraph` and `<fout>_bedGraph.json` after `<fout>.loop`: the coverage of the genome by both ends of every PET
+    (raw depth, cut 0, K20, cloops_amd.coverage), from the chromosomes still resident, each end standing for `bdg_ext` bp to either side."""
     import shutil
     if reader not in ("gpu", "host"):
         raise ValueError("reader must be 'gpu' or 'host', got %r" % (reader,))
@@ -1096,6 +1098,9 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
         if agg and not e:
             from .agg import aggLoops
             aggLoops(fout + ".loop", list(cfs), fout, res=int(agg_res) if agg_res else int(max(eps)))
+        if bdg and not e:
+            from .coverage import jd2bedgraph
+            jd2bedgraph(list(cfs), fout, ext=int(bdg_ext))
     finally:
         for f in mem:                                         # 'mem://' residents are never evicted by age
             CACHE.drop(f)
@@ -1116,7 +1121,8 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
 def main(argv=None):
     """`python -m cloops_amd -f a.bedpe.gz -o out -m 1` -- the flags of cLoops/utils.py:73-204 that
     drive the hot path (same names; -w / -j write the loop tracks, -plot the distance-cutoff picture of every sweep step, -agg the
-    aggregate pile-up around the called loops in bins of -res bp)."""
+    aggregate pile-up around the called loops in bins of -res bp, -bdg the coverage of the PET ends as a bedGraph with -bdgext bp
+    to either side of an end)."""
     import argparse
     ap = argparse.ArgumentParser(prog="cloops_amd")
     ap.add_argument("-f", dest="fnIn", required=True)
@@ -1138,6 +1144,8 @@ def main(argv=None):
     ap.add_argument("-ext", dest="ext", type=int, default=50)
     ap.add_argument("-agg", dest="agg", action="store_true")
     ap.add_argument("-res", dest="res", type=int, default=0)
+    ap.add_argument("-bdg", dest="bdg", action="store_true")
+    ap.add_argument("-bdgext", dest="bdgext", type=int, default=75)
     op = ap.parse_args(argv)
     if op.mode == 0:                                          # pipe.py:306-327
         eps = sorted(int(x) for x in str(op.eps).split(","))
@@ -1151,5 +1159,5 @@ def main(argv=None):
     sys.stderr.write("mode:%s\t eps:%s\t minPts:%s\t hic:%s\t\n" % (op.mode, eps, minPts, hic))
     pipe(op.fnIn.split(","), op.fnOut, eps, minPts, op.chroms, op.cpu, op.tmp, hic, op.washU, op.juice, op.cut,
          op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader, fmt=op.fmt, ext=op.ext,
-         agg=op.agg, agg_res=op.res)
+         agg=op.agg, agg_res=op.res, bdg=op.bdg, bdg_ext=op.bdgext)
     return 0

@@ -336,6 +336,52 @@ int cl_track_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t*
 int cl_track_free(cl_chrom* c);
 
 /*
+ * 1D coverage of the genome by the PET ends (K20): the signal track that is loaded next to a loop track, as the runs of a
+ * bedGraph.  The reference has no counterpart; every value is an integer.
+ *
+ * Kept rows: all rows for cut <= 0, otherwise the rows with Y - X >= cut.  End points: `ends` is a bit set -- 1 takes every
+ * kept row's X, 2 every kept row's Y, 3 both (a row with X == Y then contributes twice); *n_ends is their number, those whose
+ * interval turns out empty included.  The interval of an end point p:
+ *   window mode (res == 0, ext >= 1)   [max(0, p - ext), p + ext): the start / end of a washU record (cLoops/io.py:306-307)
+ *   bin mode (res >= 1, ext == 0)      [b, b + res) with b = floor(p / res) * res (floor also for negative p), start clamped to 0
+ * An interval with end <= start after the clamp is dropped (only p < 0 can do that).  depth(t) is the number of intervals that
+ * contain base t.  The runs are the maximal [start, end) of constant depth > 0 in ascending order: zero depth is not reported, and
+ * two adjacent stretches of equal depth are ONE run (as many intervals end as begin at a position).
+ *
+ * cl_cov_build -- builds the runs on the device in scratch of its own -> *n_runs, *max_depth (the largest depth; n_ends < 2^32),
+ * *n_ends, *area = the sum of depth * (end - start) over the runs (= the sum of the kept intervals' lengths).  An empty handle, a
+ * cut that removes every row, or only empty intervals: zero runs and CL_OK.  Errors: CL_ERR_ARG for a NULL handle or NULL outputs,
+ * ends outside 1..3, ext < 1 in window mode or ext >= 2^29, res < 0, res >= 2^29, res > 0 with ext != 0, more than 2^31 - 4096 end
+ * points, or runs in flight.  The scratch lives until the next build (which rebuilds it: nothing of an earlier build is read
+ * again), cl_cov_free or cl_chrom_destroy; the handle's layouts, count cache, K8 / K13 / K14 / K19 state and results stay untouched.
+ *
+ * cl_cov_runs -- runs [first, first + count) of the last build into host memory: start and end as int32, depth as uint32.
+ * Errors: CL_ERR_ARG for no build, a range outside [0, n_runs], NULL outputs with count > 0, or runs in flight.
+ *
+ * cl_cov_text -- line lengths and offsets of the text of the built runs, one line per run, `name\tstart\tend\tvalue\n` ->
+ * *n_bytes of the whole text.  scale_den == 0: value = the depth in decimal.  Otherwise a fixed-point number with exactly three
+ * decimals: q = (depth * scale_num + scale_den / 2) / scale_den in unsigned 64-bit arithmetic (both divisions round down), value
+ * = q / 1000, '.', q % 1000 with three digits; scale_num <= 2^30 keeps depth * scale_num inside 64 bits.  Counts per million end
+ * points: scale_num = 10^9, scale_den = the n_ends of every chromosome written.  No floating point touches the text.  Errors:
+ * CL_ERR_ARG for no build, a NULL name / n_bytes, a name longer than CL_TRACK_NAME_MAX bytes, scale_den < 0, scale_num outside
+ * [0, 2^30] (outside [1, 2^30] with scale_den > 0), or runs in flight.
+ *
+ * cl_cov_chunks, cl_cov_render -- as cl_track_chunks / cl_track_render over that text: chunk k is runs [run_bounds[k],
+ * run_bounds[k + 1]), bytes [byte_bounds[k], byte_bounds[k + 1]); no chunk is empty and none splits a line.  Errors: CL_ERR_ARG
+ * for no built text, a budget below the longest line the template allows (CL_TRACK_NAME_MAX + 44 bytes covers every template), cap
+ * too small, a chunk index out of range, or runs in flight.
+ *
+ * cl_cov_free -- releases the scratch of cl_cov_build.
+ */
+int cl_cov_build(cl_chrom* c, int64_t cut, int32_t ends, int64_t ext, int64_t res, int64_t* n_runs, uint32_t* max_depth,
+                 int64_t* n_ends, int64_t* area);
+int cl_cov_runs(cl_chrom* c, int64_t first, int64_t count, int32_t* start_out, int32_t* end_out, uint32_t* depth_out);
+int cl_cov_text(cl_chrom* c, const char* name, int64_t scale_num, int64_t scale_den, int64_t* n_bytes);
+int cl_cov_chunks(cl_chrom* c, int64_t budget, int64_t cap, int64_t* run_bounds, int64_t* byte_bounds, int64_t* n_chunks);
+int cl_cov_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n_bytes);
+int cl_cov_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
