@@ -704,6 +704,65 @@ class Chromosome(_Handle):
             for p in bufs:
                 self._lib.cl_host_free(ctypes.c_void_p(p))
 
+    def peaks_sort(self, cut=0, ends=3):
+        """K21: this chromosome's PET ends sorted once on the device and kept for peaks_call / peaks_count / peaks_summits.  Rows
+        with Y - X >= cut (all for cut <= 0); ends: 1 = X, 2 = Y, 3 = both -> (n_ends, vmin, vmax): the end points taken, the
+        smallest and the largest of them (0, 0, 0 without end points)  (cl_peak_sort)"""
+        ne, lo, hi = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._peaks = 0
+        _lib.check(self._lib.cl_peak_sort(self._h, int(cut), int(ends), ctypes.byref(ne), ctypes.byref(lo), ctypes.byref(hi)))
+        return int(ne.value), int(lo.value), int(hi.value)
+
+    def peaks_call(self, eps, minPts):
+        """the candidate peaks of (eps, minPts) over the sorted end points: 1D DBSCAN in the order of the positions, a border point
+        between two chains of cores going to the left one -> (n_peaks, n_cores, n_clustered); the peaks stay on the device for
+        peaks_get until the next call or sort  (cl_peak_call)"""
+        npk, nc, ncl = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._peaks = 0
+        _lib.check(self._lib.cl_peak_call(self._h, int(eps), int(minPts), ctypes.byref(npk), ctypes.byref(nc), ctypes.byref(ncl)))
+        self._peaks = int(npk.value)
+        return int(npk.value), int(nc.value), int(ncl.value)
+
+    def peaks_get(self, first=0, count=None):
+        """peaks [first, first + count) of the last peaks_call (all from `first` on by default) -> (start int32, end int32, n_points
+        uint32, n_cores uint32); [start, end) is half-open  (cl_peak_get)"""
+        first = int(first)
+        count = max(0, getattr(self, "_peaks", 0) - first) if count is None else int(count)
+        n = max(0, count)
+        s, e = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        p, c = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        _lib.check(self._lib.cl_peak_get(self._h, first, count, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p),
+                                         p.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p)))
+        return s, e, p, c
+
+    def peaks_count(self, starts, ends):
+        """the sorted end points in every half-open interval [starts[k], ends[k]) (int64 bounds; any order, overlapping, empty or
+        beyond the end points) -> uint32 counts  (cl_peak_count)"""
+        s, e = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
+        if s.ndim != 1 or s.shape != e.shape:
+            raise ValueError("peaks_count: starts and ends must be one-dimensional and of equal length")
+        out = np.zeros(len(s), dtype=np.uint32)
+        _lib.check(self._lib.cl_peak_count(self._h, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p), len(s),
+                                           out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def peaks_summits(self, starts, ends, w):
+        """the summit of every interval [starts[k], ends[k]) (ascending and disjoint): the position of its end point with the most
+        end points within w bp, the smallest on ties, and that number -> (pos int32, -1 for an interval without points; cnt
+        uint32)  (cl_peak_summits)"""
+        s, e = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
+        if s.ndim != 1 or s.shape != e.shape:
+            raise ValueError("peaks_summits: starts and ends must be one-dimensional and of equal length")
+        pos, cnt = np.zeros(len(s), dtype=np.int32), np.zeros(len(s), dtype=np.uint32)
+        _lib.check(self._lib.cl_peak_summits(self._h, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p), len(s), int(w),
+                                             pos.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
+        return pos, cnt
+
+    def peaks_free(self):
+        """releases the device scratch of peaks_sort and the calls after it  (cl_peak_free)"""
+        _lib.check(self._lib.cl_peak_free(self._h))
+        self._peaks = 0
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

@@ -239,6 +239,17 @@ struct cl_chrom {
         long long R = 0, total = 0, num = 0, den = 0;                // runs; bytes of the whole text and its scale (cl_cov_text)
         std::vector<long long> crun, cbyte;                          // the last cl_cov_chunks: run / byte bounds
     } cv;
+    // K21 (k_peak.hip): the sorted end-point keys (in / out, sort scratch), per element the ranks of its window's two edges, the core
+    // flags and their scan, the chain-head flags and their scan, per peak the indices of its first / last core and the four results,
+    // counters; the intervals of a count / summit call with their results; kept from cl_peak_sort to the next sort, cl_peak_free or
+    // destruction
+    DevBuf pk_kin, pk_key, pk_tmp, pk_lo, pk_hi, pk_flag, pk_C, pk_head, pk_H, pk_a, pk_b, pk_start, pk_end, pk_np, pk_nc, pk_ctr,
+           pk_ivs, pk_ive, pk_best, pk_opos, pk_ocnt;
+    struct PeakState {
+        bool sorted = false, called = false;
+        int base = 0;                                                // the value of key 0
+        long long m = 0, P = 0;                                      // end points; peaks of the last cl_peak_call
+    } pk;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;

@@ -382,6 +382,54 @@ int cl_cov_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n
 int cl_cov_free(cl_chrom* c);
 
 /*
+ * Peaks of the PET ends (K21): where the ends themselves pile up -- the binding sites or anchors looked at next to the loops -- as
+ * 1D density clustering of the end points, counts of end points in intervals and the summits of intervals.  The reference has no
+ * counterpart; every value is an integer (the significance test stays on the host, cloops_amd/peaks.py).
+ *
+ * End points, as for cl_cov_build: the rows with Y - X >= cut take part (all for cut <= 0); `ends` is 1, 2 or 3 for X, Y or both
+ * (a row with X == Y counts twice under 3).  S is the ascending multiset of these m values; equal values are separate points.
+ * m <= 2^31 - 4096.  lb(x) = #{p in S : p < x}, ub(x) = #{p in S : p <= x}.
+ *
+ * Candidate peaks of a setting (eps, min_pts), 1 <= eps < 2^29, min_pts >= 1:
+ *   n(i) = #{j : |S[j] - S[i]| <= eps} = ub(S[i] + eps) - lb(S[i] - eps), the point itself included; point i is a core iff
+ *   n(i) >= min_pts.  A chain is a maximal set of cores in which neighbouring cores, in the order of S, lie at most eps apart
+ *   (equal positions are 0 apart); chain k has its first core at position a_k and its last at b_k.  The members of peak k are the
+ *   points at positions p with max(a_k - eps, b_(k-1) + eps + 1) <= p <= b_k + eps (b_(-1) = -infinity): a border point within eps
+ *   of the cores of two chains belongs to the left one, as in sequential DBSCAN over ascending points.  They are a contiguous index
+ *   range [i0, i1) of S, and the peak is start = S[i0], end = S[i1 - 1] + 1 (half-open, BED), n_points = i1 - i0, n_cores = the
+ *   cores of the chain.  Peaks come in ascending order and are disjoint.
+ * Counts: for any half-open interval [s, e) with int64 bounds, #{p in S : s <= p < e}; intervals may overlap, be unordered, be
+ * empty (e <= s: 0), and reach below S[0] or beyond S[m - 1].
+ * Summits: for ascending, pairwise disjoint intervals (starts[k] <= ends[k] <= starts[k + 1]) and a half-width w, 1 <= w < 2^29:
+ * the position of the member point with the largest n_w(i) = #{j : |S[j] - S[i]| <= w}, the smallest such position on ties, and
+ * that n_w; an interval without points gives position -1 and count 0.
+ *
+ * cl_peak_sort -- the end points as keys, sorted once on the device in scratch of its own -> *n_ends = m, *vmin = S[0], *vmax =
+ * S[m - 1].  The sorted array stays until the next sort, cl_peak_free or cl_chrom_destroy, and serves every call, get, count and
+ * summit call in between.  An empty handle or a cut that removes every row: zero end points, vmin = vmax = 0 and CL_OK.  A sort
+ * forgets the peaks called before it.
+ * cl_peak_call -- the candidate peaks of (eps, min_pts) over the sorted end points -> *n_peaks, *n_cores (all cores), *n_clustered
+ * (the sum of n_points).  A setting without cores (or no end points): zeros and CL_OK.  It replaces the peaks of the call before.
+ * cl_peak_get -- peaks [first, first + count) of the last call into host memory: start and end as int32, n_points and n_cores as
+ * uint32.
+ * cl_peak_count -- counts[k] = the end points in [starts[k], ends[k]) for n intervals.
+ * cl_peak_summits -- pos[k], cnt[k] = the summit of [starts[k], ends[k]) for n intervals and the half-width w.
+ * cl_peak_free -- releases the scratch of cl_peak_sort and of the calls after it.
+ *
+ * Errors: CL_ERR_ARG for a NULL handle or NULL outputs (arrays may be NULL when their count is 0), ends outside 1..3, eps or w
+ * outside [1, 2^29), min_pts < 1, a call, get, count or summit before a sort, a get before a call, a range outside [0, n_peaks],
+ * summit intervals that are not ascending and disjoint, more than 2^31 - 4096 end points (or intervals), or runs in flight; all of
+ * them are found on the host before any launch.  The handle's layouts, count cache, K8 / K13 / K14 / K19 / K20 state and results
+ * stay untouched.
+ */
+int cl_peak_sort(cl_chrom* c, int64_t cut, int32_t ends, int64_t* n_ends, int64_t* vmin, int64_t* vmax);
+int cl_peak_call(cl_chrom* c, int64_t eps, int64_t min_pts, int64_t* n_peaks, int64_t* n_cores, int64_t* n_clustered);
+int cl_peak_get(cl_chrom* c, int64_t first, int64_t count, int32_t* start, int32_t* end, uint32_t* n_points, uint32_t* n_cores);
+int cl_peak_count(cl_chrom* c, const int64_t* starts, const int64_t* ends, int64_t n, uint32_t* counts);
+int cl_peak_summits(cl_chrom* c, const int64_t* starts, const int64_t* ends, int64_t n, int64_t w, int32_t* pos, uint32_t* cnt);
+int cl_peak_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
