@@ -119,6 +119,10 @@ PROTOTYPES = {
     "cl_peak_count": (_int, [_vp, _vp, _vp, _i64, _vp]),
     "cl_peak_summits": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "cl_peak_free": (_int, [_vp]),
+    "cl_dom_tracks": (_int, [_vp, _i64, _i64, _i64, _i64p, _i64p, _i64p]),
+    "cl_dom_get": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "cl_dom_count": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "cl_dom_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

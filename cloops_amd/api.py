@@ -763,6 +763,44 @@ class Chromosome(_Handle):
         _lib.check(self._lib.cl_peak_free(self._h))
         self._peaks = 0
 
+    def domains_tracks(self, cut=0, res=10000, w=10):
+        """K22: the three insulation tracks of this chromosome over bins of `res` bp with a window of `w` bins, kept on the device for
+        domains_get / domains_count.  Rows with Y - X >= cut (all for cut <= 0), sorted by X once per cut (K19's table, shared with
+        agg_loops): another w or res sorts nothing -> (n_bins, bin0, n_kept); entry k of a track stands for the boundary at the start
+        of bin bin0 + k (0, 0, 0 without rows)  (cl_dom_tracks)"""
+        nb, b0, nk = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_dom_tracks(self._h, int(cut), int(res), int(w), ctypes.byref(nb), ctypes.byref(b0), ctypes.byref(nk)))
+        self._dom_bins = int(nb.value)
+        return int(nb.value), int(b0.value), int(nk.value)                   # (a refused call leaves the earlier tracks and their size)
+
+    def domains_get(self, first=0, count=None):
+        """entries [first, first + count) of the last domains_tracks (all from `first` on by default) -> (cross, up, down) uint32: the
+        rows that cross the boundary inside the window, and those that stay in the window before / behind it  (cl_dom_get)"""
+        first = int(first)
+        count = max(0, getattr(self, "_dom_bins", 0) - first) if count is None else int(count)
+        n = max(0, count)
+        a, b, d = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        _lib.check(self._lib.cl_dom_get(self._h, first, count, a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p),
+                                        d.ctypes.data_as(ctypes.c_void_p)))
+        return a, b, d
+
+    def domains_count(self, starts, ends):
+        """the kept rows of the last domains_tracks in every half-open interval [starts[k], ends[k]) (int64 bounds; ascending and
+        disjoint, possibly empty or abutting) -> (intra, nx, ny) uint32: rows with both ends, with X, with Y inside  (cl_dom_count)"""
+        s, e = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
+        if s.ndim != 1 or s.shape != e.shape:
+            raise ValueError("domains_count: starts and ends must be one-dimensional and of equal length")
+        a, b, d = (np.zeros(len(s), dtype=np.uint32) for _ in range(3))
+        _lib.check(self._lib.cl_dom_count(self._h, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p), len(s),
+                                          a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p),
+                                          d.ctypes.data_as(ctypes.c_void_p)))
+        return a, b, d
+
+    def domains_free(self):
+        """releases the tracks and the device scratch of domains_tracks / domains_count  (cl_dom_free)"""
+        _lib.check(self._lib.cl_dom_free(self._h))
+        self._dom_bins = 0
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

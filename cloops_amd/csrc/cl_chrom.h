@@ -250,6 +250,17 @@ struct cl_chrom {
         int base = 0;                                                // the value of key 0
         long long m = 0, P = 0;                                      // end points; peaks of the last cl_peak_call
     } pk;
+    // K22 (k_domain.hip): the three difference arrays over the bins (n_bins + 1 entries each) and their scans (cross, up, down: n_bins
+    // entries each), the scan's scratch, the range of the kept rows' coordinates; the intervals of a count call and their three
+    // counters.  The rows themselves are K19's X-sorted table (ag_sx / ag_sy / ag_kept, agg_table), shared.  Kept from cl_dom_tracks
+    // to the next one, cl_dom_free or destruction
+    DevBuf dm_diff, dm_trk, dm_tmp, dm_rng, dm_ivs, dm_ive, dm_cnt;
+    struct DomState {
+        bool ready = false;
+        int cut = 0, res = 0, w = 0;
+        int pmin = 0, pmax = 0;                                      // smallest / largest coordinate of the kept rows (of `cut`)
+        long long bmin = 0, n_bins = 0, n_kept = 0;
+    } dm;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
@@ -371,3 +382,6 @@ __device__ __forceinline__ int k8_ub(const u64* __restrict__ t, int m, long long
 // builds the tables of (chromosome, cut) unless the handle holds them already (c->sig_tx / sig_ty; c->sig_m[0] on the device = the
 // number of valid entries); enqueued on c->stream, c->n > 0
 int sig_tables(cl_chrom* c, int cut);
+// K19's table (k_agg.hip), shared with K22 (k_domain.hip): the rows with Y - X >= cut sorted by X (c->ag_sx: X + 2^30 as u32, c->ag_sy:
+// their Y, c->ag_kept rows) unless the handle holds it for this cut already; c->n > 0
+int agg_table(cl_chrom* c, int cut);

@@ -181,8 +181,8 @@ static bool k19_wave_form()
     return false;
 }
 
-// the X-sorted table of (chromosome, cut) unless the handle holds it already; c->n > 0
-static int agg_table(cl_chrom* c, int cut)
+// the X-sorted table of (chromosome, cut) unless the handle holds it already; c->n > 0 (declared in cl_chrom.h: K22 shares it)
+int agg_table(cl_chrom* c, int cut)
 {
     if (c->ag_ready && c->ag_cut == cut) return CL_OK;
     c->ag_ready = false;

@@ -430,6 +430,46 @@ int cl_peak_summits(cl_chrom* c, const int64_t* starts, const int64_t* ends, int
 int cl_peak_free(cl_chrom* c);
 
 /*
+ * Domains (K22): the integers behind a domain call -- three insulation tracks over the bins of a chromosome and the PETs of called
+ * domains.  The reference has no counterpart, so these definitions are the specification; the scores and thresholds stay on the host
+ * (cloops_amd/domains.py).
+ *
+ * Kept rows, as for cl_agg_loops, cl_cov_build and cl_peak_sort: the rows with Y - X >= cut take part (all for cut <= 0).
+ * Bins: res >= 1; the bin of a coordinate p is floor(p / res), floor also for negative p.  bx, by: the bins of a row's X and Y; bmin,
+ * bmax: the smallest and largest bin over the X and Y of the kept rows.  The tracks have n_bins = bmax - bmin + 2 entries, for
+ * b = bmin .. bmax + 1; entry b describes the boundary at the START of bin b, at position b res.  With the window w >= 1 (in bins):
+ *   cross(b) = #{rows : b - w <= bx <  b <= by < b + w}     the insulation square of Crane et al. 2015
+ *   up(b)    = #{rows : b - w <= bx <= by < b}              the upstream triangle
+ *   down(b)  = #{rows : b <= bx <= by < b + w}              the downstream triangle
+ * A row with by < bx adds to none of them, but counts in n_kept, bmin and bmax.  Duplicated rows count each time.
+ * Range form (what the kernel does): a row with bx <= by adds 1 to cross on [max(bx + 1, by - w + 1), min(bx + w, by)], to up on
+ * [by + 1, bx + w] and to down on [by - w + 1, bx], each only where the interval is not empty (and inside bmin .. bmax + 1).
+ * Domain counts, over the kept rows of the last cl_dom_tracks, for ascending, pairwise disjoint half-open intervals [s_k, e_k) in bp
+ * (int64 bounds; intervals may be empty or abut): nx_k = #{X in [s_k, e_k)}, ny_k = #{Y in [s_k, e_k)}, intra_k = #{X and Y both in
+ * [s_k, e_k)}.
+ *
+ * cl_dom_tracks -- the three tracks of (cut, res, w) on the device -> *n_bins, *bin0 = bmin, *n_kept.  The kept rows sorted by X are
+ * K19's table, shared with cl_agg_loops: it is built when the handle does not hold it for this cut, so a second call with another w
+ * (or res) does not sort again, and cl_agg_loops at another cut rebuilds it for itself (cl_dom_count then builds it again).  The
+ * tracks stay until the next cl_dom_tracks, cl_dom_free or cl_chrom_destroy.  An empty handle or a cut that removes every row:
+ * n_bins = 0, bin0 = 0, n_kept = 0 and CL_OK.
+ * cl_dom_get -- entries [first, first + count) of the three tracks into host memory, entry k standing for b = bin0 + k.
+ * cl_dom_count -- intra[k], nx[k], ny[k] of the n intervals.
+ * cl_dom_free -- releases the tracks and the scratch of the calls (K19's table stays with the handle).
+ *
+ * Errors: CL_ERR_ARG for a NULL handle or NULL outputs (arrays may be NULL when their count is 0), res outside [1, 2^29), w outside
+ * [1, 1024], w res >= 2^29, the span of ALL rows of the handle (whatever the cut) giving more than 2^24 bins at res, a get or count
+ * before tracks, a get range outside [0, n_bins], count intervals that are not ascending and disjoint (starts[k] <= ends[k] <=
+ * starts[k + 1]), n < 0 or more than 2^31 - 4096 intervals, or runs in flight; all of them are found on the host before any launch.  A
+ * refused call zeroes its scalar outputs and leaves the earlier state usable.  The handle's layouts, count cache, K8 / K13 / K14 /
+ * K20 / K21 state and results stay untouched.
+ */
+int cl_dom_tracks(cl_chrom* c, int64_t cut, int64_t res, int64_t w, int64_t* n_bins, int64_t* bin0, int64_t* n_kept);
+int cl_dom_get(cl_chrom* c, int64_t first, int64_t count, uint32_t* cross, uint32_t* up, uint32_t* down);
+int cl_dom_count(cl_chrom* c, const int64_t* starts, const int64_t* ends, int64_t n, uint32_t* intra, uint32_t* nx, uint32_t* ny);
+int cl_dom_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
