@@ -267,6 +267,8 @@ class Chromosome(_Handle):
         if k <= 0:
             return np.zeros(0, dtype=BOX_DTYPE)
         ptr = self._lib.cl_boxes_host(self._h)
+        if not ptr:                                # (no result, or a run made with the export off: nothing to view)
+            raise _lib.CloopsHipError(_lib.CL_ERR_ARG, "the last run has no exported cluster table")
         view = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_int32)), shape=(k * 5,)).view(BOX_DTYPE)
         return view.copy() if copy else view
 
@@ -378,6 +380,7 @@ class Chromosome(_Handle):
         coordinates (cl_cluster_weighted of include/cloops_hip.h)."""
         if self._inflight:
             raise RuntimeError("asynchronous runs in flight: call wait() first")
+        self.set_table_export(True)                 # (a run with want_boxes=False may have switched it off: the boxes below are read)
         labels = np.empty(self.n, dtype=np.int32)
         nc = ctypes.c_int32(0)
         ml = ctypes.c_int32(-1)

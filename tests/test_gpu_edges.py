@@ -5,6 +5,7 @@ import pytest
 
 import oracle
 from cloops_amd import api, _lib
+from table_check import check_table
 
 pytestmark = pytest.mark.gpu
 ALL = ["v2", "v1", "block"]
@@ -18,6 +19,7 @@ def run_all(X, Y, eps, minPts, cut=0, variants=ALL):
             want = oracle.single_dbscan(v, X, Y, eps, minPts, cut)["labels"]
             assert np.array_equal(got.labels, want), (v, eps, minPts, cut, int((got.labels != want).sum()))
             assert got.n_clusters == len(np.unique(want[want >= 0]))
+            check_table(X, Y, want, got, (v, eps, minPts, cut))          # every row of the cluster table
     finally:
         ch.close()
 
@@ -121,7 +123,7 @@ def test_large_eps_giant_component_16M():
         got = ch.cluster("v2", 5000, 20, pinned=True)
         want = oracle.labels("v2", X, Y, 5000, 20)
         assert np.array_equal(got.labels, want)
-        # cluster table against a host recomputation for the biggest clusters
+        check_table(X, Y, want, got)                       # every row (one sort of 16 M labels), then the biggest clusters by masks
         big = np.argsort(-got.boxes["count"])[:5]
         for c in big:
             sel = want == c

@@ -9,6 +9,7 @@ against the sequential oracle for the three variants (test_cfg2_labels_equal_ora
 import numpy as np
 import pytest
 
+import table_check
 from cloops_amd import api
 from cloops_amd.synth import synth_chrom
 
@@ -17,20 +18,8 @@ CHR1 = 248956422
 
 
 def check_table(X, Y, res):
-    lab = res.labels
-    b = res.boxes
-    K = len(b)
-    sel = lab >= 0
-    assert (lab[sel] < K).all()
-    cnt = np.bincount(lab[sel], minlength=K)
-    assert np.array_equal(cnt, b["count"])
-    assert res.n_clusters == int((cnt > 0).sum())
-    for name, arr, fn, init in (("min_x", X, np.minimum, np.iinfo(np.int32).max), ("max_x", X, np.maximum, np.iinfo(np.int32).min),
-                                ("min_y", Y, np.minimum, np.iinfo(np.int32).max), ("max_y", Y, np.maximum, np.iinfo(np.int32).min)):
-        want = np.full(K, init, np.int64)
-        fn.at(want, lab[sel], arr[sel])
-        live = cnt > 0
-        assert np.array_equal(want[live], b[name][live].astype(np.int64)), name
+    """every row of the table against numpy on the run's own labels (no oracle at these sizes)"""
+    table_check.check_table(X, Y, res.labels, res)
 
 
 @pytest.fixture(scope="module")

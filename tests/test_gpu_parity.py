@@ -6,6 +6,7 @@ import pytest
 import golden_util as G
 import oracle
 from cloops_amd import api
+from table_check import check_table
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +43,7 @@ def test_families_golden(variant, family):
     for k, ids, X, Y, eps, minPts, gold in G.family_cases(family):
         res = gpu_labels(variant, X, Y, eps, minPts)
         assert np.array_equal(res.labels, gold[variant]), (family, k, variant, eps, minPts)
+        check_table(X, Y, gold[variant], res, (family, k))
 
 
 @pytest.mark.parametrize("variant", ROT)
@@ -53,12 +55,7 @@ def test_chr21_golden(variant, eps, minPts):
     assert np.array_equal(res.labels, gold)
     m = G.meta()["chr21_%s_%d_%d" % (variant, eps, minPts)]
     assert res.n_clusters == m["clusters"]
-    # cluster table against a host recomputation from the labels
-    for c in np.unique(gold[gold >= 0])[:50]:
-        sel = gold == c
-        b = res.boxes[c]
-        assert (b["count"], b["min_x"], b["max_x"], b["min_y"], b["max_y"]) == (
-            sel.sum(), X[sel].min(), X[sel].max(), Y[sel].min(), Y[sel].max())
+    check_table(X, Y, gold, res)                          # every row of the cluster table against the golden labels
 
 
 @pytest.mark.parametrize("variant", ["v2", "v1"])
@@ -77,6 +74,7 @@ def test_synth150k_golden(variant):
     for eps, minPts in ((2000, 5), (5000, 20)):
         res = gpu_labels(variant, X, Y, eps, minPts)
         assert np.array_equal(res.labels, z["%s_%d_%d" % (variant, eps, minPts)])
+        check_table(X, Y, z["%s_%d_%d" % (variant, eps, minPts)], res, (eps, minPts))
 
 
 @pytest.mark.parametrize("variant", ROT)
@@ -88,6 +86,7 @@ def test_oracle_midsize(variant):
         res = gpu_labels(variant, X, Y, eps, minPts)
         want = oracle.labels(variant, X, Y, eps, minPts)
         assert np.array_equal(res.labels, want), (variant, eps, minPts, int((res.labels != want).sum()))
+        check_table(X, Y, want, res, (eps, minPts))
 
 
 @pytest.mark.parametrize("variant", ROT)
@@ -139,10 +138,13 @@ def test_dense400k_headline_regime(variant):
             res = ch.cluster(variant, eps, minPts, cut)
             assert np.array_equal(res.labels, z[key]), key
             assert res.n_clusters == m["runs"][key]["clusters"]
+            check_table(X, Y, z[key], res, key)
             if variant != "block":
                 # a later run of the same eps under another cut reads the cached words + its cut band: against the oracle
                 res2 = ch.cluster(variant, eps, 20, cut + 700)
                 assert ch.last_region_mode() == 2
-                assert np.array_equal(res2.labels, oracle.single_dbscan(variant, X, Y, eps, 20, cut + 700)["labels"]), (key, "re-use")
+                want2 = oracle.single_dbscan(variant, X, Y, eps, 20, cut + 700)["labels"]
+                assert np.array_equal(res2.labels, want2), (key, "re-use")
+                check_table(X, Y, want2, res2, (key, "re-use"))
     finally:
         ch.close()

@@ -11,6 +11,7 @@ import pytest
 import golden_util as G
 import closed_form_model as M
 from cloops_amd import api
+from table_check import check_table
 
 pytestmark = pytest.mark.gpu
 
@@ -44,11 +45,7 @@ def test_random_cases_vs_closed_form(wx, wy):
         got = run(X, Y, eps, minPts, wx, wy)
         want = scaled_labels_model(X, Y, eps, minPts, wx, wy)
         assert np.array_equal(got.labels, want), (k, n, eps, minPts)
-        lab = got.labels
-        for c in np.unique(lab[lab >= 0])[:20]:          # boxes are UNSCALED
-            sel = lab == c
-            b = got.boxes[c]
-            assert (b["min_x"], b["max_x"], b["min_y"], b["max_y"], b["count"]) == (X[sel].min(), X[sel].max(), Y[sel].min(), Y[sel].max(), sel.sum())
+        check_table(X, Y, want, got, (k, n, eps, minPts))   # boxes are UNSCALED: every row against the model's labels
 
 
 def test_unit_weights_equal_variant1():
