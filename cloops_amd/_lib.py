@@ -34,6 +34,8 @@ CL_INGEST_TIMES = 6
 CL_INGEST_BEDPE, CL_INGEST_PAIRS = 0, 1
 DIST_LOGBINS = 3840          # CL_DIST_LOGBINS
 CL_KDE_MAX_GRID = 1024
+CL_KDIS_KMAX = 64
+CL_KDIS_BINS = 3968          # 31 octaves x 128 log bins: d < 2^31
 
 
 class ClBox(ctypes.Structure):
@@ -123,6 +125,10 @@ PROTOTYPES = {
     "cl_dom_get": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "cl_dom_count": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "cl_dom_free": (_int, [_vp]),
+    "cl_kdis_build": (_int, [_vp, _i64, _vp, _i32, _i64p]),
+    "cl_kdis_get": (_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "cl_kdis_hist": (_int, [_vp, _i32, _vp, _u64p, _u64p]),
+    "cl_kdis_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

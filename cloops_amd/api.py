@@ -804,6 +804,43 @@ class Chromosome(_Handle):
         _lib.check(self._lib.cl_dom_free(self._h))
         self._dom_bins = 0
 
+    def kdis_build(self, ks, cut=0):
+        """K23: the distance |dx| + |dy| of every kept row to its k-th nearest other kept row, for up to 8 strictly ascending k in
+        [1, 64] in one pass, and the log-binned histogram per k, kept on the device for kdis_get / kdis_hist.  Rows with Y - X >= cut
+        (all for cut <= 0) in the order of K19's table (ascending X, equal X in input order; shared with agg_loops and
+        domains_tracks).  k = minPts - 1: a row is a core of (eps, minPts) iff its d_k <= eps -> n_kept  (cl_kdis_build)"""
+        ks = np.ascontiguousarray(np.atleast_1d(np.asarray(ks)), dtype=np.int32)
+        if ks.ndim != 1:
+            raise ValueError("kdis_build: ks must be one-dimensional")
+        nk = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_kdis_build(self._h, int(cut), ks.ctypes.data_as(ctypes.c_void_p), len(ks), ctypes.byref(nk)))
+        self._kdis_rows = int(nk.value)                                      # (a refused call leaves the earlier results and their size)
+        return int(nk.value)
+
+    def kdis_get(self, which=0, first=0, count=None):
+        """entries [first, first + count) of the last kdis_build for its ks[which], in table order (all from `first` on by default)
+        -> (x, y, d) int32: the row's coordinates and its k-distance, -1 where the kept rows have no k-th neighbour  (cl_kdis_get)"""
+        first = int(first)
+        count = max(0, getattr(self, "_kdis_rows", 0) - first) if count is None else int(count)
+        n = max(0, count)
+        x, y, d = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        _lib.check(self._lib.cl_kdis_get(self._h, int(which), first, count, x.ctypes.data_as(ctypes.c_void_p),
+                                         y.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p)))
+        return x, y, d
+
+    def kdis_hist(self, which=0):
+        """the histogram of the last kdis_build for its ks[which] -> (hist uint64[CL_KDIS_BINS] over the log bins of ests.logbin for
+        d >= 1, n_zero: rows with d == 0, n_none: rows without a k-th neighbour)  (cl_kdis_hist)"""
+        hist = np.zeros(_lib.CL_KDIS_BINS, dtype=np.uint64)
+        nz, nn = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(self._lib.cl_kdis_hist(self._h, int(which), hist.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nz), ctypes.byref(nn)))
+        return hist, int(nz.value), int(nn.value)
+
+    def kdis_free(self):
+        """releases the k-distances and histograms of kdis_build  (cl_kdis_free)"""
+        _lib.check(self._lib.cl_kdis_free(self._h))
+        self._kdis_rows = 0
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

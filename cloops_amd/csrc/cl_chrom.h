@@ -30,6 +30,12 @@ static inline int bits_for(unsigned v) { int b = 0; while (v) { ++b; v >>= 1; } 
 #define K7_STEP_BLOCKS 256       // ... of the sweep step's k7_summary: 1024 threads each (every workgroup ends with up to 5 888 atomics into the two
 #define K7_STEP_THREADS 1024      //     histograms -- 2048 x 256 threads: 67 us per chr1 step, 256 x 1024: 47 us)
 #define K7_LOGBINS 3840          // 30 octaves x 128: bin = floor(log2 d) * 128 + the next 7 bits of d (monotone in d)
+__device__ __forceinline__ int k7_logbin(unsigned d)      // d >= 1 (shared by K7 in k_sweep.hip and K23 in k_kdis.hip)
+{
+    const int e = 31 - __clz((int)d);
+    const unsigned m = e >= 7 ? ((d >> (e - 7)) & 127u) : ((d << (7 - e)) & 127u);
+    return e * 128 + (int)m;
+}
 #define K7_FINE 2048
 #define K7_XSHIFT 11.0           // sums are taken over x = log2|d| - K7_XSHIFT (less cancellation in sum x^2 - (sum x)^2 / n)
 #define CAND_BLOCK 2048
@@ -261,6 +267,16 @@ struct cl_chrom {
         int pmin = 0, pmax = 0;                                      // smallest / largest coordinate of the kept rows (of `cut`)
         long long bmin = 0, n_bins = 0, n_kept = 0;
     } dm;
+    // K23 (k_kdis.hip): X, Y of the kept rows in table order (copies: cl_agg_loops at another cut may rebuild K19's table while the
+    // results live), d_k of every row for every asked k (n_k arrays of n_kept), per k the histogram + n_zero + n_none.  Kept from
+    // cl_kdis_build to the next build, cl_kdis_free or destruction
+    DevBuf kd_x, kd_y, kd_d, kd_hist;
+    struct KdisState {
+        bool ready = false;
+        int cut = 0, n_k = 0;
+        int ks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        long long n_kept = 0;
+    } kd;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
@@ -382,6 +398,6 @@ __device__ __forceinline__ int k8_ub(const u64* __restrict__ t, int m, long long
 // builds the tables of (chromosome, cut) unless the handle holds them already (c->sig_tx / sig_ty; c->sig_m[0] on the device = the
 // number of valid entries); enqueued on c->stream, c->n > 0
 int sig_tables(cl_chrom* c, int cut);
-// K19's table (k_agg.hip), shared with K22 (k_domain.hip): the rows with Y - X >= cut sorted by X (c->ag_sx: X + 2^30 as u32, c->ag_sy:
+// K19's table (k_agg.hip), shared with K22 (k_domain.hip) and K23 (k_kdis.hip): the rows with Y - X >= cut sorted by X (c->ag_sx: X + 2^30 as u32, c->ag_sy:
 // their Y, c->ag_kept rows) unless the handle holds it for this cut already; c->n > 0
 int agg_table(cl_chrom* c, int cut);

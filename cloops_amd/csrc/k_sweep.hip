@@ -53,12 +53,6 @@ __device__ __forceinline__ double k7_log2(unsigned d, const double* __restrict__
     p = fma(p, r, 1.4426950408889634);                                //  1 / ln 2
     return ((double)e + lg[k]) + p * r;
 }
-__device__ __forceinline__ int k7_logbin(unsigned d)      // d >= 1
-{
-    const int e = 31 - __clz((int)d);
-    const unsigned m = e >= 7 ? ((d >> (e - 7)) & 127u) : ((d << (7 - e)) & 127u);
-    return e * 128 + (int)m;
-}
 // f(group, |d|) for every PET of a group, in a fixed order per thread (deterministic partial sums): the block works
 // on fixed contiguous ranges of the sources
 template <typename F>

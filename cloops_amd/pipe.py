@@ -1037,7 +1037,7 @@ def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp, fmt="bedpe", ext=50):
 
 def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0, cut=0, plot=0, max_cut=False,
          log=None, reader="gpu", fmt="auto", ext=50, agg=0, agg_res=0, bdg=0, bdg_ext=75, peaks=0, peak_eps=(100, 200),
-         peak_minPts=(5, 10), domains=0, dom_res=10000, dom_w=(10,)):
+         peak_minPts=(5, 10), domains=0, dom_res=10000, dom_w=(10,), kdis=0, kdis_k=(4, 9, 19)):
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
@@ -1058,7 +1058,10 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     (cut 0, K21, cloops_amd.peaks) for every (eps, minPts) of `peak_eps` x `peak_minPts`, from the chromosomes still resident.
     `domains` writes `<fout>_domains.txt`, `<fout>_domains.bed`, `<fout>_boundaries.txt`, `<fout>_insulation_w<W>.bedGraph` and
     `<fout>_domains.json` after `<fout>.loop`: the domains of every chromosome (cut 0, K22, cloops_amd.domains) in bins of `dom_res` bp
-    for every window of `dom_w`, from the chromosomes still resident."""
+    for every window of `dom_w`, from the chromosomes still resident.
+    `kdis` writes `<fout>_kdis.txt` and `<fout>_kdis.json` after `<fout>.loop`: the k-distance curves of the PETs and the eps they
+    suggest (cut 0, K23, cloops_amd.esteps) for every k = minPts - 1 of `kdis_k`, from the chromosomes still resident.  The suggestion
+    is reported, not fed into the sweep."""
     import shutil
     if reader not in ("gpu", "host"):
         raise ValueError("reader must be 'gpu' or 'host', got %r" % (reader,))
@@ -1113,6 +1116,9 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
         if domains and not e:
             from .domains import jd2domains
             jd2domains(list(cfs), fout, res=int(dom_res), w=dom_w)
+        if kdis and not e:
+            from .esteps import jd2esteps
+            jd2esteps(list(cfs), fout, ks=kdis_k)
     finally:
         for f in mem:                                         # 'mem://' residents are never evicted by age
             CACHE.drop(f)
@@ -1135,7 +1141,8 @@ def main(argv=None):
     drive the hot path (same names; -w / -j write the loop tracks, -plot the distance-cutoff picture of every sweep step, -agg the
     aggregate pile-up around the called loops in bins of -res bp, -bdg the coverage of the PET ends as a bedGraph with -bdgext bp
     to either side of an end, -peaks the peaks of the PET ends for every setting of -peakeps x -peakminPts, -domains the domains and
-    boundaries in bins of -domres bp for every window of -domw bins)."""
+    boundaries in bins of -domres bp for every window of -domw bins, -kdis the k-distance curves of the PETs and the eps they suggest for
+    every k = minPts - 1 of -kdisk)."""
     import argparse
     ap = argparse.ArgumentParser(prog="cloops_amd")
     ap.add_argument("-f", dest="fnIn", required=True)
@@ -1165,6 +1172,8 @@ def main(argv=None):
     ap.add_argument("-domains", dest="domains", action="store_true")
     ap.add_argument("-domres", dest="domres", type=int, default=10000)
     ap.add_argument("-domw", dest="domw", default="10")
+    ap.add_argument("-kdis", dest="kdis", action="store_true")
+    ap.add_argument("-kdisk", dest="kdisk", default="4,9,19")
     op = ap.parse_args(argv)
     if op.mode == 0:                                          # pipe.py:306-327
         eps = sorted(int(x) for x in str(op.eps).split(","))
@@ -1179,5 +1188,5 @@ def main(argv=None):
     pipe(op.fnIn.split(","), op.fnOut, eps, minPts, op.chroms, op.cpu, op.tmp, hic, op.washU, op.juice, op.cut,
          op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader, fmt=op.fmt, ext=op.ext,
          agg=op.agg, agg_res=op.res, bdg=op.bdg, bdg_ext=op.bdgext, peaks=op.peaks, peak_eps=op.peakeps,
-         peak_minPts=op.peakminPts, domains=op.domains, dom_res=op.domres, dom_w=op.domw)
+         peak_minPts=op.peakminPts, domains=op.domains, dom_res=op.domres, dom_w=op.domw, kdis=op.kdis, kdis_k=op.kdisk)
     return 0

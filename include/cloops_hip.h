@@ -470,6 +470,47 @@ int cl_dom_count(cl_chrom* c, const int64_t* starts, const int64_t* ends, int64_
 int cl_dom_free(cl_chrom* c);
 
 /*
+ * k-distances (K23): the distance of every PET to its k-th nearest neighbour, and its log-binned histogram -- the curve a user reads
+ * a sensible eps of DBSCAN from.  The reference has no counterpart, so these definitions are the specification; quantiles and the
+ * suggested eps stay on the host (cloops_amd/esteps.py).
+ *
+ * Kept rows, as for cl_agg_loops and cl_dom_tracks: the rows with Y - X >= cut take part (all for cut <= 0), m of them.  Duplicated
+ * rows are separate points.
+ * Table order: the kept rows ascending by X, rows of equal X in input order (K19's table, a stable sort).
+ * k-distance: for a kept row p and 1 <= k <= CL_KDIS_KMAX, d_k(p) is the k-th smallest of |Xp - Xq| + |Yp - Yq| over the kept rows
+ * q != p; a duplicate of p is a neighbour at distance 0.  With m - 1 < k there is no k-th neighbour and d_k = -1 for every row.  Every
+ * coordinate of a handle satisfies |v| < 2^29, so d_k <= 2^31 - 4 fits int32.  A row is a core of (eps, minPts) -- its neighbour count,
+ * itself included, is >= minPts -- iff d_(minPts - 1) <= eps: k = minPts - 1.
+ * Histogram, per k: hist[b] = #{rows : d_k >= 1 and logbin(d_k) == b} with the log bins of cl_dist_summary (bin = floor(log2 d) * 128
+ * + the 7 bits below the leading one), CL_KDIS_BINS = 31 * 128 of them for d < 2^31; n_zero = #{rows : d_k == 0}; n_none = #{rows :
+ * d_k == -1}.  Histograms of different chromosomes add.
+ * Cost: a row reads the rows whose X lies within its d_kmax of its own X, hundreds to a few thousand on ChIA-PET / HiChIP densities;
+ * it is quadratic only on an input with almost all X equal.
+ *
+ * cl_kdis_build -- d_k of every kept row for the n_k values of ks (1 <= n_k <= 8, strictly ascending, each in [1, CL_KDIS_KMAX]) in
+ * ONE pass that keeps the ks[n_k - 1] smallest distances per row, and their histograms, on the device -> *n_kept.  A build with
+ * (5, 10, 20) equals three builds with one k each.  The kept rows sorted by X are K19's table: it is built when the handle does not
+ * hold it for this cut, exactly as by cl_dom_tracks.  The results stay until the next build, cl_kdis_free or cl_chrom_destroy (X and
+ * Y of the table are copied beside them, so cl_agg_loops at another cut does not disturb them).  An empty handle or a cut that
+ * removes every row: n_kept = 0, empty gets, zero histograms and CL_OK.
+ * cl_kdis_get -- entries [first, first + count) in table order for ks[which]: the row's X and Y, and its d.
+ * cl_kdis_hist -- hist[CL_KDIS_BINS], *n_zero and *n_none for ks[which].
+ * cl_kdis_free -- releases the results (K19's table stays with the handle).
+ *
+ * Errors: CL_ERR_ARG for a NULL handle or NULL outputs (the arrays of a get may be NULL when count is 0), n_k outside 1..8, a k
+ * outside 1..CL_KDIS_KMAX or ks not strictly ascending, which outside 0..n_k - 1, a get or hist before a build, a range outside
+ * [0, n_kept], or runs in flight; all of them are found on the host before any launch.  A refused call zeroes its scalar outputs and
+ * leaves the earlier state usable.  The handle's layouts, count cache, K8 / K13 / K14 / K20 / K21 / K22 state and results stay
+ * untouched.
+ */
+#define CL_KDIS_KMAX 64
+#define CL_KDIS_BINS 3968
+int cl_kdis_build(cl_chrom* c, int64_t cut, const int32_t* ks, int32_t n_k, int64_t* n_kept);
+int cl_kdis_get(cl_chrom* c, int32_t which, int64_t first, int64_t count, int32_t* x, int32_t* y, int32_t* d);
+int cl_kdis_hist(cl_chrom* c, int32_t which, uint64_t* hist, uint64_t* n_zero, uint64_t* n_none);
+int cl_kdis_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
