@@ -23,7 +23,8 @@
 //   k_union_c     cores of one strip within eps in q form a chain = a contiguous run of the core array, and chains are the nodes
 //                 of the union-find: tiles of the CORE array with a left halo make their chains in LDS (open flags while staging,
 //                 heads and skips by ballots), then the cross-strip core-core edges by lock-free hooking on the chain heads (the
-//                 window one strip below holds cores only: nothing to step over).  k_chain_c: the chains as a kernel of their
+//                 window one strip below holds cores only: nothing to step over), searched from the cores no chain mate dominates
+//                 only, compacted into a work list per tile.  k_chain_c: the chains as a kernel of their
 //                 own (developer A/B).  k_union_overflow: cores whose window is not staged.
 //   k_flatten_c   root per core, component key / core count per root, the root list.
 //   k_border_q    variant 2's border rule for the walkers; the cores around a tile's position range are a contiguous slice of the
@@ -787,8 +788,21 @@ __device__ __forceinline__ int lower_bound_pairs(const int2* __restrict__ pv, in
 // resets written; parent[c] = c was set for every core by k_prep_c (another tile may unite with a head before its own tile runs).
 // A core whose window is not staged (a strip population beyond the halo) would need chain ids of other tiles: it is listed and
 // k_union_overflow takes it behind this kernel.
+//
+// Only UNDOMINATED cores search.  One edge per pair of chains is enough, so a core may stay out whenever chain mates are sure to
+// reach everything it could reach.  With the cores of a strip ordered by the key (sp, index in the core array), a core a is
+// dominated when a core a1 in front of it (same strip, q_a - q_a1 <= eps) AND a core a2 behind it (same strip, q_a2 - q_a <= eps)
+// both have a smaller key.  a1 and a2 are chain mates of a (the array is sorted by q inside a strip: every gap between them is
+// <= eps).  A candidate b of a with q_b <= q_a has q_a1 - eps <= q_a - eps <= q_b <= q_a <= q_a1 + eps and sp_b >= sp_a - peps >=
+// sp_a1 - peps: a1 reaches it too; with q_b >= q_a the same holds for a2.  A replacement that is dominated itself is replaced in
+// turn on the side b lies on; the key falls strictly every time, so that ends at an undominated core of the same chain that
+// reaches b: the undominated cores find the same (chain, chain) pairs.  The test only has to be sound: it looks at the UK nearest
+// staged cores on either side, and a side without a dominator among them (not staged, another strip, farther than eps) counts
+// as not dominated.  The survivors' tile-local indices are compacted into an LDS work list (ballots, a prefix over the waves'
+// counts) and all 256 threads take work items from it: a wave with four fifths of its lanes idle would issue the same instructions.
+#define LU_STRIPS 64             // rows of the cores-only strip table staged per tile: those of the strips from the first own core's on
 struct HeadReset { int* compkey; int* ncore; int* bsize; int* usize; int* state; };
-template <int NT, int HALO, bool FUSE>
+template <int NT, int HALO, bool FUSE, int UK>
 __global__ void __launch_bounds__(256)
 k_union_c(GridParams g, int ntiles, const int* __restrict__ lcnt, const int2* __restrict__ cpair, int* chainid,
           const int* __restrict__ cstrip, int* cskip, int* parent, HeadReset hr, int* __restrict__ ckey_prune /* or null */,
@@ -796,11 +810,16 @@ k_union_c(GridParams g, int ntiles, const int* __restrict__ lcnt, const int2* __
 {
     constexpr int WIN = NT + HALO;
     constexpr int NCH = WIN / 64;
+    constexpr int PER = NT / 256;
+    static_assert(NT % 256 == 0 && HALO % 64 == 0 && HALO >= UK && WIN <= 65536, "whole rounds of own cores, a wave-aligned halo that holds the test's reach, 16-bit work items");
     __shared__ int2 lw[WIN];
     __shared__ int lx[WIN];
     __shared__ int lend[WIN];                            // where a walk goes on behind the staged core's chain
     __shared__ unsigned long long l_ob[FUSE ? NCH : 1];
     __shared__ int l_found;
+    __shared__ unsigned short l_work[NT];                // the surviving cores (indices into lw), in core order
+    __shared__ int l_nsurv[PER * 4];                     // survivors per round and wave
+    __shared__ int l_cs[LU_STRIPS];                      // cstrip[s0 - 1 ..], s0 = strip of the tile's first own core
     const int C = lcnt[0];
     const int tile = ltile_of_block(blockIdx.x);
     const int t0 = tile * NT;
@@ -809,7 +828,8 @@ k_union_c(GridParams g, int ntiles, const int* __restrict__ lcnt, const int2* __
     const int lane = threadIdx.x & 63;
     const int nmask = ~(g.peps - 1);
     if (FUSE && threadIdx.x == 0) l_found = -1;
-    int pf_tb[NT / 256], pf_b[NT / 256];
+    int pf_cs = 0;
+    static_assert(LU_STRIPS == 64, "one staged row of the strip table per lane of a wave");
     {
         // (every load of the thread in flight before the first LDS store: the rolled loop was WIN / 256 dependent round trips per tile)
         constexpr int SU = (WIN + 255) / 256;
@@ -822,16 +842,13 @@ k_union_c(GridParams g, int ntiles, const int* __restrict__ lcnt, const int2* __
             mv[u] = in ? cpair[gi] : (gi < 0 ? make_int2(0, INT_MIN) : make_int2(INT_MAX, INT_MAX));
             pvl[u] = (FUSE && lane == 0 && gi > 0 && gi < C) ? cpair[gi - 1] : make_int2(0, 0);      // the first lane of a wave reads its predecessor
         }
-        // the rows of the cores-only strip table the thread's OWN cores will need for their windows (strip s-1 = [cstrip[s-1], cstrip[s])):
-        // requested as soon as their pairs are here, in flight while the tile makes its chains
-        if (HALO % 256 == 0) {
-#pragma unroll
-            for (int u2 = 0; u2 < NT / 256; ++u2) {
-                const int gi = t0 + u2 * 256 + (int)threadIdx.x;
-                const int s = mv[HALO / 256 + u2].y >> g.rbits;
-                const bool ok = gi < C && s > 0;
-                pf_tb[u2] = ok ? cstrip[s - 1] : 0; pf_b[u2] = ok ? cstrip[s] : 0;
-            }
+        // the rows of the cores-only strip table the tile's cores will need for their windows (strip s-1 = [cstrip[s-1], cstrip[s])):
+        // the tile's first own core (t0 < C) is staged by lane 0 of one wave, which requests the rows from its strip on as soon as the
+        // pair is here -- in flight while the tile makes its chains.  (A work item belongs to no thread in particular: the rows cannot
+        // ride in registers.)  Row S + 1 is the table's last.
+        if (((int)threadIdx.x >> 6) == (HALO % 256) / 64) {
+            const int r = (__builtin_amdgcn_readfirstlane(mv[HALO / 256].y) >> g.rbits) - 1 + lane;
+            pf_cs = (r >= 0 && r <= g.S + 1) ? cstrip[r] : 0;
         }
 #pragma unroll
         for (int u = 0; u < SU; ++u) {
@@ -908,12 +925,50 @@ k_union_c(GridParams g, int ntiles, const int* __restrict__ lcnt, const int2* __
     }
     const int wbeg = max(base, 0);
     LdsPairs w; w.a = lw; w.base = base;
-    constexpr int PER = NT / 256;
+    // which of the thread's own cores are undominated (see above): the UK staged neighbours on either side, all reads in flight at once
+    const int klo = max(0, -base), khi = min(WIN, C - base);      // the staged entries that are cores
+    if (((int)threadIdx.x >> 6) == (HALO % 256) / 64) l_cs[lane] = pf_cs;
+    int myrank[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int k = HALO + u * 256 + (int)threadIdx.x;
+        const bool in = k < khi;
+        const int2 me = lw[k];
+        int2 nl[UK], nr[UK];
+#pragma unroll
+        for (int d = 0; d < UK; ++d) { nl[d] = lw[k - 1 - d]; nr[d] = lw[min(k + 1 + d, WIN - 1)]; }
+        bool dl = false, dr = false;
+#pragma unroll
+        for (int d = 0; d < UK; ++d) {
+            // in front: an equal sp loses to the smaller index; behind: it does not
+            dl |= (k - 1 - d >= klo) & ((nl[d].y & nmask) == (me.y & nmask)) & (me.x - nl[d].x <= g.eps) & (nl[d].y <= me.y);
+            dr |= (k + 1 + d < khi) & ((nr[d].y & nmask) == (me.y & nmask)) & (nr[d].x - me.x <= g.eps) & (nr[d].y < me.y);
+        }
+        const bool surv = in && (!(dl && dr) || L_ABL(1 << 14));      // (ablation bit 14: every core searches)
+        const unsigned long long sb = __ballot(surv);
+        myrank[u] = surv ? lane_rank(sb) : -1;
+        if (lane == 0) l_nsurv[u * 4 + ((int)threadIdx.x >> 6)] = __popcll(sb);
+        LSTAT(12, in ? 1 : 0);
+    }
+    __syncthreads();
+    int nwork = 0;
+    {
+        int run = 0;
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            int mine = 0;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) { if (v == ((int)threadIdx.x >> 6)) mine = run; run += l_nsurv[u * 4 + v]; }
+            if (myrank[u] >= 0) l_work[mine + myrank[u]] = (unsigned short)(HALO + u * 256 + (int)threadIdx.x);
+        }
+        nwork = run;
+    }
+    __syncthreads();
     // (one copy of the body: unrolled over the thread's cores the kernel was 80 KB of code -- more than the instruction cache two CUs share)
 #pragma unroll 1
-    for (int u = 0; u < PER; ++u) {
-        const int i = t0 + u * 256 + (int)threadIdx.x;
-        const bool in = i < C;
+    for (int t = (int)threadIdx.x & ~63; t < nwork; t += 256) {      // (whole waves: the union-find steps below are agreed on by ballots)
+        const bool in = t + lane < nwork;
+        const int i = in ? base + (int)l_work[t + lane] : C;
         int Bs[LU_MAXB];
 #pragma unroll
         for (int k = 0; k < LU_MAXB; ++k) Bs[k] = -1;
@@ -926,9 +981,12 @@ k_union_c(GridParams g, int ntiles, const int* __restrict__ lcnt, const int2* __
             const int2 me = lw[i - base];
             A = lx[i - base];
             const int s = me.y >> g.rbits;
-            int tb, b;                                    // (strip 0 has nothing below: an empty range)
-            if (HALO % 256 == 0) { tb = u == 0 ? pf_tb[0] : pf_tb[NT / 256 - 1]; b = u == 0 ? pf_b[0] : pf_b[NT / 256 - 1]; }
-            else { tb = s > 0 ? cstrip[s - 1] : 0; b = s > 0 ? cstrip[s] : 0; }
+            int tb = 0, b = 0;                            // (strip 0 has nothing below: an empty range)
+            if (s > 0) {
+                const int rel = s - (lw[HALO].y >> g.rbits);       // (>= 0: strips ascend along the core array)
+                if (rel + 1 < LU_STRIPS) { tb = l_cs[rel]; b = l_cs[rel + 1]; }
+                else { tb = cstrip[s - 1]; b = cstrip[s]; }      // (a tile of more strips than are staged)
+            }
             if (tb < b) {
                 const int qlo = me.x - g.eps, qhi = me.x + g.eps;
                 const int T = me.y - g.peps;             // every candidate lies one strip below: "within eps in p" is sp_j >= sp_i - peps
@@ -1034,7 +1092,8 @@ k_union_c(GridParams g, int ntiles, const int* __restrict__ lcnt, const int2* __
             if (rep && !L_ABL(1 << 15)) { uf_unite(parent, A, B); ++st_un; }      // (ablation bit 15: the walks without the union-find steps)
         }
 #ifdef CLOOPS_DEVEL
-        LSTAT(12, in ? 1 : 0); LSTAT(13, st_it); LSTAT(14, st_touch); LSTAT(15, st_un); LSTAT(16, st_glb); LSTAT(17, st_jump);
+        LSTAT(23, in ? 1 : 0);                           // cores that searched (12: every core of the tile, counted with the test)
+        LSTAT(13, st_it); LSTAT(14, st_touch); LSTAT(15, st_un); LSTAT(16, st_glb); LSTAT(17, st_jump);
         { int mx = st_it; for (int o2 = 32; o2 > 0; o2 >>= 1) mx = max(mx, __shfl_down(mx, o2)); if (lane == 0 && LSTAT_ON) { atomicAdd(&g_lstat[18], (unsigned long long)mx); atomicAdd(&g_lstat[19], 1ull); }
           if (LSTAT_ON && st_it > 2) atomicAdd(&g_lstat[20], 1ull); if (LSTAT_ON && st_it > 4) atomicAdd(&g_lstat[21], 1ull); if (LSTAT_ON && st_it > 8) atomicAdd(&g_lstat[22], 1ull); }
 #else
@@ -2113,18 +2172,26 @@ int lists_union_flatten(cl_chrom* c, const GridParams& g, int nm, const ListRun&
     int* prune = (c->run_level >= 4 && g.variant == CL_VARIANT_CDBSCAN2) ? L.ckey : (int*)nullptr;
 #define LU_ARGS g, nt, L.lcnt, (const int2*)L.cpair, c->chainflag.as<int>(), (const int*)L.cstrip, c->cellfirst.as<int>() /* cskip: the cell minima are in the keys */, \
                 c->parent.as<int>(), hr, prune, c->ulist.as<int>() /* the overflow list: free until k_mark_uncertain_l */, c->counters.as<int>()
+    // UK: the neighbours on either side that k_union_c's domination test looks at
+    constexpr int UK = 4;
+    const bool big = (long long)c->n > 80LL * g.S;
+#define LU_LAUNCH(HALO_, FUSE_, UK_) hipLaunchKernelGGL((k_union_c<UNT, HALO_, FUSE_, UK_>), dim3(ltile_grid(nt)), dim3(256), 0, c->stream, LU_ARGS)
+    bool wide = false;
+#ifdef CLOOPS_DEVEL
+    { const char* e = getenv("CLOOPS_UNION_K"); wide = e && atoi(e) == 8; }      // 8: the wider test (developer A/B)
+#endif
     if (c->fuse_chains) {
-        if ((long long)c->n > 80LL * g.S) hipLaunchKernelGGL((k_union_c<UNT, 512, true>), dim3(ltile_grid(nt)), dim3(256), 0, c->stream, LU_ARGS);
-        else hipLaunchKernelGGL((k_union_c<UNT, 128, true>), dim3(ltile_grid(nt)), dim3(256), 0, c->stream, LU_ARGS);
+        if (!wide) { if (big) LU_LAUNCH(512, true, UK); else LU_LAUNCH(128, true, UK); }
+#ifdef CLOOPS_DEVEL
+        else { if (big) LU_LAUNCH(512, true, 8); else LU_LAUNCH(128, true, 8); }
+#endif
         hipLaunchKernelGGL(k_union_overflow, dim3(1024), dim3(256), 0, c->stream, g, (const int*)c->counters.as<int>(), (const int*)c->ulist.as<int>(), (const int2*)L.cpair,
                            (const int*)c->chainflag.as<int>(), (const int*)L.cstrip, (const int*)c->cellfirst.as<int>(), c->parent.as<int>());
     }
 #ifdef CLOOPS_DEVEL
-    else {
-        if ((long long)c->n > 80LL * g.S) hipLaunchKernelGGL((k_union_c<UNT, 512, false>), dim3(ltile_grid(nt)), dim3(256), 0, c->stream, LU_ARGS);
-        else hipLaunchKernelGGL((k_union_c<UNT, 128, false>), dim3(ltile_grid(nt)), dim3(256), 0, c->stream, LU_ARGS);
-    }
+    else { if (big) LU_LAUNCH(512, false, UK); else LU_LAUNCH(128, false, UK); }
 #endif
+#undef LU_LAUNCH
 #undef LU_ARGS
     hipLaunchKernelGGL(k_flatten_c, dim3(nblocks(nm, FLC_TPB * FLC_PER)), dim3(FLC_TPB), 0, c->stream, L.lcnt, (const int*)c->chainflag.as<int>(),
                        (const int*)c->parent.as<int>(), (const int*)L.ckey, croot_of(c),

@@ -23,6 +23,6 @@ for eps, m, cut in settings:
     v = list(out)
     print("(%5d, %2d, %4d): M %9d cores %9d walkers %8d | border: walkers %8d iters %9d (%.2f each, global %d) roots %.2f hinted %.3f owned %.3f | per wave: max iters %.1f" % (
         eps, m, cut, v[10], v[8], v[9], v[0], v[1], v[1] / max(1, v[0]), v[2], v[3] / max(1, v[0]), v[4] / max(1, v[0]), v[5] / max(1, v[0]), v[6] / max(1, v[7])))
-    print("      union: cores %d walk rounds %.2f touches %.3f unites %.4f global-path %.4f jumps %.3f (per core)" % (
-        v[12], v[13] / max(1, v[12]), v[14] / max(1, v[12]), v[15] / max(1, v[12]), v[16] / max(1, v[12]), v[17] / max(1, v[12])))
+    print("      union: cores %d searched %d (%.3f) walk rounds %.2f touches %.3f unites %.4f global-path %.4f jumps %.3f (per core)" % (
+        v[12], v[23], v[23] / max(1, v[12]), v[13] / max(1, v[12]), v[14] / max(1, v[12]), v[15] / max(1, v[12]), v[16] / max(1, v[12]), v[17] / max(1, v[12])))
     print("      union: per wave max rounds %.1f; cores with > 2 / 4 / 8 rounds: %.3f %.3f %.3f" % (v[18] / max(1, v[19]), v[20] / max(1, v[12]), v[21] / max(1, v[12]), v[22] / max(1, v[12])))
