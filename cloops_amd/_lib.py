@@ -36,6 +36,8 @@ DIST_LOGBINS = 3840          # CL_DIST_LOGBINS
 CL_KDE_MAX_GRID = 1024
 CL_KDIS_KMAX = 64
 CL_KDIS_BINS = 3968          # 31 octaves x 128 log bins: d < 2^31
+CL_MAT_WMAX = 8192           # bins a side of a dense window
+CL_MAT_CELLS_MAX = 16777216  # 2^24 cells of a dense window
 
 
 class ClBox(ctypes.Structure):
@@ -129,6 +131,11 @@ PROTOTYPES = {
     "cl_kdis_get": (_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp]),
     "cl_kdis_hist": (_int, [_vp, _i32, _vp, _u64p, _u64p]),
     "cl_kdis_free": (_int, [_vp]),
+    "cl_mat_window": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64p, _i64p]),
+    "cl_mat_cells": (_int, [_vp, _i64, _i64, _i32, _i64p, _i64p, _i64p]),
+    "cl_mat_cells_get": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "cl_mat_v4c": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64p, _i64p, _i64p]),
+    "cl_mat_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

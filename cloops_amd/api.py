@@ -841,6 +841,59 @@ class Chromosome(_Handle):
         _lib.check(self._lib.cl_kdis_free(self._h))
         self._kdis_rows = 0
 
+    def mat_window(self, res, bx0, by0, nx, ny, cut=0, mirror=False):
+        """K24: the dense contact matrix of the bins [bx0, bx0 + nx) x [by0, by0 + ny) of `res` bp (bin of p = floor(p / res)) over the
+        rows with Y - X >= cut (all for cut <= 0).  With `mirror` a row with bx != by also counts at its transposed cell, so a window on
+        the diagonal is symmetric with its diagonal counted once -> (uint32 [nx, ny], n_in: the sum, n_kept)  (cl_mat_window)"""
+        nx, ny = int(nx), int(ny)
+        if not (1 <= nx <= _lib.CL_MAT_WMAX and 1 <= ny <= _lib.CL_MAT_WMAX and nx * ny <= _lib.CL_MAT_CELLS_MAX):
+            raise ValueError("mat_window: needs 1 <= nx, ny <= %d and nx ny <= %d, got %d x %d" % (_lib.CL_MAT_WMAX, _lib.CL_MAT_CELLS_MAX, nx, ny))
+        out = np.zeros((nx, ny), dtype=np.uint32)
+        n_in, nk = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_mat_window(self._h, int(cut), int(res), int(bx0), int(by0), nx, ny, 1 if mirror else 0,
+                                           out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n_in), ctypes.byref(nk)))
+        return out, int(n_in.value), int(nk.value)
+
+    def mat_cells(self, res, cut=0, fold=False):
+        """K24: the non-empty cells (bx, by) of the kept rows at `res` bp, ascending by bx then by, with their counts, kept on the device
+        for mat_cells_get; `fold` puts a row into (min(bx, by), max(bx, by)) -> (n_cells, n_kept, max_count)  (cl_mat_cells)"""
+        nc, nk, mc = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_mat_cells(self._h, int(cut), int(res), 1 if fold else 0, ctypes.byref(nc), ctypes.byref(nk), ctypes.byref(mc)))
+        self._mat_cells = int(nc.value)                                      # (a refused call leaves the earlier cells and their number)
+        return int(nc.value), int(nk.value), int(mc.value)
+
+    def mat_cells_get(self, first=0, count=None):
+        """cells [first, first + count) of the last mat_cells (all from `first` on by default) -> (bx int32, by int32, cnt uint32)
+        (cl_mat_cells_get)"""
+        first = int(first)
+        count = max(0, getattr(self, "_mat_cells", 0) - first) if count is None else int(count)
+        n = max(0, count)
+        bx, by = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        cnt = np.zeros(n, dtype=np.uint32)
+        _lib.check(self._lib.cl_mat_cells_get(self._h, first, count, bx.ctypes.data_as(ctypes.c_void_p), by.ctypes.data_as(ctypes.c_void_p),
+                                              cnt.ctypes.data_as(ctypes.c_void_p)))
+        return bx, by, cnt
+
+    def mat_v4c(self, res, v0, v1, b0, nb, cut=0):
+        """K24: the virtual-4C profile of the viewpoint [v0, v1) bp over the bins [b0, b0 + nb) of `res` bp: a kept row adds 1 at the bin
+        of its Y when its X lies in the viewpoint, and 1 at the bin of its X when its Y does -> (uint32 [nb], n_x, n_y: the rows with X /
+        Y in the viewpoint, n_kept)  (cl_mat_v4c)"""
+        nb = int(nb)
+        if not 0 <= nb <= (1 << 24):
+            raise ValueError("mat_v4c: nb must lie in [0, 2^24], got %d" % nb)
+        if int(v0) > int(v1):
+            raise ValueError("mat_v4c: the viewpoint needs v0 <= v1, got [%d, %d)" % (int(v0), int(v1)))
+        out = np.zeros(nb, dtype=np.uint32)
+        nx, ny, nk = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_mat_v4c(self._h, int(cut), int(res), int(v0), int(v1), int(b0), nb, out.ctypes.data_as(ctypes.c_void_p),
+                                        ctypes.byref(nx), ctypes.byref(ny), ctypes.byref(nk)))
+        return out, int(nx.value), int(ny.value), int(nk.value)
+
+    def mat_free(self):
+        """releases the cells of mat_cells and the device scratch of the mat_* calls  (cl_mat_free)"""
+        _lib.check(self._lib.cl_mat_free(self._h))
+        self._mat_cells = 0
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

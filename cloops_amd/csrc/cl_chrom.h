@@ -277,6 +277,15 @@ struct cl_chrom {
         int ks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         long long n_kept = 0;
     } kd;
+    // K24 (k_matrix.hip): the dense output of a window / virtual-4C call, the table ranges and counters of a call, and for the cells
+    // the keys (in / sorted, sort and scan scratch), head flags, their scan, the run starts and the result (bx, by, cnt of every cell:
+    // copies, so cl_agg_loops at another cut does not disturb them).  The rows are K19's table, shared.  The cells are kept from
+    // cl_mat_cells to the next one, cl_mat_free or destruction
+    DevBuf mx_out, mx_ctr, mx_key, mx_sorted, mx_tmp, mx_flag, mx_scan, mx_start, mx_bx, mx_by, mx_cnt;
+    struct MatState {
+        bool ready = false;
+        long long n_cells = 0, n_kept = 0, max_count = 0;
+    } mx;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
@@ -398,6 +407,60 @@ __device__ __forceinline__ int k8_ub(const u64* __restrict__ t, int m, long long
 // builds the tables of (chromosome, cut) unless the handle holds them already (c->sig_tx / sig_ty; c->sig_m[0] on the device = the
 // number of valid entries); enqueued on c->stream, c->n > 0
 int sig_tables(cl_chrom* c, int cut);
-// K19's table (k_agg.hip), shared with K22 (k_domain.hip) and K23 (k_kdis.hip): the rows with Y - X >= cut sorted by X (c->ag_sx: X + 2^30 as u32, c->ag_sy:
+// K19's table (k_agg.hip), shared with K22 (k_domain.hip), K23 (k_kdis.hip) and K24 (k_matrix.hip): the rows with Y - X >= cut sorted by X (c->ag_sx: X + 2^30 as u32, c->ag_sy:
 // their Y, c->ag_kept rows) unless the handle holds it for this cut already; c->n > 0
 int agg_table(cl_chrom* c, int cut);
+
+// first index of [0, m) with sx[idx] >= t (m if none), by the 64 lanes of a wave together (all call, with the same arguments):
+// 64 probes cut the range into 65 parts per round; sx ascends, so the lanes whose probe is below t are a prefix and a ballot
+// counts them
+__device__ __forceinline__ int k19_lb_wave(const u32* __restrict__ sx, int m, u32 t)
+{
+    const int lane = threadIdx.x & 63;
+    int lo = 0, len = m;                                     // the answer lies in [lo, lo + len]
+    while (len > 0) {
+        const int step = len / 65 + 1;
+        const long long pos = (long long)lo + (long long)(lane + 1) * step - 1;
+        const bool below = pos < (long long)lo + len && sx[pos] < t;
+        const int nb = __popcll(__ballot(below));
+        // probe nb - 1 is below t, probe nb (if inside the range) is not
+        const long long nlo = (long long)lo + (long long)nb * step;
+        const long long end = (long long)lo + len, nhi = nlo + step - 1 < end ? nlo + step - 1 : end;
+        lo = (int)nlo; len = (int)(nhi - nlo);
+    }
+    return lo;
+}
+
+
+// v / d by multiply-shift (Granlund-Montgomery, exact for all u32 v), the divisor made on the host: K12 (k_fingerprint.hip) and K24
+// (k_matrix.hip)
+struct K12Div { u32 magic; int sh1, sh2; };
+__device__ __forceinline__ u32 k12_div(const K12Div& d, u32 v)
+{
+    const u32 t1 = __umulhi(d.magic, v);
+    return (t1 + ((v - t1) >> d.sh1)) >> d.sh2;
+}
+static inline K12Div k12_divisor(u32 d)
+{
+    K12Div r;
+    int l = 0; while ((1ull << l) < d) ++l;                          // ceil(log2 d)
+    r.magic = (u32)((((1ull << 32) * ((1ull << l) - d)) / d) + 1);
+    r.sh1 = l < 1 ? l : 1; r.sh2 = l > 1 ? l - 1 : 0;
+    return r;
+}
+
+// K22 (k_domain.hip) and K24 (k_matrix.hip): wave aggregation in front of an atomic
+#define K22_NONE INT_MIN                // no target (bins and domain numbers lie far above)
+// What this lane has to add at `target` for a wave whose lanes each add `delta` at their target (K22_NONE: none): the lanes that share
+// the first active lane's target are summed into that lane.  Called by all 64 lanes together.
+__device__ __forceinline__ u32 k22_agg(int target, u32 delta)
+{
+    const u64 act = __ballot(target != K22_NONE);
+    if (!act) return 0u;                                                        // (the same in every lane)
+    const int leader = __ffsll((long long)act) - 1;
+    const int lt = __shfl(target, leader);
+    const u64 same = __ballot(target == lt);
+    if (target == K22_NONE) return 0u;
+    if (target != lt) return delta;
+    return (int)(threadIdx.x & 63) == leader ? (u32)__popcll(same) * delta : 0u;
+}

@@ -2147,6 +2147,8 @@ static void free_chrom(cl_chrom* c)
                       &c->pk_start, &c->pk_end, &c->pk_np, &c->pk_nc, &c->pk_ctr, &c->pk_ivs, &c->pk_ive, &c->pk_best, &c->pk_opos, &c->pk_ocnt,
                       &c->dm_diff, &c->dm_trk, &c->dm_tmp, &c->dm_rng, &c->dm_ivs, &c->dm_ive, &c->dm_cnt,
                       &c->kd_x, &c->kd_y, &c->kd_d, &c->kd_hist,
+                      &c->mx_out, &c->mx_ctr, &c->mx_key, &c->mx_sorted, &c->mx_tmp, &c->mx_flag, &c->mx_scan, &c->mx_start, &c->mx_bx,
+                      &c->mx_by, &c->mx_cnt,
                       &c->ulist, &c->lo, &c->hi, &c->recs, &c->counters, &c->chainflag, &c->chainhead, &c->usize, &c->b_cstart, &c->b_ckey, &c->b_nb, &c->b_cx, &c->b_cy, &c->tile_s0, &c->bq, &c->bsp, &c->brow, &c->bstrip, &c->btile, &c->sel_tmp, &c->cand_box, &c->cand_step, &c->cand_keep, &c->cand_out, &c->dhist,
                       &c->rc_cnt, &c->rc_pre, &c->rc_poff, &c->rc_dpre, &c->rc_D, &c->rc_blen, &c->rootlist, &c->cflag8, &c->blk_tmp,
                       &c->l_mask, &c->l_rank, &c->l_blk, &c->l_cstrip, &c->l_wpos, &c->l_wenc, &c->l_dist, &c->l_aux, &c->l_tab, &c->l_fix, &c->bkey,

@@ -69,26 +69,7 @@ __global__ void k19_loop_keys(const int* __restrict__ cx, int n_loops, int* __re
     idx[k] = (u32)k;
 }
 
-// first index of [0, m) with sx[idx] >= t (m if none), by the 64 lanes of a wave together (all call, with the same arguments):
-// 64 probes cut the range into 65 parts per round; sx ascends, so the lanes whose probe is below t are a prefix and a ballot
-// counts them
-__device__ __forceinline__ int k19_lb_wave(const u32* __restrict__ sx, int m, u32 t)
-{
-    const int lane = threadIdx.x & 63;
-    int lo = 0, len = m;                                     // the answer lies in [lo, lo + len]
-    while (len > 0) {
-        const int step = len / 65 + 1;
-        const long long pos = (long long)lo + (long long)(lane + 1) * step - 1;
-        const bool below = pos < (long long)lo + len && sx[pos] < t;
-        const int nb = __popcll(__ballot(below));
-        // probe nb - 1 is below t, probe nb (if inside the range) is not
-        const long long nlo = (long long)lo + (long long)nb * step;
-        const long long end = (long long)lo + len, nhi = nlo + step - 1 < end ? nlo + step - 1 : end;
-        lo = (int)nlo; len = (int)(nhi - nlo);
-    }
-    return lo;
-}
-
+// (k19_lb_wave: cl_chrom.h, shared with K24)
 enum { K19_LL = 1, K19_UL = 2, K19_UR = 4, K19_LR = 8 };
 
 template <int NT>

@@ -34,7 +34,6 @@
 #define K22_WMAX 1024                   // w lies in [1, 1024]: 2 w + 1 <= K22_BW
 #define K22_MAXRES (1ll << 29)          // res and w res lie below 2^29
 #define K22_MAXBINS (1ll << 24)         // bins of a handle at one res
-#define K22_NONE INT_MIN                // no target (bins and domain numbers lie far above)
 static_assert(2 * K22_WMAX + 1 <= K22_BW, "the window of one bin must fit the LDS window");
 
 __device__ __forceinline__ int k22_bin(int p, int res)          // floor(p / res), res >= 1
@@ -43,19 +42,7 @@ __device__ __forceinline__ int k22_bin(int p, int res)          // floor(p / res
     return q - ((p - q * res) < 0 ? 1 : 0);
 }
 
-// What this lane has to add at `target` for a wave whose lanes each add `delta` at their target (K22_NONE: none): the lanes that share
-// the first active lane's target are summed into that lane.  Called by all 64 lanes together.
-__device__ __forceinline__ u32 k22_agg(int target, u32 delta)
-{
-    const u64 act = __ballot(target != K22_NONE);
-    if (!act) return 0u;                                                        // (the same in every lane)
-    const int leader = __ffsll((long long)act) - 1;
-    const int lt = __shfl(target, leader);
-    const u64 same = __ballot(target == lt);
-    if (target == K22_NONE) return 0u;
-    if (target != lt) return delta;
-    return (int)(threadIdx.x & 63) == leader ? (u32)__popcll(same) * delta : 0u;
-}
+// (k22_agg, K22_NONE: cl_chrom.h, shared with K24)
 
 // rng: {min Y key, max Y key, first X key, last X key}, keys = coordinate + 2^30; rng[0] preset to ~0 and rng[1] to 0
 __global__ void __launch_bounds__(TPB)

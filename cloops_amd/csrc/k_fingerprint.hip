@@ -25,14 +25,7 @@
 #define K12_GRID 1024                   // workgroups of the grid-stride kernels
 enum { K12_MIN = 0, K12_MAX = 1, K12_KEPT = 2, K12_POS = 3, K12_NOVF = 4, K12_NPAIR = 5, K12_HDR = 16 };   // fp_small: header, then hist
 
-struct K12Div { u32 magic; int sh1, sh2; };         // v / bs by multiply-shift (Granlund-Montgomery, exact for all u32 v)
-
-__device__ __forceinline__ u32 k12_div(const K12Div& d, u32 v)
-{
-    const u32 t1 = __umulhi(d.magic, v);
-    return (t1 + ((v - t1) >> d.sh1)) >> d.sh2;
-}
-
+// (K12Div, k12_div, k12_divisor: cl_chrom.h, shared with K24)
 __device__ __forceinline__ bool k12_keep(int x, int y, int cut)
 {
     return cut <= 0 || (long long)y - (long long)x >= (long long)cut;        // parseJd(jd, cut), cLoops/io.py:213-216
@@ -181,15 +174,6 @@ k12_ovf_pairs(const u32* __restrict__ ov, int k, int* __restrict__ s, u32* __res
         const int p = atomicAdd(&s[K12_NPAIR], 1);
         if (p < cap) { pv[p] = ov[i]; pm[p] = (u32)len; }
     }
-}
-
-static K12Div k12_divisor(u32 d)
-{
-    K12Div r;
-    int l = 0; while ((1ull << l) < d) ++l;                          // ceil(log2 d)
-    r.magic = (u32)((((1ull << 32) * ((1ull << l) - d)) / d) + 1);
-    r.sh1 = l < 1 ? l : 1; r.sh2 = l > 1 ? l - 1 : 0;
-    return r;
 }
 
 static int k12_grid(long long n) { return (int)std::max(1ll, std::min<long long>(K12_GRID, (n + TPB - 1) / TPB)); }

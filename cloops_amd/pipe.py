@@ -1037,7 +1037,7 @@ def _read_gpu(fs, fout, chroms, cut, auto_eps, tmp, fmt="bedpe", ext=50):
 
 def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0, cut=0, plot=0, max_cut=False,
          log=None, reader="gpu", fmt="auto", ext=50, agg=0, agg_res=0, bdg=0, bdg_ext=75, peaks=0, peak_eps=(100, 200),
-         peak_minPts=(5, 10), domains=0, dom_res=10000, dom_w=(10,), kdis=0, kdis_k=(4, 9, 19)):
+         peak_minPts=(5, 10), domains=0, dom_res=10000, dom_w=(10,), kdis=0, kdis_k=(4, 9, 19), mat=0, mat_res=10000):
     """cLoops/pipe.py:206-295: BEDPE -> per-chromosome PETs -> (eps, minPts) sweep with the chained
     distance cutoff on the GPU(s) -> candidate loops -> significance -> `<fout>.loop`.
 
@@ -1061,7 +1061,10 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
     for every window of `dom_w`, from the chromosomes still resident.
     `kdis` writes `<fout>_kdis.txt` and `<fout>_kdis.json` after `<fout>.loop`: the k-distance curves of the PETs and the eps they
     suggest (cut 0, K23, cloops_amd.esteps) for every k = minPts - 1 of `kdis_k`, from the chromosomes still resident.  The suggestion
-    is reported, not fed into the sweep."""
+    is reported, not fed into the sweep.
+    `mat` writes `<fout>_cells.txt` (bg2: `chrom start1 end1 chrom start2 end2 count`) and `<fout>_cells.json` after `<fout>.loop`: the
+    non-empty cells of every chromosome's contact matrix in bins of `mat_res` bp (folded onto the upper triangle, cut 0, K24,
+    cloops_amd.matrix), from the chromosomes still resident."""
     import shutil
     if reader not in ("gpu", "host"):
         raise ValueError("reader must be 'gpu' or 'host', got %r" % (reader,))
@@ -1119,6 +1122,9 @@ def pipe(fs, fout, eps, minPts, chroms="", cpu=1, tmp=0, hic=0, washU=0, juice=0
         if kdis and not e:
             from .esteps import jd2esteps
             jd2esteps(list(cfs), fout, ks=kdis_k)
+        if mat and not e:
+            from .matrix import jd2cells
+            jd2cells(list(cfs), fout, res=int(mat_res))
     finally:
         for f in mem:                                         # 'mem://' residents are never evicted by age
             CACHE.drop(f)
@@ -1142,7 +1148,7 @@ def main(argv=None):
     aggregate pile-up around the called loops in bins of -res bp, -bdg the coverage of the PET ends as a bedGraph with -bdgext bp
     to either side of an end, -peaks the peaks of the PET ends for every setting of -peakeps x -peakminPts, -domains the domains and
     boundaries in bins of -domres bp for every window of -domw bins, -kdis the k-distance curves of the PETs and the eps they suggest for
-    every k = minPts - 1 of -kdisk)."""
+    every k = minPts - 1 of -kdisk, -mat the non-empty cells of the contact matrices in bins of -matres bp)."""
     import argparse
     ap = argparse.ArgumentParser(prog="cloops_amd")
     ap.add_argument("-f", dest="fnIn", required=True)
@@ -1174,6 +1180,8 @@ def main(argv=None):
     ap.add_argument("-domw", dest="domw", default="10")
     ap.add_argument("-kdis", dest="kdis", action="store_true")
     ap.add_argument("-kdisk", dest="kdisk", default="4,9,19")
+    ap.add_argument("-mat", dest="mat", action="store_true")
+    ap.add_argument("-matres", dest="matres", type=int, default=10000)
     op = ap.parse_args(argv)
     if op.mode == 0:                                          # pipe.py:306-327
         eps = sorted(int(x) for x in str(op.eps).split(","))
@@ -1188,5 +1196,6 @@ def main(argv=None):
     pipe(op.fnIn.split(","), op.fnOut, eps, minPts, op.chroms, op.cpu, op.tmp, hic, op.washU, op.juice, op.cut,
          op.plot, op.max_cut, log=lambda m: sys.stderr.write(m + "\n"), reader=op.reader, fmt=op.fmt, ext=op.ext,
          agg=op.agg, agg_res=op.res, bdg=op.bdg, bdg_ext=op.bdgext, peaks=op.peaks, peak_eps=op.peakeps,
-         peak_minPts=op.peakminPts, domains=op.domains, dom_res=op.domres, dom_w=op.domw, kdis=op.kdis, kdis_k=op.kdisk)
+         peak_minPts=op.peakminPts, domains=op.domains, dom_res=op.domres, dom_w=op.domw, kdis=op.kdis, kdis_k=op.kdisk,
+         mat=op.mat, mat_res=op.matres)
     return 0

@@ -511,6 +511,50 @@ int cl_kdis_hist(cl_chrom* c, int32_t which, uint64_t* hist, uint64_t* n_zero, u
 int cl_kdis_free(cl_chrom* c);
 
 /*
+ * Contact matrices (K24): the binned contact map of a chromosome in the three forms a contact workflow asks for -- a dense window for
+ * a heatmap, the non-empty cells of the whole chromosome for an export or a comparison, and the profile of one viewpoint (virtual
+ * 4C).  The reference has no counterpart, so these definitions are the specification; labels, text and scaling stay on the host
+ * (cloops_amd/matrix.py).  cl_contact_hist (K12) bins from the data's minimum and returns only the histogram of the cell counts; the
+ * bins here are genome coordinates.
+ *
+ * Kept rows, as for cl_dom_tracks: the rows with Y - X >= cut take part (all for cut <= 0), n_kept of them.  Duplicated rows count each
+ * time.
+ * Bins: res >= 1; the bin of a coordinate p is floor(p / res), floor also for negative p (the rule of cl_dom_tracks).  bx, by: the
+ * bins of a row's X and Y.
+ *
+ * cl_mat_window -- out is nx * ny uint32, row-major [i][j]: out[i][j] = #{kept rows : bx - bx0 == i and by - by0 == j}.  With
+ * mirror != 0 a row with bx != by additionally counts at (by - bx0, bx - by0) when that cell lies in the window: a window on the
+ * diagonal (bx0 == by0, nx == ny) is then a symmetric matrix whose diagonal cells are counted once.  *n_in = the sum of out.  The
+ * window may lie anywhere; cells beyond the data are 0.  Limits: 1 <= nx, ny <= CL_MAT_WMAX, nx * ny <= CL_MAT_CELLS_MAX, |bx0|,
+ * |by0| <= 2^30, res in [1, 2^29).
+ * cl_mat_cells -- the distinct (bx, by) of the kept rows, ascending by bx then by, each with its count, kept on the device ->
+ * *n_cells, *n_kept, *max_count (the largest count).  With fold != 0 a row's cell is (min(bx, by), max(bx, by)).  The sum of the
+ * counts is n_kept.  No limit on the number of bins (64-bit keys, sorted over the bits in use only).  The cells stay with the handle
+ * until the next cl_mat_cells, cl_mat_free or cl_chrom_destroy (copies: cl_agg_loops at another cut does not disturb them).
+ * cl_mat_cells_get -- cells [first, first + count) inside [0, n_cells] into host memory; the arrays may be NULL when count is 0.
+ * cl_mat_v4c -- the viewpoint is the half-open interval [v0, v1) in bp, v0 <= v1.  Every kept row adds 1 at bin by if its X lies in
+ * the viewpoint, and 1 at bin bx if its Y lies in it (both may happen).  out[k], k < nb, is the total at bin b0 + k; *n_x = #{X in
+ * viewpoint}, *n_y = #{Y in viewpoint} over all kept rows, whether or not their other end falls in [b0, b0 + nb).  Limits: 0 <= nb <=
+ * 2^24 (out may be NULL for nb == 0), |b0| <= 2^30, res in [1, 2^29).
+ * cl_mat_free -- releases the cells and the scratch of the calls (K19's table stays with the handle).
+ *
+ * The kept rows sorted by X are K19's table, built when the handle does not hold it for this cut, exactly as by cl_dom_tracks and
+ * cl_kdis_build.  An empty handle or a cut that removes every row: zero outputs, n_cells = 0 and CL_OK.
+ * Errors: CL_ERR_ARG for a NULL handle or NULL outputs, a limit violated, v0 > v1, a get before cl_mat_cells or outside its range, or
+ * runs in flight; all of them are found on the host before any launch.  A refused call zeroes its scalar outputs and leaves the
+ * earlier state usable.  The handle's layouts, count cache, K8 / K13 / K14 / K20 - K23 state and results stay untouched.
+ */
+#define CL_MAT_WMAX 8192
+#define CL_MAT_CELLS_MAX 16777216
+int cl_mat_window(cl_chrom* c, int64_t cut, int64_t res, int64_t bx0, int64_t by0, int64_t nx, int64_t ny, int32_t mirror,
+                  uint32_t* out, int64_t* n_in, int64_t* n_kept);
+int cl_mat_cells(cl_chrom* c, int64_t cut, int64_t res, int32_t fold, int64_t* n_cells, int64_t* n_kept, int64_t* max_count);
+int cl_mat_cells_get(cl_chrom* c, int64_t first, int64_t count, int32_t* bx, int32_t* by, uint32_t* cnt);
+int cl_mat_v4c(cl_chrom* c, int64_t cut, int64_t res, int64_t v0, int64_t v1, int64_t b0, int64_t nb, uint32_t* out, int64_t* n_x,
+               int64_t* n_y, int64_t* n_kept);
+int cl_mat_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
