@@ -38,6 +38,7 @@ CL_KDIS_KMAX = 64
 CL_KDIS_BINS = 3968          # 31 octaves x 128 log bins: d < 2^31
 CL_MAT_WMAX = 8192           # bins a side of a dense window
 CL_MAT_CELLS_MAX = 16777216  # 2^24 cells of a dense window
+CL_BAL_BINS_MAX = 16777216   # 2^24 bins of a balanced chromosome
 
 
 class ClBox(ctypes.Structure):
@@ -136,6 +137,12 @@ PROTOTYPES = {
     "cl_mat_cells_get": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "cl_mat_v4c": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64p, _i64p, _i64p]),
     "cl_mat_free": (_int, [_vp]),
+    "cl_bal_marginals": (_int, [_vp, _i32, _i64p, _i64p, _i64p]),
+    "cl_bal_marginals_get": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "cl_bal_iterate": (_int, [_vp, _vp, _i32, _f64, _i32p, _i32p, _f64p, _f64p]),
+    "cl_bal_weights_get": (_int, [_vp, _i64, _i64, _vp]),
+    "cl_bal_cells_get": (_int, [_vp, _i64, _i64, _vp]),
+    "cl_bal_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

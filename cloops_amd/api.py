@@ -860,6 +860,7 @@ class Chromosome(_Handle):
         nc, nk, mc = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         _lib.check(self._lib.cl_mat_cells(self._h, int(cut), int(res), 1 if fold else 0, ctypes.byref(nc), ctypes.byref(nk), ctypes.byref(mc)))
         self._mat_cells = int(nc.value)                                      # (a refused call leaves the earlier cells and their number)
+        self._bal_bins = 0                                                   # (K25's state went with the earlier cells)
         return int(nc.value), int(nk.value), int(mc.value)
 
     def mat_cells_get(self, first=0, count=None):
@@ -893,6 +894,63 @@ class Chromosome(_Handle):
         """releases the cells of mat_cells and the device scratch of the mat_* calls  (cl_mat_free)"""
         _lib.check(self._lib.cl_mat_free(self._h))
         self._mat_cells = 0
+        self._bal_bins = 0
+
+    def bal_marginals(self, ignore_diags=2):
+        """K25: the raw marginals of the folded cells of the last mat_cells(fold=True), kept on the device with the cells' transposed
+        order for bal_iterate.  A cell is used iff by - bx >= ignore_diags; the bins are b0 = the first cell's bx .. the largest by
+        -> (b0, nb, n_used)  (cl_bal_marginals)"""
+        b0, nb, nu = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_bal_marginals(self._h, int(ignore_diags), ctypes.byref(b0), ctypes.byref(nb), ctypes.byref(nu)))
+        self._bal_bins = int(nb.value)
+        return int(b0.value), int(nb.value), int(nu.value)
+
+    def bal_marginals_get(self, first=0, count=None):
+        """bins [first, first + count) of the last bal_marginals (all from `first` on by default) -> (sum uint64: the counts of the used
+        cells that touch the bin, nnz uint32: their number)  (cl_bal_marginals_get)"""
+        first = int(first)
+        count = max(0, getattr(self, "_bal_bins", 0) - first) if count is None else int(count)
+        n = max(0, count)
+        s, z = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        _lib.check(self._lib.cl_bal_marginals_get(self._h, first, count, s.ctypes.data_as(ctypes.c_void_p), z.ctypes.data_as(ctypes.c_void_p)))
+        return s, z
+
+    def bal_iterate(self, valid, max_iters=200, tol=1e-5):
+        """K25: iterative correction over the used cells, from w = 1 on the bins with valid != 0, until the variance of the non-zero
+        marginals falls below tol or max_iters iterations are done -> (iters, converged, var, scale); the weights stay on the device
+        for bal_weights / bal_cells_get.  May be repeated with another mask or tol  (cl_bal_iterate)"""
+        valid = np.asarray(valid)
+        nb = getattr(self, "_bal_bins", 0)
+        if valid.ndim != 1 or len(valid) != nb:
+            raise ValueError("bal_iterate: the mask needs one entry per bin (%d), got shape %s" % (nb, valid.shape))
+        v = np.ascontiguousarray(valid != 0, dtype=np.uint32)
+        it, cv, var, sc = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _lib.check(self._lib.cl_bal_iterate(self._h, v.ctypes.data_as(ctypes.c_void_p), int(max_iters), float(tol), ctypes.byref(it),
+                                            ctypes.byref(cv), ctypes.byref(var), ctypes.byref(sc)))
+        return int(it.value), bool(cv.value), float(var.value), float(sc.value)
+
+    def bal_weights(self, first=0, count=None):
+        """the weights of the bins [first, first + count) after the last bal_iterate -> float64, NaN at the bins that are masked or
+        got no weight  (cl_bal_weights_get)"""
+        first = int(first)
+        count = max(0, getattr(self, "_bal_bins", 0) - first) if count is None else int(count)
+        w = np.zeros(max(0, count), dtype=np.float64)
+        _lib.check(self._lib.cl_bal_weights_get(self._h, first, count, w.ctypes.data_as(ctypes.c_void_p)))
+        return w
+
+    def bal_cells_get(self, first=0, count=None):
+        """the balanced values cnt weight[bx] weight[by] of the cells [first, first + count) of mat_cells, in their order -> float64
+        (cl_bal_cells_get)"""
+        first = int(first)
+        count = max(0, getattr(self, "_mat_cells", 0) - first) if count is None else int(count)
+        v = np.zeros(max(0, count), dtype=np.float64)
+        _lib.check(self._lib.cl_bal_cells_get(self._h, first, count, v.ctypes.data_as(ctypes.c_void_p)))
+        return v
+
+    def bal_free(self):
+        """releases the marginals, weights and device scratch of the bal_* calls; the cells stay  (cl_bal_free)"""
+        _lib.check(self._lib.cl_bal_free(self._h))
+        self._bal_bins = 0
 
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)

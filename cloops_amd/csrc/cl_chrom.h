@@ -285,7 +285,20 @@ struct cl_chrom {
     struct MatState {
         bool ready = false;
         long long n_cells = 0, n_kept = 0, max_count = 0;
+        int res = 0; bool fold = false;                              // what the cells were made with (K25 refuses unfolded cells)
     } mx;
+    // K25 (k_balance.hip): the transposed order of K24's folded cells (sort scratch, then by / bx / cnt of every cell ascending by
+    // (by, bx)), the integer marginals (sum, nnz per bin), the caller's mask, the weights w, the marginals s of an iteration, the
+    // per-tile carry records of both orders (integer and fp64), the partial sums of the update's reduction, the 32-byte record of a
+    // loop and the balanced values of a get.  Kept from cl_bal_marginals to the next cl_mat_cells, cl_mat_free, cl_bal_free or
+    // destruction
+    DevBuf bl_kin, bl_kout, bl_vin, bl_vout, bl_tmp, bl_tby, bl_tbx, bl_tcnt, bl_sum, bl_nnz, bl_valid, bl_w, bl_s, bl_icar, bl_dcar,
+           bl_part, bl_rec, bl_out;
+    struct BalState {
+        bool ready = false, iterated = false;
+        int ignore_diags = 0;
+        long long b0 = 0, nb = 0, n_used = 0, n_cells = 0;
+    } bl;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
@@ -319,6 +332,8 @@ Table make_table_slot(cl_chrom* c, int slot);
 Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
 int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_out);
+// k_balance.hip: drops K25's state and buffers (the cells they were made from are going away)
+void bal_release(cl_chrom* c);
 // k_block.hip, k_weighted.hip
 int run_block(cl_chrom* c, int eps, int minPts, int cut, int32_t* labels_out);
 int run_weighted(cl_chrom* c, int eps, int minPts, int wx, int wy, int32_t* labels_out);

@@ -15,7 +15,7 @@
 
 #include "../../include/cloops_hip.h"
 
-#define CL_VERSION_NUM 104   // 0.1.4
+#define CL_VERSION_NUM 105   // 0.1.5
 
 typedef unsigned long long u64;
 typedef unsigned int u32;

@@ -2149,6 +2149,8 @@ static void free_chrom(cl_chrom* c)
                       &c->kd_x, &c->kd_y, &c->kd_d, &c->kd_hist,
                       &c->mx_out, &c->mx_ctr, &c->mx_key, &c->mx_sorted, &c->mx_tmp, &c->mx_flag, &c->mx_scan, &c->mx_start, &c->mx_bx,
                       &c->mx_by, &c->mx_cnt,
+                      &c->bl_kin, &c->bl_kout, &c->bl_vin, &c->bl_vout, &c->bl_tmp, &c->bl_tby, &c->bl_tbx, &c->bl_tcnt, &c->bl_sum, &c->bl_nnz,
+                      &c->bl_valid, &c->bl_w, &c->bl_s, &c->bl_icar, &c->bl_dcar, &c->bl_part, &c->bl_rec, &c->bl_out,
                       &c->ulist, &c->lo, &c->hi, &c->recs, &c->counters, &c->chainflag, &c->chainhead, &c->usize, &c->b_cstart, &c->b_ckey, &c->b_nb, &c->b_cx, &c->b_cy, &c->tile_s0, &c->bq, &c->bsp, &c->brow, &c->bstrip, &c->btile, &c->sel_tmp, &c->cand_box, &c->cand_step, &c->cand_keep, &c->cand_out, &c->dhist,
                       &c->rc_cnt, &c->rc_pre, &c->rc_poff, &c->rc_dpre, &c->rc_D, &c->rc_blen, &c->rootlist, &c->cflag8, &c->blk_tmp,
                       &c->l_mask, &c->l_rank, &c->l_blk, &c->l_cstrip, &c->l_wpos, &c->l_wenc, &c->l_dist, &c->l_aux, &c->l_tab, &c->l_fix, &c->bkey,

@@ -1,0 +1,631 @@
+// k_balance.hip -- K25: matrix balancing (iterative correction, ICE) of the folded cells that K24 left on the device -- kernels and C
+// entry points.
+#include <cmath>
+#include "cl_chrom.h"
+
+// ==========================================================================================
+// K25: one weight per bin so that the rows of the weighted contact matrix have equal sums
+// ==========================================================================================
+// Definitions: include/cloops_hip.h, cl_bal_marginals.  The reference has nothing of the kind; tests/balance_cases.py restates the
+// definitions in numpy.  Input: K24's cells (c->mx_bx, c->mx_by, c->mx_cnt: ascending by (bx, by), bx <= by).
+// A marginal of bin i has a row part (the cells with bx == i: a run of the cells as they lie) and a column part (the cells with by ==
+// i and bx != i: a run of the cells sorted by (by, bx), the transposed order that cl_bal_marginals builds once with one rocPRIM radix
+// sort of (key, cell index) pairs over the bits in use and one gather).  Both are sums over runs of equal sorted keys:
+//   k25_marg<V>     blockIdx.y = order (0: as they lie, 1: transposed), one workgroup per K25_TILE consecutive cells, 8 consecutive
+//                   cells per thread (two 16-byte loads per array on a full tile; with 4-byte loads an iteration over the 2.77 M
+//                   cells of chr1 at 10 kb took 62 instead of 37 us).  Segmented inclusive scan by key: inside the thread, then over the threads (wave shuffles, then
+//                   the four wave totals).  A run that lies inside the tile is stored by the thread of its last cell: every key has ONE
+//                   run per order, so no atomics.  The run that opens the tile and the run that closes it go to the tile's carry record
+//                   (one record when the tile is one run).
+//   k25_fold<V>     one thread per tile and order: a piece that starts a chain (the closing piece of a tile, or an opening piece whose
+//                   key differs from the key before it) adds the opening pieces of the tiles that follow while their key is its own,
+//                   in tile order, and stores the total.  A run over several whole tiles is a walk over their records.
+//                   V = K25I (sum as u64 and nnz as u32: the raw marginals) or K25D (fp64: (w[bx] cnt) w[by], the iteration's s).
+//   k25_stat1       s[i] = row part + column part (and both parts back to zero for the next pass); count and sum of the s != 0: a
+//                   fixed share of the bins per thread in ascending order, a fixed tree over the workgroup -> one partial per workgroup.
+//   k25_stat2       every workgroup folds the partials in index order to the mean, then w[i] /= s[i] / mean and the partial sums of
+//                   (s / mean - 1)^2 the same way.
+//   k25_stat3       one workgroup: folds those to var, counts the iteration and sets `stop` in the loop's record when var < tol (or
+//                   when no s differs from zero).  Every kernel of the loop begins by reading `stop` and returns at once when it is set:
+//                   the host enqueues K25_BLOCK iterations at a time and reads the 32-byte record after each block.
+// Every fp64 sum is taken in an order that depends on the cells and nb alone: two runs give the same bytes.  No fp64 atomics, no
+// workgroup waits on another, plain launches in the handle's stream.  Only vector stores and integer HIP atomics (the count of used
+// cells); every index is checked against its array before a load or store.
+#define K25_TILE 2048                   // cells per workgroup (K24's tile): 8 per thread, no LDS beyond the wave totals
+#define K25_U (K25_TILE / TPB)
+#define K25_PARTS 1024                  // most workgroups (= partial sums) of k25_stat1 / k25_stat2
+#define K25_BLOCK 16                    // iterations enqueued between two reads of the record
+static_assert(CL_BAL_BINS_MAX == (1 << 24), "the limit of include/cloops_hip.h");
+
+struct K25Rec { int iters, converged, stop, pad; double var, scale; };        // the loop's record (32 bytes)
+static_assert(sizeof(K25Rec) == 32, "the record is read back as 32 bytes");
+
+struct K25I {                           // the integer pass
+    u64 s; u32 n;
+    struct Out { u64* s; u32* n; };
+    struct Ctx { int ign; };
+    __device__ __forceinline__ static K25I zero() { return K25I{0ull, 0u}; }
+    __device__ __forceinline__ static K25I add(const K25I& a, const K25I& b) { return K25I{a.s + b.s, a.n + b.n}; }
+    __device__ __forceinline__ static K25I up(const K25I& a, int d)
+    {
+        K25I r;
+        r.s = (u64)__shfl_up((unsigned long long)a.s, (unsigned)d);
+        r.n = (u32)__shfl_up((int)a.n, (unsigned)d);
+        return r;
+    }
+    __device__ __forceinline__ static void store(const Out& o, size_t i, const K25I& v) { o.s[i] = v.s; o.n[i] = v.n; }
+};
+struct K25D {                           // the fp64 pass
+    double s;
+    struct Out { double* s; };
+    __device__ __forceinline__ static K25D zero() { return K25D{0.0}; }
+    __device__ __forceinline__ static K25D add(const K25D& a, const K25D& b) { return K25D{a.s + b.s}; }
+    __device__ __forceinline__ static K25D up(const K25D& a, int d) { return K25D{__shfl_up(a.s, (unsigned)d)}; }
+    __device__ __forceinline__ static void store(const Out& o, size_t i, const K25D& v) { o.s[i] = v.s; }
+};
+template <typename V> struct K25Car { int kf, kl, single, pad; V vf, vl; };     // a tile's opening piece (kf, vf) and closing piece (kl, vl; none when single)
+
+struct K25In {
+    const int* key[2]; const int* oth[2]; const u32* cnt[2];                    // per order: the run key, the other bin, the count
+    int n, ign, b0, nb;
+    int vec;                                                                    // all six arrays start at multiples of 16 bytes
+    const double* w;                                                            // fp64 pass: nb weights
+};
+
+// what a cell adds to the run of `k` (o: its other bin)
+__device__ __forceinline__ K25I k25_term(const K25In& in, int ph, int k, int o, u32 c, K25I*)
+{
+    const int d = ph ? k - o : o - k;                                           // by - bx >= 0
+    return (d >= in.ign && !(ph && d == 0)) ? K25I{(u64)c, 1u} : K25I::zero();
+}
+__device__ __forceinline__ K25D k25_term(const K25In& in, int ph, int k, int o, u32 c, K25D*)
+{
+    const int d = ph ? k - o : o - k;
+    const long long ix = (long long)(ph ? o : k) - in.b0, iy = (long long)(ph ? k : o) - in.b0;
+    if (d < in.ign || (ph && d == 0) || ix < 0 || ix >= in.nb || iy < 0 || iy >= in.nb) return K25D::zero();
+    return K25D{(in.w[ix] * (double)c) * in.w[iy]};
+}
+
+template <typename V>
+__global__ void __launch_bounds__(TPB)
+k25_marg(K25In in, typename V::Out out, K25Car<V>* __restrict__ car, int ntiles, u64* __restrict__ n_used, const K25Rec* __restrict__ rec)
+{
+    __shared__ V wv[TPB / 64];
+    __shared__ int wf[TPB / 64];
+    __shared__ u32 wu[TPB / 64];
+    if (rec && rec->stop) return;                                               // (the whole grid)
+    const int ph = blockIdx.y ? 1 : 0;
+    const long long t0 = (long long)blockIdx.x * K25_TILE;
+    if (t0 >= in.n || (int)blockIdx.x >= ntiles) return;                        // (the whole workgroup)
+    const int tn = (int)(in.n - t0 < K25_TILE ? in.n - t0 : K25_TILE);
+    const int* __restrict__ key = in.key[ph] + t0;
+    const int* __restrict__ oth = in.oth[ph] + t0;
+    const u32* __restrict__ cnt = in.cnt[ph] + t0;
+    const int base = (int)threadIdx.x * K25_U, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int kfirst = key[0], klast = key[tn - 1];
+    int k[K25_U], o[K25_U];
+    u32 cc[K25_U];
+    V v[K25_U];
+    u32 used = 0u;
+    if (in.vec && tn == K25_TILE) {                                             // (the whole workgroup) a full tile of 16-byte aligned arrays: two
+        static_assert(K25_U == 8, "two 16-byte loads per array and thread");   // 16-byte loads per array instead of eight of 4 bytes
+        const int4 ka = ((const int4*)(key + base))[0], kb = ((const int4*)(key + base))[1];
+        const int4 oa = ((const int4*)(oth + base))[0], ob = ((const int4*)(oth + base))[1];
+        const uint4 ca = ((const uint4*)(cnt + base))[0], cb = ((const uint4*)(cnt + base))[1];
+        k[0] = ka.x; k[1] = ka.y; k[2] = ka.z; k[3] = ka.w; k[4] = kb.x; k[5] = kb.y; k[6] = kb.z; k[7] = kb.w;
+        o[0] = oa.x; o[1] = oa.y; o[2] = oa.z; o[3] = oa.w; o[4] = ob.x; o[5] = ob.y; o[6] = ob.z; o[7] = ob.w;
+        cc[0] = ca.x; cc[1] = ca.y; cc[2] = ca.z; cc[3] = ca.w; cc[4] = cb.x; cc[5] = cb.y; cc[6] = cb.z; cc[7] = cb.w;
+    } else {
+#pragma unroll
+        for (int u = 0; u < K25_U; ++u) {
+            const int il = base + u;
+            if (il < tn) { k[u] = key[il]; o[u] = oth[il]; cc[u] = cnt[il]; }
+            else { k[u] = klast; o[u] = klast; cc[u] = 0u; }                    // (behind the tile's end: more of its last run, adding nothing)
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < K25_U; ++u) {
+        const bool live = base + u < tn;
+        v[u] = live ? k25_term(in, ph, k[u], o[u], cc[u], (V*)nullptr) : V::zero();
+        if (!ph) used += (live && o[u] - k[u] >= in.ign) ? 1u : 0u;
+    }
+    const int kprev = base == 0 ? 0 : (base - 1 < tn ? key[base - 1] : klast);
+    const int knext = base + K25_U < tn ? key[base + K25_U] : klast;
+    // inside the thread: v[u] = the sum of its run's cells from the run's head (or the thread's first cell) to u
+    bool h0 = base == 0 || k[0] != kprev, any = h0;
+    int first_head = h0 ? 0 : K25_U;                                            // the thread's cells before it belong to a run that began earlier
+#pragma unroll
+    for (int u = 1; u < K25_U; ++u) {
+        const bool h = k[u] != k[u - 1];
+        if (!h) v[u] = V::add(v[u - 1], v[u]);
+        else if (first_head == K25_U) first_head = u;
+        any |= h;
+    }
+    // over the threads: (f, x) = (a head in the thread, the sum of its last run); inclusive segmented scan in the wave
+    int f = any ? 1 : 0;
+    V x = v[K25_U - 1];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const V tx = V::up(x, d);
+        const int tf = __shfl_up(f, (unsigned)d);
+        if (lane >= d) { if (!f) x = V::add(tx, x); f |= tf; }
+    }
+    if (lane == 63) { wv[wave] = x; wf[wave] = f; }
+    V ex = V::up(x, 1);                                                         // exclusive: what the threads before this one leave open
+    int ef = __shfl_up(f, 1u);
+    if (lane == 0) { ex = V::zero(); ef = 0; }
+    __syncthreads();
+    V px = V::zero();                                                           // the same of the waves before this one
+    for (int q = 0; q < wave; ++q) px = wf[q] ? wv[q] : V::add(px, wv[q]);
+    const V cin = ef ? ex : V::add(px, ex);
+    // stores: the thread of a run's last cell has its total
+    K25Car<V>* my = car + (size_t)ph * (size_t)ntiles + blockIdx.x;
+#pragma unroll
+    for (int u = 0; u < K25_U; ++u) {
+        const int il = base + u;
+        if (il >= tn) continue;
+        const int kn = u + 1 < K25_U ? k[u + 1] : knext;
+        const bool tile_end = il == tn - 1;
+        if (!tile_end && kn == k[u]) continue;                                  // not the last cell of its run
+        const V tot = u < first_head ? V::add(cin, v[u]) : v[u];
+        if (k[u] == kfirst) {                                                   // the run that opens the tile
+            my->kf = k[u]; my->vf = tot;
+            if (tile_end) { my->kl = k[u]; my->vl = V::zero(); my->single = 1; my->pad = 0; }
+        } else if (tile_end) {
+            my->kl = k[u]; my->vl = tot; my->single = 0; my->pad = 0;
+        } else {
+            const long long g = (long long)k[u] - in.b0;
+            if (g >= 0 && g < in.nb) V::store(out, (size_t)ph * (size_t)in.nb + (size_t)g, tot);
+        }
+    }
+    if (n_used && !ph) {                                                        // (wave-uniform)
+        for (int o = 32; o > 0; o >>= 1) used += (u32)__shfl_xor((int)used, o);
+        if (lane == 0) wu[wave] = used;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            u64 s = 0;
+            for (int q = 0; q < TPB / 64; ++q) s += wu[q];
+            if (s) atomicAdd(n_used, s);
+        }
+    }
+}
+
+template <typename V>
+__global__ void __launch_bounds__(TPB)
+k25_fold(const K25Car<V>* __restrict__ car, int ntiles, int b0, int nb, typename V::Out out, const K25Rec* __restrict__ rec)
+{
+    if (rec && rec->stop) return;
+    const int ph = blockIdx.y ? 1 : 0;
+    const long long t = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (t >= ntiles) return;
+    const K25Car<V>* r = car + (size_t)ph * (size_t)ntiles;
+    const K25Car<V> me = r[t];
+    for (int piece = 0; piece < 2; ++piece) {
+        int key; V tot; long long nx = t + 1;
+        if (piece == 0) {                                                       // the opening piece: a chain's start unless the tile before ends with its key
+            if (t > 0 && r[t - 1].kl == me.kf) continue;
+            key = me.kf; tot = me.vf;
+            if (!me.single) nx = ntiles;                                        // (its run ends inside this tile)
+        } else {
+            if (me.single) continue;
+            key = me.kl; tot = me.vl;
+        }
+        for (; nx < ntiles; ++nx) {
+            const K25Car<V> o = r[nx];
+            if (o.kf != key) break;
+            tot = V::add(tot, o.vf);
+            if (!o.single) break;
+        }
+        const long long g = (long long)key - b0;
+        if (g >= 0 && g < nb) V::store(out, (size_t)ph * (size_t)nb + (size_t)g, tot);
+    }
+}
+
+// tby / tbx / tcnt[i] = by / bx / cnt of cell order[i]
+__global__ void __launch_bounds__(TPB)
+k25_keys(const int* __restrict__ bx, const int* __restrict__ by, int n, int b0, int bits, u64* __restrict__ key, u32* __restrict__ val)
+{
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    key[i] = ((u64)(u32)(by[i] - b0) << bits) | (u64)(u32)(bx[i] - b0);         // b0 <= bx <= by
+    val[i] = (u32)i;
+}
+
+__global__ void __launch_bounds__(TPB)
+k25_gather(const u32* __restrict__ order, const int* __restrict__ bx, const int* __restrict__ by, const u32* __restrict__ cnt, int n,
+           int* __restrict__ tbx, int* __restrict__ tby, u32* __restrict__ tcnt)
+{
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const u32 j = order[i];
+    if (j >= (u32)n) return;
+    tbx[i] = bx[j]; tby[i] = by[j]; tcnt[i] = cnt[j];
+}
+
+// sum / nnz = row part + column part
+__global__ void __launch_bounds__(TPB)
+k25_join(const u64* __restrict__ ps, const u32* __restrict__ pn, int nb, u64* __restrict__ sum, u32* __restrict__ nnz)
+{
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= nb) return;
+    sum[i] = ps[i] + ps[(size_t)nb + i];
+    nnz[i] = pn[i] + pn[(size_t)nb + i];
+}
+
+__global__ void __launch_bounds__(TPB)
+k25_init(const u32* __restrict__ valid, int nb, double* __restrict__ w, double* __restrict__ parts2, K25Rec* __restrict__ rec, double nan)
+{
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i == 0) { rec->iters = 0; rec->converged = 0; rec->stop = 0; rec->pad = 0; rec->var = nan; rec->scale = nan; }
+    if (i >= nb) return;
+    w[i] = valid[i] ? 1.0 : 0.0;
+    parts2[i] = 0.0; parts2[(size_t)nb + i] = 0.0;
+}
+
+// sum of (a, b) over the workgroup in a fixed tree; the result in thread 0
+__device__ __forceinline__ void k25_wg_sum(double& a, double& b, double* la, double* lb)
+{
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, (unsigned)o); b += __shfl_down(b, (unsigned)o); }
+    if ((threadIdx.x & 63) == 0) { la[threadIdx.x >> 6] = a; lb[threadIdx.x >> 6] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) { a = la[0]; b = lb[0]; for (int q = 1; q < TPB / 64; ++q) { a += la[q]; b += lb[q]; } }
+    __syncthreads();
+}
+
+// the bins of workgroup g: [g per, min((g + 1) per, nb)), per a multiple of TPB; thread t takes them at stride TPB, ascending
+__global__ void __launch_bounds__(TPB)
+k25_stat1(double* __restrict__ parts2, int nb, int per, double* __restrict__ s, double* __restrict__ pcnt, double* __restrict__ psum,
+          const K25Rec* __restrict__ rec)
+{
+    __shared__ double la[TPB / 64], lb[TPB / 64];
+    if (rec->stop) return;
+    const long long lo = (long long)blockIdx.x * per, hi = lo + per < nb ? lo + per : nb;
+    double n = 0.0, t = 0.0;
+    for (long long i = lo + threadIdx.x; i < hi; i += TPB) {
+        const double v = parts2[i] + parts2[(size_t)nb + i];
+        parts2[i] = 0.0; parts2[(size_t)nb + i] = 0.0;
+        s[i] = v;
+        if (v != 0.0) { n += 1.0; t += v; }
+    }
+    k25_wg_sum(n, t, la, lb);
+    if (threadIdx.x == 0) { pcnt[blockIdx.x] = n; psum[blockIdx.x] = t; }
+}
+
+// the partials p[0 .. np) folded in index order by the workgroup: thread t takes p[t], p[t + TPB], ..; then the tree
+__device__ __forceinline__ void k25_fold_parts(const double* __restrict__ pa, const double* __restrict__ pb, int np, double& a, double& b,
+                                               double* la, double* lb)
+{
+    a = 0.0; b = 0.0;
+    for (int q = threadIdx.x; q < np; q += TPB) { a += pa[q]; b += pb[q]; }
+    k25_wg_sum(a, b, la, lb);
+}
+
+__global__ void __launch_bounds__(TPB)
+k25_stat2(const double* __restrict__ s, int nb, int per, int np, const double* __restrict__ pcnt, const double* __restrict__ psum,
+          double* __restrict__ w, double* __restrict__ pvar, const K25Rec* __restrict__ rec)
+{
+    __shared__ double la[TPB / 64], lb[TPB / 64];
+    __shared__ double l_mean;
+    if (rec->stop) return;
+    double n, t;
+    k25_fold_parts(pcnt, psum, np, n, t, la, lb);
+    if (threadIdx.x == 0) l_mean = n > 0.0 ? t / n : 0.0;
+    __syncthreads();
+    const double mean = l_mean;
+    double dv = 0.0, unused = 0.0;
+    if (mean != 0.0) {                                                          // (n == 0: no bin to update; k25_stat3 ends the loop)
+        const long long lo = (long long)blockIdx.x * per, hi = lo + per < nb ? lo + per : nb;
+        for (long long i = lo + threadIdx.x; i < hi; i += TPB) {
+            const double v = s[i];
+            if (v == 0.0) continue;
+            const double q = v / mean;
+            w[i] = w[i] / q;
+            dv += (q - 1.0) * (q - 1.0);
+        }
+    }
+    k25_wg_sum(dv, unused, la, lb);
+    if (threadIdx.x == 0) pvar[blockIdx.x] = dv;
+}
+
+__global__ void __launch_bounds__(TPB)
+k25_stat3(int np, const double* __restrict__ pcnt, const double* __restrict__ psum, const double* __restrict__ pvar, double tol,
+          K25Rec* __restrict__ rec)
+{
+    __shared__ double la[TPB / 64], lb[TPB / 64];
+    if (rec->stop) return;
+    double n, t, dv, unused;
+    k25_fold_parts(pcnt, psum, np, n, t, la, lb);
+    k25_fold_parts(pvar, pvar, np, dv, unused, la, lb);
+    if (threadIdx.x != 0) return;
+    if (!(n > 0.0)) { rec->stop = 1; return; }                                  // no s differs from zero: the record stays as k25_init left it
+    const double var = dv / n;
+    rec->iters += 1;
+    rec->var = var;
+    rec->scale = t / n;
+    if (var < tol) { rec->converged = 1; rec->stop = 1; }
+}
+
+// weight[i] = w[i] / root where w[i] > 0 (root = sqrt(scale), taken on the host), NaN elsewhere
+__global__ void __launch_bounds__(TPB)
+k25_weights(const double* __restrict__ w, int nb, double root, double nan, double* __restrict__ weight)
+{
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= nb) return;
+    const double v = w[i];
+    weight[i] = v > 0.0 ? v / root : nan;
+}
+
+__global__ void __launch_bounds__(TPB)
+k25_cells(const int* __restrict__ bx, const int* __restrict__ by, const u32* __restrict__ cnt, long long first, long long count, long long n,
+          int b0, int nb, const double* __restrict__ weight, double nan, double* __restrict__ out)
+{
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= count || first + i >= n) return;
+    const long long ix = (long long)bx[first + i] - b0, iy = (long long)by[first + i] - b0;
+    out[i] = (ix < 0 || ix >= nb || iy < 0 || iy >= nb) ? nan : ((double)cnt[first + i] * weight[ix]) * weight[iy];
+}
+
+// ---- K25 host side ------------------------------------------------------------------------------
+void bal_release(cl_chrom* c)
+{
+    for (DevBuf* b : {&c->bl_kin, &c->bl_kout, &c->bl_vin, &c->bl_vout, &c->bl_tmp, &c->bl_tby, &c->bl_tbx, &c->bl_tcnt, &c->bl_sum, &c->bl_nnz,
+                      &c->bl_valid, &c->bl_w, &c->bl_s, &c->bl_icar, &c->bl_dcar, &c->bl_part, &c->bl_rec, &c->bl_out}) b->release();
+    c->bl = cl_chrom::BalState();
+}
+
+static long long k25_floordiv(long long p, long long res)
+{
+    const long long q = p / res;
+    return q - ((p - q * res) < 0 ? 1 : 0);
+}
+
+static K25In k25_input(cl_chrom* c, const cl_chrom::BalState& st)
+{
+    K25In in{};
+    in.key[0] = c->mx_bx.as<int>(); in.oth[0] = c->mx_by.as<int>(); in.cnt[0] = c->mx_cnt.as<u32>();
+    in.key[1] = c->bl_tby.as<int>(); in.oth[1] = c->bl_tbx.as<int>(); in.cnt[1] = c->bl_tcnt.as<u32>();
+    in.n = (int)st.n_cells; in.ign = st.ignore_diags; in.b0 = (int)st.b0; in.nb = (int)st.nb;
+    in.w = nullptr;
+    in.vec = 1;
+    for (int ph = 0; ph < 2; ++ph)
+        for (const void* p : {(const void*)in.key[ph], (const void*)in.oth[ph], (const void*)in.cnt[ph]}) if ((uintptr_t)p % 16) in.vec = 0;
+    return in;
+}
+
+// workgroups of k25_stat1 / k25_stat2 over nb bins and the bins of each (a multiple of TPB)
+static void k25_parts(long long nb, int& np, int& per)
+{
+    long long p = (nb + K25_PARTS - 1) / K25_PARTS;
+    p = (p + TPB - 1) / TPB * TPB;
+    per = (int)std::max<long long>(p, TPB);
+    np = (int)std::max<long long>((nb + per - 1) / per, 1);
+}
+
+static int bal_marginals(cl_chrom* c, cl_chrom::BalState& st)
+{
+    const int n = (int)st.n_cells;
+    const size_t sn = (size_t)n;
+    int rc;
+    int hb0 = 0;
+    HIP_TRY(hipMemcpyAsync(&hb0, c->mx_bx.as<int>(), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // the bins of all rows of the handle bound those of the cells (as in cl_mat_cells): by - b0 fits the key's bits
+    const long long bmax = k25_floordiv(std::max(c->st.xmax, c->st.ymax), c->mx.res);
+    if (bmax < hb0 || bmax - hb0 >= (1ll << 30)) return fail(CL_ERR_HIP, "cl_bal_marginals: the cells' bins are not ones this handle can have");
+    const int bits = std::max(1, bits_for((unsigned)(bmax - hb0)));
+    if ((rc = c->bl_kin.ensure(sn * 8)) || (rc = c->bl_kout.ensure(sn * 8)) || (rc = c->bl_vin.ensure(sn * 4)) || (rc = c->bl_vout.ensure(sn * 4)) ||
+        (rc = c->bl_tby.ensure(sn * 4)) || (rc = c->bl_tbx.ensure(sn * 4)) || (rc = c->bl_tcnt.ensure(sn * 4)) || (rc = c->bl_rec.ensure(64))) return rc;
+    LAUNCH(k25_keys, n, c->mx_bx.as<int>(), c->mx_by.as<int>(), n, hb0, bits, c->bl_kin.as<u64>(), c->bl_vin.as<u32>());
+    HIP_TRY(hipGetLastError());
+    size_t bytes = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (u32*)nullptr, (u32*)nullptr, sn, 0, 2 * bits, c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs size query (balance)", hipGetErrorString(e));
+    if ((rc = c->bl_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
+    bytes = c->bl_tmp.bytes;
+    e = rocprim::radix_sort_pairs(c->bl_tmp.p, bytes, c->bl_kin.as<u64>(), c->bl_kout.as<u64>(), c->bl_vin.as<u32>(), c->bl_vout.as<u32>(), sn, 0, 2 * bits,
+                                  c->stream);
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs(balance)", hipGetErrorString(e));
+    LAUNCH(k25_gather, n, c->bl_vout.as<u32>(), c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), n, c->bl_tbx.as<int>(),
+           c->bl_tby.as<int>(), c->bl_tcnt.as<u32>());
+    HIP_TRY(hipGetLastError());
+    int hb1 = 0;
+    HIP_TRY(hipMemcpyAsync(&hb1, c->bl_tby.as<int>() + (sn - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hb1 < hb0 || (long long)hb1 > bmax) return fail(CL_ERR_HIP, "cl_bal_marginals: the transposed order ends with a bin no cell can have");
+    st.b0 = hb0; st.nb = (long long)hb1 - hb0 + 1;
+    if (st.nb > CL_BAL_BINS_MAX) return fail(CL_ERR_ARG, "cl_bal_marginals: more than CL_BAL_BINS_MAX bins (use a coarser res)");
+    const size_t snb = (size_t)st.nb;
+    const int ntiles = (int)((sn + K25_TILE - 1) / K25_TILE);
+    // bl_out serves as the two integer parts here (sum: 2 nb u64, then nnz: 2 nb u32); later as the balanced values of a get
+    if ((rc = c->bl_out.ensure(snb * 24)) || (rc = c->bl_sum.ensure(snb * 8)) || (rc = c->bl_nnz.ensure(snb * 4)) ||
+        (rc = c->bl_icar.ensure((size_t)ntiles * 2 * sizeof(K25Car<K25I>)))) return rc;
+    HIP_TRY(hipMemsetAsync(c->bl_out.p, 0, snb * 24, c->stream));
+    HIP_TRY(hipMemsetAsync(c->bl_rec.p, 0, 64, c->stream));
+    u64* d_used = c->bl_rec.as<u64>() + 4;                                      // (behind the loop's record)
+    K25I::Out out{c->bl_out.as<u64>(), (u32*)(c->bl_out.as<u64>() + 2 * snb)};
+    const K25In in = k25_input(c, st);
+    hipLaunchKernelGGL(k25_marg<K25I>, dim3((unsigned)ntiles, 2u), dim3(TPB), 0, c->stream, in, out, c->bl_icar.as<K25Car<K25I>>(), ntiles, d_used,
+                       (const K25Rec*)nullptr);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k25_fold<K25I>, dim3((unsigned)nblocks(ntiles), 2u), dim3(TPB), 0, c->stream, (const K25Car<K25I>*)c->bl_icar.as<K25Car<K25I>>(),
+                       ntiles, in.b0, in.nb, out, (const K25Rec*)nullptr);
+    HIP_TRY(hipGetLastError());
+    LAUNCH(k25_join, st.nb, (const u64*)out.s, (const u32*)out.n, in.nb, c->bl_sum.as<u64>(), c->bl_nnz.as<u32>());
+    HIP_TRY(hipGetLastError());
+    u64 hu = 0;
+    HIP_TRY(hipMemcpyAsync(&hu, d_used, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    st.n_used = (long long)hu;
+    return CL_OK;
+}
+
+// the checks every K25 call shares; -> CL_OK with c usable
+static int bal_enter(cl_chrom* c, const char* who, bool need_marginals)
+{
+    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
+    if (c->enq != c->deq) return fail(CL_ERR_ARG, who, "asynchronous runs still in flight");
+    if (!c->mx.ready) return fail(CL_ERR_ARG, who, "no cells on this handle (cl_mat_cells)");
+    if (!c->mx.fold) return fail(CL_ERR_ARG, who, "the cells are not folded (cl_mat_cells with fold = 1)");
+    if (need_marginals && !c->bl.ready) return fail(CL_ERR_ARG, who, "no marginals on this handle (cl_bal_marginals)");
+    return CL_OK;
+}
+
+extern "C" int cl_bal_marginals(cl_chrom* c, int32_t ignore_diags, int64_t* b0, int64_t* nb, int64_t* n_used)
+{
+    if (b0) *b0 = 0;
+    if (nb) *nb = 0;
+    if (n_used) *n_used = 0;
+    int rc = bal_enter(c, "cl_bal_marginals", false);
+    if (rc != CL_OK) return rc;
+    if (!b0 || !nb || !n_used) return fail(CL_ERR_ARG, "cl_bal_marginals: bad arguments");
+    if (ignore_diags < 0) return fail(CL_ERR_ARG, "cl_bal_marginals: ignore_diags below 0");
+    cl_chrom::BalState st;
+    st.ready = true;
+    st.ignore_diags = ignore_diags;
+    st.n_cells = c->mx.n_cells;
+    if (st.n_cells == 0) { bal_release(c); c->bl = st; return CL_OK; }          // (no rows, or a cut that keeps none: no HIP call)
+    HIP_TRY(hipSetDevice(c->device));
+    c->bl.ready = false; c->bl.iterated = false;                                // (the earlier state's buffers are written from here on)
+    rc = bal_marginals(c, st);
+    if (rc != CL_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        bal_release(c);
+        return rc;
+    }
+    c->bl = st;
+    *b0 = st.b0; *nb = st.nb; *n_used = st.n_used;
+    return CL_OK;
+}
+
+extern "C" int cl_bal_marginals_get(cl_chrom* c, int64_t first, int64_t count, uint64_t* sum, uint32_t* nnz)
+{
+    int rc = bal_enter(c, "cl_bal_marginals_get", true);
+    if (rc != CL_OK) return rc;
+    if (first < 0 || count < 0 || first > c->bl.nb || count > c->bl.nb - first) return fail(CL_ERR_ARG, "cl_bal_marginals_get: range outside the bins");
+    if (count > 0 && (!sum || !nnz)) return fail(CL_ERR_ARG, "cl_bal_marginals_get: bad arguments");
+    if (count == 0) return CL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipError_t e = hipMemcpyAsync(sum, c->bl_sum.as<u64>() + first, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(nnz, c->bl_nnz.as<u32>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_marginals_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
+    return CL_OK;
+}
+
+static int bal_iterate(cl_chrom* c, const uint32_t* valid, int max_iters, double tol, K25Rec& h)
+{
+    const cl_chrom::BalState& st = c->bl;
+    const size_t snb = (size_t)st.nb;
+    const int ntiles = (int)(((size_t)st.n_cells + K25_TILE - 1) / K25_TILE);
+    int np, per, rc;
+    k25_parts(st.nb, np, per);
+    // bl_w: w, then the weights; bl_s: the two parts of s, then s; bl_part: count, sum and var partials
+    if ((rc = c->bl_valid.ensure(snb * 4)) || (rc = c->bl_w.ensure(snb * 16)) || (rc = c->bl_s.ensure(snb * 24)) ||
+        (rc = c->bl_part.ensure((size_t)np * 24)) || (rc = c->bl_dcar.ensure((size_t)ntiles * 2 * sizeof(K25Car<K25D>))) ||
+        (rc = c->bl_rec.ensure(64))) return rc;
+    const double nan = std::nan("");
+    double *w = c->bl_w.as<double>(), *weight = w + snb, *parts2 = c->bl_s.as<double>(), *s = parts2 + 2 * snb;
+    double *pcnt = c->bl_part.as<double>(), *psum = pcnt + np, *pvar = psum + np;
+    K25Rec* rec = c->bl_rec.as<K25Rec>();
+    HIP_TRY(hipMemcpyAsync(c->bl_valid.p, valid, snb * 4, hipMemcpyHostToDevice, c->stream));
+    LAUNCH(k25_init, st.nb, (const u32*)c->bl_valid.as<u32>(), (int)st.nb, w, parts2, rec, nan);
+    HIP_TRY(hipGetLastError());
+    K25In in = k25_input(c, st);
+    in.w = w;
+    K25D::Out out{parts2};
+    K25Car<K25D>* car = c->bl_dcar.as<K25Car<K25D>>();
+    h = K25Rec{0, 0, 0, 0, nan, nan};
+    for (int done = 0; done < max_iters && !h.stop;) {
+        const int blk = std::min(K25_BLOCK, max_iters - done);
+        for (int k = 0; k < blk; ++k) {
+            hipLaunchKernelGGL(k25_marg<K25D>, dim3((unsigned)ntiles, 2u), dim3(TPB), 0, c->stream, in, out, car, ntiles, (u64*)nullptr, (const K25Rec*)rec);
+            hipLaunchKernelGGL(k25_fold<K25D>, dim3((unsigned)nblocks(ntiles), 2u), dim3(TPB), 0, c->stream, (const K25Car<K25D>*)car, ntiles, in.b0, in.nb,
+                               out, (const K25Rec*)rec);
+            hipLaunchKernelGGL(k25_stat1, dim3((unsigned)np), dim3(TPB), 0, c->stream, parts2, in.nb, per, s, pcnt, psum, (const K25Rec*)rec);
+            hipLaunchKernelGGL(k25_stat2, dim3((unsigned)np), dim3(TPB), 0, c->stream, (const double*)s, in.nb, per, np, (const double*)pcnt,
+                               (const double*)psum, w, pvar, (const K25Rec*)rec);
+            hipLaunchKernelGGL(k25_stat3, dim3(1), dim3(TPB), 0, c->stream, np, (const double*)pcnt, (const double*)psum, (const double*)pvar, tol, rec);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(&h, rec, sizeof(K25Rec), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        done += blk;
+        if (h.iters < 0 || h.iters > done) return fail(CL_ERR_HIP, "cl_bal_iterate: the record holds a count no loop can have");
+    }
+    const double root = std::sqrt(h.scale);                                     // (NaN when nothing was iterated: every weight NaN)
+    LAUNCH(k25_weights, st.nb, (const double*)w, (int)st.nb, root, nan, weight);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CL_OK;
+}
+
+extern "C" int cl_bal_iterate(cl_chrom* c, const uint32_t* valid, int32_t max_iters, double tol, int32_t* iters, int32_t* converged,
+                              double* var, double* scale)
+{
+    const double nan = std::nan("");
+    if (iters) *iters = 0;
+    if (converged) *converged = 0;
+    if (var) *var = nan;
+    if (scale) *scale = nan;
+    int rc = bal_enter(c, "cl_bal_iterate", true);
+    if (rc != CL_OK) return rc;
+    if (!iters || !converged || !var || !scale) return fail(CL_ERR_ARG, "cl_bal_iterate: bad arguments");
+    if (max_iters < 0) return fail(CL_ERR_ARG, "cl_bal_iterate: max_iters below 0");
+    if (!(tol >= 0.0)) return fail(CL_ERR_ARG, "cl_bal_iterate: tol below 0 or not a number");
+    if (c->bl.nb > 0 && !valid) return fail(CL_ERR_ARG, "cl_bal_iterate: no mask");
+    if (c->bl.nb == 0) { c->bl.iterated = true; return CL_OK; }
+    HIP_TRY(hipSetDevice(c->device));
+    c->bl.iterated = false;
+    K25Rec h{};
+    rc = bal_iterate(c, valid, max_iters, tol, h);
+    if (rc != CL_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    c->bl.iterated = true;
+    *iters = h.iters; *converged = h.converged; *var = h.var; *scale = h.scale;
+    return CL_OK;
+}
+
+extern "C" int cl_bal_weights_get(cl_chrom* c, int64_t first, int64_t count, double* weight)
+{
+    int rc = bal_enter(c, "cl_bal_weights_get", true);
+    if (rc != CL_OK) return rc;
+    if (!c->bl.iterated) return fail(CL_ERR_ARG, "cl_bal_weights_get: no weights on this handle (cl_bal_iterate)");
+    if (first < 0 || count < 0 || first > c->bl.nb || count > c->bl.nb - first) return fail(CL_ERR_ARG, "cl_bal_weights_get: range outside the bins");
+    if (count > 0 && !weight) return fail(CL_ERR_ARG, "cl_bal_weights_get: bad arguments");
+    if (count == 0) return CL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const hipError_t e = hipMemcpyAsync(weight, c->bl_w.as<double>() + (size_t)c->bl.nb + first, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_weights_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
+    return CL_OK;
+}
+
+extern "C" int cl_bal_cells_get(cl_chrom* c, int64_t first, int64_t count, double* balanced)
+{
+    int rc = bal_enter(c, "cl_bal_cells_get", true);
+    if (rc != CL_OK) return rc;
+    if (!c->bl.iterated) return fail(CL_ERR_ARG, "cl_bal_cells_get: no weights on this handle (cl_bal_iterate)");
+    if (first < 0 || count < 0 || first > c->bl.n_cells || count > c->bl.n_cells - first) return fail(CL_ERR_ARG, "cl_bal_cells_get: range outside the cells");
+    if (count > 0 && !balanced) return fail(CL_ERR_ARG, "cl_bal_cells_get: bad arguments");
+    if (count == 0) return CL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->bl_out.ensure((size_t)count * 8))) return rc;
+    LAUNCH(k25_cells, count, c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), (long long)first, (long long)count, c->bl.n_cells,
+           (int)c->bl.b0, (int)c->bl.nb, (const double*)(c->bl_w.as<double>() + (size_t)c->bl.nb), std::nan(""), c->bl_out.as<double>());
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(balanced, c->bl_out.p, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_cells_get", hipGetErrorString(e != hipSuccess ? e : e2));
+    return CL_OK;
+}
+
+extern "C" int cl_bal_free(cl_chrom* c)
+{
+    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
+    if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_bal_free: asynchronous runs still in flight");
+    if (c->n > 0) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    bal_release(c);
+    return CL_OK;
+}

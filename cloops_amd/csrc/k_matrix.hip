@@ -265,6 +265,7 @@ static void mat_release(cl_chrom* c)
     for (DevBuf* b : {&c->mx_out, &c->mx_ctr, &c->mx_key, &c->mx_sorted, &c->mx_tmp, &c->mx_flag, &c->mx_scan, &c->mx_start,
                       &c->mx_bx, &c->mx_by, &c->mx_cnt}) b->release();
     c->mx = cl_chrom::MatState();
+    bal_release(c);                                                             // (K25's weights belong to these cells)
 }
 
 // mx_ctr: four ints (table ranges), then two 64-bit counters; zeroed
@@ -447,8 +448,10 @@ extern "C" int cl_mat_cells(cl_chrom* c, int64_t cut, int64_t res, int32_t fold,
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_mat_cells: asynchronous runs still in flight");
     cl_chrom::MatState st;
     st.ready = true;
-    if (c->n == 0) { c->mx = st; return CL_OK; }
+    st.res = (int)res; st.fold = fold != 0;
+    if (c->n == 0) { bal_release(c); c->mx = st; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
+    bal_release(c);                                                             // (K25's state belongs to the earlier cells; every K25 call ends synchronised)
     int rc = agg_table(c, k24_cut(cut));
     if (rc == CL_OK) {
         st.n_kept = c->ag_kept;

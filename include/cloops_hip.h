@@ -555,6 +555,46 @@ int cl_mat_v4c(cl_chrom* c, int64_t cut, int64_t res, int64_t v0, int64_t v1, in
 int cl_mat_free(cl_chrom* c);
 
 /*
+ * Matrix balancing (K25): iterative correction (ICE, Imakaev 2012) of the folded cells of the last cl_mat_cells -- one weight per bin
+ * so that every valid row of the weighted matrix has the same sum.  The reference has no counterpart, so these definitions are the
+ * specification (tests/balance_cases.py restates them in numpy); the mask's rule, the texts and the files stay on the host
+ * (cloops_amd/balance.py).
+ *
+ * Input: the cells (bx, by, cnt) of cl_mat_cells(c, cut, res, fold = 1), bx <= by, ascending.  They stand for the symmetric matrix A with
+ * A[i][j] = A[j][i] = cnt; a diagonal cell counts once.  Bins: b0 = bx of the first cell .. b1 = the largest by, nb = b1 - b0 + 1.  A
+ * cell is used iff by - bx >= ignore_diags (0 uses every cell).
+ * Raw marginals (exact integers): sum[i] = the sum of cnt over the used cells that touch bin b0 + i (an off-diagonal cell touches both
+ * of its bins, a diagonal cell its bin once), nnz[i] = the number of such cells.  *n_used = the number of used cells.
+ * Iteration (fp64): w[i] = 1 where valid[i] != 0, else 0.  Up to max_iters times: (1) s[i] = the sum over the used cells that touch i
+ * of (w[bx] cnt) w[by]; (2) over the bins with s[i] != 0: mean = their mean, var = the mean of (s[i] / mean - 1)^2; (3) w[i] /=
+ * s[i] / mean on those bins; (4) the iteration counts, and the loop stops as converged if var < tol.  No s[i] != 0 at all: 0
+ * iterations, not converged, var = scale = NaN (also with max_iters = 0 or nb = 0).
+ * Result: scale = the last mean; weight[i] = w[i] / sqrt(scale) where w[i] > 0, NaN elsewhere; the balanced value of a cell -- of
+ * EVERY cell, also those nearer the diagonal than ignore_diags -- is ((double)cnt weight[bx]) weight[by], NaN where a weight is NaN.
+ *
+ * cl_bal_marginals -- builds the transposed order of the cells (sorted by (by, bx): both halves of a marginal are then sums over runs
+ * of sorted keys) and the raw marginals -> *b0, *nb, *n_used.  nb <= CL_BAL_BINS_MAX.
+ * cl_bal_marginals_get -- sum / nnz of the bins [first, first + count) inside [0, nb].
+ * cl_bal_iterate -- valid: nb words (may be NULL when nb is 0).  May be called again with another mask, max_iters or tol without
+ * another cl_bal_marginals.  Sums are taken in a fixed order: two calls with the same input give the same bytes.
+ * cl_bal_weights_get, cl_bal_cells_get -- the weights of the bins / the balanced values of the cells [first, first + count) of the
+ * last cl_bal_iterate.
+ * cl_bal_free -- releases the state (the cells stay).  The next cl_mat_cells, cl_mat_free and cl_chrom_destroy release it as well.
+ *
+ * A handle with no rows or no cells: nb = 0 and CL_OK everywhere.  Errors: CL_ERR_ARG for a NULL handle or NULL outputs, no cells on
+ * the handle or cells that are not folded, ignore_diags < 0, nb > CL_BAL_BINS_MAX, max_iters < 0, tol < 0 or NaN, cl_bal_iterate or a
+ * get before cl_bal_marginals, weights or balanced values before cl_bal_iterate, a range outside the bins or cells, or runs in flight.
+ */
+#define CL_BAL_BINS_MAX 16777216
+int cl_bal_marginals(cl_chrom* c, int32_t ignore_diags, int64_t* b0, int64_t* nb, int64_t* n_used);
+int cl_bal_marginals_get(cl_chrom* c, int64_t first, int64_t count, uint64_t* sum, uint32_t* nnz);
+int cl_bal_iterate(cl_chrom* c, const uint32_t* valid, int32_t max_iters, double tol, int32_t* iters, int32_t* converged, double* var,
+                   double* scale);
+int cl_bal_weights_get(cl_chrom* c, int64_t first, int64_t count, double* weight);
+int cl_bal_cells_get(cl_chrom* c, int64_t first, int64_t count, double* balanced);
+int cl_bal_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
