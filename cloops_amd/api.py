@@ -27,6 +27,10 @@ def device_count():
     return _lib.load().cl_device_count()
 
 
+def _vp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
 def _as_i32(a, name):
     a = np.asarray(a)
     if a.ndim != 1:
@@ -509,6 +513,87 @@ class Chromosome(_Handle):
                                           ctypes.byref(nkept)))
         return S, stats, mats, int(nkept.value)
 
+    # ---- text that the device writes (K14 tracks, K20 coverage): chunk bounds, one chunk, all chunks double-buffered ----
+    def _text_chunks(self, entry, attr, budget):
+        """`entry`: cl_track_chunks / cl_cov_chunks -> (line bounds, byte bounds), also kept as self.<attr> for _text_render"""
+        nc = ctypes.c_int64(0)
+        _lib.check(entry(self._h, int(budget), 0, None, None, ctypes.byref(nc)))
+        rec = np.zeros(nc.value + 1, dtype=np.int64)
+        byt = np.zeros(nc.value + 1, dtype=np.int64)
+        _lib.check(entry(self._h, int(budget), len(rec), _vp(rec), _vp(byt), ctypes.byref(nc)))
+        setattr(self, attr, (rec, byt))
+        return rec, byt
+
+    def _text_render(self, entry, bounds, chunk, out):
+        """`entry`: cl_track_render / cl_cov_render; bounds: what _text_chunks kept -> bytes, or with `out` their number"""
+        nb = ctypes.c_int64(0)
+        if out is None:
+            rec, byt = bounds
+            cap = max(1, int(byt[chunk + 1] - byt[chunk])) if 0 <= chunk < len(rec) - 1 else 1     # (the library reports the index)
+            buf = np.empty(cap, dtype=np.uint8)
+            _lib.check(entry(self._h, int(chunk), _vp(buf), len(buf), ctypes.byref(nb)))
+            return buf[:nb.value].tobytes()
+        if isinstance(out, tuple):
+            ptr, cap = out
+        else:
+            a = np.frombuffer(out, dtype=np.uint8)
+            ptr, cap = a.ctypes.data, len(a)
+        _lib.check(entry(self._h, int(chunk), ctypes.c_void_p(ptr), int(cap), ctypes.byref(nb)))
+        return int(nb.value)
+
+    def _text_iter(self, render, chunks, budget):
+        """the chunks of `chunks(budget)` in order, as memoryviews of two page-locked buffers: chunk k + 1 is rendered and copied to
+        the host by `render` (on a helper thread; the library call releases the GIL) while the caller consumes chunk k"""
+        rec, byt = chunks(budget)
+        K = len(rec) - 1
+        if K == 0:
+            return
+        size = int(np.max(np.diff(byt)))
+        bufs = []
+        pool = None
+        fut = None
+        try:
+            for _ in range(2):
+                bufs.append(_lib.host_alloc(size))
+            from concurrent.futures import ThreadPoolExecutor
+            pool = ThreadPoolExecutor(1)
+            fut = pool.submit(render, 0, (bufs[0], size))
+            for k in range(K):
+                nb = fut.result()
+                fut = pool.submit(render, k + 1, (bufs[(k + 1) & 1], size)) if k + 1 < K else None
+                yield memoryview((ctypes.c_char * nb).from_address(bufs[k & 1])).cast("B")
+        finally:                                   # (also when the caller abandons the generator: no render may outlive its buffer)
+            if fut is not None:
+                try:
+                    fut.result()
+                except Exception:
+                    pass
+            if pool is not None:
+                pool.shutdown()
+            for p in bufs:
+                self._lib.cl_host_free(ctypes.c_void_p(p))
+
+    # ---- ranged read-back (the *_get methods) and interval arguments ----
+    def _range(self, size_attr, first, count):
+        """-> (first, count, entries to allocate): count None = all from `first` on of the self.<size_attr> results on the device"""
+        first = int(first)
+        count = max(0, getattr(self, size_attr, 0) - first) if count is None else int(count)
+        return first, count, max(0, count)
+
+    def _get(self, entry, size_attr, first, count, dtypes, *lead):
+        """`entry(handle, *lead, first, count, one array per dtype)` -> those arrays"""
+        first, count, n = self._range(size_attr, first, count)
+        out = tuple(np.zeros(n, dtype=t) for t in dtypes)
+        _lib.check(entry(self._h, *lead, first, count, *[_vp(a) for a in out]))
+        return out
+
+    @staticmethod
+    def _intervals(starts, ends, who):
+        s, e = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
+        if s.ndim != 1 or s.shape != e.shape:
+            raise ValueError("%s: starts and ends must be one-dimensional and of equal length" % who)
+        return s, e
+
     TRACK_KINDS = {"washu": _lib.CL_TRACK_WASHU, "juice": _lib.CL_TRACK_JUICE}
     TRACK_NAME_MAX = _lib.CL_TRACK_NAME_MAX
     TRACK_BUDGET = 64 << 20                        # default bytes per rendered chunk
@@ -534,36 +619,12 @@ class Chromosome(_Handle):
     def track_chunks(self, budget=TRACK_BUDGET):
         """the built track split into chunks of at most `budget` bytes, none splitting a line -> (record bounds, byte bounds), int64
         [chunks + 1]: chunk k is records rec[k] .. rec[k + 1] - 1, bytes byt[k] .. byt[k + 1] - 1 of the text  (cl_track_chunks)"""
-        nc = ctypes.c_int64(0)
-        _lib.check(self._lib.cl_track_chunks(self._h, int(budget), 0, None, None, ctypes.byref(nc)))
-        rec = np.zeros(nc.value + 1, dtype=np.int64)
-        byt = np.zeros(nc.value + 1, dtype=np.int64)
-        _lib.check(self._lib.cl_track_chunks(self._h, int(budget), len(rec), rec.ctypes.data_as(ctypes.c_void_p),
-                                             byt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nc)))
-        self._track_bounds = (rec, byt)
-        return rec, byt
+        return self._text_chunks(self._lib.cl_track_chunks, "_track_bounds", budget)
 
     def track_render(self, chunk, out=None):
         """the text of chunk `chunk` of the last track_chunks -> bytes; with `out` (a writable buffer: bytearray, numpy uint8, or
         a (pointer, capacity) pair of page-locked memory) it is written there and its length returned  (cl_track_render)"""
-        nb = ctypes.c_int64(0)
-        if out is None:
-            buf = np.empty(self._track_cap(chunk), dtype=np.uint8)
-            _lib.check(self._lib.cl_track_render(self._h, int(chunk), buf.ctypes.data_as(ctypes.c_void_p), len(buf), ctypes.byref(nb)))
-            return buf[:nb.value].tobytes()
-        if isinstance(out, tuple):
-            ptr, cap = out
-        else:
-            a = np.frombuffer(out, dtype=np.uint8)
-            ptr, cap = a.ctypes.data, len(a)
-        _lib.check(self._lib.cl_track_render(self._h, int(chunk), ctypes.c_void_p(ptr), int(cap), ctypes.byref(nb)))
-        return int(nb.value)
-
-    def _track_cap(self, chunk):
-        rec, byt = getattr(self, "_track_bounds", ([0], [0]))
-        if not 0 <= chunk < len(rec) - 1:
-            return 1                               # the library reports the index
-        return max(1, int(byt[chunk + 1] - byt[chunk]))
+        return self._text_render(self._lib.cl_track_render, getattr(self, "_track_bounds", ([0], [0])), chunk, out)
 
     def track_free(self):
         """releases the device scratch of track_build  (cl_track_free)"""
@@ -573,34 +634,7 @@ class Chromosome(_Handle):
         """the chunks of the built track in order, as memoryviews of two page-locked buffers: chunk k + 1 is rendered and copied
         to the host (by a helper thread; the library call releases the GIL) while the caller consumes chunk k.  A view is valid
         until the next one is requested."""
-        rec, byt = self.track_chunks(budget)
-        K = len(rec) - 1
-        if K == 0:
-            return
-        size = int(np.max(np.diff(byt)))
-        bufs = []
-        pool = None
-        fut = None
-        try:
-            for _ in range(2):
-                bufs.append(_lib.host_alloc(size))
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(1)
-            fut = pool.submit(self.track_render, 0, (bufs[0], size))
-            for k in range(K):
-                nb = fut.result()
-                fut = pool.submit(self.track_render, k + 1, (bufs[(k + 1) & 1], size)) if k + 1 < K else None
-                yield memoryview((ctypes.c_char * nb).from_address(bufs[k & 1])).cast("B")
-        finally:
-            if fut is not None:
-                try:
-                    fut.result()
-                except Exception:
-                    pass
-            if pool is not None:
-                pool.shutdown()
-            for p in bufs:
-                self._lib.cl_host_free(ctypes.c_void_p(p))
+        return self._text_iter(self.track_render, self.track_chunks, budget)
 
     COVERAGE_SCALE_MAX = 1 << 30                   # largest scale numerator of coverage_text
 
@@ -621,13 +655,7 @@ class Chromosome(_Handle):
     def coverage_runs(self, first=0, count=None):
         """runs [first, first + count) of the built coverage (all from `first` on by default) -> (start int32, end int32, depth
         uint32)  (cl_cov_runs)"""
-        first = int(first)
-        count = max(0, getattr(self, "_cov_runs", 0) - first) if count is None else int(count)
-        n = max(0, count)
-        s, e, d = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint32)
-        _lib.check(self._lib.cl_cov_runs(self._h, first, count, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p),
-                                         d.ctypes.data_as(ctypes.c_void_p)))
-        return s, e, d
+        return self._get(self._lib.cl_cov_runs, "_cov_runs", first, count, (np.int32, np.int32, np.uint32))
 
     def coverage_text(self, name, scale=None):
         """the bedGraph text of the built runs, one line `name\\tstart\\tend\\tvalue\\n` per run, laid out on the device -> its bytes.
@@ -643,32 +671,12 @@ class Chromosome(_Handle):
     def coverage_chunks(self, budget=TRACK_BUDGET):
         """the coverage text split into chunks of at most `budget` bytes, none splitting a line -> (run bounds, byte bounds), int64
         [chunks + 1]  (cl_cov_chunks)"""
-        nc = ctypes.c_int64(0)
-        _lib.check(self._lib.cl_cov_chunks(self._h, int(budget), 0, None, None, ctypes.byref(nc)))
-        run = np.zeros(nc.value + 1, dtype=np.int64)
-        byt = np.zeros(nc.value + 1, dtype=np.int64)
-        _lib.check(self._lib.cl_cov_chunks(self._h, int(budget), len(run), run.ctypes.data_as(ctypes.c_void_p),
-                                           byt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nc)))
-        self._cov_bounds = (run, byt)
-        return run, byt
+        return self._text_chunks(self._lib.cl_cov_chunks, "_cov_bounds", budget)
 
     def coverage_render(self, chunk, out=None):
         """the text of chunk `chunk` of the last coverage_chunks -> bytes; with `out` (a writable buffer or a (pointer, capacity)
         pair of page-locked memory) it is written there and its length returned  (cl_cov_render)"""
-        nb = ctypes.c_int64(0)
-        if out is None:
-            run, byt = getattr(self, "_cov_bounds", ([0], [0]))
-            cap = max(1, int(byt[chunk + 1] - byt[chunk])) if 0 <= chunk < len(run) - 1 else 1     # (the library reports the index)
-            buf = np.empty(cap, dtype=np.uint8)
-            _lib.check(self._lib.cl_cov_render(self._h, int(chunk), buf.ctypes.data_as(ctypes.c_void_p), len(buf), ctypes.byref(nb)))
-            return buf[:nb.value].tobytes()
-        if isinstance(out, tuple):
-            ptr, cap = out
-        else:
-            a = np.frombuffer(out, dtype=np.uint8)
-            ptr, cap = a.ctypes.data, len(a)
-        _lib.check(self._lib.cl_cov_render(self._h, int(chunk), ctypes.c_void_p(ptr), int(cap), ctypes.byref(nb)))
-        return int(nb.value)
+        return self._text_render(self._lib.cl_cov_render, getattr(self, "_cov_bounds", ([0], [0])), chunk, out)
 
     def coverage_free(self):
         """releases the device scratch of coverage_build  (cl_cov_free)"""
@@ -678,34 +686,7 @@ class Chromosome(_Handle):
     def coverage_iter(self, budget=TRACK_BUDGET):
         """the chunks of the coverage text in order, as memoryviews of two page-locked buffers, like track_iter: chunk k + 1 is
         rendered and copied while the caller consumes chunk k.  A view is valid until the next one is requested."""
-        run, byt = self.coverage_chunks(budget)
-        K = len(run) - 1
-        if K == 0:
-            return
-        size = int(np.max(np.diff(byt)))
-        bufs = []
-        pool = None
-        fut = None
-        try:
-            for _ in range(2):
-                bufs.append(_lib.host_alloc(size))
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(1)
-            fut = pool.submit(self.coverage_render, 0, (bufs[0], size))
-            for k in range(K):
-                nb = fut.result()
-                fut = pool.submit(self.coverage_render, k + 1, (bufs[(k + 1) & 1], size)) if k + 1 < K else None
-                yield memoryview((ctypes.c_char * nb).from_address(bufs[k & 1])).cast("B")
-        finally:
-            if fut is not None:
-                try:
-                    fut.result()
-                except Exception:
-                    pass
-            if pool is not None:
-                pool.shutdown()
-            for p in bufs:
-                self._lib.cl_host_free(ctypes.c_void_p(p))
+        return self._text_iter(self.coverage_render, self.coverage_chunks, budget)
 
     def peaks_sort(self, cut=0, ends=3):
         """K21: this chromosome's PET ends sorted once on the device and kept for peaks_call / peaks_count / peaks_summits.  Rows
@@ -729,21 +710,12 @@ class Chromosome(_Handle):
     def peaks_get(self, first=0, count=None):
         """peaks [first, first + count) of the last peaks_call (all from `first` on by default) -> (start int32, end int32, n_points
         uint32, n_cores uint32); [start, end) is half-open  (cl_peak_get)"""
-        first = int(first)
-        count = max(0, getattr(self, "_peaks", 0) - first) if count is None else int(count)
-        n = max(0, count)
-        s, e = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-        p, c = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
-        _lib.check(self._lib.cl_peak_get(self._h, first, count, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p),
-                                         p.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p)))
-        return s, e, p, c
+        return self._get(self._lib.cl_peak_get, "_peaks", first, count, (np.int32, np.int32, np.uint32, np.uint32))
 
     def peaks_count(self, starts, ends):
         """the sorted end points in every half-open interval [starts[k], ends[k]) (int64 bounds; any order, overlapping, empty or
         beyond the end points) -> uint32 counts  (cl_peak_count)"""
-        s, e = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
-        if s.ndim != 1 or s.shape != e.shape:
-            raise ValueError("peaks_count: starts and ends must be one-dimensional and of equal length")
+        s, e = self._intervals(starts, ends, "peaks_count")
         out = np.zeros(len(s), dtype=np.uint32)
         _lib.check(self._lib.cl_peak_count(self._h, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p), len(s),
                                            out.ctypes.data_as(ctypes.c_void_p)))
@@ -753,9 +725,7 @@ class Chromosome(_Handle):
         """the summit of every interval [starts[k], ends[k]) (ascending and disjoint): the position of its end point with the most
         end points within w bp, the smallest on ties, and that number -> (pos int32, -1 for an interval without points; cnt
         uint32)  (cl_peak_summits)"""
-        s, e = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
-        if s.ndim != 1 or s.shape != e.shape:
-            raise ValueError("peaks_summits: starts and ends must be one-dimensional and of equal length")
+        s, e = self._intervals(starts, ends, "peaks_summits")
         pos, cnt = np.zeros(len(s), dtype=np.int32), np.zeros(len(s), dtype=np.uint32)
         _lib.check(self._lib.cl_peak_summits(self._h, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p), len(s), int(w),
                                              pos.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p)))
@@ -779,20 +749,12 @@ class Chromosome(_Handle):
     def domains_get(self, first=0, count=None):
         """entries [first, first + count) of the last domains_tracks (all from `first` on by default) -> (cross, up, down) uint32: the
         rows that cross the boundary inside the window, and those that stay in the window before / behind it  (cl_dom_get)"""
-        first = int(first)
-        count = max(0, getattr(self, "_dom_bins", 0) - first) if count is None else int(count)
-        n = max(0, count)
-        a, b, d = (np.zeros(n, dtype=np.uint32) for _ in range(3))
-        _lib.check(self._lib.cl_dom_get(self._h, first, count, a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p),
-                                        d.ctypes.data_as(ctypes.c_void_p)))
-        return a, b, d
+        return self._get(self._lib.cl_dom_get, "_dom_bins", first, count, (np.uint32, np.uint32, np.uint32))
 
     def domains_count(self, starts, ends):
         """the kept rows of the last domains_tracks in every half-open interval [starts[k], ends[k]) (int64 bounds; ascending and
         disjoint, possibly empty or abutting) -> (intra, nx, ny) uint32: rows with both ends, with X, with Y inside  (cl_dom_count)"""
-        s, e = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
-        if s.ndim != 1 or s.shape != e.shape:
-            raise ValueError("domains_count: starts and ends must be one-dimensional and of equal length")
+        s, e = self._intervals(starts, ends, "domains_count")
         a, b, d = (np.zeros(len(s), dtype=np.uint32) for _ in range(3))
         _lib.check(self._lib.cl_dom_count(self._h, s.ctypes.data_as(ctypes.c_void_p), e.ctypes.data_as(ctypes.c_void_p), len(s),
                                           a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p),
@@ -820,13 +782,7 @@ class Chromosome(_Handle):
     def kdis_get(self, which=0, first=0, count=None):
         """entries [first, first + count) of the last kdis_build for its ks[which], in table order (all from `first` on by default)
         -> (x, y, d) int32: the row's coordinates and its k-distance, -1 where the kept rows have no k-th neighbour  (cl_kdis_get)"""
-        first = int(first)
-        count = max(0, getattr(self, "_kdis_rows", 0) - first) if count is None else int(count)
-        n = max(0, count)
-        x, y, d = (np.zeros(n, dtype=np.int32) for _ in range(3))
-        _lib.check(self._lib.cl_kdis_get(self._h, int(which), first, count, x.ctypes.data_as(ctypes.c_void_p),
-                                         y.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p)))
-        return x, y, d
+        return self._get(self._lib.cl_kdis_get, "_kdis_rows", first, count, (np.int32, np.int32, np.int32), int(which))
 
     def kdis_hist(self, which=0):
         """the histogram of the last kdis_build for its ks[which] -> (hist uint64[CL_KDIS_BINS] over the log bins of ests.logbin for
@@ -866,14 +822,7 @@ class Chromosome(_Handle):
     def mat_cells_get(self, first=0, count=None):
         """cells [first, first + count) of the last mat_cells (all from `first` on by default) -> (bx int32, by int32, cnt uint32)
         (cl_mat_cells_get)"""
-        first = int(first)
-        count = max(0, getattr(self, "_mat_cells", 0) - first) if count is None else int(count)
-        n = max(0, count)
-        bx, by = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-        cnt = np.zeros(n, dtype=np.uint32)
-        _lib.check(self._lib.cl_mat_cells_get(self._h, first, count, bx.ctypes.data_as(ctypes.c_void_p), by.ctypes.data_as(ctypes.c_void_p),
-                                              cnt.ctypes.data_as(ctypes.c_void_p)))
-        return bx, by, cnt
+        return self._get(self._lib.cl_mat_cells_get, "_mat_cells", first, count, (np.int32, np.int32, np.uint32))
 
     def mat_v4c(self, res, v0, v1, b0, nb, cut=0):
         """K24: the virtual-4C profile of the viewpoint [v0, v1) bp over the bins [b0, b0 + nb) of `res` bp: a kept row adds 1 at the bin
@@ -908,12 +857,7 @@ class Chromosome(_Handle):
     def bal_marginals_get(self, first=0, count=None):
         """bins [first, first + count) of the last bal_marginals (all from `first` on by default) -> (sum uint64: the counts of the used
         cells that touch the bin, nnz uint32: their number)  (cl_bal_marginals_get)"""
-        first = int(first)
-        count = max(0, getattr(self, "_bal_bins", 0) - first) if count is None else int(count)
-        n = max(0, count)
-        s, z = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
-        _lib.check(self._lib.cl_bal_marginals_get(self._h, first, count, s.ctypes.data_as(ctypes.c_void_p), z.ctypes.data_as(ctypes.c_void_p)))
-        return s, z
+        return self._get(self._lib.cl_bal_marginals_get, "_bal_bins", first, count, (np.uint64, np.uint32))
 
     def bal_iterate(self, valid, max_iters=200, tol=1e-5):
         """K25: iterative correction over the used cells, from w = 1 on the bins with valid != 0, until the variance of the non-zero
@@ -932,20 +876,12 @@ class Chromosome(_Handle):
     def bal_weights(self, first=0, count=None):
         """the weights of the bins [first, first + count) after the last bal_iterate -> float64, NaN at the bins that are masked or
         got no weight  (cl_bal_weights_get)"""
-        first = int(first)
-        count = max(0, getattr(self, "_bal_bins", 0) - first) if count is None else int(count)
-        w = np.zeros(max(0, count), dtype=np.float64)
-        _lib.check(self._lib.cl_bal_weights_get(self._h, first, count, w.ctypes.data_as(ctypes.c_void_p)))
-        return w
+        return self._get(self._lib.cl_bal_weights_get, "_bal_bins", first, count, (np.float64,))[0]
 
     def bal_cells_get(self, first=0, count=None):
         """the balanced values cnt weight[bx] weight[by] of the cells [first, first + count) of mat_cells, in their order -> float64
         (cl_bal_cells_get)"""
-        first = int(first)
-        count = max(0, getattr(self, "_mat_cells", 0) - first) if count is None else int(count)
-        v = np.zeros(max(0, count), dtype=np.float64)
-        _lib.check(self._lib.cl_bal_cells_get(self._h, first, count, v.ctypes.data_as(ctypes.c_void_p)))
-        return v
+        return self._get(self._lib.cl_bal_cells_get, "_mat_cells", first, count, (np.float64,))[0]
 
     def bal_free(self):
         """releases the marginals, weights and device scratch of the bal_* calls; the cells stay  (cl_bal_free)"""

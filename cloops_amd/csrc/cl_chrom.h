@@ -5,6 +5,8 @@
 #pragma once
 #include "cl_common.h"
 #include "cl_table.h"
+#include "cl_prim.h"
+#include "cl_textout.h"
 
 #define BIGTPB 1024
 #define AGG_H 512
@@ -52,30 +54,6 @@ struct K7Src {
 };
 
 struct K7Part { double sx[2]; double sxx[2]; long long n_all[2]; long long n_pos[2]; };
-
-// ------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------
-struct DevBuf {
-    void* p = nullptr; size_t bytes = 0;
-    bool fresh = false;               // (re)allocated since the flag was last cleared
-    bool owned = true;                // false: a slice of the handle's arena (never freed on its own)
-    int ensure(size_t need)
-    {
-        if (need <= bytes) return CL_OK;
-        fresh = true;
-        if (p && owned) (void)hipFree(p);
-        p = nullptr; bytes = 0; owned = true;
-        size_t want = need + need / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "hipMalloc", hipGetErrorString(e));
-        bytes = want;
-        return CL_OK;
-    }
-    void adopt(void* slice, size_t n) { if (p && owned) (void)hipFree(p); p = slice; bytes = n; owned = false; fresh = true; }
-    void release() { if (p && owned) (void)hipFree(p); p = nullptr; bytes = 0; owned = true; }
-    template <typename T> T* as() { return (T*)p; }
-};
 
 struct cl_chrom {
     long long tmp_n = -1;             // n the rocPRIM temporary storage was last sized for
@@ -225,25 +203,24 @@ struct cl_chrom {
     // between calls
     DevBuf ag_kin, ag_vin, ag_sx, ag_sy, ag_tmp, ag_m, ag_cx, ag_cy, ag_lkin, ag_lkout, ag_lvin, ag_order, ag_ltmp, ag_sum, ag_stats, ag_mats;
     bool ag_ready = false; int ag_cut = 0, ag_kept = 0;          // the table is built for ag_cut and holds ag_kept rows
-    // K14 (k_track.hip): tile counts / offsets, kept rows, keys, line lengths / ends, ids, names, chunk bounds, render output;
-    // kept from cl_track_build to the next build or cl_track_free
-    DevBuf tk_tcnt, tk_toff, tk_row, tk_keys, tk_sorted, tk_len, tk_end, tk_tmp, tk_ids, tk_names, tk_bnd, tk_out;
+    // K14 (k_track.hip): tile counts / offsets, kept rows, keys, scratch, ids, names; the text itself (line lengths / ends, chunk
+    // bounds, render output: cl_textout.h); kept from cl_track_build to the next build or cl_track_free
+    DevBuf tk_tcnt, tk_toff, tk_row, tk_keys, tk_sorted, tk_tmp, tk_ids, tk_names;
+    TextOut tk_txt;
     struct TrackState {
         bool built = false, ids = false;
         int kind = 0, la = 0, lb = 0, gbits = 0;
-        long long cut = 0, ext = 0, R = 0, total = 0;                // records, bytes of the whole text
-        std::vector<long long> crec, cbyte;                          // the last cl_track_chunks: record / byte bounds
+        long long cut = 0, ext = 0;
     } tk;
     // K20 (k_cover.hip): the sorted end-point keys (in / out, sort scratch), per candidate break point its depth after / before and
-    // its rank among the other side's candidates, the run-start flags and their scan, counters, the runs (start, end, depth), line
-    // lengths / ends, the name, chunk bounds, render output; kept from cl_cov_build to the next build, cl_cov_free or destruction
-    DevBuf cv_kin, cv_key, cv_tmp, cv_dcur, cv_dprev, cv_xr, cv_flag, cv_scan, cv_ctr, cv_start, cv_end, cv_depth, cv_len, cv_lend, cv_name,
-           cv_bnd, cv_out;
+    // its rank among the other side's candidates, the run-start flags and their scan, counters, the runs (start, end, depth), the
+    // name; the text of the runs (cl_textout.h); kept from cl_cov_build to the next build, cl_cov_free or destruction
+    DevBuf cv_kin, cv_key, cv_tmp, cv_dcur, cv_dprev, cv_xr, cv_flag, cv_scan, cv_ctr, cv_start, cv_end, cv_depth, cv_name;
+    TextOut cv_txt;
     struct CovState {
         bool built = false, text = false;
         int la = 0;
-        long long R = 0, total = 0, num = 0, den = 0;                // runs; bytes of the whole text and its scale (cl_cov_text)
-        std::vector<long long> crun, cbyte;                          // the last cl_cov_chunks: run / byte bounds
+        long long R = 0, num = 0, den = 0;                           // runs; the scale of their text (cl_cov_text)
     } cv;
     // K21 (k_peak.hip): the sorted end-point keys (in / out, sort scratch), per element the ranks of its window's two edges, the core
     // flags and their scan, the chain-head flags and their scan, per peak the indices of its first / last core and the four results,
@@ -323,6 +300,24 @@ struct cl_chrom {
 #define LAUNCH(kernel, nthreads, ...) \
     hipLaunchKernelGGL(kernel, dim3(nblocks(nthreads)), dim3(TPB), 0, c->stream, __VA_ARGS__)
 
+// ---- ranged read-back of a unit's results (the cl_*_get entry points) ----
+// [first, first + count) lies inside [0, size)
+static inline bool range_ok(int64_t first, int64_t count, int64_t size)
+{
+    return first >= 0 && count >= 0 && first <= size && count <= size - first;
+}
+// the parts to the host through c->stream, one synchronisation, one joint report under the entry point's name
+struct CopyOut { void* dst; const void* src; size_t bytes; };
+static inline int read_back(cl_chrom* c, const char* who, std::initializer_list<CopyOut> parts)
+{
+    hipError_t e = hipSuccess;
+    for (const CopyOut& p : parts)
+        if (e == hipSuccess) e = hipMemcpyAsync(p.dst, p.src, p.bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return fail_at(CL_ERR_HIP, who, "copy", hipGetErrorString(e != hipSuccess ? e : e2));
+    return CL_OK;
+}
+
 // cloops_hip.hip
 int ensure_workspace(cl_chrom* c, int S);
 int ensure_events(cl_chrom* c);
@@ -332,8 +327,29 @@ Table make_table_slot(cl_chrom* c, int slot);
 Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
 int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_out);
-// k_balance.hip: drops K25's state and buffers (the cells they were made from are going away)
+// Every analysis unit drops its own state and buffers (k_track.hip, k_cover.hip, k_peak.hip, k_domain.hip, k_kdis.hip,
+// k_matrix.hip, k_balance.hip, k_fingerprint.hip, k_anchor.hip, k_agg.hip): called by the unit's own entry points and by the
+// handle's destruction.  mat_release calls bal_release: K25's weights belong to K24's cells
+void track_release(cl_chrom* c);
+void cov_release(cl_chrom* c);
+void peak_release(cl_chrom* c);
+void dom_release(cl_chrom* c);
+void kdis_release(cl_chrom* c);
+void mat_release(cl_chrom* c);
 void bal_release(cl_chrom* c);
+void fp_release(cl_chrom* c);
+void anchor_release(cl_chrom* c);
+void agg_release(cl_chrom* c);
+// what a unit's cl_*_free entry point does around its release function
+static inline int unit_free(cl_chrom* c, const char* who, void (*release)(cl_chrom*))
+{
+    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
+    if (c->enq != c->deq) return fail(CL_ERR_ARG, who, "asynchronous runs still in flight");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    release(c);
+    return CL_OK;
+}
 // k_block.hip, k_weighted.hip
 int run_block(cl_chrom* c, int eps, int minPts, int cut, int32_t* labels_out);
 int run_weighted(cl_chrom* c, int eps, int minPts, int wx, int wy, int32_t* labels_out);
@@ -381,11 +397,6 @@ int lists_emit_records(cl_chrom* c, const GridParams& g, int nm, const ListRun& 
 int lists_scatter_owner(cl_chrom* c, int nm, const ListRun& L);
 int lists_final(cl_chrom* c, const GridParams& g, int nm, const ListRun& L, bool rows, int* pair_count);
 int lists_rowmask(cl_chrom* c, int* total);
-
-// kernel of k_track.hip that K20 (k_cover.hip) launches too: the chunk bounds over the running sum of line lengths
-__global__ void __launch_bounds__(TPB)
-k14_bounds(const long long* __restrict__ end, long long R, long long step, long long K, long long* __restrict__ brec,
-           long long* __restrict__ bbyte);
 
 // kernels of k_sweep.hip that the step tail (finish_enqueue) launches
 __global__ void __launch_bounds__(256)

@@ -40,7 +40,16 @@ static inline int fail(int code, const char* what, const char* detail = nullptr)
     return code;
 }
 
-#define HIP_TRY(expr)                                                              \
+// "<who>: <what>[: detail]" -- for code that several entry points share: the text still names the one that was called
+static inline int fail_at(int code, const char* who, const char* what, const char* detail = nullptr)
+{
+    g_err = who;
+    g_err += ": "; g_err += what;
+    if (detail) { g_err += ": "; g_err += detail; }
+    return code;
+}
+
+#define HIP_TRY(expr)                                                             \
     do {                                                                           \
         hipError_t e_ = (expr);                                                    \
         if (e_ != hipSuccess) return fail(CL_ERR_HIP, #expr, hipGetErrorString(e_)); \

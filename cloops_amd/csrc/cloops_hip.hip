@@ -2135,29 +2135,16 @@ static void free_chrom(cl_chrom* c)
     DevBuf* bufs[] = {&c->keys_in, &c->keys_out, &c->vals_in, &c->vals_out, &c->sort_tmp, &c->scan_tmp, &c->qb_key, &c->qb_val, &c->sv, &c->sa,
                       &c->strip, &c->cnt, &c->parent, &c->root, &c->head, &c->headidx, &c->cellfirst, &c->compkey,
                       &c->ncore, &c->bsize, &c->owner, &c->state, &c->flag, &c->rankscan, &c->slot[0].labels, &c->slot[0].table, &c->slot[1].labels, &c->slot[1].table, &c->slot[0].slab, &c->slot[1].slab, &c->slot[0].d_step, &c->slot[1].d_step, &c->slot[0].pairs, &c->slot[1].pairs, &c->hdr, &c->k7_cls, &c->k7_parts, &c->sig_tx, &c->sig_ty, &c->sig_tmp, &c->sig_sorttmp, &c->sig_m, &c->sig_win, &c->sig_out,
-                      &c->fp_small, &c->fp_keys, &c->fp_sorted, &c->fp_tmp, &c->fp_pairs,
-                      &c->an_s, &c->an_e, &c->an_dir, &c->an_mask, &c->an_wsum,
-                      &c->ag_kin, &c->ag_vin, &c->ag_sx, &c->ag_sy, &c->ag_tmp, &c->ag_m, &c->ag_cx, &c->ag_cy, &c->ag_lkin, &c->ag_lkout, &c->ag_lvin,
-                      &c->ag_order, &c->ag_ltmp, &c->ag_sum, &c->ag_stats, &c->ag_mats,
-                      &c->tk_tcnt, &c->tk_toff, &c->tk_row, &c->tk_keys, &c->tk_sorted, &c->tk_len, &c->tk_end, &c->tk_tmp, &c->tk_ids,
-                      &c->tk_names, &c->tk_bnd, &c->tk_out,
-                      &c->cv_kin, &c->cv_key, &c->cv_tmp, &c->cv_dcur, &c->cv_dprev, &c->cv_xr, &c->cv_flag, &c->cv_scan, &c->cv_ctr, &c->cv_start,
-                      &c->cv_end, &c->cv_depth, &c->cv_len, &c->cv_lend, &c->cv_name, &c->cv_bnd, &c->cv_out,
-                      &c->pk_kin, &c->pk_key, &c->pk_tmp, &c->pk_lo, &c->pk_hi, &c->pk_flag, &c->pk_C, &c->pk_head, &c->pk_H, &c->pk_a, &c->pk_b,
-                      &c->pk_start, &c->pk_end, &c->pk_np, &c->pk_nc, &c->pk_ctr, &c->pk_ivs, &c->pk_ive, &c->pk_best, &c->pk_opos, &c->pk_ocnt,
-                      &c->dm_diff, &c->dm_trk, &c->dm_tmp, &c->dm_rng, &c->dm_ivs, &c->dm_ive, &c->dm_cnt,
-                      &c->kd_x, &c->kd_y, &c->kd_d, &c->kd_hist,
-                      &c->mx_out, &c->mx_ctr, &c->mx_key, &c->mx_sorted, &c->mx_tmp, &c->mx_flag, &c->mx_scan, &c->mx_start, &c->mx_bx,
-                      &c->mx_by, &c->mx_cnt,
-                      &c->bl_kin, &c->bl_kout, &c->bl_vin, &c->bl_vout, &c->bl_tmp, &c->bl_tby, &c->bl_tbx, &c->bl_tcnt, &c->bl_sum, &c->bl_nnz,
-                      &c->bl_valid, &c->bl_w, &c->bl_s, &c->bl_icar, &c->bl_dcar, &c->bl_part, &c->bl_rec, &c->bl_out,
                       &c->ulist, &c->lo, &c->hi, &c->recs, &c->counters, &c->chainflag, &c->chainhead, &c->usize, &c->b_cstart, &c->b_ckey, &c->b_nb, &c->b_cx, &c->b_cy, &c->tile_s0, &c->bq, &c->bsp, &c->brow, &c->bstrip, &c->btile, &c->sel_tmp, &c->cand_box, &c->cand_step, &c->cand_keep, &c->cand_out, &c->dhist,
                       &c->rc_cnt, &c->rc_pre, &c->rc_poff, &c->rc_dpre, &c->rc_D, &c->rc_blen, &c->rootlist, &c->cflag8, &c->blk_tmp,
                       &c->l_mask, &c->l_rank, &c->l_blk, &c->l_cstrip, &c->l_wpos, &c->l_wenc, &c->l_dist, &c->l_aux, &c->l_tab, &c->l_fix, &c->bkey,
                       &c->fq, &c->fsp, &c->frow, &c->fstrip,
                       &c->kde_ent, &c->kde_sorted, &c->kde_ctr, &c->kde_tmp, &c->kde_part};
     for (DevBuf* b : bufs) b->release();
-    c->arena.release();                                  // (after its slices have been dropped)
+    for (void (*unit)(cl_chrom*) : {fp_release, anchor_release, agg_release, track_release, cov_release, peak_release, dom_release, kdis_release,
+                                    mat_release /* (and K25's: bal_release) */})
+        unit(c);
+    c->arena.release();                                 // (after its slices have been dropped)
     if (c->own_xy) { if (c->d_x) (void)hipFree(c->d_x); if (c->d_y) (void)hipFree(c->d_y); }
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     for (auto& sl : c->slot) {

@@ -162,6 +162,13 @@ static bool k19_wave_form()
     return false;
 }
 
+void agg_release(cl_chrom* c)
+{
+    for (DevBuf* b : {&c->ag_kin, &c->ag_vin, &c->ag_sx, &c->ag_sy, &c->ag_tmp, &c->ag_m, &c->ag_cx, &c->ag_cy, &c->ag_lkin, &c->ag_lkout, &c->ag_lvin,
+                      &c->ag_order, &c->ag_ltmp, &c->ag_sum, &c->ag_stats, &c->ag_mats}) b->release();
+    c->ag_ready = false;
+}
+
 // the X-sorted table of (chromosome, cut) unless the handle holds it already; c->n > 0 (declared in cl_chrom.h: K22 shares it)
 int agg_table(cl_chrom* c, int cut)
 {
@@ -173,13 +180,11 @@ int agg_table(cl_chrom* c, int cut)
         (rc = c->ag_sy.ensure((size_t)n * 4)) || (rc = c->ag_m.ensure(64))) return rc;
     LAUNCH(k19_split, n, c->d_x, c->d_y, n, cut, c->ag_kin.as<u32>(), c->ag_vin.as<int>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs<SortConfig>(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, (int*)nullptr, (int*)nullptr, (size_t)n, 0, 32, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs size query (agg table)", hipGetErrorString(e));
-    if ((rc = c->ag_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->ag_tmp.bytes;
-    e = rocprim::radix_sort_pairs<SortConfig>(c->ag_tmp.p, bytes, c->ag_kin.as<u32>(), c->ag_sx.as<u32>(), c->ag_vin.as<int>(), c->ag_sy.as<int>(), (size_t)n, 0, 32, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs(agg table)", hipGetErrorString(e));
+    if ((rc = prim_run(c->ag_tmp, "radix_sort_pairs(agg table)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, c->ag_kin.as<u32>(), c->ag_sx.as<u32>(), c->ag_vin.as<int>(), c->ag_sy.as<int>(),
+                                                         (size_t)n, 0, 32, c->stream);
+        })))
+        return rc;
     hipLaunchKernelGGL(k19_count_valid, dim3(1), dim3(64), 0, c->stream, c->ag_sx.as<u32>(), n, c->ag_m.as<int>());
     HIP_TRY(hipGetLastError());
     int hm = 0;
@@ -203,13 +208,11 @@ static int agg_loops(cl_chrom* c, const K19Par& p, int n_loops, const int32_t* c
     HIP_TRY(hipMemsetAsync(c->ag_sum.p, 0, ww * 8, c->stream));
     LAUNCH(k19_loop_keys, n_loops, c->ag_cx.as<int>(), n_loops, c->ag_lkin.as<int>(), c->ag_lvin.as<u32>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs<SortConfig>(nullptr, bytes, (int*)nullptr, (int*)nullptr, (u32*)nullptr, (u32*)nullptr, nl, 0, 32, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs size query (agg loops)", hipGetErrorString(e));
-    if ((rc = c->ag_ltmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->ag_ltmp.bytes;
-    e = rocprim::radix_sort_pairs<SortConfig>(c->ag_ltmp.p, bytes, c->ag_lkin.as<int>(), c->ag_lkout.as<int>(), c->ag_lvin.as<u32>(), c->ag_order.as<u32>(), nl, 0, 32, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs(agg loops)", hipGetErrorString(e));
+    if ((rc = prim_run(c->ag_ltmp, "radix_sort_pairs(agg loops)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, c->ag_lkin.as<int>(), c->ag_lkout.as<int>(), c->ag_lvin.as<u32>(),
+                                                         c->ag_order.as<u32>(), nl, 0, 32, c->stream);
+        })))
+        return rc;
     int* d_stats = stats_out ? c->ag_stats.as<int>() : nullptr;
     int* d_mats = mats_out ? c->ag_mats.as<int>() : nullptr;
     if (k19_wave_form())

@@ -134,6 +134,11 @@ static int k13_lds_max()
 }
 
 // ---- K13 host entry point -----------------------------------------------------------------------
+void anchor_release(cl_chrom* c)
+{
+    for (DevBuf* b : {&c->an_s, &c->an_e, &c->an_dir, &c->an_mask, &c->an_wsum}) b->release();
+}
+
 // hs / he / ws: host staging of the copies, owned by the caller so that they outlive the stream synchronisation that follows an
 // error return here
 static int anchor_mask(cl_chrom* c, const std::vector<std::pair<int64_t, int64_t>>& merged, uint64_t* mask, int64_t* n_kept,

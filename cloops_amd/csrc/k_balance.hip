@@ -417,14 +417,11 @@ static int bal_marginals(cl_chrom* c, cl_chrom::BalState& st)
         (rc = c->bl_tby.ensure(sn * 4)) || (rc = c->bl_tbx.ensure(sn * 4)) || (rc = c->bl_tcnt.ensure(sn * 4)) || (rc = c->bl_rec.ensure(64))) return rc;
     LAUNCH(k25_keys, n, c->mx_bx.as<int>(), c->mx_by.as<int>(), n, hb0, bits, c->bl_kin.as<u64>(), c->bl_vin.as<u32>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (u32*)nullptr, (u32*)nullptr, sn, 0, 2 * bits, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs size query (balance)", hipGetErrorString(e));
-    if ((rc = c->bl_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->bl_tmp.bytes;
-    e = rocprim::radix_sort_pairs(c->bl_tmp.p, bytes, c->bl_kin.as<u64>(), c->bl_kout.as<u64>(), c->bl_vin.as<u32>(), c->bl_vout.as<u32>(), sn, 0, 2 * bits,
-                                  c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs(balance)", hipGetErrorString(e));
+    if ((rc = prim_run(c->bl_tmp, "radix_sort_pairs(balance)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, c->bl_kin.as<u64>(), c->bl_kout.as<u64>(), c->bl_vin.as<u32>(), c->bl_vout.as<u32>(), sn, 0,
+                                             2 * bits, c->stream);
+        })))
+        return rc;
     LAUNCH(k25_gather, n, c->bl_vout.as<u32>(), c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), n, c->bl_tbx.as<int>(),
            c->bl_tby.as<int>(), c->bl_tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
@@ -501,15 +498,12 @@ extern "C" int cl_bal_marginals_get(cl_chrom* c, int64_t first, int64_t count, u
 {
     int rc = bal_enter(c, "cl_bal_marginals_get", true);
     if (rc != CL_OK) return rc;
-    if (first < 0 || count < 0 || first > c->bl.nb || count > c->bl.nb - first) return fail(CL_ERR_ARG, "cl_bal_marginals_get: range outside the bins");
+    if (!range_ok(first, count, c->bl.nb)) return fail(CL_ERR_ARG, "cl_bal_marginals_get: range outside the bins");
     if (count > 0 && (!sum || !nnz)) return fail(CL_ERR_ARG, "cl_bal_marginals_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    hipError_t e = hipMemcpyAsync(sum, c->bl_sum.as<u64>() + first, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(nnz, c->bl_nnz.as<u32>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_marginals_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    return read_back(c, "cl_bal_marginals_get", {{sum, c->bl_sum.as<u64>() + first, (size_t)count * 8},
+                                                 {nnz, c->bl_nnz.as<u32>() + first, (size_t)count * 4}});
 }
 
 static int bal_iterate(cl_chrom* c, const uint32_t* valid, int max_iters, double tol, K25Rec& h)
@@ -589,14 +583,11 @@ extern "C" int cl_bal_weights_get(cl_chrom* c, int64_t first, int64_t count, dou
     int rc = bal_enter(c, "cl_bal_weights_get", true);
     if (rc != CL_OK) return rc;
     if (!c->bl.iterated) return fail(CL_ERR_ARG, "cl_bal_weights_get: no weights on this handle (cl_bal_iterate)");
-    if (first < 0 || count < 0 || first > c->bl.nb || count > c->bl.nb - first) return fail(CL_ERR_ARG, "cl_bal_weights_get: range outside the bins");
+    if (!range_ok(first, count, c->bl.nb)) return fail(CL_ERR_ARG, "cl_bal_weights_get: range outside the bins");
     if (count > 0 && !weight) return fail(CL_ERR_ARG, "cl_bal_weights_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const hipError_t e = hipMemcpyAsync(weight, c->bl_w.as<double>() + (size_t)c->bl.nb + first, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_weights_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    return read_back(c, "cl_bal_weights_get", {{weight, c->bl_w.as<double>() + (size_t)c->bl.nb + first, (size_t)count * 8}});
 }
 
 extern "C" int cl_bal_cells_get(cl_chrom* c, int64_t first, int64_t count, double* balanced)
@@ -604,18 +595,16 @@ extern "C" int cl_bal_cells_get(cl_chrom* c, int64_t first, int64_t count, doubl
     int rc = bal_enter(c, "cl_bal_cells_get", true);
     if (rc != CL_OK) return rc;
     if (!c->bl.iterated) return fail(CL_ERR_ARG, "cl_bal_cells_get: no weights on this handle (cl_bal_iterate)");
-    if (first < 0 || count < 0 || first > c->bl.n_cells || count > c->bl.n_cells - first) return fail(CL_ERR_ARG, "cl_bal_cells_get: range outside the cells");
+    if (!range_ok(first, count, c->bl.n_cells)) return fail(CL_ERR_ARG, "cl_bal_cells_get: range outside the cells");
     if (count > 0 && !balanced) return fail(CL_ERR_ARG, "cl_bal_cells_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = c->bl_out.ensure((size_t)count * 8))) return rc;
     LAUNCH(k25_cells, count, c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), (long long)first, (long long)count, c->bl.n_cells,
            (int)c->bl.b0, (int)c->bl.nb, (const double*)(c->bl_w.as<double>() + (size_t)c->bl.nb), std::nan(""), c->bl_out.as<double>());
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(balanced, c->bl_out.p, (size_t)count * 8, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_cells_get", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_cells_get", hipGetErrorString(e));
+    return read_back(c, "cl_bal_cells_get", {{balanced, c->bl_out.p, (size_t)count * 8}});
 }
 
 extern "C" int cl_bal_free(cl_chrom* c)

@@ -202,31 +202,18 @@ k15_render(const uint4* __restrict__ in, const K15Rec* __restrict__ rec, const l
 {
     extern __shared__ uint4 k15_lds[];
     char* buf = (char*)k15_lds;
-    const long long q0 = (long long)blockIdx.x * K15_T;
-    const long long q1 = q0 + K15_T < R ? q0 + K15_T : R;
-    const long long g0 = q0 > 0 ? end[q0 - 1] : 0, g1 = end[q1 - 1];   // the tile's span in out
-    const long long a0 = g0 & ~15ll;                                    // LDS byte i <-> out byte a0 + i
-    const bool fits = g1 - a0 <= K15_LDS;
-    const long long j = q0 + threadIdx.x;
-    if (j < q1) {
+    const TextTile tile = text_tile(end, 0, R, 0, K15_T);
+    const bool fits = tile.g1 - tile.a0 <= K15_LDS;
+    const long long j = tile.q0 + threadIdx.x;
+    if (j < tile.q1) {
         const long long p0 = j > 0 ? end[j - 1] : 0;
         const K15Rec r = rec[j];
-        if (fits) k15_emit<FMT>(buf, (int)(p0 - a0), in, r);
+        if (fits) k15_emit<FMT>(buf, (int)(p0 - tile.a0), in, r);
         else k15_emit<FMT>(out + p0, 0, in, r);
     }
     if (!fits) return;                                                  // uniform over the workgroup
     __syncthreads();
-    // the span [g0, g1) as 16-byte words of out: whole words with one store each, the two edge words byte by byte
-    const long long w0 = g0 >> 4, w1 = (g1 + 15) >> 4;
-    for (long long w = w0 + threadIdx.x; w < w1; w += blockDim.x) {
-        const long long b = w << 4;
-        if (b >= g0 && b + 16 <= g1) {
-            *(uint4*)(out + b) = k15_lds[(b - a0) >> 4];
-        } else {
-            const long long s = b > g0 ? b : g0, e = b + 16 < g1 ? b + 16 : g1;
-            for (long long i = s; i < e; ++i) out[i] = buf[i - a0];
-        }
-    }
+    text_flush(out, k15_lds, tile.g0, tile.g1, tile.a0);
 }
 
 // ---- K15 host side ------------------------------------------------------------------------------
@@ -236,10 +223,10 @@ struct cl_conv {
     bool own_stream = false;
     int fmt = 0;
     long long ext = 0, budget = 0, lmax = 0;
-    DevBuf in, tcnt, toff, ends, rec, len, end, tmp, err, out;
+    DevBuf in, tcnt, toff, ends, rec, tmp, err;
+    TextOut txt;                                  // the last feed's text: txt.R lines of txt.total bytes (a feed is its own chunk)
     long long lines = 0;                          // lines of every feed so far: cl_conv_error's line numbers
     bool fed = false;                             // the last feed's lines can be rendered
-    long long R = 0, nbytes = 0;                  // ... how many, and the bytes of their text
     long long err_line = 0;
     int err_kind = 0;
     hipEvent_t ev[6] = {};                        // feed: copy start / copy end / kernels end; render: start / kernel end / copy end
@@ -250,7 +237,8 @@ static void conv_free(cl_conv* c)
 {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->in, &c->tcnt, &c->toff, &c->ends, &c->rec, &c->len, &c->end, &c->tmp, &c->err, &c->out}) b->release();
+    for (DevBuf* b : {&c->in, &c->tcnt, &c->toff, &c->ends, &c->rec, &c->tmp, &c->err}) b->release();
+    text_release(c->txt);
     for (hipEvent_t& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -307,13 +295,10 @@ static int conv_feed(cl_conv* c, const char* bytes, long long cut, long long* co
     HIP_TRY(hipMemsetAsync(c->err.p, 0x7f, 4, c->stream));          // no bad line: 0x7f7f7f7f, above any line index
     hipLaunchKernelGGL(k15_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
-    size_t bytes_tmp = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes_tmp, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan size query", hipGetErrorString(e));
-    if ((rc = c->tmp.ensure(std::max<size_t>(bytes_tmp, 16)))) return rc;
-    bytes_tmp = c->tmp.bytes;
-    e = rocprim::exclusive_scan(c->tmp.p, bytes_tmp, c->tcnt.as<u32>(), c->toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(tiles)", hipGetErrorString(e));
+    if ((rc = prim_run(c->tmp, "exclusive_scan(tiles)", [&](void* tmp, size_t& nb) {
+            return rocprim::exclusive_scan(tmp, nb, c->tcnt.as<u32>(), c->toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
+        })))
+        return rc;
     hipLaunchKernelGGL(k15_lines, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->toff.as<u32>(), c->lmax,
                        c->ends.as<u32>());
     HIP_TRY(hipGetLastError());
@@ -327,25 +312,19 @@ static int conv_feed(cl_conv* c, const char* bytes, long long cut, long long* co
         if ((rc = conv_read(c, &last_end, c->ends.as<u32>() + (L - 1)))) return rc;
         *consumed = (long long)last_end + 1;
     }
-    if ((rc = c->rec.ensure((size_t)L * sizeof(K15Rec))) || (rc = c->len.ensure((size_t)L * 8)) || (rc = c->end.ensure((size_t)L * 8))) return rc;
+    if ((rc = c->rec.ensure((size_t)L * sizeof(K15Rec))) || (rc = c->txt.len.ensure((size_t)L * 8)) || (rc = c->txt.end.ensure((size_t)L * 8))) return rc;
     const unsigned grid = (unsigned)((L + K15_T - 1) / K15_T);
     if (c->fmt == CL_CONV_HICPRO)
         hipLaunchKernelGGL(k15_parse<CL_CONV_HICPRO>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
-                           c->rec.as<K15Rec>(), c->len.as<long long>(), c->err.as<int>());
+                           c->rec.as<K15Rec>(), c->txt.len.as<long long>(), c->err.as<int>());
     else if (c->fmt == CL_CONV_PAIRS)
         hipLaunchKernelGGL(k15_parse<CL_CONV_PAIRS>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
-                           c->rec.as<K15Rec>(), c->len.as<long long>(), c->err.as<int>());
+                           c->rec.as<K15Rec>(), c->txt.len.as<long long>(), c->err.as<int>());
     else
         hipLaunchKernelGGL(k15_parse<CL_CONV_JUICER>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->ext,
-                           c->rec.as<K15Rec>(), c->len.as<long long>(), c->err.as<int>());
+                           c->rec.as<K15Rec>(), c->txt.len.as<long long>(), c->err.as<int>());
     HIP_TRY(hipGetLastError());
-    bytes_tmp = 0;
-    e = rocprim::inclusive_scan(nullptr, bytes_tmp, (long long*)nullptr, (long long*)nullptr, (size_t)L, rocprim::plus<long long>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan size query", hipGetErrorString(e));
-    if ((rc = c->tmp.ensure(std::max<size_t>(bytes_tmp, 16)))) return rc;
-    bytes_tmp = c->tmp.bytes;
-    e = rocprim::inclusive_scan(c->tmp.p, bytes_tmp, c->len.as<long long>(), c->end.as<long long>(), (size_t)L, rocprim::plus<long long>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan(lines)", hipGetErrorString(e));
+    if ((rc = text_scan(c->txt, c->tmp, L, c->stream))) return rc;
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     if ((rc = conv_read(c, bad, c->err.p))) return rc;
     *L_out = L;
@@ -360,7 +339,7 @@ extern "C" int cl_conv_feed(cl_conv* c, const char* bytes, int64_t n, int32_t la
     if (n_bytes) *n_bytes = 0;
     if (!consumed || !n_lines || !n_bytes || n < 0 || (n > 0 && !bytes)) return fail(CL_ERR_ARG, "cl_conv_feed: bad arguments");
     if (n > c->budget) return fail(CL_ERR_ARG, "cl_conv_feed: more bytes than the handle's budget");
-    c->fed = false; c->R = 0; c->nbytes = 0; c->err_line = 0; c->err_kind = 0;
+    c->fed = false; text_reset(c->txt); c->err_line = 0; c->err_kind = 0;
     c->ms_h2d = c->ms_feed = c->ms_render = c->ms_d2h = 0;
     long long cut = n;                                                  // complete lines only, unless the input ends here
     if (!last) {
@@ -384,8 +363,8 @@ extern "C" int cl_conv_feed(cl_conv* c, const char* bytes, int64_t n, int32_t la
         return rc;
     }
     const long long R = bad < L ? bad : L;
-    long long total = 0;
-    if (R > 0 && (rc = conv_read(c, &total, c->end.as<long long>() + (R - 1)))) return rc;
+    if (R > 0 && (rc = text_total(c->txt, R, c->stream))) return rc;                 // (the lines in front of the first bad one)
+    const long long total = c->txt.total;
     u32 flags = 0;
     if (bad < L && (rc = conv_read(c, &flags, (const char*)c->rec.p + (size_t)bad * sizeof(K15Rec) + offsetof(K15Rec, flags)))) return rc;
     (void)hipEventElapsedTime(&c->ms_h2d, c->ev[0], c->ev[1]);
@@ -393,8 +372,6 @@ extern "C" int cl_conv_feed(cl_conv* c, const char* bytes, int64_t n, int32_t la
     const long long first = c->lines;
     c->lines += L;
     c->fed = true;
-    c->R = R;
-    c->nbytes = total;
     *consumed = used;
     *n_lines = R;
     *n_bytes = total;
@@ -410,33 +387,31 @@ extern "C" int cl_conv_render(cl_conv* c, char* out, int64_t cap, int64_t* n_byt
 {
     if (!c) return fail(CL_ERR_ARG, "null converter handle");
     if (n_bytes) *n_bytes = 0;
-    if (!n_bytes || (!out && c->nbytes > 0)) return fail(CL_ERR_ARG, "cl_conv_render: bad arguments");
+    TextOut& txt = c->txt;
+    if (!n_bytes || (!out && txt.total > 0)) return fail(CL_ERR_ARG, "cl_conv_render: bad arguments");
     if (!c->fed) return fail(CL_ERR_ARG, "cl_conv_render: no feed to render");
-    if (cap < c->nbytes) return fail(CL_ERR_ARG, "cl_conv_render: capacity below the feed's bytes");
-    if (c->R == 0 || c->nbytes == 0) return CL_OK;                      // no lines, or header lines only
+    if (cap < txt.total) return fail(CL_ERR_ARG, "cl_conv_render: capacity below the feed's bytes");
+    if (txt.R == 0 || txt.total == 0) return CL_OK;                     // no lines, or header lines only
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = c->out.ensure((size_t)c->nbytes + 16))) return rc;
-    const unsigned grid = (unsigned)((c->R + K15_T - 1) / K15_T);
+    if ((rc = text_reserve(txt, txt.total))) return rc;
+    const unsigned grid = (unsigned)((txt.R + K15_T - 1) / K15_T);
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     if (c->fmt == CL_CONV_HICPRO)
         hipLaunchKernelGGL(k15_render<CL_CONV_HICPRO>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),
-                           c->end.as<long long>(), c->R, c->out.as<char>());
+                           txt.end.as<long long>(), txt.R, txt.out.as<char>());
     else if (c->fmt == CL_CONV_PAIRS)
         hipLaunchKernelGGL(k15_render<CL_CONV_PAIRS>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),
-                           c->end.as<long long>(), c->R, c->out.as<char>());
+                           txt.end.as<long long>(), txt.R, txt.out.as<char>());
     else
         hipLaunchKernelGGL(k15_render<CL_CONV_JUICER>, dim3(grid), dim3(K15_T), K15_LDS, c->stream, c->in.as<uint4>(), c->rec.as<K15Rec>(),
-                           c->end.as<long long>(), c->R, c->out.as<char>());
+                           txt.end.as<long long>(), txt.R, txt.out.as<char>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[4], c->stream));
-    hipError_t e = hipMemcpyAsync(out, c->out.p, (size_t)c->nbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(c->ev[5], c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_conv_render: copy", hipGetErrorString(e != hipSuccess ? e : e2));
+    if ((rc = text_copy_out(txt, c->stream, out, txt.total, "cl_conv_render", c->ev[5]))) return rc;
     (void)hipEventElapsedTime(&c->ms_render, c->ev[3], c->ev[4]);
     (void)hipEventElapsedTime(&c->ms_d2h, c->ev[4], c->ev[5]);
-    *n_bytes = c->nbytes;
+    *n_bytes = txt.total;
     return CL_OK;
 }
 

@@ -157,15 +157,12 @@ k20_render(K20Tpl t, long long r0, long long r1, long long b0, const long long* 
     extern __shared__ uint4 k20_lds[];
     __shared__ char nm[CL_TRACK_NAME_MAX];
     char* buf = (char*)k20_lds;
-    const long long q0 = r0 + (long long)blockIdx.x * K20_T;
-    const long long q1 = q0 + K20_T < r1 ? q0 + K20_T : r1;
     for (int k = threadIdx.x; k < CL_TRACK_NAME_MAX; k += blockDim.x) nm[k] = t.name[k];
-    const long long g0 = (q0 > 0 ? lend[q0 - 1] : 0) - b0, g1 = lend[q1 - 1] - b0;   // the tile's span in out
-    const long long a0 = g0 & ~15ll;                                    // LDS byte i <-> out byte a0 + i
+    const TextTile tile = text_tile(lend, r0, r1, b0, K20_T);
     __syncthreads();
-    const long long j = q0 + threadIdx.x;
-    if (j < q1) {
-        int pos = (int)((j > 0 ? lend[j - 1] : 0) - b0 - a0);
+    const long long j = tile.q0 + threadIdx.x;
+    if (j < tile.q1) {
+        int pos = (int)((j > 0 ? lend[j - 1] : 0) - b0 - tile.a0);
         for (int k = 0; k < t.la; ++k) buf[pos + k] = nm[k];
         pos += t.la; buf[pos++] = '\t';
         pos = cl_put(buf, pos, t.start[j]); buf[pos++] = '\t';
@@ -186,17 +183,7 @@ k20_render(K20Tpl t, long long r0, long long r1, long long b0, const long long* 
         buf[pos++] = '\n';
     }
     __syncthreads();
-    // the span [g0, g1) as 16-byte words of out: whole words with one store each, the two edge words byte by byte
-    const long long w0 = g0 >> 4, w1 = (g1 + 15) >> 4;
-    for (long long w = w0 + threadIdx.x; w < w1; w += blockDim.x) {
-        const long long b = w << 4;
-        if (b >= g0 && b + 16 <= g1) {
-            *(uint4*)(out + b) = k20_lds[(b - a0) >> 4];
-        } else {
-            const long long s = b > g0 ? b : g0, e = b + 16 < g1 ? b + 16 : g1;
-            for (long long i = s; i < e; ++i) out[i] = buf[i - a0];
-        }
-    }
+    text_flush(out, k20_lds, tile.g0, tile.g1, tile.a0);
 }
 
 // ---- K20 host side ------------------------------------------------------------------------------
@@ -213,11 +200,12 @@ static K20Tpl k20_tpl(cl_chrom* c)
     return t;
 }
 
-static void cov_release(cl_chrom* c)
+void cov_release(cl_chrom* c)
 {
     for (DevBuf* b : {&c->cv_kin, &c->cv_key, &c->cv_tmp, &c->cv_dcur, &c->cv_dprev, &c->cv_xr, &c->cv_flag, &c->cv_scan, &c->cv_ctr,
-                      &c->cv_start, &c->cv_end, &c->cv_depth, &c->cv_len, &c->cv_lend, &c->cv_name, &c->cv_bnd, &c->cv_out})
+                      &c->cv_start, &c->cv_end, &c->cv_depth, &c->cv_name})
         b->release();
+    text_release(c->cv_txt);
     c->cv = cl_chrom::CovState();
 }
 
@@ -249,13 +237,10 @@ static int cov_build(cl_chrom* c, long long cut, int ends, int ext, int res, int
     if (m == 0) { c->cv.built = true; return CL_OK; }
     if (m > (long long)n * ne) return fail(CL_ERR_HIP, "cl_cov_build: the key pass counted more end points than rows allow");
     // S: the end points in ascending order, sorted over the bits in use
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, (size_t)m, 0, ebit, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query (coverage)", hipGetErrorString(e));
-    if ((rc = c->cv_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->cv_tmp.bytes;
-    e = rocprim::radix_sort_keys(c->cv_tmp.p, bytes, c->cv_kin.as<u32>(), c->cv_key.as<u32>(), (size_t)m, 0, ebit, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(coverage)", hipGetErrorString(e));
+    if ((rc = prim_run(c->cv_tmp, "radix_sort_keys(coverage)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->cv_kin.as<u32>(), c->cv_key.as<u32>(), (size_t)m, 0, ebit, c->stream);
+        })))
+        return rc;
     // candidates, flags, their scan
     const size_t m2 = 2 * (size_t)m;
     if ((rc = c->cv_dcur.ensure(m2 * 4)) || (rc = c->cv_dprev.ensure(m2 * 4)) || (rc = c->cv_xr.ensure(m2 * 4)) ||
@@ -265,13 +250,10 @@ static int cov_build(cl_chrom* c, long long cut, int ends, int ext, int res, int
     hipLaunchKernelGGL(k20_breaks, dim3((unsigned)((m + K20_TILE - 1) / K20_TILE)), dim3(TPB), 0, c->stream, c->cv_key.as<u32>(), (int)m, p,
                        c->cv_dcur.as<u32>(), c->cv_dprev.as<u32>(), c->cv_xr.as<u32>(), c->cv_flag.as<u32>(), ctr);
     HIP_TRY(hipGetLastError());
-    bytes = 0;
-    e = rocprim::exclusive_scan(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, 0u, m2 + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan size query (coverage)", hipGetErrorString(e));
-    if ((rc = c->cv_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->cv_tmp.bytes;
-    e = rocprim::exclusive_scan(c->cv_tmp.p, bytes, c->cv_flag.as<u32>(), c->cv_scan.as<u32>(), 0u, m2 + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(coverage)", hipGetErrorString(e));
+    if ((rc = prim_run(c->cv_tmp, "exclusive_scan(coverage)", [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->cv_flag.as<u32>(), c->cv_scan.as<u32>(), 0u, m2 + 1, rocprim::plus<u32>(), c->stream);
+        })))
+        return rc;
     u32 hR = 0;
     HIP_TRY(hipMemcpyAsync(&hR, c->cv_scan.as<u32>() + m2, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&hctr[K20_MAXD], ctr + K20_MAXD, 8, hipMemcpyDeviceToHost, c->stream));
@@ -312,6 +294,7 @@ extern "C" int cl_cov_build(cl_chrom* c, int64_t cut, int32_t ends, int64_t ext,
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_build: asynchronous runs still in flight");
     HIP_TRY(hipSetDevice(c->device));
     c->cv = cl_chrom::CovState();                                      // (the buffers stay: the next build reuses their memory, not their content)
+    text_reset(c->cv_txt);
     if (c->n == 0) { c->cv.built = true; return CL_OK; }
     const int rc = cov_build(c, cut, ends, (int)ext, (int)res, n_runs, max_depth, n_ends, area);
     if (rc != CL_OK) {
@@ -325,17 +308,14 @@ extern "C" int cl_cov_runs(cl_chrom* c, int64_t first, int64_t count, int32_t* s
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (!c->cv.built) return fail(CL_ERR_ARG, "cl_cov_runs: no coverage built on this handle");
-    if (first < 0 || count < 0 || first > c->cv.R || count > c->cv.R - first) return fail(CL_ERR_ARG, "cl_cov_runs: range outside the runs");
+    if (!range_ok(first, count, c->cv.R)) return fail(CL_ERR_ARG, "cl_cov_runs: range outside the runs");
     if (count > 0 && (!start_out || !end_out || !depth_out)) return fail(CL_ERR_ARG, "cl_cov_runs: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_runs: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    hipError_t e = hipMemcpyAsync(start_out, c->cv_start.as<int>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(end_out, c->cv_end.as<int>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(depth_out, c->cv_depth.as<u32>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_cov_runs: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    return read_back(c, "cl_cov_runs", {{start_out, c->cv_start.as<int>() + first, (size_t)count * 4},
+                                        {end_out, c->cv_end.as<int>() + first, (size_t)count * 4},
+                                        {depth_out, c->cv_depth.as<u32>() + first, (size_t)count * 4}});
 }
 
 static int cov_text(cl_chrom* c, std::vector<char>& hn, int64_t* n_bytes)
@@ -343,24 +323,14 @@ static int cov_text(cl_chrom* c, std::vector<char>& hn, int64_t* n_bytes)
     cl_chrom::CovState& s = c->cv;
     const long long R = s.R;
     int rc;
-    if ((rc = c->cv_name.ensure(CL_TRACK_NAME_MAX)) || (rc = c->cv_len.ensure((size_t)R * 8)) || (rc = c->cv_lend.ensure((size_t)R * 8))) return rc;
+    TextOut& txt = c->cv_txt;
+    if ((rc = c->cv_name.ensure(CL_TRACK_NAME_MAX)) || (rc = txt.len.ensure((size_t)R * 8)) || (rc = txt.end.ensure((size_t)R * 8))) return rc;
     HIP_TRY(hipMemcpyAsync(c->cv_name.p, hn.data(), CL_TRACK_NAME_MAX, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k20_lens, dim3(k20_grid(R)), dim3(TPB), 0, c->stream, k20_tpl(c), R, c->cv_len.as<long long>());
+    hipLaunchKernelGGL(k20_lens, dim3(k20_grid(R)), dim3(TPB), 0, c->stream, k20_tpl(c), R, txt.len.as<long long>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0;
-    hipError_t e = rocprim::inclusive_scan(nullptr, bytes, (long long*)nullptr, (long long*)nullptr, (size_t)R, rocprim::plus<long long>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan size query (coverage)", hipGetErrorString(e));
-    if ((rc = c->cv_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->cv_tmp.bytes;
-    e = rocprim::inclusive_scan(c->cv_tmp.p, bytes, c->cv_len.as<long long>(), c->cv_lend.as<long long>(), (size_t)R, rocprim::plus<long long>(),
-                                c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan(coverage lines)", hipGetErrorString(e));
-    long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, c->cv_lend.as<long long>() + (R - 1), 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    s.total = total;
+    if ((rc = text_scan(txt, c->cv_tmp, R, c->stream)) || (rc = text_total(txt, R, c->stream))) return rc;
     s.text = true;
-    *n_bytes = total;
+    *n_bytes = txt.total;
     return CL_OK;
 }
 
@@ -376,7 +346,8 @@ extern "C" int cl_cov_text(cl_chrom* c, const char* name, int64_t scale_num, int
         return fail(CL_ERR_ARG, "cl_cov_text: needs scale_den >= 0 and 1 <= scale_num <= 2^30 (0 allowed with scale_den = 0)");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_text: asynchronous runs still in flight");
     cl_chrom::CovState& s = c->cv;
-    s.text = false; s.total = 0; s.crun.clear(); s.cbyte.clear();
+    s.text = false;
+    text_reset(c->cv_txt);
     s.la = (int)la; s.num = scale_num; s.den = scale_den;
     if (s.R == 0) { s.text = true; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
@@ -395,37 +366,8 @@ extern "C" int cl_cov_chunks(cl_chrom* c, int64_t budget, int64_t cap, int64_t* 
     if (!c->cv.built || !c->cv.text) return fail(CL_ERR_ARG, "cl_cov_chunks: no coverage text on this handle (cl_cov_build, cl_cov_text)");
     if (budget < k20_lcap(c)) return fail(CL_ERR_ARG, "cl_cov_chunks: budget below the longest line the template allows");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_chunks: asynchronous runs still in flight");
-    cl_chrom::CovState& s = c->cv;
-    s.crun.assign(1, 0);
-    s.cbyte.assign(1, 0);
-    if (s.R > 0) {
-        HIP_TRY(hipSetDevice(c->device));
-        const long long step = budget - k20_lcap(c) + 1;
-        const long long K = (s.total + step - 1) / step;
-        int rc;
-        if ((rc = c->cv_bnd.ensure((size_t)(K + 1) * 16))) return rc;
-        long long* brec = c->cv_bnd.as<long long>();
-        long long* bbyte = brec + (K + 1);
-        hipLaunchKernelGGL(k14_bounds, dim3((unsigned)((K + 1 + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->cv_lend.as<long long>(), s.R, step, K,
-                           brec, bbyte);
-        HIP_TRY(hipGetLastError());
-        std::vector<long long> hr((size_t)K + 1), hb((size_t)K + 1);
-        hipError_t e = hipMemcpyAsync(hr.data(), brec, (size_t)(K + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), bbyte, (size_t)(K + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e2 = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_cov_chunks: bounds readback", hipGetErrorString(e != hipSuccess ? e : e2));
-        for (long long k = 1; k <= K; ++k)
-            if (hr[k] != s.crun.back()) { s.crun.push_back(hr[k]); s.cbyte.push_back(hb[k]); }   // empty chunks dropped
-        if (s.crun.back() != s.R || s.cbyte.back() != s.total) return fail(CL_ERR_HIP, "cl_cov_chunks: bounds do not cover the text");
-    }
-    const long long nc = (long long)s.crun.size() - 1;
-    *n_chunks = nc;
-    if (run_bounds) {
-        if (cap < nc + 1) return fail(CL_ERR_ARG, "cl_cov_chunks: capacity below n_chunks + 1");
-        std::copy(s.crun.begin(), s.crun.end(), run_bounds);
-        std::copy(s.cbyte.begin(), s.cbyte.end(), byte_bounds);
-    }
-    return CL_OK;
+    if (c->cv_txt.R > 0) HIP_TRY(hipSetDevice(c->device));
+    return text_chunks(c->cv_txt, c->stream, budget, k20_lcap(c), cap, run_bounds, byte_bounds, n_chunks, "cl_cov_chunks");
 }
 
 extern "C" int cl_cov_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n_bytes)
@@ -434,32 +376,23 @@ extern "C" int cl_cov_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap,
     if (n_bytes) *n_bytes = 0;
     if (!out || !n_bytes) return fail(CL_ERR_ARG, "cl_cov_render: bad arguments");
     cl_chrom::CovState& s = c->cv;
-    if (!s.built || !s.text || s.crun.empty()) return fail(CL_ERR_ARG, "cl_cov_render: no chunks made on this handle (cl_cov_chunks)");
-    if (chunk < 0 || chunk + 1 >= (int64_t)s.crun.size()) return fail(CL_ERR_ARG, "cl_cov_render: chunk index out of range");
+    TextOut& txt = c->cv_txt;
+    if (!s.built || !s.text || txt.crec.empty()) return fail(CL_ERR_ARG, "cl_cov_render: no chunks made on this handle (cl_cov_chunks)");
+    if (chunk < 0 || chunk + 1 >= (int64_t)txt.crec.size()) return fail(CL_ERR_ARG, "cl_cov_render: chunk index out of range");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_render: asynchronous runs still in flight");
-    const long long r0 = s.crun[chunk], r1 = s.crun[chunk + 1], b0 = s.cbyte[chunk], nb = s.cbyte[chunk + 1] - b0;
-    if (cap < nb) return fail(CL_ERR_ARG, "cl_cov_render: capacity below the chunk's bytes");
+    const TextChunk k = text_chunk(txt, chunk);
+    if (cap < k.nb) return fail(CL_ERR_ARG, "cl_cov_render: capacity below the chunk's bytes");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = c->cv_out.ensure((size_t)nb + 16))) return rc;
-    const long long tiles = (r1 - r0 + K20_T - 1) / K20_T;
+    if ((rc = text_reserve(txt, k.nb))) return rc;
+    const long long tiles = (k.r1 - k.r0 + K20_T - 1) / K20_T;
     const size_t lds = (((size_t)K20_T * k20_lcap(c) + 16 + 15) / 16) * 16;   // the span plus the shift of its first word
-    hipLaunchKernelGGL(k20_render, dim3((unsigned)tiles), dim3(K20_T), lds, c->stream, k20_tpl(c), r0, r1, b0, c->cv_lend.as<long long>(),
-                       c->cv_out.as<char>());
+    hipLaunchKernelGGL(k20_render, dim3((unsigned)tiles), dim3(K20_T), lds, c->stream, k20_tpl(c), k.r0, k.r1, k.b0, txt.end.as<long long>(),
+                       txt.out.as<char>());
     HIP_TRY(hipGetLastError());
-    hipError_t e = hipMemcpyAsync(out, c->cv_out.p, (size_t)nb, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_cov_render: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    *n_bytes = nb;
+    if ((rc = text_copy_out(txt, c->stream, out, k.nb, "cl_cov_render"))) return rc;
+    *n_bytes = k.nb;
     return CL_OK;
 }
 
-extern "C" int cl_cov_free(cl_chrom* c)
-{
-    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_free: asynchronous runs still in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    cov_release(c);
-    return CL_OK;
-}
+extern "C" int cl_cov_free(cl_chrom* c) { return unit_free(c, "cl_cov_free", cov_release); }

@@ -199,7 +199,7 @@ static long long k22_floordiv(long long p, long long res)
     return q - ((p - q * res) < 0 ? 1 : 0);
 }
 
-static void dom_release(cl_chrom* c)
+void dom_release(cl_chrom* c)
 {
     for (DevBuf* b : {&c->dm_diff, &c->dm_trk, &c->dm_tmp, &c->dm_rng, &c->dm_ivs, &c->dm_ive, &c->dm_cnt}) b->release();
     c->dm = cl_chrom::DomState();
@@ -251,13 +251,10 @@ static int dom_tracks(cl_chrom* c, int cut, int res, int w, cl_chrom::DomState& 
     hipLaunchKernelGGL(k22_tracks, dim3((unsigned)(((long long)m + K22_TILE - 1) / K22_TILE)), dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(),
                        c->ag_sy.as<int>(), m, res, w, (int)bmin, (int)nb, c->dm_diff.as<u32>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0;
-    hipError_t e = rocprim::inclusive_scan(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, words, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan size query (domains)", hipGetErrorString(e));
-    if ((rc = c->dm_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->dm_tmp.bytes;
-    e = rocprim::inclusive_scan(c->dm_tmp.p, bytes, c->dm_diff.as<u32>(), c->dm_trk.as<u32>(), words, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan(domains)", hipGetErrorString(e));
+    if ((rc = prim_run(c->dm_tmp, "inclusive_scan(domains)", [&](void* tmp, size_t& bytes) {
+            return rocprim::inclusive_scan(tmp, bytes, c->dm_diff.as<u32>(), c->dm_trk.as<u32>(), words, rocprim::plus<u32>(), c->stream);
+        })))
+        return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     st.bmin = bmin; st.n_bins = nb;
     st.ready = true;
@@ -303,19 +300,15 @@ extern "C" int cl_dom_get(cl_chrom* c, int64_t first, int64_t count, uint32_t* c
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (!c->dm.ready) return fail(CL_ERR_ARG, "cl_dom_get: no tracks on this handle (cl_dom_tracks)");
-    if (first < 0 || count < 0 || first > c->dm.n_bins || count > c->dm.n_bins - first) return fail(CL_ERR_ARG, "cl_dom_get: range outside the bins");
+    if (!range_ok(first, count, c->dm.n_bins)) return fail(CL_ERR_ARG, "cl_dom_get: range outside the bins");
     if (count > 0 && (!cross || !up || !down)) return fail(CL_ERR_ARG, "cl_dom_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_dom_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t stride = (size_t)c->dm.n_bins + 1;
     const u32* trk = c->dm_trk.as<u32>();
-    hipError_t e = hipMemcpyAsync(cross, trk + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(up, trk + stride + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(down, trk + 2 * stride + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_dom_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    const size_t nb = (size_t)count * 4;
+    return read_back(c, "cl_dom_get", {{cross, trk + first, nb}, {up, trk + stride + first, nb}, {down, trk + 2 * stride + first, nb}});
 }
 
 static int dom_count(cl_chrom* c, const int64_t* starts, const int64_t* ends, long long n, uint32_t* intra, uint32_t* nx, uint32_t* ny)
@@ -360,12 +353,4 @@ extern "C" int cl_dom_count(cl_chrom* c, const int64_t* starts, const int64_t* e
     return rc;
 }
 
-extern "C" int cl_dom_free(cl_chrom* c)
-{
-    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_dom_free: asynchronous runs still in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    dom_release(c);
-    return CL_OK;
-}
+extern "C" int cl_dom_free(cl_chrom* c) { return unit_free(c, "cl_dom_free", dom_release); }

@@ -179,6 +179,11 @@ k12_ovf_pairs(const u32* __restrict__ ov, int k, int* __restrict__ s, u32* __res
 static int k12_grid(long long n) { return (int)std::max(1ll, std::min<long long>(K12_GRID, (n + TPB - 1) / TPB)); }
 
 // ---- K12 host entry point -----------------------------------------------------------------------
+void fp_release(cl_chrom* c)
+{
+    for (DevBuf* b : {&c->fp_small, &c->fp_keys, &c->fp_sorted, &c->fp_tmp, &c->fp_pairs}) b->release();
+}
+
 static int contact_hist(cl_chrom* c, int cut, int bin_size, int64_t cap, int64_t* values, int64_t* mult, int64_t* n_distinct,
                         int64_t* n_cells, int64_t* n_kept, int32_t* min_c)
 {
@@ -207,13 +212,10 @@ static int contact_hist(cl_chrom* c, int cut, int bin_size, int64_t cap, int64_t
     hipLaunchKernelGGL(k12_keys, dim3(k12_grid((n + K12_ITEMS - 1) / K12_ITEMS)), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, cut, minc, dv, b, m, s,
                        c->fp_keys.as<u64>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (size_t)m, 0, 2 * b, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query", hipGetErrorString(e));
-    if ((rc = c->fp_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->fp_tmp.bytes;
-    e = rocprim::radix_sort_keys(c->fp_tmp.p, bytes, c->fp_keys.as<u64>(), c->fp_sorted.as<u64>(), (size_t)m, 0, 2 * b, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(cells)", hipGetErrorString(e));
+    if ((rc = prim_run(c->fp_tmp, "radix_sort_keys(cells)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->fp_keys.as<u64>(), c->fp_sorted.as<u64>(), (size_t)m, 0, 2 * b, c->stream);
+        })))
+        return rc;
     // run lengths -> LDS histogram + overflow list (fp_keys is free again: the overflow list lives there)
     const int ovf_cap = m / K12_HB + 1;
     u32* ovf = (u32*)c->fp_keys.p;                                    // ovf_cap u32 <= m * 8 bytes
@@ -230,13 +232,10 @@ static int contact_hist(cl_chrom* c, int cut, int bin_size, int64_t cap, int64_t
     u32* pv = c->fp_pairs.as<u32>();
     u32* pm = pv + pcap;
     if (novf > 0) {
-        bytes = 0;
-        e = rocprim::radix_sort_keys(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, (size_t)novf, 0, 32, c->stream);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query", hipGetErrorString(e));
-        if ((rc = c->fp_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-        bytes = c->fp_tmp.bytes;
-        e = rocprim::radix_sort_keys(c->fp_tmp.p, bytes, ovf, ovs, (size_t)novf, 0, 32, c->stream);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(overflow)", hipGetErrorString(e));
+        if ((rc = prim_run(c->fp_tmp, "radix_sort_keys(overflow)", [&](void* tmp, size_t& bytes) {
+                return rocprim::radix_sort_keys(tmp, bytes, ovf, ovs, (size_t)novf, 0, 32, c->stream);
+            })))
+            return rc;
         hipLaunchKernelGGL(k12_ovf_pairs, dim3(k12_grid(novf)), dim3(TPB), 0, c->stream, ovs, novf, s, pv, pm, pcap);
         HIP_TRY(hipGetLastError());
     }
@@ -283,6 +282,6 @@ extern "C" int cl_contact_hist(cl_chrom* c, int32_t cut, int32_t bin_size, int64
     HIP_TRY(hipSetDevice(c->device));
     const int rc = contact_hist(c, cut, bin_size, cap, values, mult, n_distinct, n_cells, n_kept, min_c);
     if (rc != CL_OK) (void)hipStreamSynchronize(c->stream);          // nothing of ours may still be running when the scratch goes
-    for (DevBuf* b : {&c->fp_small, &c->fp_keys, &c->fp_sorted, &c->fp_tmp, &c->fp_pairs}) b->release();
+    fp_release(c);
     return rc;
 }

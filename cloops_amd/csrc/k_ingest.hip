@@ -606,13 +606,10 @@ static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* 
     HIP_TRY(hipMemsetAsync(c->err.as<u32>() + 7, 0x7f, 4, c->stream));
     hipLaunchKernelGGL(k15_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
-    size_t bytes_tmp = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes_tmp, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan size query", hipGetErrorString(e));
-    if ((rc = ingest_scan_tmp(c, bytes_tmp))) return rc;
-    bytes_tmp = c->tmp.bytes;
-    e = rocprim::exclusive_scan(c->tmp.p, bytes_tmp, c->tcnt.as<u32>(), c->toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(tiles)", hipGetErrorString(e));
+    if ((rc = prim_run(c->tmp, "exclusive_scan(tiles)", [&](void* tmp, size_t& nb) {
+            return rocprim::exclusive_scan(tmp, nb, c->tcnt.as<u32>(), c->toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
+        })))
+        return rc;
     u32 nl = 0;
     if ((rc = ingest_read(c, &nl, c->toff.as<u32>() + tiles))) return rc;
     const long long L = nl;                                             // >= 1: the chunk ends with a '\n'
@@ -731,15 +728,9 @@ extern "C" int cl_ingest_names(cl_ingest* c, cl_ingest_name* out, int64_t cap, i
 
 static int ingest_sort_pairs_u32(cl_ingest* c, u32* ki, u32* ko, u32* vi, u32* vo, size_t n, unsigned bits)
 {
-    size_t bytes_tmp = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes_tmp, ki, ko, vi, vo, n, 0, bits, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs size query", hipGetErrorString(e));
-    int rc;
-    if ((rc = ingest_scan_tmp(c, bytes_tmp))) return rc;
-    bytes_tmp = c->tmp.bytes;
-    e = rocprim::radix_sort_pairs(c->tmp.p, bytes_tmp, ki, ko, vi, vo, n, 0, bits, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs", hipGetErrorString(e));
-    return CL_OK;
+    return prim_run(c->tmp, "radix_sort_pairs", [&](void* tmp, size_t& nb) {
+        return rocprim::radix_sort_pairs(tmp, nb, ki, ko, vi, vo, n, 0, bits, c->stream);
+    });
 }
 
 extern "C" int cl_ingest_commit(cl_ingest* c, int64_t chunk, int64_t line0, const uint64_t* hashes, const int32_t* ids, const uint32_t* name_off,
@@ -843,13 +834,11 @@ static int ingest_unique(cl_ingest* c, K16Chrom* h)
     size_t bytes_tmp = 0;
     const u32* rows = nullptr;
     if (!wide) {                                                        // one packed key of 62 bits
-        e = rocprim::radix_sort_pairs(nullptr, bytes_tmp, (u64*)nullptr, (u64*)nullptr, (u32*)nullptr, (u32*)nullptr, (size_t)n, 0, 62, c->stream);
-        if (e == hipSuccess && (rc = ingest_scan_tmp(c, bytes_tmp)) == CL_OK) {
-            bytes_tmp = c->tmp.bytes;
-            e = rocprim::radix_sort_pairs(c->tmp.p, bytes_tmp, k0.as<u64>(), k1.as<u64>(), v0.as<u32>(), v1.as<u32>(), (size_t)n, 0, 62, c->stream);
-        }
+        rc = prim_run(c->tmp, "cl_ingest_finish: radix_sort_pairs", [&](void* tmp, size_t& nb) {
+            return rocprim::radix_sort_pairs(tmp, nb, k0.as<u64>(), k1.as<u64>(), v0.as<u32>(), v1.as<u32>(), (size_t)n, 0, 62, c->stream);
+        });
         rows = v1.as<u32>();
-    } else {                                                            // any int64: by cB, then (stable) by cA
+    } else {                                                            // any int64: by cB, then (stable) by cA; sized once for the two sorts
         e = rocprim::radix_sort_pairs(nullptr, bytes_tmp, (long long*)nullptr, (long long*)nullptr, (u32*)nullptr, (u32*)nullptr, (size_t)n, 0, 64, c->stream);
         if (e == hipSuccess && (rc = ingest_scan_tmp(c, bytes_tmp)) == CL_OK) {
             bytes_tmp = c->tmp.bytes;
@@ -865,14 +854,10 @@ static int ingest_unique(cl_ingest* c, K16Chrom* h)
     if (rc != CL_OK) { drop(); return rc; }
     if (e != hipSuccess) { drop(); return fail(CL_ERR_HIP, "cl_ingest_finish: radix_sort_pairs", hipGetErrorString(e)); }
     hipLaunchKernelGGL(k16_mark, dim3(k16_grid(n)), dim3(TPB), 0, c->stream, h->a.as<long long>(), h->b.as<long long>(), rows, n, keep.as<u32>());
-    bytes_tmp = 0;
-    e = rocprim::exclusive_scan(nullptr, bytes_tmp, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)n, rocprim::plus<u32>(), c->stream);
-    if (e == hipSuccess && (rc = ingest_scan_tmp(c, bytes_tmp)) == CL_OK) {
-        bytes_tmp = c->tmp.bytes;
-        e = rocprim::exclusive_scan(c->tmp.p, bytes_tmp, keep.as<u32>(), pos.as<u32>(), 0u, (size_t)n, rocprim::plus<u32>(), c->stream);
-    }
+    rc = prim_run(c->tmp, "cl_ingest_finish: exclusive_scan", [&](void* tmp, size_t& nb) {
+        return rocprim::exclusive_scan(tmp, nb, keep.as<u32>(), pos.as<u32>(), 0u, (size_t)n, rocprim::plus<u32>(), c->stream);
+    });
     if (rc != CL_OK) { drop(); return rc; }
-    if (e != hipSuccess) { drop(); return fail(CL_ERR_HIP, "cl_ingest_finish: exclusive_scan", hipGetErrorString(e)); }
     u32 lastp = 0, lastk = 0;
     e = hipMemcpyAsync(&lastk, keep.as<u32>() + (n - 1), 4, hipMemcpyDeviceToHost, c->stream);
     if (e != hipSuccess || (rc = ingest_read(c, &lastp, pos.as<u32>() + (n - 1)))) { drop(); return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: copy") : rc; }
@@ -969,16 +954,12 @@ extern "C" int cl_ingest_finish(cl_ingest* c, cl_ingest* other, int32_t n_ids, i
         if (e != hipSuccess || (rc = ingest_read(c, &nd, dcnt))) { drop(); return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: memset") : rc; }
         if (nd > 0) {
             if ((rc = sk.ensure((size_t)nd * 8)) || (rc = c->dist.ensure((size_t)nd * 8))) { drop(); return rc; }
-            size_t bytes_tmp = 0;
-            e = rocprim::radix_sort_pairs(nullptr, bytes_tmp, (long long*)nullptr, (long long*)nullptr, (long long*)nullptr, (long long*)nullptr, (size_t)nd, 0, 64,
-                                          c->stream);
-            if (e == hipSuccess && (rc = ingest_scan_tmp(c, bytes_tmp)) == CL_OK) {
-                bytes_tmp = c->tmp.bytes;
-                e = rocprim::radix_sort_pairs(c->tmp.p, bytes_tmp, dk.as<long long>(), sk.as<long long>(), dv.as<long long>(), c->dist.as<long long>(), (size_t)nd,
-                                              0, 64, c->stream);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            rc = prim_run(c->tmp, "cl_ingest_finish: distances", [&](void* tmp, size_t& nb) {
+                return rocprim::radix_sort_pairs(tmp, nb, dk.as<long long>(), sk.as<long long>(), dv.as<long long>(), c->dist.as<long long>(), (size_t)nd, 0,
+                                                 64, c->stream);
+            });
             if (rc != CL_OK) { drop(); return rc; }
+            e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) { drop(); return fail(CL_ERR_HIP, "cl_ingest_finish: distances", hipGetErrorString(e)); }
         }
         c->n_dist = (long long)nd;

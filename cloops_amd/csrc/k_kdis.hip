@@ -128,7 +128,7 @@ k23_hist(const int* __restrict__ d, int m, u64* __restrict__ out)
 }
 
 // ---- K23 host side ------------------------------------------------------------------------------
-static void kdis_release(cl_chrom* c)
+void kdis_release(cl_chrom* c)
 {
     for (DevBuf* b : {&c->kd_x, &c->kd_y, &c->kd_d, &c->kd_hist}) b->release();
     c->kd = cl_chrom::KdisState();
@@ -203,19 +203,14 @@ extern "C" int cl_kdis_get(cl_chrom* c, int32_t which, int64_t first, int64_t co
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (!c->kd.ready) return fail(CL_ERR_ARG, "cl_kdis_get: no k-distances on this handle (cl_kdis_build)");
     if (which < 0 || which >= c->kd.n_k) return fail(CL_ERR_ARG, "cl_kdis_get: which outside the ks of the build");
-    if (first < 0 || count < 0 || first > c->kd.n_kept || count > c->kd.n_kept - first) return fail(CL_ERR_ARG, "cl_kdis_get: range outside the kept rows");
+    if (!range_ok(first, count, c->kd.n_kept)) return fail(CL_ERR_ARG, "cl_kdis_get: range outside the kept rows");
     if (count > 0 && (!x || !y || !d)) return fail(CL_ERR_ARG, "cl_kdis_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_kdis_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)count * 4;
     const int* dk = c->kd_d.as<int>() + (size_t)which * (size_t)c->kd.n_kept;
-    hipError_t e = hipMemcpyAsync(x, c->kd_x.as<int>() + first, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(y, c->kd_y.as<int>() + first, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, dk + first, bytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_kdis_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    return read_back(c, "cl_kdis_get", {{x, c->kd_x.as<int>() + first, bytes}, {y, c->kd_y.as<int>() + first, bytes}, {d, dk + first, bytes}});
 }
 
 extern "C" int cl_kdis_hist(cl_chrom* c, int32_t which, uint64_t* hist, uint64_t* n_zero, uint64_t* n_none)
@@ -233,20 +228,10 @@ extern "C" int cl_kdis_hist(cl_chrom* c, int32_t which, uint64_t* hist, uint64_t
     static_assert(sizeof(uint64_t) == sizeof(u64), "the histogram is copied as it lies");
     const u64* src = c->kd_hist.as<u64>() + (size_t)which * (CL_KDIS_BINS + 2);
     uint64_t tail[2] = {0, 0};
-    hipError_t e = hipMemcpyAsync(hist, src, (size_t)CL_KDIS_BINS * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(tail, src + CL_KDIS_BINS, 16, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);                      // (no copy to the stack may still be pending)
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_kdis_hist: copy", hipGetErrorString(e != hipSuccess ? e : e2));
+    const int rc = read_back(c, "cl_kdis_hist", {{hist, src, (size_t)CL_KDIS_BINS * 8}, {tail, src + CL_KDIS_BINS, 16}});
+    if (rc) return rc;                                                          // (synchronised: no copy to the stack is pending)
     *n_zero = tail[0]; *n_none = tail[1];
     return CL_OK;
 }
 
-extern "C" int cl_kdis_free(cl_chrom* c)
-{
-    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_kdis_free: asynchronous runs still in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    kdis_release(c);
-    return CL_OK;
-}
+extern "C" int cl_kdis_free(cl_chrom* c) { return unit_free(c, "cl_kdis_free", kdis_release); }

@@ -260,7 +260,7 @@ static int k24_knob(const char* name)
 
 static int k24_cut(int64_t cut) { return cut <= 0 ? 0 : (int)std::min<int64_t>(cut, 1ll << 30); }   // |Y - X| < 2^30: a larger cut keeps no row either
 
-static void mat_release(cl_chrom* c)
+void mat_release(cl_chrom* c)
 {
     for (DevBuf* b : {&c->mx_out, &c->mx_ctr, &c->mx_key, &c->mx_sorted, &c->mx_tmp, &c->mx_flag, &c->mx_scan, &c->mx_start,
                       &c->mx_bx, &c->mx_by, &c->mx_cnt}) b->release();
@@ -403,20 +403,16 @@ static int mat_cells(cl_chrom* c, int res, bool fold, cl_chrom::MatState& st)
     const K24Bin b = k24_binning(res);
     LAUNCH(k24_keys, m, c->ag_sx.as<u32>(), c->ag_sy.as<int>(), m, b, (int)bmin, bits, fold ? 1 : 0, c->mx_key.as<u64>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0, sbytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, sm, 0, 2 * bits, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query (matrix cells)", hipGetErrorString(e));
-    e = rocprim::exclusive_scan(nullptr, sbytes, (u32*)nullptr, (u32*)nullptr, 0u, sm + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan size query (matrix cells)", hipGetErrorString(e));
-    if ((rc = c->mx_tmp.ensure(std::max<size_t>(std::max(bytes, sbytes), 16)))) return rc;
-    bytes = c->mx_tmp.bytes;
-    e = rocprim::radix_sort_keys(c->mx_tmp.p, bytes, c->mx_key.as<u64>(), c->mx_sorted.as<u64>(), sm, 0, 2 * bits, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(matrix cells)", hipGetErrorString(e));
+    if ((rc = prim_run(c->mx_tmp, "radix_sort_keys(matrix cells)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->mx_key.as<u64>(), c->mx_sorted.as<u64>(), sm, 0, 2 * bits, c->stream);
+        })))
+        return rc;
     LAUNCH(k24_heads, (long long)m + 1, c->mx_sorted.as<u64>(), m, c->mx_flag.as<u32>());
     HIP_TRY(hipGetLastError());
-    sbytes = c->mx_tmp.bytes;
-    e = rocprim::exclusive_scan(c->mx_tmp.p, sbytes, c->mx_flag.as<u32>(), c->mx_scan.as<u32>(), 0u, sm + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(matrix cells)", hipGetErrorString(e));
+    if ((rc = prim_run(c->mx_tmp, "exclusive_scan(matrix cells)", [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->mx_flag.as<u32>(), c->mx_scan.as<u32>(), 0u, sm + 1, rocprim::plus<u32>(), c->stream);
+        })))
+        return rc;
     u32 nc = 0;
     HIP_TRY(hipMemcpyAsync(&nc, c->mx_scan.as<u32>() + sm, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -472,26 +468,14 @@ extern "C" int cl_mat_cells_get(cl_chrom* c, int64_t first, int64_t count, int32
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (!c->mx.ready) return fail(CL_ERR_ARG, "cl_mat_cells_get: no cells on this handle (cl_mat_cells)");
-    if (first < 0 || count < 0 || first > c->mx.n_cells || count > c->mx.n_cells - first) return fail(CL_ERR_ARG, "cl_mat_cells_get: range outside the cells");
+    if (!range_ok(first, count, c->mx.n_cells)) return fail(CL_ERR_ARG, "cl_mat_cells_get: range outside the cells");
     if (count > 0 && (!bx || !by || !cnt)) return fail(CL_ERR_ARG, "cl_mat_cells_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_mat_cells_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)count * 4;
-    hipError_t e = hipMemcpyAsync(bx, c->mx_bx.as<int>() + first, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(by, c->mx_by.as<int>() + first, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt, c->mx_cnt.as<u32>() + first, bytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_mat_cells_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    return read_back(c, "cl_mat_cells_get", {{bx, c->mx_bx.as<int>() + first, bytes}, {by, c->mx_by.as<int>() + first, bytes},
+                                             {cnt, c->mx_cnt.as<u32>() + first, bytes}});
 }
 
-extern "C" int cl_mat_free(cl_chrom* c)
-{
-    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_mat_free: asynchronous runs still in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    mat_release(c);
-    return CL_OK;
-}
+extern "C" int cl_mat_free(cl_chrom* c) { return unit_free(c, "cl_mat_free", mat_release); }

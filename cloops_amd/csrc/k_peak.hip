@@ -233,7 +233,7 @@ k21_summit_out(const u64* __restrict__ best, const long long* __restrict__ ivs, 
 // ---- K21 host side ------------------------------------------------------------------------------
 static int k21_grid(long long work) { return (int)std::max(1ll, std::min<long long>(4096, (work + TPB - 1) / TPB)); }
 
-static void peak_release(cl_chrom* c)
+void peak_release(cl_chrom* c)
 {
     for (DevBuf* b : {&c->pk_kin, &c->pk_key, &c->pk_tmp, &c->pk_lo, &c->pk_hi, &c->pk_flag, &c->pk_C, &c->pk_head, &c->pk_H, &c->pk_a,
                       &c->pk_b, &c->pk_start, &c->pk_end, &c->pk_np, &c->pk_nc, &c->pk_ctr, &c->pk_ivs, &c->pk_ive, &c->pk_best,
@@ -244,15 +244,9 @@ static void peak_release(cl_chrom* c)
 
 static int peak_scan(cl_chrom* c, const u32* in, u32* out, size_t n, const char* what)
 {
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, 0u, n, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, what, hipGetErrorString(e));
-    int rc;
-    if ((rc = c->pk_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->pk_tmp.bytes;
-    e = rocprim::exclusive_scan(c->pk_tmp.p, bytes, in, out, 0u, n, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, what, hipGetErrorString(e));
-    return CL_OK;
+    return prim_run(c->pk_tmp, what, [&](void* tmp, size_t& bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<u32>(), c->stream);
+    });
 }
 
 static int peak_sort(cl_chrom* c, long long cut, int ends, int64_t* n_ends, int64_t* vmin, int64_t* vmax)
@@ -276,13 +270,10 @@ static int peak_sort(cl_chrom* c, long long cut, int ends, int64_t* n_ends, int6
     if (m > (long long)n * ne) return fail(CL_ERR_HIP, "cl_peak_sort: the key pass counted more end points than rows allow");
     c->pk.base = base;
     if (m == 0) { c->pk.sorted = true; return CL_OK; }
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, (size_t)m, 0, ebit, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query (peaks)", hipGetErrorString(e));
-    if ((rc = c->pk_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->pk_tmp.bytes;
-    e = rocprim::radix_sort_keys(c->pk_tmp.p, bytes, c->pk_kin.as<u32>(), c->pk_key.as<u32>(), (size_t)m, 0, ebit, c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(peaks)", hipGetErrorString(e));
+    if ((rc = prim_run(c->pk_tmp, "radix_sort_keys(peaks)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->pk_kin.as<u32>(), c->pk_key.as<u32>(), (size_t)m, 0, ebit, c->stream);
+        })))
+        return rc;
     u32 k0 = 0, k1 = 0;
     HIP_TRY(hipMemcpyAsync(&k0, c->pk_key.as<u32>(), 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&k1, c->pk_key.as<u32>() + (m - 1), 4, hipMemcpyDeviceToHost, c->stream));
@@ -397,18 +388,14 @@ extern "C" int cl_peak_get(cl_chrom* c, int64_t first, int64_t count, int32_t* s
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (!c->pk.sorted || !c->pk.called) return fail(CL_ERR_ARG, "cl_peak_get: no peaks called on this handle (cl_peak_sort, cl_peak_call)");
-    if (first < 0 || count < 0 || first > c->pk.P || count > c->pk.P - first) return fail(CL_ERR_ARG, "cl_peak_get: range outside the peaks");
+    if (!range_ok(first, count, c->pk.P)) return fail(CL_ERR_ARG, "cl_peak_get: range outside the peaks");
     if (count > 0 && (!start || !end || !n_points || !n_cores)) return fail(CL_ERR_ARG, "cl_peak_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_peak_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    hipError_t e = hipMemcpyAsync(start, c->pk_start.as<int>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(end, c->pk_end.as<int>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_points, c->pk_np.as<u32>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_cores, c->pk_nc.as<u32>() + first, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_peak_get: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    return CL_OK;
+    const size_t nb = (size_t)count * 4;
+    return read_back(c, "cl_peak_get", {{start, c->pk_start.as<int>() + first, nb}, {end, c->pk_end.as<int>() + first, nb},
+                                        {n_points, c->pk_np.as<u32>() + first, nb}, {n_cores, c->pk_nc.as<u32>() + first, nb}});
 }
 
 // the n intervals of a count / summit call on the device (c->pk_ivs, c->pk_ive)
@@ -489,12 +476,4 @@ extern "C" int cl_peak_summits(cl_chrom* c, const int64_t* starts, const int64_t
     return rc;
 }
 
-extern "C" int cl_peak_free(cl_chrom* c)
-{
-    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_peak_free: asynchronous runs still in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    peak_release(c);
-    return CL_OK;
-}
+extern "C" int cl_peak_free(cl_chrom* c) { return unit_free(c, "cl_peak_free", peak_release); }

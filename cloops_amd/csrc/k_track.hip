@@ -1,5 +1,6 @@
 // k_track.hip -- K14: browser-track text of the PETs of a resident chromosome (cLoops/io.py jd2washU / jd2hic) rendered on the
 // device -- kernels and C entry points.
+#define CL_TEXTOUT_KERNELS                // k14_bounds is defined in this unit
 #include "cl_chrom.h"
 #include "cl_text.h"
 
@@ -22,8 +23,10 @@
 //   k14_render                one chunk: every workgroup renders 256 consecutive lines into LDS (one line per lane), placed so
 //                             that LDS and the output agree modulo 16, then writes the tile's byte span with 16-byte stores
 //                             (byte stores only in the two words it shares with its neighbours)
-// Scratch (c->tk_*) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables: it lives from
-// cl_track_build to the next build, cl_track_free or the handle's destruction.
+// k14_bounds, the tile bounds and span flush of k14_render and the host side of the text (running sum, chunks, copy-out) are
+// cl_textout.h's, shared with K20 and K15.
+// Scratch (c->tk_*, the text in c->tk_txt) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables:
+// it lives from cl_track_build to the next build, cl_track_free or the handle's destruction.
 #define K14_ITEMS 8                     // rows per thread of the filter passes
 #define K14_ROWS (TPB * K14_ITEMS)      // rows per tile: 2048
 #define K14_T 256                       // lines per render tile (one per lane)
@@ -160,27 +163,6 @@ k14_lens(K14Tpl t, long long R, long long* __restrict__ len)
     }
 }
 
-// bounds of chunk k: the first line starting at or after k * step (line j starts at end[j - 1]), and its byte offset
-__global__ void __launch_bounds__(TPB)
-k14_bounds(const long long* __restrict__ end, long long R, long long step, long long K, long long* __restrict__ brec,
-           long long* __restrict__ bbyte)
-{
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k > K) return;
-    long long rec = 0;
-    if (k > 0) {
-        const long long T = k * step;
-        long long lo = 0, len = R;                                      // first i with end[i] >= T
-        while (len > 0) {
-            const long long h = len >> 1;
-            if (end[lo + h] < T) { lo += h + 1; len -= h + 1; } else len = h;
-        }
-        rec = lo + 1 < R ? lo + 1 : R;
-    }
-    brec[k] = rec;
-    bbyte[k] = rec > 0 ? end[rec - 1] : 0;
-}
-
 // lines [r0, r1) of the track (byte b0 = the start of line r0) -> out[0 ..); K14_T lines per workgroup, staged in LDS
 template <int KIND>
 __global__ void __launch_bounds__(K14_T)
@@ -189,18 +171,15 @@ k14_render(K14Tpl t, long long r0, long long r1, long long b0, const long long* 
     extern __shared__ uint4 k14_lds[];
     __shared__ char nm[2 * K14_NAME_MAX];
     char* buf = (char*)k14_lds;
-    const long long q0 = r0 + (long long)blockIdx.x * K14_T;
-    const long long q1 = q0 + K14_T < r1 ? q0 + K14_T : r1;
     for (int k = threadIdx.x; k < 2 * K14_NAME_MAX; k += blockDim.x) nm[k] = t.names[k];
-    const long long g0 = (q0 > 0 ? end[q0 - 1] : 0) - b0, g1 = end[q1 - 1] - b0;   // the tile's span in out
-    const long long a0 = g0 & ~15ll;                                    // LDS byte i <-> out byte a0 + i
+    const TextTile tile = text_tile(end, r0, r1, b0, K14_T);
     __syncthreads();
-    const long long j = q0 + threadIdx.x;
-    if (j < q1) {
+    const long long j = tile.q0 + threadIdx.x;
+    if (j < tile.q1) {
         K14F f;
         int side;
         k14_fields<KIND>(t, j, f, side);
-        int p = (int)((j > 0 ? end[j - 1] : 0) - b0 - a0);
+        int p = (int)((j > 0 ? end[j - 1] : 0) - b0 - tile.a0);
         if (KIND == CL_TRACK_WASHU) {
             const char* own = side ? nm + K14_NAME_MAX : nm;
             const char* par = side ? nm : nm + K14_NAME_MAX;
@@ -223,17 +202,7 @@ k14_render(K14Tpl t, long long r0, long long r1, long long b0, const long long* 
         }
     }
     __syncthreads();
-    // the span [g0, g1) as 16-byte words of out: whole words with one store each, the two edge words byte by byte
-    const long long w0 = g0 >> 4, w1 = (g1 + 15) >> 4;
-    for (long long w = w0 + threadIdx.x; w < w1; w += blockDim.x) {
-        const long long b = w << 4;
-        if (b >= g0 && b + 16 <= g1) {
-            *(uint4*)(out + b) = k14_lds[(b - a0) >> 4];
-        } else {
-            const long long s = b > g0 ? b : g0, e = b + 16 < g1 ? b + 16 : g1;
-            for (long long i = s; i < e; ++i) out[i] = buf[i - a0];
-        }
-    }
+    text_flush(out, k14_lds, tile.g0, tile.g1, tile.a0);
 }
 
 // ---- K14 host side ------------------------------------------------------------------------------
@@ -258,11 +227,11 @@ static K14Tpl k14_tpl(cl_chrom* c)
 
 static int k14_grid(long long work) { return (int)std::max(1ll, std::min<long long>(4096, (work + TPB - 1) / TPB)); }
 
-static void track_release(cl_chrom* c)
+void track_release(cl_chrom* c)
 {
-    for (DevBuf* b : {&c->tk_tcnt, &c->tk_toff, &c->tk_row, &c->tk_keys, &c->tk_sorted, &c->tk_len, &c->tk_end, &c->tk_tmp,
-                      &c->tk_ids, &c->tk_names, &c->tk_bnd, &c->tk_out})
+    for (DevBuf* b : {&c->tk_tcnt, &c->tk_toff, &c->tk_row, &c->tk_keys, &c->tk_sorted, &c->tk_tmp, &c->tk_ids, &c->tk_names})
         b->release();
+    text_release(c->tk_txt);
     c->tk = cl_chrom::TrackState();
 }
 
@@ -286,13 +255,10 @@ static int track_build(cl_chrom* c, const int64_t* ids, std::vector<char>& hn, i
     HIP_TRY(hipMemsetAsync(c->tk_tcnt.as<u32>() + tiles, 0, 4, c->stream));
     hipLaunchKernelGGL(k14_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, (long long)s.cut, c->tk_tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, (u32*)nullptr, (u32*)nullptr, 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan size query", hipGetErrorString(e));
-    if ((rc = c->tk_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->tk_tmp.bytes;
-    e = rocprim::exclusive_scan(c->tk_tmp.p, bytes, c->tk_tcnt.as<u32>(), c->tk_toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(tiles)", hipGetErrorString(e));
+    if ((rc = prim_run(c->tk_tmp, "exclusive_scan(tiles)", [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->tk_tcnt.as<u32>(), c->tk_toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
+        })))
+        return rc;
     hipLaunchKernelGGL(k14_compact, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, (long long)s.cut, c->tk_toff.as<u32>(),
                        c->tk_row.as<u32>());
     HIP_TRY(hipGetLastError());
@@ -300,7 +266,6 @@ static int track_build(cl_chrom* c, const int64_t* ids, std::vector<char>& hn, i
     HIP_TRY(hipMemcpyAsync(&m, c->tk_toff.as<u32>() + tiles, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const long long R = s.kind == CL_TRACK_WASHU ? 2ll * m : (long long)m;
-    s.R = R;
     if (R == 0) { s.built = true; *n_records = 0; *n_bytes = 0; return CL_OK; }
     // washU: records in key order (p, generation), sorted over the bits in use
     if (s.kind == CL_TRACK_WASHU) {
@@ -311,36 +276,23 @@ static int track_build(cl_chrom* c, const int64_t* ids, std::vector<char>& hn, i
         hipLaunchKernelGGL(k14_keys, dim3(k14_grid(m)), dim3(TPB), 0, c->stream, c->tk_row.as<u32>(), (long long)m, c->d_x, c->d_y, pmin,
                            s.gbits, c->tk_keys.as<u64>());
         HIP_TRY(hipGetLastError());
-        bytes = 0;
-        e = rocprim::radix_sort_keys(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (size_t)R, 0, ebit, c->stream);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query", hipGetErrorString(e));
-        if ((rc = c->tk_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-        bytes = c->tk_tmp.bytes;
-        e = rocprim::radix_sort_keys(c->tk_tmp.p, bytes, c->tk_keys.as<u64>(), c->tk_sorted.as<u64>(), (size_t)R, 0, ebit, c->stream);
-        if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(track)", hipGetErrorString(e));
+        if ((rc = prim_run(c->tk_tmp, "radix_sort_keys(track)", [&](void* tmp, size_t& bytes) {
+                return rocprim::radix_sort_keys(tmp, bytes, c->tk_keys.as<u64>(), c->tk_sorted.as<u64>(), (size_t)R, 0, ebit, c->stream);
+            })))
+            return rc;
     }
     // line lengths and their running sum
-    if ((rc = c->tk_len.ensure((size_t)R * 8)) || (rc = c->tk_end.ensure((size_t)R * 8))) return rc;
+    TextOut& txt = c->tk_txt;
+    if ((rc = txt.len.ensure((size_t)R * 8)) || (rc = txt.end.ensure((size_t)R * 8))) return rc;
     if (s.kind == CL_TRACK_WASHU)
-        hipLaunchKernelGGL(k14_lens<CL_TRACK_WASHU>, dim3(k14_grid(R)), dim3(TPB), 0, c->stream, k14_tpl(c), R, c->tk_len.as<long long>());
+        hipLaunchKernelGGL(k14_lens<CL_TRACK_WASHU>, dim3(k14_grid(R)), dim3(TPB), 0, c->stream, k14_tpl(c), R, txt.len.as<long long>());
     else
-        hipLaunchKernelGGL(k14_lens<CL_TRACK_JUICE>, dim3(k14_grid(R)), dim3(TPB), 0, c->stream, k14_tpl(c), R, c->tk_len.as<long long>());
+        hipLaunchKernelGGL(k14_lens<CL_TRACK_JUICE>, dim3(k14_grid(R)), dim3(TPB), 0, c->stream, k14_tpl(c), R, txt.len.as<long long>());
     HIP_TRY(hipGetLastError());
-    bytes = 0;
-    e = rocprim::inclusive_scan(nullptr, bytes, (long long*)nullptr, (long long*)nullptr, (size_t)R, rocprim::plus<long long>(), c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan size query", hipGetErrorString(e));
-    if ((rc = c->tk_tmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->tk_tmp.bytes;
-    e = rocprim::inclusive_scan(c->tk_tmp.p, bytes, c->tk_len.as<long long>(), c->tk_end.as<long long>(), (size_t)R, rocprim::plus<long long>(),
-                                c->stream);
-    if (e != hipSuccess) return fail(CL_ERR_HIP, "inclusive_scan(lines)", hipGetErrorString(e));
-    long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, c->tk_end.as<long long>() + (R - 1), 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    s.total = total;
+    if ((rc = text_scan(txt, c->tk_tmp, R, c->stream)) || (rc = text_total(txt, R, c->stream))) return rc;
     s.built = true;
     *n_records = R;
-    *n_bytes = total;
+    *n_bytes = txt.total;
     return CL_OK;
 }
 
@@ -380,37 +332,8 @@ extern "C" int cl_track_chunks(cl_chrom* c, int64_t budget, int64_t cap, int64_t
     if (!c->tk.built) return fail(CL_ERR_ARG, "cl_track_chunks: no track built on this handle");
     if (budget < k14_lcap(c)) return fail(CL_ERR_ARG, "cl_track_chunks: budget below the longest line the template allows");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_track_chunks: asynchronous runs still in flight");
-    cl_chrom::TrackState& s = c->tk;
-    s.crec.assign(1, 0);
-    s.cbyte.assign(1, 0);
-    if (s.R > 0) {
-        HIP_TRY(hipSetDevice(c->device));
-        const long long step = budget - k14_lcap(c) + 1;
-        const long long K = (s.total + step - 1) / step;
-        int rc;
-        if ((rc = c->tk_bnd.ensure((size_t)(K + 1) * 16))) return rc;
-        long long* brec = c->tk_bnd.as<long long>();
-        long long* bbyte = brec + (K + 1);
-        hipLaunchKernelGGL(k14_bounds, dim3((unsigned)((K + 1 + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->tk_end.as<long long>(), s.R, step, K,
-                           brec, bbyte);
-        HIP_TRY(hipGetLastError());
-        std::vector<long long> hr((size_t)K + 1), hb((size_t)K + 1);
-        hipError_t e = hipMemcpyAsync(hr.data(), brec, (size_t)(K + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), bbyte, (size_t)(K + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t e2 = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_track_chunks: bounds readback", hipGetErrorString(e != hipSuccess ? e : e2));
-        for (long long k = 1; k <= K; ++k)
-            if (hr[k] != s.crec.back()) { s.crec.push_back(hr[k]); s.cbyte.push_back(hb[k]); }   // empty chunks dropped
-        if (s.crec.back() != s.R || s.cbyte.back() != s.total) return fail(CL_ERR_HIP, "cl_track_chunks: bounds do not cover the track");
-    }
-    const long long nc = (long long)s.crec.size() - 1;
-    *n_chunks = nc;
-    if (rec_bounds) {
-        if (cap < nc + 1) return fail(CL_ERR_ARG, "cl_track_chunks: capacity below n_chunks + 1");
-        std::copy(s.crec.begin(), s.crec.end(), rec_bounds);
-        std::copy(s.cbyte.begin(), s.cbyte.end(), byte_bounds);
-    }
-    return CL_OK;
+    if (c->tk_txt.R > 0) HIP_TRY(hipSetDevice(c->device));
+    return text_chunks(c->tk_txt, c->stream, budget, k14_lcap(c), cap, rec_bounds, byte_bounds, n_chunks, "cl_track_chunks");
 }
 
 extern "C" int cl_track_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n_bytes)
@@ -419,36 +342,27 @@ extern "C" int cl_track_render(cl_chrom* c, int64_t chunk, char* out, int64_t ca
     if (n_bytes) *n_bytes = 0;
     if (!out || !n_bytes) return fail(CL_ERR_ARG, "cl_track_render: bad arguments");
     cl_chrom::TrackState& s = c->tk;
-    if (!s.built || s.crec.empty()) return fail(CL_ERR_ARG, "cl_track_render: no chunks made on this handle (cl_track_chunks)");
-    if (chunk < 0 || chunk + 1 >= (int64_t)s.crec.size()) return fail(CL_ERR_ARG, "cl_track_render: chunk index out of range");
+    TextOut& txt = c->tk_txt;
+    if (!s.built || txt.crec.empty()) return fail(CL_ERR_ARG, "cl_track_render: no chunks made on this handle (cl_track_chunks)");
+    if (chunk < 0 || chunk + 1 >= (int64_t)txt.crec.size()) return fail(CL_ERR_ARG, "cl_track_render: chunk index out of range");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_track_render: asynchronous runs still in flight");
-    const long long r0 = s.crec[chunk], r1 = s.crec[chunk + 1], b0 = s.cbyte[chunk], nb = s.cbyte[chunk + 1] - b0;
-    if (cap < nb) return fail(CL_ERR_ARG, "cl_track_render: capacity below the chunk's bytes");
+    const TextChunk k = text_chunk(txt, chunk);
+    if (cap < k.nb) return fail(CL_ERR_ARG, "cl_track_render: capacity below the chunk's bytes");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
-    if ((rc = c->tk_out.ensure((size_t)nb + 16))) return rc;
-    const long long tiles = (r1 - r0 + K14_T - 1) / K14_T;
+    if ((rc = text_reserve(txt, k.nb))) return rc;
+    const long long tiles = (k.r1 - k.r0 + K14_T - 1) / K14_T;
     const size_t lds = (((size_t)K14_T * k14_lcap(c) + 16 + 15) / 16) * 16;   // the span plus the shift of its first word
     if (s.kind == CL_TRACK_WASHU)
-        hipLaunchKernelGGL(k14_render<CL_TRACK_WASHU>, dim3((unsigned)tiles), dim3(K14_T), lds, c->stream, k14_tpl(c), r0, r1, b0,
-                           c->tk_end.as<long long>(), c->tk_out.as<char>());
+        hipLaunchKernelGGL(k14_render<CL_TRACK_WASHU>, dim3((unsigned)tiles), dim3(K14_T), lds, c->stream, k14_tpl(c), k.r0, k.r1, k.b0,
+                           txt.end.as<long long>(), txt.out.as<char>());
     else
-        hipLaunchKernelGGL(k14_render<CL_TRACK_JUICE>, dim3((unsigned)tiles), dim3(K14_T), lds, c->stream, k14_tpl(c), r0, r1, b0,
-                           c->tk_end.as<long long>(), c->tk_out.as<char>());
+        hipLaunchKernelGGL(k14_render<CL_TRACK_JUICE>, dim3((unsigned)tiles), dim3(K14_T), lds, c->stream, k14_tpl(c), k.r0, k.r1, k.b0,
+                           txt.end.as<long long>(), txt.out.as<char>());
     HIP_TRY(hipGetLastError());
-    hipError_t e = hipMemcpyAsync(out, c->tk_out.p, (size_t)nb, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CL_ERR_HIP, "cl_track_render: copy", hipGetErrorString(e != hipSuccess ? e : e2));
-    *n_bytes = nb;
+    if ((rc = text_copy_out(txt, c->stream, out, k.nb, "cl_track_render"))) return rc;
+    *n_bytes = k.nb;
     return CL_OK;
 }
 
-extern "C" int cl_track_free(cl_chrom* c)
-{
-    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_track_free: asynchronous runs still in flight");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    track_release(c);
-    return CL_OK;
-}
+extern "C" int cl_track_free(cl_chrom* c) { return unit_free(c, "cl_track_free", track_release); }
