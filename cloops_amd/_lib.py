@@ -143,6 +143,11 @@ PROTOTYPES = {
     "cl_bal_weights_get": (_int, [_vp, _i64, _i64, _vp]),
     "cl_bal_cells_get": (_int, [_vp, _i64, _i64, _vp]),
     "cl_bal_free": (_int, [_vp]),
+    "cl_exp_diagonals": (_int, [_vp, _vp, _i32, _i64p, _i64p]),
+    "cl_exp_diagonals_get": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "cl_exp_set": (_int, [_vp, _vp, _i64]),
+    "cl_exp_cells_get": (_int, [_vp, _i64, _i64, _vp]),
+    "cl_exp_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

@@ -816,7 +816,8 @@ class Chromosome(_Handle):
         nc, nk, mc = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         _lib.check(self._lib.cl_mat_cells(self._h, int(cut), int(res), 1 if fold else 0, ctypes.byref(nc), ctypes.byref(nk), ctypes.byref(mc)))
         self._mat_cells = int(nc.value)                                      # (a refused call leaves the earlier cells and their number)
-        self._bal_bins = 0                                                   # (K25's state went with the earlier cells)
+        self._bal_bins = 0                                                   # (K25's and K26's state went with the earlier cells)
+        self._exp_diags = 0
         return int(nc.value), int(nk.value), int(mc.value)
 
     def mat_cells_get(self, first=0, count=None):
@@ -844,6 +845,7 @@ class Chromosome(_Handle):
         _lib.check(self._lib.cl_mat_free(self._h))
         self._mat_cells = 0
         self._bal_bins = 0
+        self._exp_diags = 0
 
     def bal_marginals(self, ignore_diags=2):
         """K25: the raw marginals of the folded cells of the last mat_cells(fold=True), kept on the device with the cells' transposed
@@ -852,6 +854,7 @@ class Chromosome(_Handle):
         b0, nb, nu = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
         _lib.check(self._lib.cl_bal_marginals(self._h, int(ignore_diags), ctypes.byref(b0), ctypes.byref(nb), ctypes.byref(nu)))
         self._bal_bins = int(nb.value)
+        self._exp_diags = 0                                                  # (K26's diagonals were those of the earlier marginals)
         return int(b0.value), int(nb.value), int(nu.value)
 
     def bal_marginals_get(self, first=0, count=None):
@@ -871,6 +874,7 @@ class Chromosome(_Handle):
         it, cv, var, sc = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
         _lib.check(self._lib.cl_bal_iterate(self._h, v.ctypes.data_as(ctypes.c_void_p), int(max_iters), float(tol), ctypes.byref(it),
                                             ctypes.byref(cv), ctypes.byref(var), ctypes.byref(sc)))
+        self._exp_diags = 0                                                  # (... and of the earlier weights)
         return int(it.value), bool(cv.value), float(var.value), float(sc.value)
 
     def bal_weights(self, first=0, count=None):
@@ -887,6 +891,49 @@ class Chromosome(_Handle):
         """releases the marginals, weights and device scratch of the bal_* calls; the cells stay  (cl_bal_free)"""
         _lib.check(self._lib.cl_bal_free(self._h))
         self._bal_bins = 0
+        self._exp_diags = 0
+
+    def exp_diagonals(self, valid=None, balanced=True):
+        """K26: per diagonal d = by - bx of the folded cells the valid bin pairs, the count sum and the value sum of the used cells (d >=
+        the ignore_diags of bal_marginals, both bins valid), kept on the device for exp_diagonals_get / exp_set / exp_cells_get.
+        balanced: the weights of the last bal_iterate, a bin being valid iff its weight is a number (valid must be None); else the
+        raw counts over the bins with valid != 0 (None: all bins) -> (nd, n_used)  (cl_exp_diagonals)"""
+        ptr = None
+        if valid is not None:
+            valid = np.asarray(valid)
+            nb = getattr(self, "_bal_bins", 0)
+            if valid.ndim != 1 or len(valid) != nb:
+                raise ValueError("exp_diagonals: the mask needs one entry per bin (%d), got shape %s" % (nb, valid.shape))
+            v = np.ascontiguousarray(valid != 0, dtype=np.uint32)
+            ptr = _vp(v)
+        nd, nu = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_exp_diagonals(self._h, ptr, 1 if balanced else 0, ctypes.byref(nd), ctypes.byref(nu)))
+        self._exp_diags = int(nd.value)
+        return int(nd.value), int(nu.value)
+
+    def exp_diagonals_get(self, first=0, count=None):
+        """diagonals [first, first + count) of the last exp_diagonals (all from `first` on by default) -> (n_pairs int64, cnt_sum
+        uint64, val_sum float64)  (cl_exp_diagonals_get)"""
+        return self._get(self._lib.cl_exp_diagonals_get, "_exp_diags", first, count, (np.int64, np.uint64, np.float64))
+
+    def exp_set(self, expected):
+        """the expected value of every diagonal of the last exp_diagonals (float64 [nd]; NaN or 0: no O/E on that diagonal), for
+        exp_cells_get.  May be repeated  (cl_exp_set)"""
+        e = np.ascontiguousarray(expected, dtype=np.float64)
+        if e.ndim != 1:
+            raise ValueError("exp_set: the expected values must be one-dimensional")
+        _lib.check(self._lib.cl_exp_set(self._h, _vp(e), len(e)))
+
+    def exp_cells_get(self, first=0, count=None):
+        """the O/E values ((w[bx] cnt) w[by]) / expected[by - bx] of the cells [first, first + count) of mat_cells, in their order ->
+        float64, NaN where the cell is not used or its diagonal has no expected value  (cl_exp_cells_get)"""
+        return self._get(self._lib.cl_exp_cells_get, "_mat_cells", first, count, (np.float64,))[0]
+
+    def exp_free(self):
+        """releases the diagonals, expected values and device scratch of the exp_* calls; cells, marginals and weights stay
+        (cl_exp_free)"""
+        _lib.check(self._lib.cl_exp_free(self._h))
+        self._exp_diags = 0
 
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)

@@ -276,6 +276,18 @@ struct cl_chrom {
         int ignore_diags = 0;
         long long b0 = 0, nb = 0, n_used = 0, n_cells = 0;
     } bl;
+    // K26 (k_expected.hip): the effective weight of every bin (the ICE weight, or 1 on the caller's valid bins; NaN on the others) and
+    // the mask of the valid bins, one bit per bin; the diagonal order of the cells (sort scratch, then d = by - bx, bx - b0 and cnt of
+    // every cell ascending by d, inside a diagonal as the cells lie) and the tiles' carry records; per diagonal the valid pairs, the
+    // count sum and the value sum; the expected values of cl_exp_set; the O/E values of a get.  Kept from cl_exp_diagonals to the next
+    // one, cl_exp_free, anything that releases or rebuilds K25's state (bal_release, cl_bal_marginals, cl_bal_iterate) or destruction
+    DevBuf ex_valid, ex_w, ex_mask, ex_kin, ex_kout, ex_vin, ex_vout, ex_tmp, ex_dk, ex_dx, ex_dc, ex_car, ex_ctr, ex_pairs, ex_cnt, ex_val,
+           ex_exp, ex_out;
+    struct ExpState {
+        bool ready = false, expected = false;                        // the diagonals are built; cl_exp_set has been called since
+        int balanced = 0;
+        long long nd = 0, n_used = 0;
+    } ex;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
@@ -328,8 +340,8 @@ Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
 int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_out);
 // Every analysis unit drops its own state and buffers (k_track.hip, k_cover.hip, k_peak.hip, k_domain.hip, k_kdis.hip,
-// k_matrix.hip, k_balance.hip, k_fingerprint.hip, k_anchor.hip, k_agg.hip): called by the unit's own entry points and by the
-// handle's destruction.  mat_release calls bal_release: K25's weights belong to K24's cells
+// k_matrix.hip, k_balance.hip, k_expected.hip, k_fingerprint.hip, k_anchor.hip, k_agg.hip): called by the unit's own entry points and
+// by the handle's destruction.  mat_release calls bal_release: K25's weights belong to K24's cells; bal_release calls exp_release
 void track_release(cl_chrom* c);
 void cov_release(cl_chrom* c);
 void peak_release(cl_chrom* c);
@@ -337,6 +349,7 @@ void dom_release(cl_chrom* c);
 void kdis_release(cl_chrom* c);
 void mat_release(cl_chrom* c);
 void bal_release(cl_chrom* c);
+void exp_release(cl_chrom* c);
 void fp_release(cl_chrom* c);
 void anchor_release(cl_chrom* c);
 void agg_release(cl_chrom* c);

@@ -595,6 +595,48 @@ int cl_bal_cells_get(cl_chrom* c, int64_t first, int64_t count, double* balanced
 int cl_bal_free(cl_chrom* c);
 
 /*
+ * Expected contacts by distance and observed / expected (K26): per diagonal of the contact matrix the number of valid bin pairs, the
+ * sum of the counts and the sum of the (balanced) values of its cells -- what the P(s) curve and `cooltools expected-cis` are made
+ * of -- and, once the host has decided the expected value of every diagonal, the observed / expected value of every cell.  The
+ * reference has no counterpart, so these definitions are the specification (tests/expected_cases.py restates them in numpy); the
+ * smoothing of the curve, the texts and the files stay on the host (cloops_amd/expected.py).
+ *
+ * Input: the state after cl_mat_cells(c, cut, res, fold = 1) and cl_bal_marginals(c, ignore_diags, ..): the cells (bx, by, cnt), bx <=
+ * by, and the bins b0 .. b0 + nb - 1.  Two modes.  Balanced (balanced = 1): needs a finished cl_bal_iterate; bin i is valid iff its
+ * weight is not NaN, w[i] is that weight, and valid must be NULL.  Raw (balanced = 0): valid is nb words, nonzero meaning valid (NULL:
+ * every bin is valid), and w[i] = 1 on the valid bins.
+ * For every diagonal d = 0 .. nd - 1, nd = nb:
+ *   n_pairs[d] (int64)  = #{ i : 0 <= i, i + d < nb, valid[i] and valid[i + d] }, and 0 for d < ignore_diags;
+ *   cnt_sum[d] (uint64) = the sum of cnt over the USED cells of the diagonal: by - bx == d, d >= ignore_diags, both bins valid;
+ *   val_sum[d] (fp64)   = the sum of (w[bx] cnt) w[by] over the same cells (the order of operations inside a term is K25's).  The terms
+ *                         of a diagonal are added in an order that depends on the cells and nb alone: two calls with the same input give
+ *                         the same bytes; no fp64 atomics.  In raw mode val_sum equals cnt_sum exactly while it is below 2^53;
+ *   *n_used = the number of used cells over all diagonals.
+ * With expected[d] set (cl_exp_set): the O/E of a cell is ((w[bx] cnt) w[by]) / expected[by - bx]; NaN when the cell is not used or
+ * expected[by - bx] is NaN or 0.
+ *
+ * cl_exp_diagonals -- packs the mask to one bit per bin and counts the valid pairs of every diagonal (the autocorrelation of the
+ * mask: nb^2 / 64 and-popcount operations on 64-bit words at most, half of them with a partner word -- some 10^9 at 250 000 bins and
+ * 4 10^12 at CL_BAL_BINS_MAX), builds the diagonal order of the cells (one radix sort of (d, cell index) pairs) and takes the sums
+ * -> *nd, *n_used.
+ * cl_exp_diagonals_get -- the three arrays of the diagonals [first, first + count) inside [0, nd].
+ * cl_exp_set -- the expected value of every diagonal, count == nd; may be called again without another cl_exp_diagonals.
+ * cl_exp_cells_get -- the O/E of the cells [first, first + count) of cl_mat_cells, in their order.
+ * cl_exp_free -- releases the state (the cells, marginals and weights stay).  The next cl_exp_diagonals, cl_bal_marginals,
+ * cl_bal_iterate, cl_bal_free, cl_mat_cells, cl_mat_free and cl_chrom_destroy release it as well.
+ *
+ * nb == 0 is not an error: nd = 0, n_used = 0, and gets of count 0 succeed with NULL arrays.  Errors: CL_ERR_ARG for a NULL handle or
+ * NULL outputs, balanced not 0 or 1, balanced = 1 before cl_bal_iterate or with a mask, any call before cl_bal_marginals, a get or
+ * cl_exp_set before cl_exp_diagonals, cl_exp_cells_get before cl_exp_set, count != nd in cl_exp_set, a range outside the diagonals or
+ * the cells, or runs in flight.
+ */
+int cl_exp_diagonals(cl_chrom* c, const uint32_t* valid, int32_t balanced, int64_t* nd, int64_t* n_used);
+int cl_exp_diagonals_get(cl_chrom* c, int64_t first, int64_t count, int64_t* n_pairs, uint64_t* cnt_sum, double* val_sum);
+int cl_exp_set(cl_chrom* c, const double* expected, int64_t count);
+int cl_exp_cells_get(cl_chrom* c, int64_t first, int64_t count, double* oe);
+int cl_exp_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
