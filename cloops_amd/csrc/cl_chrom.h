@@ -58,7 +58,8 @@ struct K7Part { double sx[2]; double sxx[2]; long long n_all[2]; long long n_pos
 struct cl_chrom {
     long long tmp_n = -1;             // n the rocPRIM temporary storage was last sized for
     DevBuf arena;                     // ONE allocation behind the per-PET workspace of the handle (ensure_workspace): the first
-                                      // run of a handle pays one hipMalloc instead of forty
+                                      // run of a handle pays one hipMalloc instead of forty.  The buffers that adopt a slice of it
+                                      // do not own it and never free it, so the order in which the members die does not matter
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -196,97 +197,115 @@ struct cl_chrom {
     int kde_run = -1;                 // `deq` at the cl_dist_collect that filled them (-1: none): valid while no further run completes
     long long kde_cap = 0, kde_cnt[2] = {0, 0};
     DevBuf sig_tx, sig_ty, sig_tmp, sig_sorttmp, sig_m, sig_win, sig_out;   // K8: sorted PET tables, windows, counts
-    DevBuf fp_small, fp_keys, fp_sorted, fp_tmp, fp_pairs;       // K12 (k_fingerprint.hip): scratch of one call, freed when it returns
-    DevBuf an_s, an_e, an_dir, an_mask, an_wsum;                 // K13 (k_anchor.hip): anchors, directory, row mask, workgroup totals; kept between calls
-    // K19 (k_agg.hip): the rows that pass ag_cut sorted by X (keys in / out, Y in / out, sort scratch, their number), the loop
+    // ---- the analysis units: one struct each, released by assigning a fresh one (the unit's *_release) ----
+    // K12 (k_fingerprint.hip): scratch of one call, freed when it returns
+    struct Fp { DevBuf small, keys, sorted, tmp, pairs; } fp;
+    // K13 (k_anchor.hip): anchors, directory, row mask, workgroup totals; kept between calls
+    struct Anchor { DevBuf s, e, dir, mask, wsum; } an;
+    // K19 (k_agg.hip): the rows that pass `cut` sorted by X (keys in / out, Y in / out, sort scratch, their number), the loop
     // centres and their order by cx (keys in / out, numbers in / out, sort scratch), the sum, per-loop statistics and matrices; kept
     // between calls
-    DevBuf ag_kin, ag_vin, ag_sx, ag_sy, ag_tmp, ag_m, ag_cx, ag_cy, ag_lkin, ag_lkout, ag_lvin, ag_order, ag_ltmp, ag_sum, ag_stats, ag_mats;
-    bool ag_ready = false; int ag_cut = 0, ag_kept = 0;          // the table is built for ag_cut and holds ag_kept rows
+    struct Agg {
+        DevBuf kin, vin, sx, sy, tmp, m, cx, cy, lkin, lkout, lvin, order, ltmp, sum, stats, mats;
+        bool ready = false; int cut = 0, kept = 0;                   // the table is built for `cut` and holds `kept` rows
+    } ag;
     // K14 (k_track.hip): tile counts / offsets, kept rows, keys, scratch, ids, names; the text itself (line lengths / ends, chunk
-    // bounds, render output: cl_textout.h); kept from cl_track_build to the next build or cl_track_free
-    DevBuf tk_tcnt, tk_toff, tk_row, tk_keys, tk_sorted, tk_tmp, tk_ids, tk_names;
-    TextOut tk_txt;
-    struct TrackState {
-        bool built = false, ids = false;
-        int kind = 0, la = 0, lb = 0, gbits = 0;
-        long long cut = 0, ext = 0;
+    // bounds, render output: cl_textout.h); kept from cl_track_build to the next build, cl_track_free or destruction
+    struct Track {
+        DevBuf tcnt, toff, row, keys, sorted, tmp, ids, names;
+        TextOut txt;
+        struct State {
+            bool built = false, ids = false;
+            int kind = 0, la = 0, lb = 0, gbits = 0;
+            long long cut = 0, ext = 0;
+        } st;
     } tk;
     // K20 (k_cover.hip): the sorted end-point keys (in / out, sort scratch), per candidate break point its depth after / before and
     // its rank among the other side's candidates, the run-start flags and their scan, counters, the runs (start, end, depth), the
     // name; the text of the runs (cl_textout.h); kept from cl_cov_build to the next build, cl_cov_free or destruction
-    DevBuf cv_kin, cv_key, cv_tmp, cv_dcur, cv_dprev, cv_xr, cv_flag, cv_scan, cv_ctr, cv_start, cv_end, cv_depth, cv_name;
-    TextOut cv_txt;
-    struct CovState {
-        bool built = false, text = false;
-        int la = 0;
-        long long R = 0, num = 0, den = 0;                           // runs; the scale of their text (cl_cov_text)
+    struct Cov {
+        DevBuf kin, key, tmp, dcur, dprev, xr, flag, scan, ctr, start, end, depth, name;
+        TextOut txt;
+        struct State {
+            bool built = false, text = false;
+            int la = 0;
+            long long R = 0, num = 0, den = 0;                           // runs; the scale of their text (cl_cov_text)
+        } st;
     } cv;
     // K21 (k_peak.hip): the sorted end-point keys (in / out, sort scratch), per element the ranks of its window's two edges, the core
     // flags and their scan, the chain-head flags and their scan, per peak the indices of its first / last core and the four results,
     // counters; the intervals of a count / summit call with their results; kept from cl_peak_sort to the next sort, cl_peak_free or
     // destruction
-    DevBuf pk_kin, pk_key, pk_tmp, pk_lo, pk_hi, pk_flag, pk_C, pk_head, pk_H, pk_a, pk_b, pk_start, pk_end, pk_np, pk_nc, pk_ctr,
-           pk_ivs, pk_ive, pk_best, pk_opos, pk_ocnt;
-    struct PeakState {
-        bool sorted = false, called = false;
-        int base = 0;                                                // the value of key 0
-        long long m = 0, P = 0;                                      // end points; peaks of the last cl_peak_call
+    struct Peak {
+        DevBuf kin, key, tmp, lo, hi, flag, C, head, H, a, b, start, end, np, nc, ctr, ivs, ive, best, opos, ocnt;
+        struct State {
+            bool sorted = false, called = false;
+            int base = 0;                                                // the value of key 0
+            long long m = 0, P = 0;                                      // end points; peaks of the last cl_peak_call
+        } st;
     } pk;
     // K22 (k_domain.hip): the three difference arrays over the bins (n_bins + 1 entries each) and their scans (cross, up, down: n_bins
     // entries each), the scan's scratch, the range of the kept rows' coordinates; the intervals of a count call and their three
-    // counters.  The rows themselves are K19's X-sorted table (ag_sx / ag_sy / ag_kept, agg_table), shared.  Kept from cl_dom_tracks
+    // counters.  The rows themselves are K19's X-sorted table (ag.sx / ag.sy / ag.kept, agg_table), shared.  Kept from cl_dom_tracks
     // to the next one, cl_dom_free or destruction
-    DevBuf dm_diff, dm_trk, dm_tmp, dm_rng, dm_ivs, dm_ive, dm_cnt;
-    struct DomState {
-        bool ready = false;
-        int cut = 0, res = 0, w = 0;
-        int pmin = 0, pmax = 0;                                      // smallest / largest coordinate of the kept rows (of `cut`)
-        long long bmin = 0, n_bins = 0, n_kept = 0;
+    struct Dom {
+        DevBuf diff, trk, tmp, rng, ivs, ive, cnt;
+        struct State {
+            bool ready = false;
+            int cut = 0, res = 0, w = 0;
+            int pmin = 0, pmax = 0;                                      // smallest / largest coordinate of the kept rows (of `cut`)
+            long long bmin = 0, n_bins = 0, n_kept = 0;
+        } st;
     } dm;
     // K23 (k_kdis.hip): X, Y of the kept rows in table order (copies: cl_agg_loops at another cut may rebuild K19's table while the
     // results live), d_k of every row for every asked k (n_k arrays of n_kept), per k the histogram + n_zero + n_none.  Kept from
     // cl_kdis_build to the next build, cl_kdis_free or destruction
-    DevBuf kd_x, kd_y, kd_d, kd_hist;
-    struct KdisState {
-        bool ready = false;
-        int cut = 0, n_k = 0;
-        int ks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        long long n_kept = 0;
+    struct Kdis {
+        DevBuf x, y, d, hist;
+        struct State {
+            bool ready = false;
+            int cut = 0, n_k = 0;
+            int ks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            long long n_kept = 0;
+        } st;
     } kd;
     // K24 (k_matrix.hip): the dense output of a window / virtual-4C call, the table ranges and counters of a call, and for the cells
     // the keys (in / sorted, sort and scan scratch), head flags, their scan, the run starts and the result (bx, by, cnt of every cell:
     // copies, so cl_agg_loops at another cut does not disturb them).  The rows are K19's table, shared.  The cells are kept from
     // cl_mat_cells to the next one, cl_mat_free or destruction
-    DevBuf mx_out, mx_ctr, mx_key, mx_sorted, mx_tmp, mx_flag, mx_scan, mx_start, mx_bx, mx_by, mx_cnt;
-    struct MatState {
-        bool ready = false;
-        long long n_cells = 0, n_kept = 0, max_count = 0;
-        int res = 0; bool fold = false;                              // what the cells were made with (K25 refuses unfolded cells)
+    struct Mat {
+        DevBuf out, ctr, key, sorted, tmp, flag, scan, start, bx, by, cnt;
+        struct State {
+            bool ready = false;
+            long long n_cells = 0, n_kept = 0, max_count = 0;
+            int res = 0; bool fold = false;                              // what the cells were made with (K25 refuses unfolded cells)
+        } st;
     } mx;
     // K25 (k_balance.hip): the transposed order of K24's folded cells (sort scratch, then by / bx / cnt of every cell ascending by
     // (by, bx)), the integer marginals (sum, nnz per bin), the caller's mask, the weights w, the marginals s of an iteration, the
     // per-tile carry records of both orders (integer and fp64), the partial sums of the update's reduction, the 32-byte record of a
     // loop and the balanced values of a get.  Kept from cl_bal_marginals to the next cl_mat_cells, cl_mat_free, cl_bal_free or
     // destruction
-    DevBuf bl_kin, bl_kout, bl_vin, bl_vout, bl_tmp, bl_tby, bl_tbx, bl_tcnt, bl_sum, bl_nnz, bl_valid, bl_w, bl_s, bl_icar, bl_dcar,
-           bl_part, bl_rec, bl_out;
-    struct BalState {
-        bool ready = false, iterated = false;
-        int ignore_diags = 0;
-        long long b0 = 0, nb = 0, n_used = 0, n_cells = 0;
+    struct Bal {
+        DevBuf kin, kout, vin, vout, tmp, tby, tbx, tcnt, sum, nnz, valid, w, s, icar, dcar, part, rec, out;
+        struct State {
+            bool ready = false, iterated = false;
+            int ignore_diags = 0;
+            long long b0 = 0, nb = 0, n_used = 0, n_cells = 0;
+        } st;
     } bl;
     // K26 (k_expected.hip): the effective weight of every bin (the ICE weight, or 1 on the caller's valid bins; NaN on the others) and
     // the mask of the valid bins, one bit per bin; the diagonal order of the cells (sort scratch, then d = by - bx, bx - b0 and cnt of
     // every cell ascending by d, inside a diagonal as the cells lie) and the tiles' carry records; per diagonal the valid pairs, the
     // count sum and the value sum; the expected values of cl_exp_set; the O/E values of a get.  Kept from cl_exp_diagonals to the next
     // one, cl_exp_free, anything that releases or rebuilds K25's state (bal_release, cl_bal_marginals, cl_bal_iterate) or destruction
-    DevBuf ex_valid, ex_w, ex_mask, ex_kin, ex_kout, ex_vin, ex_vout, ex_tmp, ex_dk, ex_dx, ex_dc, ex_car, ex_ctr, ex_pairs, ex_cnt, ex_val,
-           ex_exp, ex_out;
-    struct ExpState {
-        bool ready = false, expected = false;                        // the diagonals are built; cl_exp_set has been called since
-        int balanced = 0;
-        long long nd = 0, n_used = 0;
+    struct Exp {
+        DevBuf valid, w, mask, kin, kout, vin, vout, tmp, dk, dx, dc, car, ctr, pairs, cnt, val, exp, out;
+        struct State {
+            bool ready = false, expected = false;                        // the diagonals are built; cl_exp_set has been called since
+            int balanced = 0;
+            long long nd = 0, n_used = 0;
+        } st;
     } ex;
     bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
@@ -339,20 +358,17 @@ Table make_table_slot(cl_chrom* c, int slot);
 Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
 int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_out);
-// Every analysis unit drops its own state and buffers (k_track.hip, k_cover.hip, k_peak.hip, k_domain.hip, k_kdis.hip,
-// k_matrix.hip, k_balance.hip, k_expected.hip, k_fingerprint.hip, k_anchor.hip, k_agg.hip): called by the unit's own entry points and
-// by the handle's destruction.  mat_release calls bal_release: K25's weights belong to K24's cells; bal_release calls exp_release
-void track_release(cl_chrom* c);
-void cov_release(cl_chrom* c);
-void peak_release(cl_chrom* c);
-void dom_release(cl_chrom* c);
-void kdis_release(cl_chrom* c);
-void mat_release(cl_chrom* c);
-void bal_release(cl_chrom* c);
-void exp_release(cl_chrom* c);
-void fp_release(cl_chrom* c);
-void anchor_release(cl_chrom* c);
-void agg_release(cl_chrom* c);
+// A unit drops its buffers and its state by assigning a fresh struct, and with them what was made from them: K25's marginals and
+// weights belong to K24's cells, K26's diagonals to K25's marginals and weights.  Called by the units' entry points; the handle's
+// destruction needs none of them
+static inline void track_release(cl_chrom* c) { c->tk = cl_chrom::Track(); }
+static inline void cov_release(cl_chrom* c) { c->cv = cl_chrom::Cov(); }
+static inline void peak_release(cl_chrom* c) { c->pk = cl_chrom::Peak(); }
+static inline void dom_release(cl_chrom* c) { c->dm = cl_chrom::Dom(); }
+static inline void kdis_release(cl_chrom* c) { c->kd = cl_chrom::Kdis(); }
+static inline void exp_release(cl_chrom* c) { c->ex = cl_chrom::Exp(); }
+static inline void bal_release(cl_chrom* c) { exp_release(c); c->bl = cl_chrom::Bal(); }
+static inline void mat_release(cl_chrom* c) { c->mx = cl_chrom::Mat(); bal_release(c); }
 // what a unit's cl_*_free entry point does around its release function
 static inline int unit_free(cl_chrom* c, const char* who, void (*release)(cl_chrom*))
 {
@@ -446,8 +462,8 @@ __device__ __forceinline__ int k8_ub(const u64* __restrict__ t, int m, long long
 // builds the tables of (chromosome, cut) unless the handle holds them already (c->sig_tx / sig_ty; c->sig_m[0] on the device = the
 // number of valid entries); enqueued on c->stream, c->n > 0
 int sig_tables(cl_chrom* c, int cut);
-// K19's table (k_agg.hip), shared with K22 (k_domain.hip), K23 (k_kdis.hip) and K24 (k_matrix.hip): the rows with Y - X >= cut sorted by X (c->ag_sx: X + 2^30 as u32, c->ag_sy:
-// their Y, c->ag_kept rows) unless the handle holds it for this cut already; c->n > 0
+// K19's table (k_agg.hip), shared with K22 (k_domain.hip), K23 (k_kdis.hip) and K24 (k_matrix.hip): the rows with Y - X >= cut sorted by X (c->ag.sx: X + 2^30 as u32, c->ag.sy:
+// their Y, c->ag.kept rows) unless the handle holds it for this cut already; c->n > 0
 int agg_table(cl_chrom* c, int cut);
 
 // first index of [0, m) with sx[idx] >= t (m if none), by the 64 lanes of a wave together (all call, with the same arguments):

@@ -1,4 +1,4 @@
-// cl_common.h -- shared by the translation units of libcloops_hip.so: types, error plumbing, GridParams, wave / LDS
+// cl_common.h -- shared by the translation units of libcloops_hip.so: types, error plumbing (cl_err.h), GridParams, wave / LDS
 // helpers.  Device helpers are __forceinline__, so every TU carries its own copy (no relocatable device code).
 #pragma once
 #include <cstring>
@@ -14,6 +14,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/cloops_hip.h"
+#include "cl_err.h"        // g_err, fail, fail_at, HIP_TRY
 
 #define CL_VERSION_NUM 105   // 0.1.5
 
@@ -27,33 +28,6 @@ typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_con
                                                                        rocprim::block_radix_rank_algorithm::match>>
     SortConfig;
 
-
-// ------------------------------------------------------------------------------------------
-// error plumbing (g_err lives in cloops_hip.hip)
-// ------------------------------------------------------------------------------------------
-extern thread_local std::string g_err;
-
-static inline int fail(int code, const char* what, const char* detail = nullptr)
-{
-    g_err = what;
-    if (detail) { g_err += ": "; g_err += detail; }
-    return code;
-}
-
-// "<who>: <what>[: detail]" -- for code that several entry points share: the text still names the one that was called
-static inline int fail_at(int code, const char* who, const char* what, const char* detail = nullptr)
-{
-    g_err = who;
-    g_err += ": "; g_err += what;
-    if (detail) { g_err += ": "; g_err += detail; }
-    return code;
-}
-
-#define HIP_TRY(expr)                                                             \
-    do {                                                                           \
-        hipError_t e_ = (expr);                                                    \
-        if (e_ != hipSuccess) return fail(CL_ERR_HIP, #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------
 // device helpers

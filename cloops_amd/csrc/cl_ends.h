@@ -7,7 +7,7 @@
 #define K20_ROWS (TPB * K20_ITEMS)      // rows per workgroup of the key pass: 2048
 #define K20_LIMIT ((1ll << 31) - 4096)  // end points a build takes (ranks and run numbers are 32-bit)
 
-enum { K20_NENDS = 0, K20_MAXD = 1, K20_AREA = 2, K20_CTRS = 4 };       // c->cv_ctr, u64 each
+enum { K20_NENDS = 0, K20_MAXD = 1, K20_AREA = 2, K20_CTRS = 4 };       // c->cv.ctr, u64 each
 
 __device__ __forceinline__ int k20_floor_div(int p, int res)
 {

@@ -3,7 +3,7 @@
 // the device in chunks of whole lines below a byte budget, each rendered by workgroups of T lines (one per lane) that assemble their
 // tile in LDS, placed so that LDS and the output agree modulo 16, and write the tile's byte span with 16-byte stores.
 //   device: text_tile (a workgroup's lines and span), text_flush (LDS -> out), k14_bounds (the chunks of a budget)
-//   host:   TextOut and text_scan / text_total / text_chunks / text_chunk / text_copy_out / text_release
+//   host:   TextOut and text_scan / text_total / text_chunks / text_chunk / text_copy_out; a text is released by assigning TextOut()
 // The line formats, and the argument checks and messages of the entry points, stay with the units.
 #pragma once
 #include "cl_prim.h"
@@ -150,10 +150,4 @@ static inline void text_reset(TextOut& t)
 {
     t.R = t.total = 0;
     t.crec.clear(); t.cbyte.clear();
-}
-
-static inline void text_release(TextOut& t)
-{
-    for (DevBuf* b : {&t.len, &t.end, &t.bnd, &t.out}) b->release();
-    text_reset(t);
 }

@@ -2116,47 +2116,37 @@ int ensure_cand_capacity(cl_chrom* c, long long need)
     const long long cap = std::max<long long>(std::max<long long>(need, 2 * c->cand_cap), 1 << 20);
     DevBuf nb, ns;
     int rc;
-    if ((rc = nb.ensure((size_t)cap * 16)) || (rc = ns.ensure((size_t)cap * 4))) { nb.release(); ns.release(); return rc; }
+    if ((rc = nb.ensure((size_t)cap * 16)) || (rc = ns.ensure((size_t)cap * 4))) return rc;
     if (c->cand_n > 0) {
         HIP_TRY(hipMemcpyAsync(nb.p, c->cand_box.p, (size_t)c->cand_n * 16, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(ns.p, c->cand_step.p, (size_t)c->cand_n * 4, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->cand_box.release(); c->cand_step.release();
-    c->cand_box = nb; c->cand_step = ns;
+    c->cand_box = std::move(nb); c->cand_step = std::move(ns);
     c->cand_cap = cap;
     return CL_OK;
 }
 
+// `delete c` frees every device buffer (DevBuf's destructor).  What is no DevBuf is noted first and ended afterwards, so the buffers
+// still go before the streams do.
 static void free_chrom(cl_chrom* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    DevBuf* bufs[] = {&c->keys_in, &c->keys_out, &c->vals_in, &c->vals_out, &c->sort_tmp, &c->scan_tmp, &c->qb_key, &c->qb_val, &c->sv, &c->sa,
-                      &c->strip, &c->cnt, &c->parent, &c->root, &c->head, &c->headidx, &c->cellfirst, &c->compkey,
-                      &c->ncore, &c->bsize, &c->owner, &c->state, &c->flag, &c->rankscan, &c->slot[0].labels, &c->slot[0].table, &c->slot[1].labels, &c->slot[1].table, &c->slot[0].slab, &c->slot[1].slab, &c->slot[0].d_step, &c->slot[1].d_step, &c->slot[0].pairs, &c->slot[1].pairs, &c->hdr, &c->k7_cls, &c->k7_parts, &c->sig_tx, &c->sig_ty, &c->sig_tmp, &c->sig_sorttmp, &c->sig_m, &c->sig_win, &c->sig_out,
-                      &c->ulist, &c->lo, &c->hi, &c->recs, &c->counters, &c->chainflag, &c->chainhead, &c->usize, &c->b_cstart, &c->b_ckey, &c->b_nb, &c->b_cx, &c->b_cy, &c->tile_s0, &c->bq, &c->bsp, &c->brow, &c->bstrip, &c->btile, &c->sel_tmp, &c->cand_box, &c->cand_step, &c->cand_keep, &c->cand_out, &c->dhist,
-                      &c->rc_cnt, &c->rc_pre, &c->rc_poff, &c->rc_dpre, &c->rc_D, &c->rc_blen, &c->rootlist, &c->cflag8, &c->blk_tmp,
-                      &c->l_mask, &c->l_rank, &c->l_blk, &c->l_cstrip, &c->l_wpos, &c->l_wenc, &c->l_dist, &c->l_aux, &c->l_tab, &c->l_fix, &c->bkey,
-                      &c->fq, &c->fsp, &c->frow, &c->fstrip,
-                      &c->kde_ent, &c->kde_sorted, &c->kde_ctr, &c->kde_tmp, &c->kde_part};
-    for (DevBuf* b : bufs) b->release();
-    for (void (*unit)(cl_chrom*) : {fp_release, anchor_release, agg_release, track_release, cov_release, peak_release, dom_release, kdis_release,
-                                    mat_release /* (and K25's: bal_release) */})
-        unit(c);
-    c->arena.release();                                 // (after its slices have been dropped)
-    if (c->own_xy) { if (c->d_x) (void)hipFree(c->d_x); if (c->d_y) (void)hipFree(c->d_y); }
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
+    std::vector<void*> dev, pinned{c->h_pinned};
+    std::vector<hipEvent_t> events;
+    const hipStream_t streams[3] = {c->copy_stream, c->aux_stream, c->own_stream ? c->stream : nullptr};
+    if (c->own_xy) dev = {c->d_x, c->d_y};
     for (auto& sl : c->slot) {
-        if (sl.h_boxes) (void)hipHostFree(sl.h_boxes);
-        if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
-        if (sl.ev_copied) (void)hipEventDestroy(sl.ev_copied);
-        if (c->ev_ready) for (auto& e : sl.ev) (void)hipEventDestroy(e);
+        pinned.push_back(sl.h_boxes);
+        events.insert(events.end(), {sl.ev_done, sl.ev_copied});
+        if (c->ev_ready) events.insert(events.end(), std::begin(sl.ev), std::end(sl.ev));
     }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
+    for (void* p : dev) if (p) (void)hipFree(p);
+    for (void* p : pinned) if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
 }
 
 extern "C" void cl_chrom_destroy(cl_chrom* c) { free_chrom(c); }

@@ -8,7 +8,7 @@
 // Definitions: include/cloops_hip.h, cl_agg_loops.  The reference has nothing of the kind; every number here is an integer count
 // that a few lines of numpy reproduce (tests/test_gpu_agg.py).
 // Table: the rows that pass the cut, sorted by X with Y as payload (key = X + 2^30 as u32, rows that fail the cut sort to the end as
-// ~0; one rocPRIM radix sort of pairs), built at the first call and kept with the handle, keyed by the cut (c->ag_*: scratch of its
+// ~0; one rocPRIM radix sort of pairs), built at the first call and kept with the handle, keyed by the cut (c->ag: scratch of its
 // own, apart from the sweep's layouts, q index, count cache and K8 tables, freed with the handle).  K8's tables hold the same rows
 // as 64-bit keys next to a Y-sorted copy, and exist only after cl_sig_counts / cl_quant_counts: they are neither read nor built here.
 // Loops: the centres are sorted by cx ON THE DEVICE (rocPRIM pairs of (clamped cx, loop number); 10^5 loops take tens of
@@ -162,35 +162,28 @@ static bool k19_wave_form()
     return false;
 }
 
-void agg_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->ag_kin, &c->ag_vin, &c->ag_sx, &c->ag_sy, &c->ag_tmp, &c->ag_m, &c->ag_cx, &c->ag_cy, &c->ag_lkin, &c->ag_lkout, &c->ag_lvin,
-                      &c->ag_order, &c->ag_ltmp, &c->ag_sum, &c->ag_stats, &c->ag_mats}) b->release();
-    c->ag_ready = false;
-}
-
 // the X-sorted table of (chromosome, cut) unless the handle holds it already; c->n > 0 (declared in cl_chrom.h: K22 shares it)
 int agg_table(cl_chrom* c, int cut)
 {
-    if (c->ag_ready && c->ag_cut == cut) return CL_OK;
-    c->ag_ready = false;
+    if (c->ag.ready && c->ag.cut == cut) return CL_OK;
+    c->ag.ready = false;
     const int n = (int)c->n;
     int rc;
-    if ((rc = c->ag_kin.ensure((size_t)n * 4)) || (rc = c->ag_vin.ensure((size_t)n * 4)) || (rc = c->ag_sx.ensure((size_t)n * 4)) ||
-        (rc = c->ag_sy.ensure((size_t)n * 4)) || (rc = c->ag_m.ensure(64))) return rc;
-    LAUNCH(k19_split, n, c->d_x, c->d_y, n, cut, c->ag_kin.as<u32>(), c->ag_vin.as<int>());
+    if ((rc = c->ag.kin.ensure((size_t)n * 4)) || (rc = c->ag.vin.ensure((size_t)n * 4)) || (rc = c->ag.sx.ensure((size_t)n * 4)) ||
+        (rc = c->ag.sy.ensure((size_t)n * 4)) || (rc = c->ag.m.ensure(64))) return rc;
+    LAUNCH(k19_split, n, c->d_x, c->d_y, n, cut, c->ag.kin.as<u32>(), c->ag.vin.as<int>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->ag_tmp, "radix_sort_pairs(agg table)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, c->ag_kin.as<u32>(), c->ag_sx.as<u32>(), c->ag_vin.as<int>(), c->ag_sy.as<int>(),
+    if ((rc = prim_run(c->ag.tmp, "radix_sort_pairs(agg table)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, c->ag.kin.as<u32>(), c->ag.sx.as<u32>(), c->ag.vin.as<int>(), c->ag.sy.as<int>(),
                                                          (size_t)n, 0, 32, c->stream);
         })))
         return rc;
-    hipLaunchKernelGGL(k19_count_valid, dim3(1), dim3(64), 0, c->stream, c->ag_sx.as<u32>(), n, c->ag_m.as<int>());
+    hipLaunchKernelGGL(k19_count_valid, dim3(1), dim3(64), 0, c->stream, c->ag.sx.as<u32>(), n, c->ag.m.as<int>());
     HIP_TRY(hipGetLastError());
     int hm = 0;
-    HIP_TRY(hipMemcpyAsync(&hm, c->ag_m.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hm, c->ag.m.p, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->ag_kept = hm; c->ag_cut = cut; c->ag_ready = true;
+    c->ag.kept = hm; c->ag.cut = cut; c->ag.ready = true;
     return CL_OK;
 }
 
@@ -200,29 +193,29 @@ static int agg_loops(cl_chrom* c, const K19Par& p, int n_loops, const int32_t* c
 {
     const size_t nl = (size_t)n_loops, ww = (size_t)p.WW;
     int rc;
-    if ((rc = c->ag_cx.ensure(nl * 4)) || (rc = c->ag_cy.ensure(nl * 4)) || (rc = c->ag_lkin.ensure(nl * 4)) || (rc = c->ag_lkout.ensure(nl * 4)) ||
-        (rc = c->ag_lvin.ensure(nl * 4)) || (rc = c->ag_order.ensure(nl * 4)) || (rc = c->ag_sum.ensure(ww * 8)) ||
-        (stats_out && (rc = c->ag_stats.ensure(nl * 6 * 4))) || (mats_out && (rc = c->ag_mats.ensure(nl * ww * 4)))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->ag_cx.p, cx, nl * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ag_cy.p, cy, nl * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->ag_sum.p, 0, ww * 8, c->stream));
-    LAUNCH(k19_loop_keys, n_loops, c->ag_cx.as<int>(), n_loops, c->ag_lkin.as<int>(), c->ag_lvin.as<u32>());
+    if ((rc = c->ag.cx.ensure(nl * 4)) || (rc = c->ag.cy.ensure(nl * 4)) || (rc = c->ag.lkin.ensure(nl * 4)) || (rc = c->ag.lkout.ensure(nl * 4)) ||
+        (rc = c->ag.lvin.ensure(nl * 4)) || (rc = c->ag.order.ensure(nl * 4)) || (rc = c->ag.sum.ensure(ww * 8)) ||
+        (stats_out && (rc = c->ag.stats.ensure(nl * 6 * 4))) || (mats_out && (rc = c->ag.mats.ensure(nl * ww * 4)))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->ag.cx.p, cx, nl * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ag.cy.p, cy, nl * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->ag.sum.p, 0, ww * 8, c->stream));
+    LAUNCH(k19_loop_keys, n_loops, c->ag.cx.as<int>(), n_loops, c->ag.lkin.as<int>(), c->ag.lvin.as<u32>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->ag_ltmp, "radix_sort_pairs(agg loops)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, c->ag_lkin.as<int>(), c->ag_lkout.as<int>(), c->ag_lvin.as<u32>(),
-                                                         c->ag_order.as<u32>(), nl, 0, 32, c->stream);
+    if ((rc = prim_run(c->ag.ltmp, "radix_sort_pairs(agg loops)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, c->ag.lkin.as<int>(), c->ag.lkout.as<int>(), c->ag.lvin.as<u32>(),
+                                                         c->ag.order.as<u32>(), nl, 0, 32, c->stream);
         })))
         return rc;
-    int* d_stats = stats_out ? c->ag_stats.as<int>() : nullptr;
-    int* d_mats = mats_out ? c->ag_mats.as<int>() : nullptr;
+    int* d_stats = stats_out ? c->ag.stats.as<int>() : nullptr;
+    int* d_mats = mats_out ? c->ag.mats.as<int>() : nullptr;
     if (k19_wave_form())
-        hipLaunchKernelGGL(k19_pile<64>, dim3(std::min(n_loops, 4 * K19_GRID)), dim3(64), 0, c->stream, c->ag_sx.as<u32>(), c->ag_sy.as<int>(), c->ag_kept,
-                           p, n_loops, c->ag_order.as<u32>(), c->ag_cx.as<int>(), c->ag_cy.as<int>(), c->ag_sum.as<u64>(), d_stats, d_mats);
+        hipLaunchKernelGGL(k19_pile<64>, dim3(std::min(n_loops, 4 * K19_GRID)), dim3(64), 0, c->stream, c->ag.sx.as<u32>(), c->ag.sy.as<int>(), c->ag.kept,
+                           p, n_loops, c->ag.order.as<u32>(), c->ag.cx.as<int>(), c->ag.cy.as<int>(), c->ag.sum.as<u64>(), d_stats, d_mats);
     else
-        hipLaunchKernelGGL(k19_pile<256>, dim3(std::min(n_loops, K19_GRID)), dim3(256), 0, c->stream, c->ag_sx.as<u32>(), c->ag_sy.as<int>(), c->ag_kept,
-                           p, n_loops, c->ag_order.as<u32>(), c->ag_cx.as<int>(), c->ag_cy.as<int>(), c->ag_sum.as<u64>(), d_stats, d_mats);
+        hipLaunchKernelGGL(k19_pile<256>, dim3(std::min(n_loops, K19_GRID)), dim3(256), 0, c->stream, c->ag.sx.as<u32>(), c->ag.sy.as<int>(), c->ag.kept,
+                           p, n_loops, c->ag.order.as<u32>(), c->ag.cx.as<int>(), c->ag.cy.as<int>(), c->ag.sum.as<u64>(), d_stats, d_mats);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(sum_out, c->ag_sum.p, ww * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(sum_out, c->ag.sum.p, ww * 8, hipMemcpyDeviceToHost, c->stream));
     if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d_stats, nl * 6 * 4, hipMemcpyDeviceToHost, c->stream));
     if (mats_out) HIP_TRY(hipMemcpyAsync(mats_out, d_mats, nl * ww * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -256,8 +249,8 @@ extern "C" int cl_agg_loops(cl_chrom* c, int32_t cut, int32_t res, int32_t w, in
     HIP_TRY(hipSetDevice(c->device));
     int rc = agg_table(c, cut);
     if (rc == CL_OK) {
-        if (n_kept) *n_kept = c->ag_kept;
-        if (n_loops > 0 && c->ag_kept > 0) rc = agg_loops(c, p, (int)n_loops, cx, cy, sum_out, stats_out, mats_out);
+        if (n_kept) *n_kept = c->ag.kept;
+        if (n_loops > 0 && c->ag.kept > 0) rc = agg_loops(c, p, (int)n_loops, cx, cy, sum_out, stats_out, mats_out);
         else zero_outputs();
     }
     if (rc != CL_OK) (void)hipStreamSynchronize(c->stream);          // no copy from cx / cy or to the outputs may still be pending

@@ -16,7 +16,7 @@
 //   directory  more anchors: a bucket directory over the anchors' span (2^shift coordinates per bucket, about two buckets per
 //              anchor) holds the first anchor ending at or after each bucket's start; v's bucket bounds the binary search in global
 //              memory to the anchors between two directory entries
-// Scratch (c->an_*) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables, and stays with the
+// Scratch (c->an) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables, and stays with the
 // handle between calls (freed with it): the anchor-filtering of a genome is one call per chromosome, and releasing device memory
 // slows the process's later device-to-host copies (tools/d2h_after_free_probe.cpp).
 #define K13_T 2048                      // rows per tile: 256 threads x 8
@@ -134,11 +134,6 @@ static int k13_lds_max()
 }
 
 // ---- K13 host entry point -----------------------------------------------------------------------
-void anchor_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->an_s, &c->an_e, &c->an_dir, &c->an_mask, &c->an_wsum}) b->release();
-}
-
 // hs / he / ws: host staging of the copies, owned by the caller so that they outlive the stream synchronisation that follows an
 // error return here
 static int anchor_mask(cl_chrom* c, const std::vector<std::pair<int64_t, int64_t>>& merged, uint64_t* mask, int64_t* n_kept,
@@ -165,23 +160,23 @@ static int anchor_mask(cl_chrom* c, const std::vector<std::pair<int64_t, int64_t
     }
     const int grid = (int)std::max(1ll, std::min<long long>(K13_GRID, ((long long)n + K13_T - 1) / K13_T));
     int rc;
-    if ((rc = c->an_s.ensure((size_t)na * 4)) || (rc = c->an_e.ensure((size_t)na * 4)) || (rc = c->an_mask.ensure(nw * 8)) ||
-        (rc = c->an_wsum.ensure((size_t)grid * 4)) || (!lds && (rc = c->an_dir.ensure(((size_t)a.nb + 1) * 4))))
+    if ((rc = c->an.s.ensure((size_t)na * 4)) || (rc = c->an.e.ensure((size_t)na * 4)) || (rc = c->an.mask.ensure(nw * 8)) ||
+        (rc = c->an.wsum.ensure((size_t)grid * 4)) || (!lds && (rc = c->an.dir.ensure(((size_t)a.nb + 1) * 4))))
         return rc;
-    a.s = c->an_s.as<int>(); a.e = c->an_e.as<int>(); a.dir = lds ? nullptr : c->an_dir.as<int>();
-    HIP_TRY(hipMemcpyAsync(c->an_s.p, hs.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->an_e.p, he.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream));
+    a.s = c->an.s.as<int>(); a.e = c->an.e.as<int>(); a.dir = lds ? nullptr : c->an.dir.as<int>();
+    HIP_TRY(hipMemcpyAsync(c->an.s.p, hs.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->an.e.p, he.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream));
     if (lds) {
-        hipLaunchKernelGGL(k13_mask<true>, dim3(grid), dim3(256), 0, c->stream, c->d_x, c->d_y, n, a, c->an_mask.as<u64>(), c->an_wsum.as<int>());
+        hipLaunchKernelGGL(k13_mask<true>, dim3(grid), dim3(256), 0, c->stream, c->d_x, c->d_y, n, a, c->an.mask.as<u64>(), c->an.wsum.as<int>());
     } else {
-        hipLaunchKernelGGL(k13_dir, dim3((a.nb + 1 + TPB - 1) / TPB), dim3(TPB), 0, c->stream, a, c->an_dir.as<int>());
+        hipLaunchKernelGGL(k13_dir, dim3((a.nb + 1 + TPB - 1) / TPB), dim3(TPB), 0, c->stream, a, c->an.dir.as<int>());
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k13_mask<false>, dim3(grid), dim3(256), 0, c->stream, c->d_x, c->d_y, n, a, c->an_mask.as<u64>(), c->an_wsum.as<int>());
+        hipLaunchKernelGGL(k13_mask<false>, dim3(grid), dim3(256), 0, c->stream, c->d_x, c->d_y, n, a, c->an.mask.as<u64>(), c->an.wsum.as<int>());
     }
     HIP_TRY(hipGetLastError());
     ws.assign(grid, 0);
-    HIP_TRY(hipMemcpyAsync(mask, c->an_mask.p, nw * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(ws.data(), c->an_wsum.p, (size_t)grid * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(mask, c->an.mask.p, nw * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(ws.data(), c->an.wsum.p, (size_t)grid * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     long long kept = 0;
     for (int w : ws) kept += w;

@@ -7,7 +7,7 @@
 // K25: one weight per bin so that the rows of the weighted contact matrix have equal sums
 // ==========================================================================================
 // Definitions: include/cloops_hip.h, cl_bal_marginals.  The reference has nothing of the kind; tests/balance_cases.py restates the
-// definitions in numpy.  Input: K24's cells (c->mx_bx, c->mx_by, c->mx_cnt: ascending by (bx, by), bx <= by).
+// definitions in numpy.  Input: K24's cells (c->mx.bx, c->mx.by, c->mx.cnt: ascending by (bx, by), bx <= by).
 // A marginal of bin i has a row part (the cells with bx == i: a run of the cells as they lie) and a column part (the cells with by ==
 // i and bx != i: a run of the cells sorted by (by, bx), the transposed order that cl_bal_marginals builds once with one rocPRIM radix
 // sort of (key, cell index) pairs over the bits in use and one gather).  Both are sums over runs of equal sorted keys:
@@ -210,25 +210,17 @@ k25_cells(const int* __restrict__ bx, const int* __restrict__ by, const u32* __r
 }
 
 // ---- K25 host side ------------------------------------------------------------------------------
-void bal_release(cl_chrom* c)
-{
-    exp_release(c);                                                             // (K26's diagonals belong to these marginals and weights)
-    for (DevBuf* b : {&c->bl_kin, &c->bl_kout, &c->bl_vin, &c->bl_vout, &c->bl_tmp, &c->bl_tby, &c->bl_tbx, &c->bl_tcnt, &c->bl_sum, &c->bl_nnz,
-                      &c->bl_valid, &c->bl_w, &c->bl_s, &c->bl_icar, &c->bl_dcar, &c->bl_part, &c->bl_rec, &c->bl_out}) b->release();
-    c->bl = cl_chrom::BalState();
-}
-
 static long long k25_floordiv(long long p, long long res)
 {
     const long long q = p / res;
     return q - ((p - q * res) < 0 ? 1 : 0);
 }
 
-static K25In k25_input(cl_chrom* c, const cl_chrom::BalState& st)
+static K25In k25_input(cl_chrom* c, const cl_chrom::Bal::State& st)
 {
     K25In in{};
-    in.key[0] = c->mx_bx.as<int>(); in.oth[0] = c->mx_by.as<int>(); in.cnt[0] = c->mx_cnt.as<u32>();
-    in.key[1] = c->bl_tby.as<int>(); in.oth[1] = c->bl_tbx.as<int>(); in.cnt[1] = c->bl_tcnt.as<u32>();
+    in.key[0] = c->mx.bx.as<int>(); in.oth[0] = c->mx.by.as<int>(); in.cnt[0] = c->mx.cnt.as<u32>();
+    in.key[1] = c->bl.tby.as<int>(); in.oth[1] = c->bl.tbx.as<int>(); in.cnt[1] = c->bl.tcnt.as<u32>();
     in.n = (int)st.n_cells; in.ign = st.ignore_diags; in.b0 = (int)st.b0; in.nb = (int)st.nb;
     in.w = nullptr;
     in.vec = 1;
@@ -246,53 +238,53 @@ static void k25_parts(long long nb, int& np, int& per)
     np = (int)std::max<long long>((nb + per - 1) / per, 1);
 }
 
-static int bal_marginals(cl_chrom* c, cl_chrom::BalState& st)
+static int bal_marginals(cl_chrom* c, cl_chrom::Bal::State& st)
 {
     const int n = (int)st.n_cells;
     const size_t sn = (size_t)n;
     int rc;
     int hb0 = 0;
-    HIP_TRY(hipMemcpyAsync(&hb0, c->mx_bx.as<int>(), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hb0, c->mx.bx.as<int>(), 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // the bins of all rows of the handle bound those of the cells (as in cl_mat_cells): by - b0 fits the key's bits
-    const long long bmax = k25_floordiv(std::max(c->st.xmax, c->st.ymax), c->mx.res);
+    const long long bmax = k25_floordiv(std::max(c->st.xmax, c->st.ymax), c->mx.st.res);
     if (bmax < hb0 || bmax - hb0 >= (1ll << 30)) return fail(CL_ERR_HIP, "cl_bal_marginals: the cells' bins are not ones this handle can have");
     const int bits = std::max(1, bits_for((unsigned)(bmax - hb0)));
-    if ((rc = c->bl_kin.ensure(sn * 8)) || (rc = c->bl_kout.ensure(sn * 8)) || (rc = c->bl_vin.ensure(sn * 4)) || (rc = c->bl_vout.ensure(sn * 4)) ||
-        (rc = c->bl_tby.ensure(sn * 4)) || (rc = c->bl_tbx.ensure(sn * 4)) || (rc = c->bl_tcnt.ensure(sn * 4)) || (rc = c->bl_rec.ensure(64))) return rc;
-    LAUNCH(k25_keys, n, c->mx_bx.as<int>(), c->mx_by.as<int>(), n, hb0, bits, c->bl_kin.as<u64>(), c->bl_vin.as<u32>());
+    if ((rc = c->bl.kin.ensure(sn * 8)) || (rc = c->bl.kout.ensure(sn * 8)) || (rc = c->bl.vin.ensure(sn * 4)) || (rc = c->bl.vout.ensure(sn * 4)) ||
+        (rc = c->bl.tby.ensure(sn * 4)) || (rc = c->bl.tbx.ensure(sn * 4)) || (rc = c->bl.tcnt.ensure(sn * 4)) || (rc = c->bl.rec.ensure(64))) return rc;
+    LAUNCH(k25_keys, n, c->mx.bx.as<int>(), c->mx.by.as<int>(), n, hb0, bits, c->bl.kin.as<u64>(), c->bl.vin.as<u32>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->bl_tmp, "radix_sort_pairs(balance)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_pairs(tmp, bytes, c->bl_kin.as<u64>(), c->bl_kout.as<u64>(), c->bl_vin.as<u32>(), c->bl_vout.as<u32>(), sn, 0,
+    if ((rc = prim_run(c->bl.tmp, "radix_sort_pairs(balance)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, c->bl.kin.as<u64>(), c->bl.kout.as<u64>(), c->bl.vin.as<u32>(), c->bl.vout.as<u32>(), sn, 0,
                                              2 * bits, c->stream);
         })))
         return rc;
-    LAUNCH(k25_gather, n, c->bl_vout.as<u32>(), c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), n, c->bl_tbx.as<int>(),
-           c->bl_tby.as<int>(), c->bl_tcnt.as<u32>());
+    LAUNCH(k25_gather, n, c->bl.vout.as<u32>(), c->mx.bx.as<int>(), c->mx.by.as<int>(), c->mx.cnt.as<u32>(), n, c->bl.tbx.as<int>(),
+           c->bl.tby.as<int>(), c->bl.tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
     int hb1 = 0;
-    HIP_TRY(hipMemcpyAsync(&hb1, c->bl_tby.as<int>() + (sn - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hb1, c->bl.tby.as<int>() + (sn - 1), 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (hb1 < hb0 || (long long)hb1 > bmax) return fail(CL_ERR_HIP, "cl_bal_marginals: the transposed order ends with a bin no cell can have");
     st.b0 = hb0; st.nb = (long long)hb1 - hb0 + 1;
     if (st.nb > CL_BAL_BINS_MAX) return fail(CL_ERR_ARG, "cl_bal_marginals: more than CL_BAL_BINS_MAX bins (use a coarser res)");
     const size_t snb = (size_t)st.nb;
     const int ntiles = (int)((sn + K25_TILE - 1) / K25_TILE);
-    // bl_out serves as the two integer parts here (sum: 2 nb u64, then nnz: 2 nb u32); later as the balanced values of a get
-    if ((rc = c->bl_out.ensure(snb * 24)) || (rc = c->bl_sum.ensure(snb * 8)) || (rc = c->bl_nnz.ensure(snb * 4)) ||
-        (rc = c->bl_icar.ensure((size_t)ntiles * 2 * sizeof(K25Car<K25I>)))) return rc;
-    HIP_TRY(hipMemsetAsync(c->bl_out.p, 0, snb * 24, c->stream));
-    HIP_TRY(hipMemsetAsync(c->bl_rec.p, 0, 64, c->stream));
-    u64* d_used = c->bl_rec.as<u64>() + 4;                                      // (behind the loop's record)
-    K25I::Out out{c->bl_out.as<u64>(), (u32*)(c->bl_out.as<u64>() + 2 * snb)};
+    // bl.out serves as the two integer parts here (sum: 2 nb u64, then nnz: 2 nb u32); later as the balanced values of a get
+    if ((rc = c->bl.out.ensure(snb * 24)) || (rc = c->bl.sum.ensure(snb * 8)) || (rc = c->bl.nnz.ensure(snb * 4)) ||
+        (rc = c->bl.icar.ensure((size_t)ntiles * 2 * sizeof(K25Car<K25I>)))) return rc;
+    HIP_TRY(hipMemsetAsync(c->bl.out.p, 0, snb * 24, c->stream));
+    HIP_TRY(hipMemsetAsync(c->bl.rec.p, 0, 64, c->stream));
+    u64* d_used = c->bl.rec.as<u64>() + 4;                                      // (behind the loop's record)
+    K25I::Out out{c->bl.out.as<u64>(), (u32*)(c->bl.out.as<u64>() + 2 * snb)};
     const K25In in = k25_input(c, st);
-    hipLaunchKernelGGL(k25_marg<K25I>, dim3((unsigned)ntiles, 2u), dim3(TPB), 0, c->stream, in, out, c->bl_icar.as<K25Car<K25I>>(), ntiles, d_used,
+    hipLaunchKernelGGL(k25_marg<K25I>, dim3((unsigned)ntiles, 2u), dim3(TPB), 0, c->stream, in, out, c->bl.icar.as<K25Car<K25I>>(), ntiles, d_used,
                        (const K25Rec*)nullptr);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k25_fold<K25I>, dim3((unsigned)nblocks(ntiles), 2u), dim3(TPB), 0, c->stream, (const K25Car<K25I>*)c->bl_icar.as<K25Car<K25I>>(),
+    hipLaunchKernelGGL(k25_fold<K25I>, dim3((unsigned)nblocks(ntiles), 2u), dim3(TPB), 0, c->stream, (const K25Car<K25I>*)c->bl.icar.as<K25Car<K25I>>(),
                        ntiles, in.b0, in.nb, out, (const K25Rec*)nullptr);
     HIP_TRY(hipGetLastError());
-    LAUNCH(k25_join, st.nb, (const u64*)out.s, (const u32*)out.n, in.nb, c->bl_sum.as<u64>(), c->bl_nnz.as<u32>());
+    LAUNCH(k25_join, st.nb, (const u64*)out.s, (const u32*)out.n, in.nb, c->bl.sum.as<u64>(), c->bl.nnz.as<u32>());
     HIP_TRY(hipGetLastError());
     u64 hu = 0;
     HIP_TRY(hipMemcpyAsync(&hu, d_used, 8, hipMemcpyDeviceToHost, c->stream));
@@ -306,9 +298,9 @@ static int bal_enter(cl_chrom* c, const char* who, bool need_marginals)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, who, "asynchronous runs still in flight");
-    if (!c->mx.ready) return fail(CL_ERR_ARG, who, "no cells on this handle (cl_mat_cells)");
-    if (!c->mx.fold) return fail(CL_ERR_ARG, who, "the cells are not folded (cl_mat_cells with fold = 1)");
-    if (need_marginals && !c->bl.ready) return fail(CL_ERR_ARG, who, "no marginals on this handle (cl_bal_marginals)");
+    if (!c->mx.st.ready) return fail(CL_ERR_ARG, who, "no cells on this handle (cl_mat_cells)");
+    if (!c->mx.st.fold) return fail(CL_ERR_ARG, who, "the cells are not folded (cl_mat_cells with fold = 1)");
+    if (need_marginals && !c->bl.st.ready) return fail(CL_ERR_ARG, who, "no marginals on this handle (cl_bal_marginals)");
     return CL_OK;
 }
 
@@ -321,21 +313,21 @@ extern "C" int cl_bal_marginals(cl_chrom* c, int32_t ignore_diags, int64_t* b0, 
     if (rc != CL_OK) return rc;
     if (!b0 || !nb || !n_used) return fail(CL_ERR_ARG, "cl_bal_marginals: bad arguments");
     if (ignore_diags < 0) return fail(CL_ERR_ARG, "cl_bal_marginals: ignore_diags below 0");
-    cl_chrom::BalState st;
+    cl_chrom::Bal::State st;
     st.ready = true;
     st.ignore_diags = ignore_diags;
-    st.n_cells = c->mx.n_cells;
-    if (st.n_cells == 0) { bal_release(c); c->bl = st; return CL_OK; }          // (no rows, or a cut that keeps none: no HIP call)
+    st.n_cells = c->mx.st.n_cells;
+    if (st.n_cells == 0) { bal_release(c); c->bl.st = st; return CL_OK; }          // (no rows, or a cut that keeps none: no HIP call)
     HIP_TRY(hipSetDevice(c->device));
     exp_release(c);                                                             // (every K26 call ends synchronised)
-    c->bl.ready = false; c->bl.iterated = false;                                // (the earlier state's buffers are written from here on)
+    c->bl.st.ready = false; c->bl.st.iterated = false;                                // (the earlier state's buffers are written from here on)
     rc = bal_marginals(c, st);
     if (rc != CL_OK) {
         (void)hipStreamSynchronize(c->stream);
         bal_release(c);
         return rc;
     }
-    c->bl = st;
+    c->bl.st = st;
     *b0 = st.b0; *nb = st.nb; *n_used = st.n_used;
     return CL_OK;
 }
@@ -344,36 +336,36 @@ extern "C" int cl_bal_marginals_get(cl_chrom* c, int64_t first, int64_t count, u
 {
     int rc = bal_enter(c, "cl_bal_marginals_get", true);
     if (rc != CL_OK) return rc;
-    if (!range_ok(first, count, c->bl.nb)) return fail(CL_ERR_ARG, "cl_bal_marginals_get: range outside the bins");
+    if (!range_ok(first, count, c->bl.st.nb)) return fail(CL_ERR_ARG, "cl_bal_marginals_get: range outside the bins");
     if (count > 0 && (!sum || !nnz)) return fail(CL_ERR_ARG, "cl_bal_marginals_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return read_back(c, "cl_bal_marginals_get", {{sum, c->bl_sum.as<u64>() + first, (size_t)count * 8},
-                                                 {nnz, c->bl_nnz.as<u32>() + first, (size_t)count * 4}});
+    return read_back(c, "cl_bal_marginals_get", {{sum, c->bl.sum.as<u64>() + first, (size_t)count * 8},
+                                                 {nnz, c->bl.nnz.as<u32>() + first, (size_t)count * 4}});
 }
 
 static int bal_iterate(cl_chrom* c, const uint32_t* valid, int max_iters, double tol, K25Rec& h)
 {
-    const cl_chrom::BalState& st = c->bl;
+    const cl_chrom::Bal::State& st = c->bl.st;
     const size_t snb = (size_t)st.nb;
     const int ntiles = (int)(((size_t)st.n_cells + K25_TILE - 1) / K25_TILE);
     int np, per, rc;
     k25_parts(st.nb, np, per);
-    // bl_w: w, then the weights; bl_s: the two parts of s, then s; bl_part: count, sum and var partials
-    if ((rc = c->bl_valid.ensure(snb * 4)) || (rc = c->bl_w.ensure(snb * 16)) || (rc = c->bl_s.ensure(snb * 24)) ||
-        (rc = c->bl_part.ensure((size_t)np * 24)) || (rc = c->bl_dcar.ensure((size_t)ntiles * 2 * sizeof(K25Car<K25D>))) ||
-        (rc = c->bl_rec.ensure(64))) return rc;
+    // bl.w: w, then the weights; bl.s: the two parts of s, then s; bl.part: count, sum and var partials
+    if ((rc = c->bl.valid.ensure(snb * 4)) || (rc = c->bl.w.ensure(snb * 16)) || (rc = c->bl.s.ensure(snb * 24)) ||
+        (rc = c->bl.part.ensure((size_t)np * 24)) || (rc = c->bl.dcar.ensure((size_t)ntiles * 2 * sizeof(K25Car<K25D>))) ||
+        (rc = c->bl.rec.ensure(64))) return rc;
     const double nan = std::nan("");
-    double *w = c->bl_w.as<double>(), *weight = w + snb, *parts2 = c->bl_s.as<double>(), *s = parts2 + 2 * snb;
-    double *pcnt = c->bl_part.as<double>(), *psum = pcnt + np, *pvar = psum + np;
-    K25Rec* rec = c->bl_rec.as<K25Rec>();
-    HIP_TRY(hipMemcpyAsync(c->bl_valid.p, valid, snb * 4, hipMemcpyHostToDevice, c->stream));
-    LAUNCH(k25_init, st.nb, (const u32*)c->bl_valid.as<u32>(), (int)st.nb, w, parts2, rec, nan);
+    double *w = c->bl.w.as<double>(), *weight = w + snb, *parts2 = c->bl.s.as<double>(), *s = parts2 + 2 * snb;
+    double *pcnt = c->bl.part.as<double>(), *psum = pcnt + np, *pvar = psum + np;
+    K25Rec* rec = c->bl.rec.as<K25Rec>();
+    HIP_TRY(hipMemcpyAsync(c->bl.valid.p, valid, snb * 4, hipMemcpyHostToDevice, c->stream));
+    LAUNCH(k25_init, st.nb, (const u32*)c->bl.valid.as<u32>(), (int)st.nb, w, parts2, rec, nan);
     HIP_TRY(hipGetLastError());
     K25In in = k25_input(c, st);
     in.w = w;
     K25D::Out out{parts2};
-    K25Car<K25D>* car = c->bl_dcar.as<K25Car<K25D>>();
+    K25Car<K25D>* car = c->bl.dcar.as<K25Car<K25D>>();
     h = K25Rec{0, 0, 0, 0, nan, nan};
     for (int done = 0; done < max_iters && !h.stop;) {
         const int blk = std::min(K25_BLOCK, max_iters - done);
@@ -412,15 +404,15 @@ extern "C" int cl_bal_iterate(cl_chrom* c, const uint32_t* valid, int32_t max_it
     if (!iters || !converged || !var || !scale) return fail(CL_ERR_ARG, "cl_bal_iterate: bad arguments");
     if (max_iters < 0) return fail(CL_ERR_ARG, "cl_bal_iterate: max_iters below 0");
     if (!(tol >= 0.0)) return fail(CL_ERR_ARG, "cl_bal_iterate: tol below 0 or not a number");
-    if (c->bl.nb > 0 && !valid) return fail(CL_ERR_ARG, "cl_bal_iterate: no mask");
+    if (c->bl.st.nb > 0 && !valid) return fail(CL_ERR_ARG, "cl_bal_iterate: no mask");
     exp_release(c);                                                             // (K26's diagonals were those of the earlier weights)
-    if (c->bl.nb == 0) { c->bl.iterated = true; return CL_OK; }
+    if (c->bl.st.nb == 0) { c->bl.st.iterated = true; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
-    c->bl.iterated = false;
+    c->bl.st.iterated = false;
     K25Rec h{};
     rc = bal_iterate(c, valid, max_iters, tol, h);
     if (rc != CL_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    c->bl.iterated = true;
+    c->bl.st.iterated = true;
     *iters = h.iters; *converged = h.converged; *var = h.var; *scale = h.scale;
     return CL_OK;
 }
@@ -429,29 +421,29 @@ extern "C" int cl_bal_weights_get(cl_chrom* c, int64_t first, int64_t count, dou
 {
     int rc = bal_enter(c, "cl_bal_weights_get", true);
     if (rc != CL_OK) return rc;
-    if (!c->bl.iterated) return fail(CL_ERR_ARG, "cl_bal_weights_get: no weights on this handle (cl_bal_iterate)");
-    if (!range_ok(first, count, c->bl.nb)) return fail(CL_ERR_ARG, "cl_bal_weights_get: range outside the bins");
+    if (!c->bl.st.iterated) return fail(CL_ERR_ARG, "cl_bal_weights_get: no weights on this handle (cl_bal_iterate)");
+    if (!range_ok(first, count, c->bl.st.nb)) return fail(CL_ERR_ARG, "cl_bal_weights_get: range outside the bins");
     if (count > 0 && !weight) return fail(CL_ERR_ARG, "cl_bal_weights_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return read_back(c, "cl_bal_weights_get", {{weight, c->bl_w.as<double>() + (size_t)c->bl.nb + first, (size_t)count * 8}});
+    return read_back(c, "cl_bal_weights_get", {{weight, c->bl.w.as<double>() + (size_t)c->bl.st.nb + first, (size_t)count * 8}});
 }
 
 extern "C" int cl_bal_cells_get(cl_chrom* c, int64_t first, int64_t count, double* balanced)
 {
     int rc = bal_enter(c, "cl_bal_cells_get", true);
     if (rc != CL_OK) return rc;
-    if (!c->bl.iterated) return fail(CL_ERR_ARG, "cl_bal_cells_get: no weights on this handle (cl_bal_iterate)");
-    if (!range_ok(first, count, c->bl.n_cells)) return fail(CL_ERR_ARG, "cl_bal_cells_get: range outside the cells");
+    if (!c->bl.st.iterated) return fail(CL_ERR_ARG, "cl_bal_cells_get: no weights on this handle (cl_bal_iterate)");
+    if (!range_ok(first, count, c->bl.st.n_cells)) return fail(CL_ERR_ARG, "cl_bal_cells_get: range outside the cells");
     if (count > 0 && !balanced) return fail(CL_ERR_ARG, "cl_bal_cells_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->bl_out.ensure((size_t)count * 8))) return rc;
-    LAUNCH(k25_cells, count, c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), (long long)first, (long long)count, c->bl.n_cells,
-           (int)c->bl.b0, (int)c->bl.nb, (const double*)(c->bl_w.as<double>() + (size_t)c->bl.nb), std::nan(""), c->bl_out.as<double>());
+    if ((rc = c->bl.out.ensure((size_t)count * 8))) return rc;
+    LAUNCH(k25_cells, count, c->mx.bx.as<int>(), c->mx.by.as<int>(), c->mx.cnt.as<u32>(), (long long)first, (long long)count, c->bl.st.n_cells,
+           (int)c->bl.st.b0, (int)c->bl.st.nb, (const double*)(c->bl.w.as<double>() + (size_t)c->bl.st.nb), std::nan(""), c->bl.out.as<double>());
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(CL_ERR_HIP, "cl_bal_cells_get", hipGetErrorString(e));
-    return read_back(c, "cl_bal_cells_get", {{balanced, c->bl_out.p, (size_t)count * 8}});
+    return read_back(c, "cl_bal_cells_get", {{balanced, c->bl.out.p, (size_t)count * 8}});
 }
 
 extern "C" int cl_bal_free(cl_chrom* c)

@@ -233,16 +233,17 @@ struct cl_conv {
     float ms_h2d = 0, ms_feed = 0, ms_render = 0, ms_d2h = 0;
 };
 
+// `delete c` frees the buffers; the events and the stream are noted first and ended afterwards (as free_chrom does)
 static void conv_free(cl_conv* c)
 {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->in, &c->tcnt, &c->toff, &c->ends, &c->rec, &c->tmp, &c->err}) b->release();
-    text_release(c->txt);
-    for (hipEvent_t& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+    const std::vector<hipEvent_t> events(std::begin(c->ev), std::end(c->ev));
+    const hipStream_t own = c->own_stream ? c->stream : nullptr;
     delete c;
+    for (hipEvent_t e : events)
+        if (e) (void)hipEventDestroy(e);
+    if (own) (void)hipStreamDestroy(own);
 }
 
 extern "C" int cl_conv_create(int device, void* stream, int32_t format, int64_t ext, int64_t budget, cl_conv** out)

@@ -35,7 +35,7 @@
 //   k20_area                  sum of depth * (end - start) over the runs
 // Text (cl_cov_text / chunks / render) follows K14: line lengths, their running sum, K14's bounds kernel, a render of 256 lines per
 // workgroup through LDS with 16-byte stores.  Only vector stores and ordinary HIP atomics.
-// Scratch (c->cv_*) is the handle's own, apart from the sweep's layouts, q index, count cache and the K8 / K13 / K14 / K19 state.
+// Scratch (c->cv) is the handle's own, apart from the sweep's layouts, q index, count cache and the K8 / K13 / K14 / K19 state.
 #define K20_TILE 1024                   // elements of S per workgroup of k20_breaks (4 per thread)
 #define K20_HALO 1024                   // elements staged in LDS on either side of the tile
 #define K20_T 256                       // lines per render tile (one per lane)
@@ -187,26 +187,17 @@ k20_render(K20Tpl t, long long r0, long long r1, long long b0, const long long* 
 }
 
 // ---- K20 host side ------------------------------------------------------------------------------
-static int k20_lcap(const cl_chrom* c) { return c->cv.la + 4 + 2 * K20_POS + K20_VAL; }   // longest line the template allows
+static int k20_lcap(const cl_chrom* c) { return c->cv.st.la + 4 + 2 * K20_POS + K20_VAL; }   // longest line the template allows
 
 static int k20_grid(long long work) { return (int)std::max(1ll, std::min<long long>(4096, (work + TPB - 1) / TPB)); }
 
 static K20Tpl k20_tpl(cl_chrom* c)
 {
     K20Tpl t;
-    t.start = c->cv_start.as<int>(); t.end = c->cv_end.as<int>(); t.depth = c->cv_depth.as<u32>();
-    t.name = c->cv_name.as<char>();
-    t.num = (u64)c->cv.num; t.den = (u64)c->cv.den; t.la = c->cv.la;
+    t.start = c->cv.start.as<int>(); t.end = c->cv.end.as<int>(); t.depth = c->cv.depth.as<u32>();
+    t.name = c->cv.name.as<char>();
+    t.num = (u64)c->cv.st.num; t.den = (u64)c->cv.st.den; t.la = c->cv.st.la;
     return t;
-}
-
-void cov_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->cv_kin, &c->cv_key, &c->cv_tmp, &c->cv_dcur, &c->cv_dprev, &c->cv_xr, &c->cv_flag, &c->cv_scan, &c->cv_ctr,
-                      &c->cv_start, &c->cv_end, &c->cv_depth, &c->cv_name})
-        b->release();
-    text_release(c->cv_txt);
-    c->cv = cl_chrom::CovState();
 }
 
 static int cov_build(cl_chrom* c, long long cut, int ends, int ext, int res, int64_t* n_runs, uint32_t* max_depth, int64_t* n_ends,
@@ -223,55 +214,55 @@ static int cov_build(cl_chrom* c, long long cut, int ends, int ext, int res, int
     const int vmax = res ? fdiv(pmax, res) : pmax;
     const int ebit = std::max(1, bits_for((u32)(vmax - p.vmin)));
     int rc;
-    if ((rc = c->cv_ctr.ensure(K20_CTRS * 8)) || (rc = c->cv_kin.ensure((size_t)n * ne * 4)) || (rc = c->cv_key.ensure((size_t)n * ne * 4))) return rc;
-    u64* ctr = c->cv_ctr.as<u64>();
+    if ((rc = c->cv.ctr.ensure(K20_CTRS * 8)) || (rc = c->cv.kin.ensure((size_t)n * ne * 4)) || (rc = c->cv.key.ensure((size_t)n * ne * 4))) return rc;
+    u64* ctr = c->cv.ctr.as<u64>();
     HIP_TRY(hipMemsetAsync(ctr, 0, K20_CTRS * 8, c->stream));
     hipLaunchKernelGGL(k20_keys, dim3((unsigned)(((long long)n + K20_ROWS - 1) / K20_ROWS)), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, cut, ends,
-                       res, p.vmin, c->cv_kin.as<u32>(), ctr);
+                       res, p.vmin, c->cv.kin.as<u32>(), ctr);
     HIP_TRY(hipGetLastError());
     u64 hctr[K20_CTRS] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(hctr, ctr, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const long long m = (long long)hctr[K20_NENDS];
     *n_ends = m;
-    if (m == 0) { c->cv.built = true; return CL_OK; }
+    if (m == 0) { c->cv.st.built = true; return CL_OK; }
     if (m > (long long)n * ne) return fail(CL_ERR_HIP, "cl_cov_build: the key pass counted more end points than rows allow");
     // S: the end points in ascending order, sorted over the bits in use
-    if ((rc = prim_run(c->cv_tmp, "radix_sort_keys(coverage)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_keys(tmp, bytes, c->cv_kin.as<u32>(), c->cv_key.as<u32>(), (size_t)m, 0, ebit, c->stream);
+    if ((rc = prim_run(c->cv.tmp, "radix_sort_keys(coverage)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->cv.kin.as<u32>(), c->cv.key.as<u32>(), (size_t)m, 0, ebit, c->stream);
         })))
         return rc;
     // candidates, flags, their scan
     const size_t m2 = 2 * (size_t)m;
-    if ((rc = c->cv_dcur.ensure(m2 * 4)) || (rc = c->cv_dprev.ensure(m2 * 4)) || (rc = c->cv_xr.ensure(m2 * 4)) ||
-        (rc = c->cv_flag.ensure((m2 + 1) * 4)) || (rc = c->cv_scan.ensure((m2 + 1) * 4)))
+    if ((rc = c->cv.dcur.ensure(m2 * 4)) || (rc = c->cv.dprev.ensure(m2 * 4)) || (rc = c->cv.xr.ensure(m2 * 4)) ||
+        (rc = c->cv.flag.ensure((m2 + 1) * 4)) || (rc = c->cv.scan.ensure((m2 + 1) * 4)))
         return rc;
-    HIP_TRY(hipMemsetAsync(c->cv_flag.as<u32>() + m2, 0, 4, c->stream));
-    hipLaunchKernelGGL(k20_breaks, dim3((unsigned)((m + K20_TILE - 1) / K20_TILE)), dim3(TPB), 0, c->stream, c->cv_key.as<u32>(), (int)m, p,
-                       c->cv_dcur.as<u32>(), c->cv_dprev.as<u32>(), c->cv_xr.as<u32>(), c->cv_flag.as<u32>(), ctr);
+    HIP_TRY(hipMemsetAsync(c->cv.flag.as<u32>() + m2, 0, 4, c->stream));
+    hipLaunchKernelGGL(k20_breaks, dim3((unsigned)((m + K20_TILE - 1) / K20_TILE)), dim3(TPB), 0, c->stream, c->cv.key.as<u32>(), (int)m, p,
+                       c->cv.dcur.as<u32>(), c->cv.dprev.as<u32>(), c->cv.xr.as<u32>(), c->cv.flag.as<u32>(), ctr);
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->cv_tmp, "exclusive_scan(coverage)", [&](void* tmp, size_t& bytes) {
-            return rocprim::exclusive_scan(tmp, bytes, c->cv_flag.as<u32>(), c->cv_scan.as<u32>(), 0u, m2 + 1, rocprim::plus<u32>(), c->stream);
+    if ((rc = prim_run(c->cv.tmp, "exclusive_scan(coverage)", [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->cv.flag.as<u32>(), c->cv.scan.as<u32>(), 0u, m2 + 1, rocprim::plus<u32>(), c->stream);
         })))
         return rc;
     u32 hR = 0;
-    HIP_TRY(hipMemcpyAsync(&hR, c->cv_scan.as<u32>() + m2, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hR, c->cv.scan.as<u32>() + m2, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&hctr[K20_MAXD], ctr + K20_MAXD, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const long long R = hR;
     if (R > 0) {
-        if ((rc = c->cv_start.ensure((size_t)R * 4)) || (rc = c->cv_end.ensure((size_t)R * 4)) || (rc = c->cv_depth.ensure((size_t)R * 4))) return rc;
-        hipLaunchKernelGGL(k20_runs, dim3((unsigned)((m2 + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->cv_key.as<u32>(), (int)m, p,
-                           c->cv_dcur.as<u32>(), c->cv_dprev.as<u32>(), c->cv_xr.as<u32>(), c->cv_scan.as<u32>(), R, c->cv_start.as<int>(),
-                           c->cv_end.as<int>(), c->cv_depth.as<u32>());
+        if ((rc = c->cv.start.ensure((size_t)R * 4)) || (rc = c->cv.end.ensure((size_t)R * 4)) || (rc = c->cv.depth.ensure((size_t)R * 4))) return rc;
+        hipLaunchKernelGGL(k20_runs, dim3((unsigned)((m2 + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->cv.key.as<u32>(), (int)m, p,
+                           c->cv.dcur.as<u32>(), c->cv.dprev.as<u32>(), c->cv.xr.as<u32>(), c->cv.scan.as<u32>(), R, c->cv.start.as<int>(),
+                           c->cv.end.as<int>(), c->cv.depth.as<u32>());
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k20_area, dim3(k20_grid(R)), dim3(TPB), 0, c->stream, c->cv_start.as<int>(), c->cv_end.as<int>(), c->cv_depth.as<u32>(), R, ctr);
+        hipLaunchKernelGGL(k20_area, dim3(k20_grid(R)), dim3(TPB), 0, c->stream, c->cv.start.as<int>(), c->cv.end.as<int>(), c->cv.depth.as<u32>(), R, ctr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&hctr[K20_AREA], ctr + K20_AREA, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->cv.R = R;
-    c->cv.built = true;
+    c->cv.st.R = R;
+    c->cv.st.built = true;
     *n_runs = R;
     *max_depth = (uint32_t)hctr[K20_MAXD];
     *area = (int64_t)hctr[K20_AREA];
@@ -293,9 +284,9 @@ extern "C" int cl_cov_build(cl_chrom* c, int64_t cut, int32_t ends, int64_t ext,
     if (res == 0 && (ext < 1 || ext >= (1ll << 29))) return fail(CL_ERR_ARG, "cl_cov_build: window mode (res = 0) needs 1 <= ext < 2^29");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_build: asynchronous runs still in flight");
     HIP_TRY(hipSetDevice(c->device));
-    c->cv = cl_chrom::CovState();                                      // (the buffers stay: the next build reuses their memory, not their content)
-    text_reset(c->cv_txt);
-    if (c->n == 0) { c->cv.built = true; return CL_OK; }
+    c->cv.st = cl_chrom::Cov::State();                                      // (the buffers stay: the next build reuses their memory, not their content)
+    text_reset(c->cv.txt);
+    if (c->n == 0) { c->cv.st.built = true; return CL_OK; }
     const int rc = cov_build(c, cut, ends, (int)ext, (int)res, n_runs, max_depth, n_ends, area);
     if (rc != CL_OK) {
         (void)hipStreamSynchronize(c->stream);                          // no copy to the stack may still be pending
@@ -307,28 +298,28 @@ extern "C" int cl_cov_build(cl_chrom* c, int64_t cut, int32_t ends, int64_t ext,
 extern "C" int cl_cov_runs(cl_chrom* c, int64_t first, int64_t count, int32_t* start_out, int32_t* end_out, uint32_t* depth_out)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (!c->cv.built) return fail(CL_ERR_ARG, "cl_cov_runs: no coverage built on this handle");
-    if (!range_ok(first, count, c->cv.R)) return fail(CL_ERR_ARG, "cl_cov_runs: range outside the runs");
+    if (!c->cv.st.built) return fail(CL_ERR_ARG, "cl_cov_runs: no coverage built on this handle");
+    if (!range_ok(first, count, c->cv.st.R)) return fail(CL_ERR_ARG, "cl_cov_runs: range outside the runs");
     if (count > 0 && (!start_out || !end_out || !depth_out)) return fail(CL_ERR_ARG, "cl_cov_runs: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_runs: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return read_back(c, "cl_cov_runs", {{start_out, c->cv_start.as<int>() + first, (size_t)count * 4},
-                                        {end_out, c->cv_end.as<int>() + first, (size_t)count * 4},
-                                        {depth_out, c->cv_depth.as<u32>() + first, (size_t)count * 4}});
+    return read_back(c, "cl_cov_runs", {{start_out, c->cv.start.as<int>() + first, (size_t)count * 4},
+                                        {end_out, c->cv.end.as<int>() + first, (size_t)count * 4},
+                                        {depth_out, c->cv.depth.as<u32>() + first, (size_t)count * 4}});
 }
 
 static int cov_text(cl_chrom* c, std::vector<char>& hn, int64_t* n_bytes)
 {
-    cl_chrom::CovState& s = c->cv;
+    cl_chrom::Cov::State& s = c->cv.st;
     const long long R = s.R;
     int rc;
-    TextOut& txt = c->cv_txt;
-    if ((rc = c->cv_name.ensure(CL_TRACK_NAME_MAX)) || (rc = txt.len.ensure((size_t)R * 8)) || (rc = txt.end.ensure((size_t)R * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->cv_name.p, hn.data(), CL_TRACK_NAME_MAX, hipMemcpyHostToDevice, c->stream));
+    TextOut& txt = c->cv.txt;
+    if ((rc = c->cv.name.ensure(CL_TRACK_NAME_MAX)) || (rc = txt.len.ensure((size_t)R * 8)) || (rc = txt.end.ensure((size_t)R * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->cv.name.p, hn.data(), CL_TRACK_NAME_MAX, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k20_lens, dim3(k20_grid(R)), dim3(TPB), 0, c->stream, k20_tpl(c), R, txt.len.as<long long>());
     HIP_TRY(hipGetLastError());
-    if ((rc = text_scan(txt, c->cv_tmp, R, c->stream)) || (rc = text_total(txt, R, c->stream))) return rc;
+    if ((rc = text_scan(txt, c->cv.tmp, R, c->stream)) || (rc = text_total(txt, R, c->stream))) return rc;
     s.text = true;
     *n_bytes = txt.total;
     return CL_OK;
@@ -339,15 +330,15 @@ extern "C" int cl_cov_text(cl_chrom* c, const char* name, int64_t scale_num, int
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n_bytes) *n_bytes = 0;
     if (!name || !n_bytes) return fail(CL_ERR_ARG, "cl_cov_text: bad arguments");
-    if (!c->cv.built) return fail(CL_ERR_ARG, "cl_cov_text: no coverage built on this handle");
+    if (!c->cv.st.built) return fail(CL_ERR_ARG, "cl_cov_text: no coverage built on this handle");
     const size_t la = strlen(name);
     if (la > CL_TRACK_NAME_MAX) return fail(CL_ERR_ARG, "cl_cov_text: chromosome name longer than CL_TRACK_NAME_MAX");
     if (scale_den < 0 || scale_num < 0 || scale_num > (1ll << 30) || (scale_den > 0 && scale_num < 1))
         return fail(CL_ERR_ARG, "cl_cov_text: needs scale_den >= 0 and 1 <= scale_num <= 2^30 (0 allowed with scale_den = 0)");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_text: asynchronous runs still in flight");
-    cl_chrom::CovState& s = c->cv;
+    cl_chrom::Cov::State& s = c->cv.st;
     s.text = false;
-    text_reset(c->cv_txt);
+    text_reset(c->cv.txt);
     s.la = (int)la; s.num = scale_num; s.den = scale_den;
     if (s.R == 0) { s.text = true; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
@@ -363,11 +354,11 @@ extern "C" int cl_cov_chunks(cl_chrom* c, int64_t budget, int64_t cap, int64_t* 
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n_chunks) *n_chunks = 0;
     if (!n_chunks || (!run_bounds) != (!byte_bounds)) return fail(CL_ERR_ARG, "cl_cov_chunks: bad arguments");
-    if (!c->cv.built || !c->cv.text) return fail(CL_ERR_ARG, "cl_cov_chunks: no coverage text on this handle (cl_cov_build, cl_cov_text)");
+    if (!c->cv.st.built || !c->cv.st.text) return fail(CL_ERR_ARG, "cl_cov_chunks: no coverage text on this handle (cl_cov_build, cl_cov_text)");
     if (budget < k20_lcap(c)) return fail(CL_ERR_ARG, "cl_cov_chunks: budget below the longest line the template allows");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_chunks: asynchronous runs still in flight");
-    if (c->cv_txt.R > 0) HIP_TRY(hipSetDevice(c->device));
-    return text_chunks(c->cv_txt, c->stream, budget, k20_lcap(c), cap, run_bounds, byte_bounds, n_chunks, "cl_cov_chunks");
+    if (c->cv.txt.R > 0) HIP_TRY(hipSetDevice(c->device));
+    return text_chunks(c->cv.txt, c->stream, budget, k20_lcap(c), cap, run_bounds, byte_bounds, n_chunks, "cl_cov_chunks");
 }
 
 extern "C" int cl_cov_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n_bytes)
@@ -375,8 +366,8 @@ extern "C" int cl_cov_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap,
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n_bytes) *n_bytes = 0;
     if (!out || !n_bytes) return fail(CL_ERR_ARG, "cl_cov_render: bad arguments");
-    cl_chrom::CovState& s = c->cv;
-    TextOut& txt = c->cv_txt;
+    cl_chrom::Cov::State& s = c->cv.st;
+    TextOut& txt = c->cv.txt;
     if (!s.built || !s.text || txt.crec.empty()) return fail(CL_ERR_ARG, "cl_cov_render: no chunks made on this handle (cl_cov_chunks)");
     if (chunk < 0 || chunk + 1 >= (int64_t)txt.crec.size()) return fail(CL_ERR_ARG, "cl_cov_render: chunk index out of range");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cov_render: asynchronous runs still in flight");

@@ -6,8 +6,8 @@
 // K22: cross / up / down per bin boundary as range adds over difference arrays, and counts per domain
 // ==========================================================================================
 // Definitions: include/cloops_hip.h, cl_dom_tracks.  The reference has nothing of the kind; every number here is an integer that a few
-// lines of numpy reproduce (tests/domains_cases.py).  Rows: K19's table (agg_table: the kept rows sorted by X, c->ag_sx = X + 2^30,
-// c->ag_sy = Y, c->ag_kept of them), shared with cl_agg_loops and keyed by the cut, so another w or res sorts nothing.
+// lines of numpy reproduce (tests/domains_cases.py).  Rows: K19's table (agg_table: the kept rows sorted by X, c->ag.sx = X + 2^30,
+// c->ag.sy = Y, c->ag.kept of them), shared with cl_agg_loops and keyed by the cut, so another w or res sorts nothing.
 //   k22_range                 the smallest / largest Y of the kept rows (one atomicMin / atomicMax per workgroup) and the first / last X
 //   k22_tracks                one workgroup per K22_TILE consecutive sorted rows.  A row with bx <= by adds +1 at the first bin and -1
 //                             behind the last bin of its three intervals (clipped to bmin .. bmax + 1): six updates, all at bins of
@@ -24,7 +24,7 @@
 //                             K22_DW domains from the domain of the tile's first X on in LDS (X ascends, and Y mostly lies near),
 //                             any other domain in global memory, the same per-wave aggregation, and one global atomic per LDS
 //                             counter that is not zero: one domain holding every row costs three atomics per workgroup.
-// Only vector stores and ordinary HIP atomics; every index is checked against its array before a store.  Scratch (c->dm_*) is the
+// Only vector stores and ordinary HIP atomics; every index is checked against its array before a store.  Scratch (c->dm) is the
 // handle's own, apart from the sweep's layouts, q index, count cache and the K8 / K13 / K14 / K20 / K21 state.
 #define K22_TILE 2048                   // sorted rows per workgroup of k22_tracks and k22_count (8 per thread)
 #define K22_BW 3072                     // bins per LDS window of k22_tracks (three windows: 36 KB, four workgroups per CU)
@@ -199,28 +199,22 @@ static long long k22_floordiv(long long p, long long res)
     return q - ((p - q * res) < 0 ? 1 : 0);
 }
 
-void dom_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->dm_diff, &c->dm_trk, &c->dm_tmp, &c->dm_rng, &c->dm_ivs, &c->dm_ive, &c->dm_cnt}) b->release();
-    c->dm = cl_chrom::DomState();
-}
-
 // the kept rows of `cut` sorted by X (shared with K19) and the range of their coordinates -> st (ready stays false)
-static int dom_rows(cl_chrom* c, int cut, cl_chrom::DomState& st)
+static int dom_rows(cl_chrom* c, int cut, cl_chrom::Dom::State& st)
 {
     int rc;
     if ((rc = agg_table(c, cut))) return rc;
     st.cut = cut;
-    st.n_kept = c->ag_kept;
-    if (c->ag_kept == 0) return CL_OK;
-    if (c->dm.ready && c->dm.cut == cut && c->dm.n_kept == c->ag_kept) { st.pmin = c->dm.pmin; st.pmax = c->dm.pmax; return CL_OK; }
-    const int m = c->ag_kept;
-    if ((rc = c->dm_rng.ensure(64))) return rc;
-    u32* rng = c->dm_rng.as<u32>();
+    st.n_kept = c->ag.kept;
+    if (c->ag.kept == 0) return CL_OK;
+    if (c->dm.st.ready && c->dm.st.cut == cut && c->dm.st.n_kept == c->ag.kept) { st.pmin = c->dm.st.pmin; st.pmax = c->dm.st.pmax; return CL_OK; }
+    const int m = c->ag.kept;
+    if ((rc = c->dm.rng.ensure(64))) return rc;
+    u32* rng = c->dm.rng.as<u32>();
     HIP_TRY(hipMemsetAsync(rng, 0xff, 4, c->stream));
     HIP_TRY(hipMemsetAsync(rng + 1, 0, 12, c->stream));
-    hipLaunchKernelGGL(k22_range, dim3((unsigned)std::max(1, std::min(1024, nblocks(m)))), dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(),
-                       c->ag_sy.as<int>(), m, rng);
+    hipLaunchKernelGGL(k22_range, dim3((unsigned)std::max(1, std::min(1024, nblocks(m)))), dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(),
+                       c->ag.sy.as<int>(), m, rng);
     HIP_TRY(hipGetLastError());
     u32 h[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, rng, 16, hipMemcpyDeviceToHost, c->stream));
@@ -235,7 +229,7 @@ static int dom_rows(cl_chrom* c, int cut, cl_chrom::DomState& st)
     return CL_OK;
 }
 
-static int dom_tracks(cl_chrom* c, int cut, int res, int w, cl_chrom::DomState& st)
+static int dom_tracks(cl_chrom* c, int cut, int res, int w, cl_chrom::Dom::State& st)
 {
     int rc;
     if ((rc = dom_rows(c, cut, st))) return rc;
@@ -245,14 +239,14 @@ static int dom_tracks(cl_chrom* c, int cut, int res, int w, cl_chrom::DomState& 
     const long long nb = bmax - bmin + 2;
     if (nb < 2 || nb > K22_MAXBINS) return fail(CL_ERR_HIP, "cl_dom_tracks: the kept rows span more bins than all rows");
     const size_t words = 3 * ((size_t)nb + 1);
-    if ((rc = c->dm_diff.ensure(words * 4)) || (rc = c->dm_trk.ensure(words * 4))) return rc;
-    HIP_TRY(hipMemsetAsync(c->dm_diff.p, 0, words * 4, c->stream));
+    if ((rc = c->dm.diff.ensure(words * 4)) || (rc = c->dm.trk.ensure(words * 4))) return rc;
+    HIP_TRY(hipMemsetAsync(c->dm.diff.p, 0, words * 4, c->stream));
     const int m = (int)st.n_kept;
-    hipLaunchKernelGGL(k22_tracks, dim3((unsigned)(((long long)m + K22_TILE - 1) / K22_TILE)), dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(),
-                       c->ag_sy.as<int>(), m, res, w, (int)bmin, (int)nb, c->dm_diff.as<u32>());
+    hipLaunchKernelGGL(k22_tracks, dim3((unsigned)(((long long)m + K22_TILE - 1) / K22_TILE)), dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(),
+                       c->ag.sy.as<int>(), m, res, w, (int)bmin, (int)nb, c->dm.diff.as<u32>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->dm_tmp, "inclusive_scan(domains)", [&](void* tmp, size_t& bytes) {
-            return rocprim::inclusive_scan(tmp, bytes, c->dm_diff.as<u32>(), c->dm_trk.as<u32>(), words, rocprim::plus<u32>(), c->stream);
+    if ((rc = prim_run(c->dm.tmp, "inclusive_scan(domains)", [&](void* tmp, size_t& bytes) {
+            return rocprim::inclusive_scan(tmp, bytes, c->dm.diff.as<u32>(), c->dm.trk.as<u32>(), words, rocprim::plus<u32>(), c->stream);
         })))
         return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -277,10 +271,10 @@ extern "C" int cl_dom_tracks(cl_chrom* c, int64_t cut, int64_t res, int64_t w, i
             return fail(CL_ERR_ARG, "cl_dom_tracks: the rows of this handle span more than 2^24 bins at this res");
     }
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_dom_tracks: asynchronous runs still in flight");
-    cl_chrom::DomState st;
+    cl_chrom::Dom::State st;
     if (c->n == 0) {
         st.ready = true; st.res = (int)res; st.w = (int)w;
-        c->dm = st;
+        c->dm.st = st;
         return CL_OK;
     }
     HIP_TRY(hipSetDevice(c->device));
@@ -291,7 +285,7 @@ extern "C" int cl_dom_tracks(cl_chrom* c, int64_t cut, int64_t res, int64_t w, i
         dom_release(c);
         return rc;
     }
-    c->dm = st;
+    c->dm.st = st;
     *n_bins = st.n_bins; *bin0 = st.bmin; *n_kept = st.n_kept;
     return CL_OK;
 }
@@ -299,14 +293,14 @@ extern "C" int cl_dom_tracks(cl_chrom* c, int64_t cut, int64_t res, int64_t w, i
 extern "C" int cl_dom_get(cl_chrom* c, int64_t first, int64_t count, uint32_t* cross, uint32_t* up, uint32_t* down)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (!c->dm.ready) return fail(CL_ERR_ARG, "cl_dom_get: no tracks on this handle (cl_dom_tracks)");
-    if (!range_ok(first, count, c->dm.n_bins)) return fail(CL_ERR_ARG, "cl_dom_get: range outside the bins");
+    if (!c->dm.st.ready) return fail(CL_ERR_ARG, "cl_dom_get: no tracks on this handle (cl_dom_tracks)");
+    if (!range_ok(first, count, c->dm.st.n_bins)) return fail(CL_ERR_ARG, "cl_dom_get: range outside the bins");
     if (count > 0 && (!cross || !up || !down)) return fail(CL_ERR_ARG, "cl_dom_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_dom_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t stride = (size_t)c->dm.n_bins + 1;
-    const u32* trk = c->dm_trk.as<u32>();
+    const size_t stride = (size_t)c->dm.st.n_bins + 1;
+    const u32* trk = c->dm.trk.as<u32>();
     const size_t nb = (size_t)count * 4;
     return read_back(c, "cl_dom_get", {{cross, trk + first, nb}, {up, trk + stride + first, nb}, {down, trk + 2 * stride + first, nb}});
 }
@@ -314,18 +308,18 @@ extern "C" int cl_dom_get(cl_chrom* c, int64_t first, int64_t count, uint32_t* c
 static int dom_count(cl_chrom* c, const int64_t* starts, const int64_t* ends, long long n, uint32_t* intra, uint32_t* nx, uint32_t* ny)
 {
     int rc;
-    if ((rc = agg_table(c, c->dm.cut))) return rc;                      // (cl_agg_loops at another cut has rebuilt it for itself since)
-    if (c->ag_kept != c->dm.n_kept) return fail(CL_ERR_HIP, "cl_dom_count: the sorted rows are not those of the tracks");
-    const int m = c->ag_kept;
+    if ((rc = agg_table(c, c->dm.st.cut))) return rc;                      // (cl_agg_loops at another cut has rebuilt it for itself since)
+    if (c->ag.kept != c->dm.st.n_kept) return fail(CL_ERR_HIP, "cl_dom_count: the sorted rows are not those of the tracks");
+    const int m = c->ag.kept;
     const size_t sn = (size_t)n;
-    if ((rc = c->dm_ivs.ensure(sn * 8)) || (rc = c->dm_ive.ensure(sn * 8)) || (rc = c->dm_cnt.ensure(3 * sn * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->dm_ivs.p, starts, sn * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->dm_ive.p, ends, sn * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->dm_cnt.p, 0, 3 * sn * 4, c->stream));
-    hipLaunchKernelGGL(k22_count, dim3((unsigned)(((long long)m + K22_TILE - 1) / K22_TILE)), dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(),
-                       c->ag_sy.as<int>(), m, c->dm_ivs.as<long long>(), c->dm_ive.as<long long>(), (int)n, c->dm_cnt.as<u32>());
+    if ((rc = c->dm.ivs.ensure(sn * 8)) || (rc = c->dm.ive.ensure(sn * 8)) || (rc = c->dm.cnt.ensure(3 * sn * 4))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->dm.ivs.p, starts, sn * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->dm.ive.p, ends, sn * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->dm.cnt.p, 0, 3 * sn * 4, c->stream));
+    hipLaunchKernelGGL(k22_count, dim3((unsigned)(((long long)m + K22_TILE - 1) / K22_TILE)), dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(),
+                       c->ag.sy.as<int>(), m, c->dm.ivs.as<long long>(), c->dm.ive.as<long long>(), (int)n, c->dm.cnt.as<u32>());
     HIP_TRY(hipGetLastError());
-    const u32* cnt = c->dm_cnt.as<u32>();
+    const u32* cnt = c->dm.cnt.as<u32>();
     HIP_TRY(hipMemcpyAsync(intra, cnt, sn * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(nx, cnt + sn, sn * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(ny, cnt + 2 * sn, sn * 4, hipMemcpyDeviceToHost, c->stream));
@@ -337,13 +331,13 @@ extern "C" int cl_dom_count(cl_chrom* c, const int64_t* starts, const int64_t* e
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n < 0 || n > (1ll << 31) - 4096 || (n > 0 && (!starts || !ends || !intra || !nx || !ny))) return fail(CL_ERR_ARG, "cl_dom_count: bad arguments");
-    if (!c->dm.ready) return fail(CL_ERR_ARG, "cl_dom_count: no tracks on this handle (cl_dom_tracks)");
+    if (!c->dm.st.ready) return fail(CL_ERR_ARG, "cl_dom_count: no tracks on this handle (cl_dom_tracks)");
     for (int64_t k = 0; k < n; ++k)
         if (ends[k] < starts[k] || (k > 0 && starts[k] < ends[k - 1]))
             return fail(CL_ERR_ARG, "cl_dom_count: the intervals must be ascending and disjoint");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_dom_count: asynchronous runs still in flight");
     if (n == 0) return CL_OK;
-    if (c->dm.n_kept == 0) {
+    if (c->dm.st.n_kept == 0) {
         std::memset(intra, 0, (size_t)n * 4); std::memset(nx, 0, (size_t)n * 4); std::memset(ny, 0, (size_t)n * 4);
         return CL_OK;
     }

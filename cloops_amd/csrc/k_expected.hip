@@ -7,7 +7,7 @@
 // K26: per diagonal the valid bin pairs, the count sum and the (balanced) value sum; O/E of every cell
 // ==========================================================================================
 // Definitions: include/cloops_hip.h, cl_exp_diagonals.  The reference has nothing of the kind; tests/expected_cases.py restates the
-// definitions in numpy.  Input: K24's cells (c->mx_bx, c->mx_by, c->mx_cnt), K25's bins b0 .. b0 + nb - 1 and ignore_diags, and either
+// definitions in numpy.  Input: K24's cells (c->mx.bx, c->mx.by, c->mx.cnt), K25's bins b0 .. b0 + nb - 1 and ignore_diags, and either
 // K25's weights (balanced) or the caller's mask (raw).  One array drives everything that follows: ew[i], the effective weight of bin
 // i -- the ICE weight, or 1 on a valid bin of the raw mode, NaN on every other bin.  A bin is valid iff ew[i] is a number; a cell is
 // used iff by - bx >= ignore_diags and both of its bins are valid; its value is (ew[bx] cnt) ew[by].
@@ -180,73 +180,66 @@ k26_oe(const int* __restrict__ bx, const int* __restrict__ by, const u32* __rest
 }
 
 // ---- K26 host side ------------------------------------------------------------------------------
-void exp_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->ex_valid, &c->ex_kin, &c->ex_kout, &c->ex_vin, &c->ex_vout, &c->ex_tmp, &c->ex_w, &c->ex_mask, &c->ex_dk, &c->ex_dx, &c->ex_dc, &c->ex_car, &c->ex_ctr, &c->ex_pairs, &c->ex_cnt, &c->ex_val,
-                      &c->ex_exp, &c->ex_out}) b->release();
-    c->ex = cl_chrom::ExpState();
-}
-
 // the checks every K26 call shares; -> CL_OK with c usable.  (K25's marginals imply K24's folded cells: mat_release drops both)
 static int exp_enter(cl_chrom* c, const char* who, bool need_diagonals)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, who, "asynchronous runs still in flight");
-    if (!c->bl.ready) return fail(CL_ERR_ARG, who, "no marginals on this handle (cl_bal_marginals)");
-    if (need_diagonals && !c->ex.ready) return fail(CL_ERR_ARG, who, "no diagonals on this handle (cl_exp_diagonals)");
+    if (!c->bl.st.ready) return fail(CL_ERR_ARG, who, "no marginals on this handle (cl_bal_marginals)");
+    if (need_diagonals && !c->ex.st.ready) return fail(CL_ERR_ARG, who, "no diagonals on this handle (cl_exp_diagonals)");
     return CL_OK;
 }
 
-static int exp_diagonals(cl_chrom* c, const uint32_t* valid, int balanced, cl_chrom::ExpState& st)
+static int exp_diagonals(cl_chrom* c, const uint32_t* valid, int balanced, cl_chrom::Exp::State& st)
 {
-    const cl_chrom::BalState& bl = c->bl;
+    const cl_chrom::Bal::State& bl = c->bl.st;
     const int n = (int)bl.n_cells, nb = (int)bl.nb, W = (nb + 63) / 64;
     const size_t sn = (size_t)n, snb = (size_t)nb;
     const int ntiles = (int)((sn + K25_TILE - 1) / K25_TILE);
     const double nan = std::nan("");
     int rc;
-    if ((rc = c->ex_w.ensure(snb * 8)) || (rc = c->ex_mask.ensure((size_t)W * 8)) || (rc = c->ex_pairs.ensure(snb * 8)) ||
-        (rc = c->ex_cnt.ensure(snb * 8)) || (rc = c->ex_val.ensure(snb * 8)) || (rc = c->ex_exp.ensure(snb * 8)) || (rc = c->ex_ctr.ensure(64)) ||
-        (rc = c->ex_kin.ensure(sn * 4)) || (rc = c->ex_kout.ensure(sn * 4)) || (rc = c->ex_vin.ensure(sn * 4)) || (rc = c->ex_vout.ensure(sn * 4)) ||
-        (rc = c->ex_dk.ensure(sn * 4)) || (rc = c->ex_dx.ensure(sn * 4)) || (rc = c->ex_dc.ensure(sn * 4)) ||
-        (rc = c->ex_car.ensure((size_t)ntiles * sizeof(K25Car<K26V>)))) return rc;
+    if ((rc = c->ex.w.ensure(snb * 8)) || (rc = c->ex.mask.ensure((size_t)W * 8)) || (rc = c->ex.pairs.ensure(snb * 8)) ||
+        (rc = c->ex.cnt.ensure(snb * 8)) || (rc = c->ex.val.ensure(snb * 8)) || (rc = c->ex.exp.ensure(snb * 8)) || (rc = c->ex.ctr.ensure(64)) ||
+        (rc = c->ex.kin.ensure(sn * 4)) || (rc = c->ex.kout.ensure(sn * 4)) || (rc = c->ex.vin.ensure(sn * 4)) || (rc = c->ex.vout.ensure(sn * 4)) ||
+        (rc = c->ex.dk.ensure(sn * 4)) || (rc = c->ex.dx.ensure(sn * 4)) || (rc = c->ex.dc.ensure(sn * 4)) ||
+        (rc = c->ex.car.ensure((size_t)ntiles * sizeof(K25Car<K26V>)))) return rc;
     const u32* d_valid = nullptr;
     if (valid) {
-        if ((rc = c->ex_valid.ensure(snb * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->ex_valid.p, valid, snb * 4, hipMemcpyHostToDevice, c->stream));
-        d_valid = c->ex_valid.as<u32>();
+        if ((rc = c->ex.valid.ensure(snb * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->ex.valid.p, valid, snb * 4, hipMemcpyHostToDevice, c->stream));
+        d_valid = c->ex.valid.as<u32>();
     }
-    const double* d_weight = balanced ? c->bl_w.as<double>() + snb : nullptr;   // (the weights of cl_bal_iterate: behind w)
-    double* ew = c->ex_w.as<double>();
-    LAUNCH(k26_mask, (long long)W * 64, d_valid, d_weight, nb, W, nan, ew, c->ex_mask.as<u64>());
+    const double* d_weight = balanced ? c->bl.w.as<double>() + snb : nullptr;   // (the weights of cl_bal_iterate: behind w)
+    double* ew = c->ex.w.as<double>();
+    LAUNCH(k26_mask, (long long)W * 64, d_valid, d_weight, nb, W, nan, ew, c->ex.mask.as<u64>());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k26_pairs, dim3((unsigned)((nb + K26_DB - 1) / K26_DB)), dim3(TPB), 0, c->stream, (const u64*)c->ex_mask.as<u64>(), W, nb,
-                       bl.ignore_diags, c->ex_pairs.as<long long>());
+    hipLaunchKernelGGL(k26_pairs, dim3((unsigned)((nb + K26_DB - 1) / K26_DB)), dim3(TPB), 0, c->stream, (const u64*)c->ex.mask.as<u64>(), W, nb,
+                       bl.ignore_diags, c->ex.pairs.as<long long>());
     HIP_TRY(hipGetLastError());
     // the diagonal order
-    LAUNCH(k26_keys, n, c->mx_bx.as<int>(), c->mx_by.as<int>(), n, c->ex_kin.as<u32>(), c->ex_vin.as<u32>());
+    LAUNCH(k26_keys, n, c->mx.bx.as<int>(), c->mx.by.as<int>(), n, c->ex.kin.as<u32>(), c->ex.vin.as<u32>());
     HIP_TRY(hipGetLastError());
     const int bits = std::max(1, bits_for((unsigned)(nb - 1)));
-    if ((rc = prim_run(c->ex_tmp, "radix_sort_pairs(expected)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_pairs(tmp, bytes, c->ex_kin.as<u32>(), c->ex_kout.as<u32>(), c->ex_vin.as<u32>(), c->ex_vout.as<u32>(), sn, 0,
+    if ((rc = prim_run(c->ex.tmp, "radix_sort_pairs(expected)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_pairs(tmp, bytes, c->ex.kin.as<u32>(), c->ex.kout.as<u32>(), c->ex.vin.as<u32>(), c->ex.vout.as<u32>(), sn, 0,
                                              bits, c->stream);
         })))
         return rc;
-    HIP_TRY(hipMemsetAsync(c->ex_ctr.p, 0, 64, c->stream));
-    HIP_TRY(hipMemsetAsync(c->ex_cnt.p, 0, snb * 8, c->stream));                // (a diagonal without cells has no run)
-    HIP_TRY(hipMemsetAsync(c->ex_val.p, 0, snb * 8, c->stream));
-    u64* d_used = c->ex_ctr.as<u64>();
-    LAUNCH(k26_gather, n, (const u32*)c->ex_vout.as<u32>(), c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), n, (int)bl.b0, nb,
-           bl.ignore_diags, (const double*)ew, c->ex_dk.as<int>(), c->ex_dx.as<int>(), c->ex_dc.as<u32>(), d_used);
+    HIP_TRY(hipMemsetAsync(c->ex.ctr.p, 0, 64, c->stream));
+    HIP_TRY(hipMemsetAsync(c->ex.cnt.p, 0, snb * 8, c->stream));                // (a diagonal without cells has no run)
+    HIP_TRY(hipMemsetAsync(c->ex.val.p, 0, snb * 8, c->stream));
+    u64* d_used = c->ex.ctr.as<u64>();
+    LAUNCH(k26_gather, n, (const u32*)c->ex.vout.as<u32>(), c->mx.bx.as<int>(), c->mx.by.as<int>(), c->mx.cnt.as<u32>(), n, (int)bl.b0, nb,
+           bl.ignore_diags, (const double*)ew, c->ex.dk.as<int>(), c->ex.dx.as<int>(), c->ex.dc.as<u32>(), d_used);
     HIP_TRY(hipGetLastError());
     // the sums per diagonal: runs of equal d, the keys being the diagonals themselves (b0 = 0, nb = nd)
     K25In in{};
-    for (int ph = 0; ph < 2; ++ph) { in.key[ph] = c->ex_dk.as<int>(); in.oth[ph] = c->ex_dx.as<int>(); in.cnt[ph] = c->ex_dc.as<u32>(); }
+    for (int ph = 0; ph < 2; ++ph) { in.key[ph] = c->ex.dk.as<int>(); in.oth[ph] = c->ex.dx.as<int>(); in.cnt[ph] = c->ex.dc.as<u32>(); }
     in.n = n; in.ign = bl.ignore_diags; in.b0 = 0; in.nb = nb; in.w = ew;
     in.vec = 1;
     for (const void* p : {(const void*)in.key[0], (const void*)in.oth[0], (const void*)in.cnt[0]}) if ((uintptr_t)p % 16) in.vec = 0;
-    K26V::Out out{c->ex_val.as<double>(), c->ex_cnt.as<u64>()};
-    K25Car<K26V>* car = c->ex_car.as<K25Car<K26V>>();
+    K26V::Out out{c->ex.val.as<double>(), c->ex.cnt.as<u64>()};
+    K25Car<K26V>* car = c->ex.car.as<K25Car<K26V>>();
     hipLaunchKernelGGL(k25_marg<K26V>, dim3((unsigned)ntiles, 1u), dim3(TPB), 0, c->stream, in, out, car, ntiles, (u64*)nullptr, (const K25Rec*)nullptr);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k25_fold<K26V>, dim3((unsigned)nblocks(ntiles), 1u), dim3(TPB), 0, c->stream, (const K25Car<K26V>*)car, ntiles, 0, nb, out,
@@ -267,21 +260,21 @@ extern "C" int cl_exp_diagonals(cl_chrom* c, const uint32_t* valid, int32_t bala
     if (rc != CL_OK) return rc;
     if (!nd || !n_used) return fail(CL_ERR_ARG, "cl_exp_diagonals: bad arguments");
     if (balanced != 0 && balanced != 1) return fail(CL_ERR_ARG, "cl_exp_diagonals: balanced must be 0 or 1");
-    if (balanced && !c->bl.iterated) return fail(CL_ERR_ARG, "cl_exp_diagonals: no weights on this handle (cl_bal_iterate)");
+    if (balanced && !c->bl.st.iterated) return fail(CL_ERR_ARG, "cl_exp_diagonals: no weights on this handle (cl_bal_iterate)");
     if (balanced && valid) return fail(CL_ERR_ARG, "cl_exp_diagonals: the balanced mode takes its mask from the weights (valid must be NULL)");
-    cl_chrom::ExpState st;
+    cl_chrom::Exp::State st;
     st.ready = true;
     st.balanced = balanced;
-    if (c->bl.nb == 0) { exp_release(c); c->ex = st; return CL_OK; }            // (no cells: no HIP call)
+    if (c->bl.st.nb == 0) { exp_release(c); c->ex.st = st; return CL_OK; }            // (no cells: no HIP call)
     HIP_TRY(hipSetDevice(c->device));
-    c->ex = cl_chrom::ExpState();                                               // (the earlier state's buffers are written from here on; every K26 call ends synchronised)
+    c->ex.st = cl_chrom::Exp::State();                                               // (the earlier state's buffers are written from here on; every K26 call ends synchronised)
     rc = exp_diagonals(c, valid, balanced, st);
     if (rc != CL_OK) {
         (void)hipStreamSynchronize(c->stream);
         exp_release(c);
         return rc;
     }
-    c->ex = st;
+    c->ex.st = st;
     *nd = st.nd; *n_used = st.n_used;
     return CL_OK;
 }
@@ -290,28 +283,28 @@ extern "C" int cl_exp_diagonals_get(cl_chrom* c, int64_t first, int64_t count, i
 {
     int rc = exp_enter(c, "cl_exp_diagonals_get", true);
     if (rc != CL_OK) return rc;
-    if (!range_ok(first, count, c->ex.nd)) return fail(CL_ERR_ARG, "cl_exp_diagonals_get: range outside the diagonals");
+    if (!range_ok(first, count, c->ex.st.nd)) return fail(CL_ERR_ARG, "cl_exp_diagonals_get: range outside the diagonals");
     if (count > 0 && (!n_pairs || !cnt_sum || !val_sum)) return fail(CL_ERR_ARG, "cl_exp_diagonals_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return read_back(c, "cl_exp_diagonals_get", {{n_pairs, c->ex_pairs.as<long long>() + first, (size_t)count * 8},
-                                                 {cnt_sum, c->ex_cnt.as<u64>() + first, (size_t)count * 8},
-                                                 {val_sum, c->ex_val.as<double>() + first, (size_t)count * 8}});
+    return read_back(c, "cl_exp_diagonals_get", {{n_pairs, c->ex.pairs.as<long long>() + first, (size_t)count * 8},
+                                                 {cnt_sum, c->ex.cnt.as<u64>() + first, (size_t)count * 8},
+                                                 {val_sum, c->ex.val.as<double>() + first, (size_t)count * 8}});
 }
 
 extern "C" int cl_exp_set(cl_chrom* c, const double* expected, int64_t count)
 {
     int rc = exp_enter(c, "cl_exp_set", true);
     if (rc != CL_OK) return rc;
-    if (count != c->ex.nd) return fail(CL_ERR_ARG, "cl_exp_set: count is not the number of diagonals");
+    if (count != c->ex.st.nd) return fail(CL_ERR_ARG, "cl_exp_set: count is not the number of diagonals");
     if (count > 0 && !expected) return fail(CL_ERR_ARG, "cl_exp_set: bad arguments");
     if (count > 0) {
         HIP_TRY(hipSetDevice(c->device));
-        c->ex.expected = false;
-        HIP_TRY(hipMemcpyAsync(c->ex_exp.p, expected, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
+        c->ex.st.expected = false;
+        HIP_TRY(hipMemcpyAsync(c->ex.exp.p, expected, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->ex.expected = true;
+    c->ex.st.expected = true;
     return CL_OK;
 }
 
@@ -319,18 +312,18 @@ extern "C" int cl_exp_cells_get(cl_chrom* c, int64_t first, int64_t count, doubl
 {
     int rc = exp_enter(c, "cl_exp_cells_get", true);
     if (rc != CL_OK) return rc;
-    if (!c->ex.expected) return fail(CL_ERR_ARG, "cl_exp_cells_get: no expected values on this handle (cl_exp_set)");
-    if (!range_ok(first, count, c->bl.n_cells)) return fail(CL_ERR_ARG, "cl_exp_cells_get: range outside the cells");
+    if (!c->ex.st.expected) return fail(CL_ERR_ARG, "cl_exp_cells_get: no expected values on this handle (cl_exp_set)");
+    if (!range_ok(first, count, c->bl.st.n_cells)) return fail(CL_ERR_ARG, "cl_exp_cells_get: range outside the cells");
     if (count > 0 && !oe) return fail(CL_ERR_ARG, "cl_exp_cells_get: bad arguments");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = c->ex_out.ensure((size_t)count * 8))) return rc;
-    LAUNCH(k26_oe, count, c->mx_bx.as<int>(), c->mx_by.as<int>(), c->mx_cnt.as<u32>(), (long long)first, (long long)count, c->bl.n_cells,
-           (int)c->bl.b0, (int)c->bl.nb, c->bl.ignore_diags, (const double*)c->ex_w.as<double>(), (const double*)c->ex_exp.as<double>(), std::nan(""),
-           c->ex_out.as<double>());
+    if ((rc = c->ex.out.ensure((size_t)count * 8))) return rc;
+    LAUNCH(k26_oe, count, c->mx.bx.as<int>(), c->mx.by.as<int>(), c->mx.cnt.as<u32>(), (long long)first, (long long)count, c->bl.st.n_cells,
+           (int)c->bl.st.b0, (int)c->bl.st.nb, c->bl.st.ignore_diags, (const double*)c->ex.w.as<double>(), (const double*)c->ex.exp.as<double>(), std::nan(""),
+           c->ex.out.as<double>());
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(CL_ERR_HIP, "cl_exp_cells_get", hipGetErrorString(e));
-    return read_back(c, "cl_exp_cells_get", {{oe, c->ex_out.p, (size_t)count * 8}});
+    return read_back(c, "cl_exp_cells_get", {{oe, c->ex.out.p, (size_t)count * 8}});
 }
 
 extern "C" int cl_exp_free(cl_chrom* c) { return unit_free(c, "cl_exp_free", exp_release); }

@@ -19,11 +19,11 @@
 //               compact overflow list (at most m / K12_HB entries: every entry is a distinct cell of >= K12_HB PETs)
 // The overflow list is sorted and run-length coded on the device, and both parts are compacted to (value, multiplicity) pairs, so
 // the device-to-host copy is O(distinct counts).  Distinct counts D satisfy D (D + 1) / 2 <= kept PETs.
-// Scratch (c->fp_*) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables, and is freed when the
+// Scratch (c->fp) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables, and is freed when the
 // call returns: a fingerprint is one call per chromosome, and the handle's footprint between sweep steps stays what it was.
 #define K12_HB 2048                     // LDS histogram bins (8 KB per workgroup): counts 1 .. 2047
 #define K12_GRID 1024                   // workgroups of the grid-stride kernels
-enum { K12_MIN = 0, K12_MAX = 1, K12_KEPT = 2, K12_POS = 3, K12_NOVF = 4, K12_NPAIR = 5, K12_HDR = 16 };   // fp_small: header, then hist
+enum { K12_MIN = 0, K12_MAX = 1, K12_KEPT = 2, K12_POS = 3, K12_NOVF = 4, K12_NPAIR = 5, K12_HDR = 16 };   // fp.small: header, then hist
 
 // (K12Div, k12_div, k12_divisor: cl_chrom.h, shared with K24)
 __device__ __forceinline__ bool k12_keep(int x, int y, int cut)
@@ -179,18 +179,13 @@ k12_ovf_pairs(const u32* __restrict__ ov, int k, int* __restrict__ s, u32* __res
 static int k12_grid(long long n) { return (int)std::max(1ll, std::min<long long>(K12_GRID, (n + TPB - 1) / TPB)); }
 
 // ---- K12 host entry point -----------------------------------------------------------------------
-void fp_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->fp_small, &c->fp_keys, &c->fp_sorted, &c->fp_tmp, &c->fp_pairs}) b->release();
-}
-
 static int contact_hist(cl_chrom* c, int cut, int bin_size, int64_t cap, int64_t* values, int64_t* mult, int64_t* n_distinct,
                         int64_t* n_cells, int64_t* n_kept, int32_t* min_c)
 {
     const int n = (int)c->n;
     int rc;
-    if ((rc = c->fp_small.ensure((K12_HDR + K12_HB) * 4))) return rc;
-    int* s = c->fp_small.as<int>();
+    if ((rc = c->fp.small.ensure((K12_HDR + K12_HB) * 4))) return rc;
+    int* s = c->fp.small.as<int>();
     u32* hist = (u32*)(s + K12_HDR);
     hipLaunchKernelGGL(k12_init, dim3(1), dim3(1), 0, c->stream, s);
     HIP_TRY(hipMemsetAsync(hist, 0, K12_HB * 4, c->stream));
@@ -208,19 +203,19 @@ static int contact_hist(cl_chrom* c, int cut, int bin_size, int64_t cap, int64_t
     const int b = std::max(1, bits_for(top));
     const K12Div dv = k12_divisor((u32)bin_size);
     // keys of the kept rows, sorted over their 2b bits
-    if ((rc = c->fp_keys.ensure((size_t)m * 8)) || (rc = c->fp_sorted.ensure((size_t)m * 8))) return rc;
+    if ((rc = c->fp.keys.ensure((size_t)m * 8)) || (rc = c->fp.sorted.ensure((size_t)m * 8))) return rc;
     hipLaunchKernelGGL(k12_keys, dim3(k12_grid((n + K12_ITEMS - 1) / K12_ITEMS)), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, cut, minc, dv, b, m, s,
-                       c->fp_keys.as<u64>());
+                       c->fp.keys.as<u64>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->fp_tmp, "radix_sort_keys(cells)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_keys(tmp, bytes, c->fp_keys.as<u64>(), c->fp_sorted.as<u64>(), (size_t)m, 0, 2 * b, c->stream);
+    if ((rc = prim_run(c->fp.tmp, "radix_sort_keys(cells)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->fp.keys.as<u64>(), c->fp.sorted.as<u64>(), (size_t)m, 0, 2 * b, c->stream);
         })))
         return rc;
-    // run lengths -> LDS histogram + overflow list (fp_keys is free again: the overflow list lives there)
+    // run lengths -> LDS histogram + overflow list (fp.keys is free again: the overflow list lives there)
     const int ovf_cap = m / K12_HB + 1;
-    u32* ovf = (u32*)c->fp_keys.p;                                    // ovf_cap u32 <= m * 8 bytes
+    u32* ovf = (u32*)c->fp.keys.p;                                    // ovf_cap u32 <= m * 8 bytes
     u32* ovs = ovf + ovf_cap;                                         // the sorted copy
-    hipLaunchKernelGGL(k12_runs, dim3(k12_grid(m)), dim3(TPB), 0, c->stream, c->fp_sorted.as<u64>(), m, hist, s, ovf, ovf_cap);
+    hipLaunchKernelGGL(k12_runs, dim3(k12_grid(m)), dim3(TPB), 0, c->stream, c->fp.sorted.as<u64>(), m, hist, s, ovf, ovf_cap);
     HIP_TRY(hipGetLastError());
     int novf = 0;
     HIP_TRY(hipMemcpyAsync(&novf, s + K12_NOVF, 4, hipMemcpyDeviceToHost, c->stream));
@@ -228,11 +223,11 @@ static int contact_hist(cl_chrom* c, int cut, int bin_size, int64_t cap, int64_t
     if (novf > ovf_cap) return fail(CL_ERR_HIP, "cl_contact_hist: overflow list exceeded its bound");
     // (value, multiplicity) pairs: at most K12_HB - 1 histogram bins + novf overflow runs
     const int pcap = K12_HB + novf;
-    if ((rc = c->fp_pairs.ensure((size_t)pcap * 8))) return rc;
-    u32* pv = c->fp_pairs.as<u32>();
+    if ((rc = c->fp.pairs.ensure((size_t)pcap * 8))) return rc;
+    u32* pv = c->fp.pairs.as<u32>();
     u32* pm = pv + pcap;
     if (novf > 0) {
-        if ((rc = prim_run(c->fp_tmp, "radix_sort_keys(overflow)", [&](void* tmp, size_t& bytes) {
+        if ((rc = prim_run(c->fp.tmp, "radix_sort_keys(overflow)", [&](void* tmp, size_t& bytes) {
                 return rocprim::radix_sort_keys(tmp, bytes, ovf, ovs, (size_t)novf, 0, 32, c->stream);
             })))
             return rc;
@@ -282,6 +277,6 @@ extern "C" int cl_contact_hist(cl_chrom* c, int32_t cut, int32_t bin_size, int64
     HIP_TRY(hipSetDevice(c->device));
     const int rc = contact_hist(c, cut, bin_size, cap, values, mult, n_distinct, n_cells, n_kept, min_c);
     if (rc != CL_OK) (void)hipStreamSynchronize(c->stream);          // nothing of ours may still be running when the scratch goes
-    fp_release(c);
+    c->fp = cl_chrom::Fp();
     return rc;
 }

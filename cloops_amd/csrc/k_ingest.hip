@@ -1,6 +1,7 @@
 // k_ingest.hip -- K16: the BEDPE reader of the reference (cLoops/io.py:62-189, parseRawBedpe / parseRawBedpe2, restated by
 // cloops_amd/io.py:parse_bedpe) on the device -- kernels and the C entry points of the cl_ingest handle.  K18: the same reader fed
 // with 4DN pairs text (cl_ingest_set_format), every data line read as the BEDPE line K15 writes for it.
+#include <memory>
 #include "cl_chrom.h"
 #include "cl_pairs.h"
 
@@ -505,12 +506,13 @@ struct cl_ingest {
     bool any_feed = false;
     long long err_line = 0, headers = 0;          // of the last feed: cl_ingest_error, cl_ingest_headers
     int err_kind = 0;
-    DevBuf in, tcnt, toff, ends, rec, tmp, err, nkey, nfirst, nout, th, tid, tof, tln, blob, key, val, skey, sval, start;
+    struct Feed { DevBuf in, rec, ends, key, val, skey, sval; } fd;   // what only a feed and its commit need: cl_ingest_finish drops them first
+    DevBuf tcnt, toff, tmp, err, nkey, nfirst, nout, th, tid, tof, tln, blob, start;
     long long L = 0;                              // lines of the last feed
     bool fed = false;
     u32 n_names = 0;
-    std::vector<K16Seg*> segs;
-    std::vector<K16Chrom*> chroms;
+    std::vector<std::unique_ptr<K16Seg>> segs;
+    std::vector<std::unique_ptr<K16Chrom>> chroms;
     DevBuf dist;                                  // finish: the distances in global line order
     long long n_dist = 0;
     bool finished = false;
@@ -518,25 +520,18 @@ struct cl_ingest {
     float ms[K16_MS_N] = {};
 };
 
+// `delete c` frees the buffers, the segments' and chromosomes' included; the events and the stream are noted first and ended
+// afterwards (as free_chrom does)
 static void ingest_free(cl_ingest* c)
 {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->in, &c->tcnt, &c->toff, &c->ends, &c->rec, &c->tmp, &c->err, &c->nkey, &c->nfirst, &c->nout, &c->th, &c->tid, &c->tof,
-                      &c->tln, &c->blob, &c->key, &c->val, &c->skey, &c->sval, &c->start, &c->dist})
-        b->release();
-    for (K16Seg* s : c->segs) {
-        for (DevBuf* b : {&s->a, &s->b, &s->gl, &s->sf}) b->release();
-        delete s;
-    }
-    for (K16Chrom* h : c->chroms) {
-        for (DevBuf* b : {&h->a, &h->b, &h->gl, &h->sf, &h->x, &h->y}) b->release();
-        delete h;
-    }
-    for (hipEvent_t& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+    const std::vector<hipEvent_t> events(std::begin(c->ev), std::end(c->ev));
+    const hipStream_t own = c->own_stream ? c->stream : nullptr;
     delete c;
+    for (hipEvent_t e : events)
+        if (e) (void)hipEventDestroy(e);
+    if (own) (void)hipStreamDestroy(own);
 }
 
 static void ingest_ms(cl_ingest* c, int k, int e0, int e1)             // after a synchronisation of the stream
@@ -594,17 +589,17 @@ static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* 
     const long long ne = n + (virt ? 1 : 0);
     const long long tiles = (ne + K15_TILE - 1) / K15_TILE;
     int rc;
-    if ((rc = c->in.ensure((size_t)ne + K15_PAD)) || (rc = c->tcnt.ensure((size_t)(tiles + 1) * 4)) || (rc = c->toff.ensure((size_t)(tiles + 1) * 4)))
+    if ((rc = c->fd.in.ensure((size_t)ne + K15_PAD)) || (rc = c->tcnt.ensure((size_t)(tiles + 1) * 4)) || (rc = c->toff.ensure((size_t)(tiles + 1) * 4)))
         return rc;
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    HIP_TRY(hipMemcpyAsync(c->in.p, bytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (virt) HIP_TRY(hipMemsetAsync(c->in.as<char>() + n, '\n', 1, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->fd.in.p, bytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (virt) HIP_TRY(hipMemsetAsync(c->fd.in.as<char>() + n, '\n', 1, c->stream));
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     HIP_TRY(hipMemsetAsync(c->tcnt.as<u32>() + tiles, 0, 4, c->stream));
     HIP_TRY(hipMemsetAsync(c->err.p, 0, 64, c->stream));
     HIP_TRY(hipMemsetAsync(c->err.p, 0x7f, 4, c->stream));            // no exotic line: 0x7f7f7f7f, above any line index
     HIP_TRY(hipMemsetAsync(c->err.as<u32>() + 7, 0x7f, 4, c->stream));
-    hipLaunchKernelGGL(k15_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->tcnt.as<u32>());
+    hipLaunchKernelGGL(k15_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->fd.in.as<uint4>(), ne, c->tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
     if ((rc = prim_run(c->tmp, "exclusive_scan(tiles)", [&](void* tmp, size_t& nb) {
             return rocprim::exclusive_scan(tmp, nb, c->tcnt.as<u32>(), c->toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
@@ -613,25 +608,25 @@ static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* 
     u32 nl = 0;
     if ((rc = ingest_read(c, &nl, c->toff.as<u32>() + tiles))) return rc;
     const long long L = nl;                                             // >= 1: the chunk ends with a '\n'
-    if ((rc = c->ends.ensure((size_t)L * 4)) || (rc = c->rec.ensure((size_t)L * sizeof(K16Rec)))) return rc;
-    hipLaunchKernelGGL(k15_lines, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->in.as<uint4>(), ne, c->toff.as<u32>(), L, c->ends.as<u32>());
+    if ((rc = c->fd.ends.ensure((size_t)L * 4)) || (rc = c->fd.rec.ensure((size_t)L * sizeof(K16Rec)))) return rc;
+    hipLaunchKernelGGL(k15_lines, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->fd.in.as<uint4>(), ne, c->toff.as<u32>(), L, c->fd.ends.as<u32>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
     const dim3 pgrid((unsigned)((L + K16_T - 1) / K16_T));
     if (c->fmt == CL_INGEST_PAIRS)
-        hipLaunchKernelGGL(k16_parse<CL_INGEST_PAIRS>, pgrid, dim3(K16_T), K16_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->cut, c->ext,
-                           c->rec.as<K16Rec>(), c->err.as<int>());
+        hipLaunchKernelGGL(k16_parse<CL_INGEST_PAIRS>, pgrid, dim3(K16_T), K16_LDS, c->stream, c->fd.in.as<uint4>(), c->fd.ends.as<u32>(), L, c->cut, c->ext,
+                           c->fd.rec.as<K16Rec>(), c->err.as<int>());
     else
-        hipLaunchKernelGGL(k16_parse<CL_INGEST_BEDPE>, pgrid, dim3(K16_T), K16_LDS, c->stream, c->in.as<uint4>(), c->ends.as<u32>(), L, c->cut, c->ext,
-                           c->rec.as<K16Rec>(), c->err.as<int>());
+        hipLaunchKernelGGL(k16_parse<CL_INGEST_BEDPE>, pgrid, dim3(K16_T), K16_LDS, c->stream, c->fd.in.as<uint4>(), c->fd.ends.as<u32>(), L, c->cut, c->ext,
+                           c->fd.rec.as<K16Rec>(), c->err.as<int>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[3], c->stream));
     HIP_TRY(hipMemsetAsync(c->nkey.p, 0, (size_t)K16_SLOTS * 8, c->stream));
     HIP_TRY(hipMemsetAsync(c->nfirst.p, 0xff, (size_t)K16_SLOTS * 4, c->stream));
     u32* dctr = c->err.as<u32>() + 4;
-    hipLaunchKernelGGL(k16_names, dim3(k16_grid(L)), dim3(TPB), 0, c->stream, c->rec.as<K16Rec>(), L, c->nkey.as<u64>(), c->nfirst.as<u32>(), dctr);
+    hipLaunchKernelGGL(k16_names, dim3(k16_grid(L)), dim3(TPB), 0, c->stream, c->fd.rec.as<K16Rec>(), L, c->nkey.as<u64>(), c->nfirst.as<u32>(), dctr);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k16_names_out, dim3(k16_grid(K16_SLOTS)), dim3(TPB), 0, c->stream, c->nkey.as<u64>(), c->nfirst.as<u32>(), c->rec.as<K16Rec>(),
+    hipLaunchKernelGGL(k16_names_out, dim3(k16_grid(K16_SLOTS)), dim3(TPB), 0, c->stream, c->nkey.as<u64>(), c->nfirst.as<u32>(), c->fd.rec.as<K16Rec>(),
                        L, dctr, c->nout.as<K16Name>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev[4], c->stream));
@@ -641,7 +636,7 @@ static int ingest_feed(cl_ingest* c, const char* bytes, long long n, long long* 
     c->headers = words[10];
     if ((long long)words[7] < L) {                                      // pairs: a line the converter raises on
         u32 flags = 0;
-        if ((rc = ingest_read(c, &flags, (const char*)c->rec.p + (size_t)words[7] * sizeof(K16Rec) + offsetof(K16Rec, flags)))) return rc;
+        if ((rc = ingest_read(c, &flags, (const char*)c->fd.rec.p + (size_t)words[7] * sizeof(K16Rec) + offsetof(K16Rec, flags)))) return rc;
         c->err_line = (long long)words[7] + 1;
         c->err_kind = (int)(flags >> 8);
     }
@@ -754,8 +749,8 @@ extern "C" int cl_ingest_commit(cl_ingest* c, int64_t chunk, int64_t line0, cons
     int rc;
     const size_t nt = (size_t)std::max(n_table, 1);
     if ((rc = c->th.ensure(nt * 8)) || (rc = c->tid.ensure(nt * 4)) || (rc = c->tof.ensure(nt * 4)) || (rc = c->tln.ensure(nt * 4)) ||
-        (rc = c->blob.ensure((size_t)std::max<int64_t>(names_bytes, 16))) || (rc = c->key.ensure((size_t)L * 4)) || (rc = c->val.ensure((size_t)L * 4)) ||
-        (rc = c->skey.ensure((size_t)L * 4)) || (rc = c->sval.ensure((size_t)L * 4)) || (rc = c->start.ensure(((size_t)n_ids + 1) * 4)))
+        (rc = c->blob.ensure((size_t)std::max<int64_t>(names_bytes, 16))) || (rc = c->fd.key.ensure((size_t)L * 4)) || (rc = c->fd.val.ensure((size_t)L * 4)) ||
+        (rc = c->fd.skey.ensure((size_t)L * 4)) || (rc = c->fd.sval.ensure((size_t)L * 4)) || (rc = c->start.ensure(((size_t)n_ids + 1) * 4)))
         return rc;
     HIP_TRY(hipEventRecord(c->ev[5], c->stream));
     if (n_table > 0) {
@@ -767,50 +762,39 @@ extern "C" int cl_ingest_commit(cl_ingest* c, int64_t chunk, int64_t line0, cons
     }
     int* dstatus = c->err.as<int>() + 1;
     HIP_TRY(hipMemsetAsync(dstatus, 0, 4, c->stream));
-    hipLaunchKernelGGL(k16_apply, dim3(k16_grid(L)), dim3(TPB), 0, c->stream, c->in.as<uint4>(), c->rec.as<K16Rec>(), L, c->th.as<u64>(), c->tid.as<int>(),
-                       c->tof.as<u32>(), c->tln.as<u32>(), (int)n_table, c->blob.as<unsigned char>(), (u32)n_ids, c->key.as<u32>(), c->val.as<u32>(),
+    hipLaunchKernelGGL(k16_apply, dim3(k16_grid(L)), dim3(TPB), 0, c->stream, c->fd.in.as<uint4>(), c->fd.rec.as<K16Rec>(), L, c->th.as<u64>(), c->tid.as<int>(),
+                       c->tof.as<u32>(), c->tln.as<u32>(), (int)n_table, c->blob.as<unsigned char>(), (u32)n_ids, c->fd.key.as<u32>(), c->fd.val.as<u32>(),
                        dstatus);
     HIP_TRY(hipGetLastError());
     unsigned bits = 1;
     while ((1u << bits) <= (unsigned)n_ids) ++bits;                     // keys 0 .. n_ids
-    if ((rc = ingest_sort_pairs_u32(c, c->key.as<u32>(), c->skey.as<u32>(), c->val.as<u32>(), c->sval.as<u32>(), (size_t)L, bits))) return rc;
-    hipLaunchKernelGGL(k16_bounds, dim3(k16_grid(n_ids + 1)), dim3(TPB), 0, c->stream, c->skey.as<u32>(), L, (u32)n_ids, c->start.as<u32>());
+    if ((rc = ingest_sort_pairs_u32(c, c->fd.key.as<u32>(), c->fd.skey.as<u32>(), c->fd.val.as<u32>(), c->fd.sval.as<u32>(), (size_t)L, bits))) return rc;
+    hipLaunchKernelGGL(k16_bounds, dim3(k16_grid(n_ids + 1)), dim3(TPB), 0, c->stream, c->fd.skey.as<u32>(), L, (u32)n_ids, c->start.as<u32>());
     HIP_TRY(hipGetLastError());
-    K16Seg* s = new K16Seg();
+    std::unique_ptr<K16Seg> s(new K16Seg());
     s->chunk = chunk;
     s->start.resize((size_t)n_ids + 1);
     int st = 0;
     HIP_TRY(hipMemcpyAsync(&st, dstatus, 4, hipMemcpyDeviceToHost, c->stream));
     rc = ingest_read(c, s->start.data(), c->start.p, (size_t)n_ids + 1);
     if (rc != CL_OK || st != 0) {
-        delete s;
         *status = st;
         return rc;
     }
     s->n = s->start[n_ids];
     if (s->n > 0) {
         if ((rc = s->a.ensure((size_t)s->n * 8)) || (rc = s->b.ensure((size_t)s->n * 8)) ||
-            (c->want_dist && ((rc = s->gl.ensure((size_t)s->n * 8)) || (rc = s->sf.ensure((size_t)s->n))))) {
-            for (DevBuf* b : {&s->a, &s->b, &s->gl, &s->sf}) b->release();
-            delete s;
-            return rc;
-        }
-        hipLaunchKernelGGL(k16_gather, dim3(k16_grid(s->n)), dim3(TPB), 0, c->stream, c->rec.as<K16Rec>(), c->sval.as<u32>(), s->n, (long long)line0,
+            (c->want_dist && ((rc = s->gl.ensure((size_t)s->n * 8)) || (rc = s->sf.ensure((size_t)s->n))))) return rc;
+        hipLaunchKernelGGL(k16_gather, dim3(k16_grid(s->n)), dim3(TPB), 0, c->stream, c->fd.rec.as<K16Rec>(), c->fd.sval.as<u32>(), s->n, (long long)line0,
                            s->a.as<long long>(), s->b.as<long long>(), c->want_dist ? s->gl.as<long long>() : nullptr,
                            c->want_dist ? s->sf.as<unsigned char>() : nullptr);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(c->ev[6], c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            for (DevBuf* b : {&s->a, &s->b, &s->gl, &s->sf}) b->release();
-            delete s;
-            return fail(CL_ERR_HIP, "cl_ingest_commit: gather", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(CL_ERR_HIP, "cl_ingest_commit: gather", hipGetErrorString(e));
         ingest_ms(c, K16_MS_COMMIT, 5, 6);
-        c->segs.push_back(s);
         for (int i = 0; i < n_ids; ++i) counts[i] = (int64_t)s->start[i + 1] - s->start[i];
-    } else {
-        delete s;
+        c->segs.push_back(std::move(s));
     }
     return CL_OK;
 }
@@ -823,14 +807,13 @@ static int ingest_unique(cl_ingest* c, K16Chrom* h)
     if (n >= (1ll << 31)) return fail(CL_ERR_ARG, "cl_ingest_finish: more than 2^31 PETs on one chromosome");
     int rc;
     DevBuf k0, k1, v0, v1, keep, pos;
-    auto drop = [&]() { for (DevBuf* b : {&k0, &k1, &v0, &v1, &keep, &pos}) b->release(); };
     if ((rc = k0.ensure((size_t)n * 8)) || (rc = k1.ensure((size_t)n * 8)) || (rc = v0.ensure((size_t)n * 4)) || (rc = v1.ensure((size_t)n * 4)) ||
-        (rc = keep.ensure((size_t)n * 4)) || (rc = pos.ensure((size_t)n * 4))) { drop(); return rc; }
+        (rc = keep.ensure((size_t)n * 4)) || (rc = pos.ensure((size_t)n * 4))) return rc;
     int* dwide = c->err.as<int>() + 2;
     hipError_t e = hipMemsetAsync(dwide, 0, 4, c->stream);
     hipLaunchKernelGGL(k16_pack, dim3(k16_grid(n)), dim3(TPB), 0, c->stream, h->a.as<long long>(), h->b.as<long long>(), n, k0.as<u64>(), v0.as<u32>(), dwide);
     int wide = 0;
-    if (e != hipSuccess || (rc = ingest_read(c, &wide, dwide))) { drop(); return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: memset") : rc; }
+    if (e != hipSuccess || (rc = ingest_read(c, &wide, dwide))) return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: memset") : rc;
     size_t bytes_tmp = 0;
     const u32* rows = nullptr;
     if (!wide) {                                                        // one packed key of 62 bits
@@ -851,35 +834,29 @@ static int ingest_unique(cl_ingest* c, K16Chrom* h)
         }
         rows = v0.as<u32>();
     }
-    if (rc != CL_OK) { drop(); return rc; }
-    if (e != hipSuccess) { drop(); return fail(CL_ERR_HIP, "cl_ingest_finish: radix_sort_pairs", hipGetErrorString(e)); }
+    if (rc != CL_OK) return rc;
+    if (e != hipSuccess) return fail(CL_ERR_HIP, "cl_ingest_finish: radix_sort_pairs", hipGetErrorString(e));
     hipLaunchKernelGGL(k16_mark, dim3(k16_grid(n)), dim3(TPB), 0, c->stream, h->a.as<long long>(), h->b.as<long long>(), rows, n, keep.as<u32>());
     rc = prim_run(c->tmp, "cl_ingest_finish: exclusive_scan", [&](void* tmp, size_t& nb) {
         return rocprim::exclusive_scan(tmp, nb, keep.as<u32>(), pos.as<u32>(), 0u, (size_t)n, rocprim::plus<u32>(), c->stream);
     });
-    if (rc != CL_OK) { drop(); return rc; }
+    if (rc != CL_OK) return rc;
     u32 lastp = 0, lastk = 0;
     e = hipMemcpyAsync(&lastk, keep.as<u32>() + (n - 1), 4, hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess || (rc = ingest_read(c, &lastp, pos.as<u32>() + (n - 1)))) { drop(); return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: copy") : rc; }
+    if (e != hipSuccess || (rc = ingest_read(c, &lastp, pos.as<u32>() + (n - 1)))) return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: copy") : rc;
     const long long m = (long long)lastp + lastk;
     if (m < n) {
         DevBuf oa, ob, ogl, osf;
         if ((rc = oa.ensure((size_t)m * 8)) || (rc = ob.ensure((size_t)m * 8)) ||
-            (c->want_dist && ((rc = ogl.ensure((size_t)m * 8)) || (rc = osf.ensure((size_t)m))))) {
-            for (DevBuf* b : {&oa, &ob, &ogl, &osf}) b->release();
-            drop();
-            return rc;
-        }
+            (c->want_dist && ((rc = ogl.ensure((size_t)m * 8)) || (rc = osf.ensure((size_t)m))))) return rc;
         hipLaunchKernelGGL(k16_compact, dim3(k16_grid(n)), dim3(TPB), 0, c->stream, h->a.as<long long>(), h->b.as<long long>(),
                            c->want_dist ? h->gl.as<long long>() : nullptr, c->want_dist ? h->sf.as<unsigned char>() : nullptr, keep.as<u32>(),
                            pos.as<u32>(), n, oa.as<long long>(), ob.as<long long>(), ogl.as<long long>(), osf.as<unsigned char>());
         e = hipStreamSynchronize(c->stream);
-        for (DevBuf* b : {&h->a, &h->b, &h->gl, &h->sf}) b->release();
-        h->a = oa; h->b = ob; h->gl = ogl; h->sf = osf;
+        h->a = std::move(oa); h->b = std::move(ob); h->gl = std::move(ogl); h->sf = std::move(osf);
         h->n = m;
-        if (e != hipSuccess) { drop(); return fail(CL_ERR_HIP, "cl_ingest_finish: compaction", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(CL_ERR_HIP, "cl_ingest_finish: compaction", hipGetErrorString(e));
     }
-    drop();
     return CL_OK;
 }
 
@@ -893,28 +870,29 @@ extern "C" int cl_ingest_finish(cl_ingest* c, cl_ingest* other, int32_t n_ids, i
     HIP_TRY(hipSetDevice(c->device));
     if (other) {                                                        // its segments move here
         HIP_TRY(hipStreamSynchronize(other->stream));
-        c->segs.insert(c->segs.end(), other->segs.begin(), other->segs.end());
+        c->segs.insert(c->segs.end(), std::make_move_iterator(other->segs.begin()), std::make_move_iterator(other->segs.end()));
         other->segs.clear();
         other->finished = true;
-        for (DevBuf* b : {&other->in, &other->rec, &other->ends, &other->key, &other->val, &other->skey, &other->sval, &other->tmp}) b->release();
+        other->fd = cl_ingest::Feed();
+        other->tmp.release();
     }
     c->finished = true;
-    for (DevBuf* b : {&c->in, &c->rec, &c->ends, &c->key, &c->val, &c->skey, &c->sval}) b->release();
-    std::sort(c->segs.begin(), c->segs.end(), [](const K16Seg* x, const K16Seg* y) { return x->chunk < y->chunk; });
+    c->fd = cl_ingest::Feed();
+    std::sort(c->segs.begin(), c->segs.end(), [](const std::unique_ptr<K16Seg>& x, const std::unique_ptr<K16Seg>& y) { return x->chunk < y->chunk; });
     HIP_TRY(hipEventRecord(c->ev[5], c->stream));
     int rc = CL_OK;
     long long total = 0;
     for (int id = 0; id < n_ids && rc == CL_OK; ++id) {
-        K16Chrom* h = new K16Chrom();
-        c->chroms.push_back(h);
-        for (const K16Seg* s : c->segs)
+        c->chroms.emplace_back(new K16Chrom());
+        K16Chrom* h = c->chroms.back().get();
+        for (const auto& s : c->segs)
             if ((size_t)id + 1 < s->start.size()) h->n += (long long)s->start[id + 1] - s->start[id];
         if (h->n == 0) continue;
         if ((rc = h->a.ensure((size_t)h->n * 8)) || (rc = h->b.ensure((size_t)h->n * 8)) ||
             (c->want_dist && ((rc = h->gl.ensure((size_t)h->n * 8)) || (rc = h->sf.ensure((size_t)h->n)))))
             break;
         long long at = 0;
-        for (K16Seg* s : c->segs) {
+        for (const auto& s : c->segs) {
             if ((size_t)id + 1 >= s->start.size()) continue;
             const long long p = s->start[id], m = (long long)s->start[id + 1] - p;
             if (m == 0) continue;
@@ -929,42 +907,36 @@ extern "C" int cl_ingest_finish(cl_ingest* c, cl_ingest* other, int32_t n_ids, i
     }
     if (rc != CL_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (K16Seg* s : c->segs) {
-        for (DevBuf* b : {&s->a, &s->b, &s->gl, &s->sf}) b->release();
-        delete s;
-    }
-    c->segs.clear();
+    c->segs.clear();                                                    // (merged: their buffers go now)
     for (int id = 0; id < n_ids; ++id) {
-        K16Chrom* h = c->chroms[id];
+        K16Chrom* h = c->chroms[id].get();
         if (unique && (rc = ingest_unique(c, h))) return rc;
         n_rows[id] = h->n;
         total += h->n;
     }
     if (c->want_dist && total > 0) {
         DevBuf dk, dv, sk;
-        auto drop = [&]() { for (DevBuf* b : {&dk, &dv, &sk}) b->release(); };
         unsigned long long* dcnt = (unsigned long long*)(c->err.as<u32>() + 8);
-        if ((rc = dk.ensure((size_t)total * 8)) || (rc = dv.ensure((size_t)total * 8))) { drop(); return rc; }
+        if ((rc = dk.ensure((size_t)total * 8)) || (rc = dv.ensure((size_t)total * 8))) return rc;
         hipError_t e = hipMemsetAsync(dcnt, 0, 8, c->stream);
-        for (K16Chrom* h : c->chroms)
+        for (const auto& h : c->chroms)
             if (h->n > 0)
                 hipLaunchKernelGGL(k16_dist, dim3(k16_grid(h->n)), dim3(TPB), 0, c->stream, h->a.as<long long>(), h->b.as<long long>(),
                                    h->gl.as<long long>(), h->sf.as<unsigned char>(), h->n, dcnt, dk.as<long long>(), dv.as<long long>());
         unsigned long long nd = 0;
-        if (e != hipSuccess || (rc = ingest_read(c, &nd, dcnt))) { drop(); return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: memset") : rc; }
+        if (e != hipSuccess || (rc = ingest_read(c, &nd, dcnt))) return e != hipSuccess ? fail(CL_ERR_HIP, "cl_ingest_finish: memset") : rc;
         if (nd > 0) {
-            if ((rc = sk.ensure((size_t)nd * 8)) || (rc = c->dist.ensure((size_t)nd * 8))) { drop(); return rc; }
+            if ((rc = sk.ensure((size_t)nd * 8)) || (rc = c->dist.ensure((size_t)nd * 8))) return rc;
             rc = prim_run(c->tmp, "cl_ingest_finish: distances", [&](void* tmp, size_t& nb) {
                 return rocprim::radix_sort_pairs(tmp, nb, dk.as<long long>(), sk.as<long long>(), dv.as<long long>(), c->dist.as<long long>(), (size_t)nd, 0,
                                                  64, c->stream);
             });
-            if (rc != CL_OK) { drop(); return rc; }
+            if (rc != CL_OK) return rc;
             e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) { drop(); return fail(CL_ERR_HIP, "cl_ingest_finish: distances", hipGetErrorString(e)); }
+            if (e != hipSuccess) return fail(CL_ERR_HIP, "cl_ingest_finish: distances", hipGetErrorString(e));
         }
         c->n_dist = (long long)nd;
-        drop();
-        for (K16Chrom* h : c->chroms) { h->gl.release(); h->sf.release(); }
+        for (const auto& h : c->chroms) { h->gl.release(); h->sf.release(); }
     }
     HIP_TRY(hipEventRecord(c->ev[6], c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -977,7 +949,7 @@ extern "C" int cl_ingest_finish(cl_ingest* c, cl_ingest* other, int32_t n_ids, i
 static K16Chrom* ingest_chrom(cl_ingest* c, int32_t id)
 {
     if (!c || !c->finished || id < 0 || (size_t)id >= c->chroms.size()) return nullptr;
-    return c->chroms[id];
+    return c->chroms[id].get();
 }
 
 extern "C" int cl_ingest_rows(cl_ingest* c, int32_t id, int64_t* a, int64_t* b, int64_t cap)

@@ -7,7 +7,7 @@
 // ==========================================================================================
 // Definitions: include/cloops_hip.h, cl_kdis_build.  The reference has nothing of the kind; every number here is an integer that a few
 // lines of numpy reproduce (tests/kdis_cases.py).  Rows: K19's table (agg_table: the kept rows sorted by X with a stable sort, so rows
-// of equal X stay in input order; c->ag_sx = X + 2^30, c->ag_sy = Y, c->ag_kept of them), shared with cl_agg_loops and cl_dom_tracks
+// of equal X stay in input order; c->ag.sx = X + 2^30, c->ag.sy = Y, c->ag.kept of them), shared with cl_agg_loops and cl_dom_tracks
 // and keyed by the cut: nothing is sorted here.
 //   k23_walk<CAP>             one lane per table row, K23_TILE rows per workgroup.  Lane i walks outward from its own index: step s
 //                             reads row i + s and row i - s, so neighbouring lanes read neighbouring addresses (K23_AHEAD rows of
@@ -27,7 +27,7 @@
 // Cost: a row reads the rows whose X lies within its d_kmax of its own X -- hundreds to a few thousand on ChIA-PET / HiChIP densities,
 // whatever the size of the chromosome.  It is quadratic only where almost all X are equal (then |dx| = 0 never reaches T, and the walk
 // is the brute force).
-// Only vector stores and ordinary HIP atomics; every index is checked against its array before a load or store.  Scratch (c->kd_*) is
+// Only vector stores and ordinary HIP atomics; every index is checked against its array before a load or store.  Scratch (c->kd) is
 // the handle's own, apart from the sweep's layouts, q index, count cache and the K8 / K13 / K14 / K20 / K21 / K22 state.
 #define K23_TILE TPB                    // table rows per workgroup of k23_walk, one per lane
 #define K23_AHEAD 4                     // rows a lane reads ahead on either side per round of k23_walk
@@ -128,38 +128,32 @@ k23_hist(const int* __restrict__ d, int m, u64* __restrict__ out)
 }
 
 // ---- K23 host side ------------------------------------------------------------------------------
-void kdis_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->kd_x, &c->kd_y, &c->kd_d, &c->kd_hist}) b->release();
-    c->kd = cl_chrom::KdisState();
-}
-
-static int kdis_build(cl_chrom* c, cl_chrom::KdisState& st)
+static int kdis_build(cl_chrom* c, cl_chrom::Kdis::State& st)
 {
     int rc;
     if ((rc = agg_table(c, st.cut))) return rc;
-    st.n_kept = c->ag_kept;
-    if (c->ag_kept == 0) { st.ready = true; return CL_OK; }
-    const int m = c->ag_kept;
+    st.n_kept = c->ag.kept;
+    if (c->ag.kept == 0) { st.ready = true; return CL_OK; }
+    const int m = c->ag.kept;
     const size_t sm = (size_t)m, hw = (size_t)st.n_k * (CL_KDIS_BINS + 2);
-    if ((rc = c->kd_x.ensure(sm * 4)) || (rc = c->kd_y.ensure(sm * 4)) || (rc = c->kd_d.ensure(sm * 4 * (size_t)st.n_k)) ||
-        (rc = c->kd_hist.ensure(hw * 8))) return rc;
-    HIP_TRY(hipMemsetAsync(c->kd_hist.p, 0, hw * 8, c->stream));
+    if ((rc = c->kd.x.ensure(sm * 4)) || (rc = c->kd.y.ensure(sm * 4)) || (rc = c->kd.d.ensure(sm * 4 * (size_t)st.n_k)) ||
+        (rc = c->kd.hist.ensure(hw * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(c->kd.hist.p, 0, hw * 8, c->stream));
     K23Ks ks{};
     ks.n = st.n_k;
     for (int w = 0; w < st.n_k; ++w) ks.k[w] = st.ks[w];
     const int kmax = st.ks[st.n_k - 1];
     const dim3 grid((unsigned)(((long long)m + K23_TILE - 1) / K23_TILE)), block(K23_TILE);
-    const u32* sx = c->ag_sx.as<u32>();
-    const int* sy = c->ag_sy.as<int>();
-    int *ox = c->kd_x.as<int>(), *oy = c->kd_y.as<int>(), *od = c->kd_d.as<int>();
+    const u32* sx = c->ag.sx.as<u32>();
+    const int* sy = c->ag.sy.as<int>();
+    int *ox = c->kd.x.as<int>(), *oy = c->kd.y.as<int>(), *od = c->kd.d.as<int>();
     if (kmax <= 8) hipLaunchKernelGGL(k23_walk<8>, grid, block, 0, c->stream, sx, sy, m, kmax, ks, ox, oy, od);
     else if (kmax <= 16) hipLaunchKernelGGL(k23_walk<16>, grid, block, 0, c->stream, sx, sy, m, kmax, ks, ox, oy, od);
     else if (kmax <= 32) hipLaunchKernelGGL(k23_walk<32>, grid, block, 0, c->stream, sx, sy, m, kmax, ks, ox, oy, od);
     else hipLaunchKernelGGL(k23_walk<64>, grid, block, 0, c->stream, sx, sy, m, kmax, ks, ox, oy, od);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k23_hist, dim3((unsigned)std::max(1, std::min(K23_HIST_BLOCKS, nblocks(m))), (unsigned)st.n_k), dim3(TPB), 0, c->stream,
-                       (const int*)od, m, c->kd_hist.as<u64>());
+                       (const int*)od, m, c->kd.hist.as<u64>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     st.ready = true;
@@ -177,13 +171,13 @@ extern "C" int cl_kdis_build(cl_chrom* c, int64_t cut, const int32_t* ks, int32_
         if (w > 0 && ks[w] <= ks[w - 1]) return fail(CL_ERR_ARG, "cl_kdis_build: ks must be strictly ascending");
     }
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_kdis_build: asynchronous runs still in flight");
-    cl_chrom::KdisState st;
+    cl_chrom::Kdis::State st;
     st.n_k = n_k;
     for (int w = 0; w < n_k; ++w) st.ks[w] = ks[w];
     st.cut = cut <= 0 ? 0 : (int)std::min<int64_t>(cut, 1ll << 30);             // |Y - X| < 2^30: a larger cut keeps no row either
     if (c->n == 0) {
         st.ready = true;
-        c->kd = st;
+        c->kd.st = st;
         return CL_OK;
     }
     HIP_TRY(hipSetDevice(c->device));
@@ -193,7 +187,7 @@ extern "C" int cl_kdis_build(cl_chrom* c, int64_t cut, const int32_t* ks, int32_
         kdis_release(c);
         return rc;
     }
-    c->kd = st;
+    c->kd.st = st;
     *n_kept = st.n_kept;
     return CL_OK;
 }
@@ -201,16 +195,16 @@ extern "C" int cl_kdis_build(cl_chrom* c, int64_t cut, const int32_t* ks, int32_
 extern "C" int cl_kdis_get(cl_chrom* c, int32_t which, int64_t first, int64_t count, int32_t* x, int32_t* y, int32_t* d)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (!c->kd.ready) return fail(CL_ERR_ARG, "cl_kdis_get: no k-distances on this handle (cl_kdis_build)");
-    if (which < 0 || which >= c->kd.n_k) return fail(CL_ERR_ARG, "cl_kdis_get: which outside the ks of the build");
-    if (!range_ok(first, count, c->kd.n_kept)) return fail(CL_ERR_ARG, "cl_kdis_get: range outside the kept rows");
+    if (!c->kd.st.ready) return fail(CL_ERR_ARG, "cl_kdis_get: no k-distances on this handle (cl_kdis_build)");
+    if (which < 0 || which >= c->kd.st.n_k) return fail(CL_ERR_ARG, "cl_kdis_get: which outside the ks of the build");
+    if (!range_ok(first, count, c->kd.st.n_kept)) return fail(CL_ERR_ARG, "cl_kdis_get: range outside the kept rows");
     if (count > 0 && (!x || !y || !d)) return fail(CL_ERR_ARG, "cl_kdis_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_kdis_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)count * 4;
-    const int* dk = c->kd_d.as<int>() + (size_t)which * (size_t)c->kd.n_kept;
-    return read_back(c, "cl_kdis_get", {{x, c->kd_x.as<int>() + first, bytes}, {y, c->kd_y.as<int>() + first, bytes}, {d, dk + first, bytes}});
+    const int* dk = c->kd.d.as<int>() + (size_t)which * (size_t)c->kd.st.n_kept;
+    return read_back(c, "cl_kdis_get", {{x, c->kd.x.as<int>() + first, bytes}, {y, c->kd.y.as<int>() + first, bytes}, {d, dk + first, bytes}});
 }
 
 extern "C" int cl_kdis_hist(cl_chrom* c, int32_t which, uint64_t* hist, uint64_t* n_zero, uint64_t* n_none)
@@ -219,14 +213,14 @@ extern "C" int cl_kdis_hist(cl_chrom* c, int32_t which, uint64_t* hist, uint64_t
     if (n_zero) *n_zero = 0;
     if (n_none) *n_none = 0;
     if (!hist || !n_zero || !n_none) return fail(CL_ERR_ARG, "cl_kdis_hist: bad arguments");
-    if (!c->kd.ready) return fail(CL_ERR_ARG, "cl_kdis_hist: no k-distances on this handle (cl_kdis_build)");
-    if (which < 0 || which >= c->kd.n_k) return fail(CL_ERR_ARG, "cl_kdis_hist: which outside the ks of the build");
+    if (!c->kd.st.ready) return fail(CL_ERR_ARG, "cl_kdis_hist: no k-distances on this handle (cl_kdis_build)");
+    if (which < 0 || which >= c->kd.st.n_k) return fail(CL_ERR_ARG, "cl_kdis_hist: which outside the ks of the build");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_kdis_hist: asynchronous runs still in flight");
     std::memset(hist, 0, (size_t)CL_KDIS_BINS * 8);
-    if (c->kd.n_kept == 0) return CL_OK;
+    if (c->kd.st.n_kept == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     static_assert(sizeof(uint64_t) == sizeof(u64), "the histogram is copied as it lies");
-    const u64* src = c->kd_hist.as<u64>() + (size_t)which * (CL_KDIS_BINS + 2);
+    const u64* src = c->kd.hist.as<u64>() + (size_t)which * (CL_KDIS_BINS + 2);
     uint64_t tail[2] = {0, 0};
     const int rc = read_back(c, "cl_kdis_hist", {{hist, src, (size_t)CL_KDIS_BINS * 8}, {tail, src + CL_KDIS_BINS, 16}});
     if (rc) return rc;                                                          // (synchronised: no copy to the stack is pending)

@@ -6,8 +6,8 @@
 // K24: binned counts of the kept rows over K19's X-sorted table
 // ==========================================================================================
 // Definitions: include/cloops_hip.h, cl_mat_window.  The reference has nothing of the kind; every number here is an integer count that
-// a few lines of numpy reproduce (tests/matrix_cases.py).  Rows: K19's table (agg_table: the kept rows sorted by X, c->ag_sx = X + 2^30,
-// c->ag_sy = Y, c->ag_kept of them), shared with cl_agg_loops, cl_dom_tracks and cl_kdis_build and keyed by the cut: nothing but the
+// a few lines of numpy reproduce (tests/matrix_cases.py).  Rows: K19's table (agg_table: the kept rows sorted by X, c->ag.sx = X + 2^30,
+// c->ag.sy = Y, c->ag.kept of them), shared with cl_agg_loops, cl_dom_tracks and cl_kdis_build and keyed by the cut: nothing but the
 // cells' keys is sorted here.
 // Bins: floor(p / res) without dividing a negative number: with B = ceil(2^30 / res) the key p + 2^30 + (B res - 2^30) is p + B res >= 0
 // and below 2^31, so its quotient by res (host-made multiply-shift, k12_div) minus B is the bin (K24Bin).
@@ -34,7 +34,7 @@
 // 128 instead of 127 us on the whole chromosome at 50 kb -- the rows of a wave share bx but rarely by -- inside calls of 250 - 350 us
 // (DESIGN.md, K24).  70 000 rows in one cell are 64-deep LDS conflicts, not global ones.  The LDS paths stay: with every add a
 // global atomic (CLOOPS_K24_GLOBAL) the same kernels took 36 and 778 us.
-// Only vector stores and ordinary HIP atomics; every index is checked against its array before a load or store.  Scratch (c->mx_*) is
+// Only vector stores and ordinary HIP atomics; every index is checked against its array before a load or store.  Scratch (c->mx) is
 // the handle's own, apart from the sweep's layouts, q index, count cache and the K8 / K13 / K14 / K20 - K23 state.
 #define K24_TILE 2048                   // table rows per workgroup of k24_window and k24_v4c (8 per thread)
 #define K24_CELLS 8192                  // LDS counters per workgroup (32 KB: four workgroups per CU)
@@ -260,49 +260,41 @@ static int k24_knob(const char* name)
 
 static int k24_cut(int64_t cut) { return cut <= 0 ? 0 : (int)std::min<int64_t>(cut, 1ll << 30); }   // |Y - X| < 2^30: a larger cut keeps no row either
 
-void mat_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->mx_out, &c->mx_ctr, &c->mx_key, &c->mx_sorted, &c->mx_tmp, &c->mx_flag, &c->mx_scan, &c->mx_start,
-                      &c->mx_bx, &c->mx_by, &c->mx_cnt}) b->release();
-    c->mx = cl_chrom::MatState();
-    bal_release(c);                                                             // (K25's weights belong to these cells)
-}
-
-// mx_ctr: four ints (table ranges), then two 64-bit counters; zeroed
+// mx.ctr: four ints (table ranges), then two 64-bit counters; zeroed
 static int mat_counters(cl_chrom* c)
 {
     int rc;
-    if ((rc = c->mx_ctr.ensure(32))) return rc;
-    HIP_TRY(hipMemsetAsync(c->mx_ctr.p, 0, 32, c->stream));
+    if ((rc = c->mx.ctr.ensure(32))) return rc;
+    HIP_TRY(hipMemsetAsync(c->mx.ctr.p, 0, 32, c->stream));
     return CL_OK;
 }
 
 static int mat_window(cl_chrom* c, int res, const K24Win& w, bool mirror, uint32_t* out, int64_t* n_in)
 {
-    const int m = c->ag_kept;
+    const int m = c->ag.kept;
     const size_t cells = (size_t)w.nx * (size_t)w.ny;
     int rc;
-    if ((rc = c->mx_out.ensure(cells * 4)) || (rc = mat_counters(c))) return rc;
-    HIP_TRY(hipMemsetAsync(c->mx_out.p, 0, cells * 4, c->stream));
-    int* rng = c->mx_ctr.as<int>();
+    if ((rc = c->mx.out.ensure(cells * 4)) || (rc = mat_counters(c))) return rc;
+    HIP_TRY(hipMemsetAsync(c->mx.out.p, 0, cells * 4, c->stream));
+    int* rng = c->mx.ctr.as<int>();
     u64* ctr = (u64*)(rng + 4);
     K24T t{};
     t.n = mirror ? 4 : 2;
     t.t[0] = (long long)w.bx0 * res + (1ll << 30); t.t[1] = ((long long)w.bx0 + w.nx) * res + (1ll << 30);
     t.t[2] = (long long)w.by0 * res + (1ll << 30); t.t[3] = ((long long)w.by0 + w.ny) * res + (1ll << 30);
-    hipLaunchKernelGGL(k24_ranges, dim3(1), dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(), m, t, rng);
+    hipLaunchKernelGGL(k24_ranges, dim3(1), dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(), m, t, rng);
     HIP_TRY(hipGetLastError());
     const dim3 grid((unsigned)(((long long)m + K24_TILE - 1) / K24_TILE), mirror ? 2u : 1u);
     const int no_lds = k24_knob("CLOOPS_K24_GLOBAL") ? 1 : 0;
     if (k24_knob("CLOOPS_K24_AGG"))
-        hipLaunchKernelGGL(k24_window<true>, grid, dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(), c->ag_sy.as<int>(), m, (const int*)rng,
-                           k24_binning(res), w, no_lds, c->mx_out.as<u32>(), ctr);
+        hipLaunchKernelGGL(k24_window<true>, grid, dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(), c->ag.sy.as<int>(), m, (const int*)rng,
+                           k24_binning(res), w, no_lds, c->mx.out.as<u32>(), ctr);
     else
-        hipLaunchKernelGGL(k24_window<false>, grid, dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(), c->ag_sy.as<int>(), m, (const int*)rng,
-                           k24_binning(res), w, no_lds, c->mx_out.as<u32>(), ctr);
+        hipLaunchKernelGGL(k24_window<false>, grid, dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(), c->ag.sy.as<int>(), m, (const int*)rng,
+                           k24_binning(res), w, no_lds, c->mx.out.as<u32>(), ctr);
     HIP_TRY(hipGetLastError());
     u64 h = 0;
-    HIP_TRY(hipMemcpyAsync(out, c->mx_out.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->mx.out.p, cells * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&h, ctr, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *n_in = (int64_t)h;
@@ -326,8 +318,8 @@ extern "C" int cl_mat_window(cl_chrom* c, int64_t cut, int64_t res, int64_t bx0,
     HIP_TRY(hipSetDevice(c->device));
     int rc = agg_table(c, k24_cut(cut));
     if (rc == CL_OK) {
-        *n_kept = c->ag_kept;
-        if (c->ag_kept > 0) {
+        *n_kept = c->ag.kept;
+        if (c->ag.kept > 0) {
             const K24Win w{(int)bx0, (int)by0, (int)nx, (int)ny};
             rc = mat_window(c, (int)res, w, mirror != 0, out, n_in);
         }
@@ -338,23 +330,23 @@ extern "C" int cl_mat_window(cl_chrom* c, int64_t cut, int64_t res, int64_t bx0,
 
 static int mat_v4c(cl_chrom* c, int res, int v0, int v1, int b0, int nb, uint32_t* out, int64_t* n_x, int64_t* n_y)
 {
-    const int m = c->ag_kept;
+    const int m = c->ag.kept;
     int rc;
-    if ((rc = c->mx_out.ensure(std::max<size_t>((size_t)nb * 4, 16))) || (rc = mat_counters(c))) return rc;
-    if (nb > 0) HIP_TRY(hipMemsetAsync(c->mx_out.p, 0, (size_t)nb * 4, c->stream));
-    int* rng = c->mx_ctr.as<int>();
+    if ((rc = c->mx.out.ensure(std::max<size_t>((size_t)nb * 4, 16))) || (rc = mat_counters(c))) return rc;
+    if (nb > 0) HIP_TRY(hipMemsetAsync(c->mx.out.p, 0, (size_t)nb * 4, c->stream));
+    int* rng = c->mx.ctr.as<int>();
     u64* ctr = (u64*)(rng + 4);
     K24T t{};
     t.n = 2;
     t.t[0] = (long long)v0 + (1ll << 30); t.t[1] = (long long)v1 + (1ll << 30);
-    hipLaunchKernelGGL(k24_ranges, dim3(1), dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(), m, t, rng);
+    hipLaunchKernelGGL(k24_ranges, dim3(1), dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(), m, t, rng);
     HIP_TRY(hipGetLastError());
     const dim3 grid((unsigned)(((long long)m + K24_TILE - 1) / K24_TILE), 2u);
-    hipLaunchKernelGGL(k24_v4c, grid, dim3(TPB), 0, c->stream, c->ag_sx.as<u32>(), c->ag_sy.as<int>(), m, (const int*)rng, k24_binning(res), v0, v1,
-                       b0, nb, c->mx_out.as<u32>(), ctr);
+    hipLaunchKernelGGL(k24_v4c, grid, dim3(TPB), 0, c->stream, c->ag.sx.as<u32>(), c->ag.sy.as<int>(), m, (const int*)rng, k24_binning(res), v0, v1,
+                       b0, nb, c->mx.out.as<u32>(), ctr);
     HIP_TRY(hipGetLastError());
     u64 h[2] = {0, 0};
-    if (nb > 0) HIP_TRY(hipMemcpyAsync(out, c->mx_out.p, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    if (nb > 0) HIP_TRY(hipMemcpyAsync(out, c->mx.out.p, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *n_x = (int64_t)h[0]; *n_y = (int64_t)h[1];
@@ -378,18 +370,18 @@ extern "C" int cl_mat_v4c(cl_chrom* c, int64_t cut, int64_t res, int64_t v0, int
     HIP_TRY(hipSetDevice(c->device));
     int rc = agg_table(c, k24_cut(cut));
     if (rc == CL_OK) {
-        *n_kept = c->ag_kept;
+        *n_kept = c->ag.kept;
         // every coordinate satisfies |p| < 2^29: a bound beyond +-2^30 selects the same rows as the bound clamped there
         const int a = (int)std::max<int64_t>(-(1ll << 30), std::min<int64_t>(v0, 1ll << 30)), e = (int)std::max<int64_t>(-(1ll << 30), std::min<int64_t>(v1, 1ll << 30));
-        if (c->ag_kept > 0) rc = mat_v4c(c, (int)res, a, e, (int)b0, (int)nb, out, n_x, n_y);
+        if (c->ag.kept > 0) rc = mat_v4c(c, (int)res, a, e, (int)b0, (int)nb, out, n_x, n_y);
     }
     if (rc != CL_OK) { (void)hipStreamSynchronize(c->stream); *n_x = 0; *n_y = 0; *n_kept = 0; }
     return rc;
 }
 
-static int mat_cells(cl_chrom* c, int res, bool fold, cl_chrom::MatState& st)
+static int mat_cells(cl_chrom* c, int res, bool fold, cl_chrom::Mat::State& st)
 {
-    const int m = c->ag_kept;
+    const int m = c->ag.kept;
     const size_t sm = (size_t)m;
     int rc;
     // the bins of ALL rows of the handle (whatever the cut) bound those of the kept rows: bmin only has to lie at or below every bin, and
@@ -398,33 +390,33 @@ static int mat_cells(cl_chrom* c, int res, bool fold, cl_chrom::MatState& st)
     if (bmax < bmin || bmax - bmin >= (1ll << 30)) return fail(CL_ERR_HIP, "cl_mat_cells: the handle's coordinate range is not one a handle can have");
     if ((rc = mat_counters(c))) return rc;
     const int bits = std::max(1, bits_for((unsigned)(bmax - bmin)));            // bmax - bmin < 2^30: 2 bits <= 60
-    if ((rc = c->mx_key.ensure(sm * 8)) || (rc = c->mx_sorted.ensure(sm * 8)) || (rc = c->mx_flag.ensure((sm + 1) * 4)) ||
-        (rc = c->mx_scan.ensure((sm + 1) * 4))) return rc;
+    if ((rc = c->mx.key.ensure(sm * 8)) || (rc = c->mx.sorted.ensure(sm * 8)) || (rc = c->mx.flag.ensure((sm + 1) * 4)) ||
+        (rc = c->mx.scan.ensure((sm + 1) * 4))) return rc;
     const K24Bin b = k24_binning(res);
-    LAUNCH(k24_keys, m, c->ag_sx.as<u32>(), c->ag_sy.as<int>(), m, b, (int)bmin, bits, fold ? 1 : 0, c->mx_key.as<u64>());
+    LAUNCH(k24_keys, m, c->ag.sx.as<u32>(), c->ag.sy.as<int>(), m, b, (int)bmin, bits, fold ? 1 : 0, c->mx.key.as<u64>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->mx_tmp, "radix_sort_keys(matrix cells)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_keys(tmp, bytes, c->mx_key.as<u64>(), c->mx_sorted.as<u64>(), sm, 0, 2 * bits, c->stream);
+    if ((rc = prim_run(c->mx.tmp, "radix_sort_keys(matrix cells)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->mx.key.as<u64>(), c->mx.sorted.as<u64>(), sm, 0, 2 * bits, c->stream);
         })))
         return rc;
-    LAUNCH(k24_heads, (long long)m + 1, c->mx_sorted.as<u64>(), m, c->mx_flag.as<u32>());
+    LAUNCH(k24_heads, (long long)m + 1, c->mx.sorted.as<u64>(), m, c->mx.flag.as<u32>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->mx_tmp, "exclusive_scan(matrix cells)", [&](void* tmp, size_t& bytes) {
-            return rocprim::exclusive_scan(tmp, bytes, c->mx_flag.as<u32>(), c->mx_scan.as<u32>(), 0u, sm + 1, rocprim::plus<u32>(), c->stream);
+    if ((rc = prim_run(c->mx.tmp, "exclusive_scan(matrix cells)", [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->mx.flag.as<u32>(), c->mx.scan.as<u32>(), 0u, sm + 1, rocprim::plus<u32>(), c->stream);
         })))
         return rc;
     u32 nc = 0;
-    HIP_TRY(hipMemcpyAsync(&nc, c->mx_scan.as<u32>() + sm, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&nc, c->mx.scan.as<u32>() + sm, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (nc < 1 || nc > (u32)m) return fail(CL_ERR_HIP, "cl_mat_cells: the scan left a number of cells no table can have");
     const size_t sc = (size_t)nc;
-    if ((rc = c->mx_start.ensure((sc + 1) * 4)) || (rc = c->mx_bx.ensure(sc * 4)) || (rc = c->mx_by.ensure(sc * 4)) || (rc = c->mx_cnt.ensure(sc * 4))) return rc;
-    LAUNCH(k24_starts, (long long)m + 1, c->mx_sorted.as<u64>(), c->mx_flag.as<u32>(), c->mx_scan.as<u32>(), m, (int)nc, (int)bmin, bits,
-           c->mx_start.as<int>(), c->mx_bx.as<int>(), c->mx_by.as<int>());
+    if ((rc = c->mx.start.ensure((sc + 1) * 4)) || (rc = c->mx.bx.ensure(sc * 4)) || (rc = c->mx.by.ensure(sc * 4)) || (rc = c->mx.cnt.ensure(sc * 4))) return rc;
+    LAUNCH(k24_starts, (long long)m + 1, c->mx.sorted.as<u64>(), c->mx.flag.as<u32>(), c->mx.scan.as<u32>(), m, (int)nc, (int)bmin, bits,
+           c->mx.start.as<int>(), c->mx.bx.as<int>(), c->mx.by.as<int>());
     HIP_TRY(hipGetLastError());
-    int* maxc = c->mx_ctr.as<int>();                                            // (zeroed above)
-    hipLaunchKernelGGL(k24_counts, dim3((unsigned)std::max(1, std::min(1024, nblocks((long long)nc)))), dim3(TPB), 0, c->stream, c->mx_start.as<int>(),
-                       (int)nc, c->mx_cnt.as<u32>(), maxc);
+    int* maxc = c->mx.ctr.as<int>();                                            // (zeroed above)
+    hipLaunchKernelGGL(k24_counts, dim3((unsigned)std::max(1, std::min(1024, nblocks((long long)nc)))), dim3(TPB), 0, c->stream, c->mx.start.as<int>(),
+                       (int)nc, c->mx.cnt.as<u32>(), maxc);
     HIP_TRY(hipGetLastError());
     int hmax = 0;
     HIP_TRY(hipMemcpyAsync(&hmax, maxc, 4, hipMemcpyDeviceToHost, c->stream));
@@ -442,24 +434,24 @@ extern "C" int cl_mat_cells(cl_chrom* c, int64_t cut, int64_t res, int32_t fold,
     if (!n_cells || !n_kept || !max_count) return fail(CL_ERR_ARG, "cl_mat_cells: bad arguments");
     if (res < 1 || res >= K24_MAXRES) return fail(CL_ERR_ARG, "cl_mat_cells: res outside [1, 2^29)");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_mat_cells: asynchronous runs still in flight");
-    cl_chrom::MatState st;
+    cl_chrom::Mat::State st;
     st.ready = true;
     st.res = (int)res; st.fold = fold != 0;
-    if (c->n == 0) { bal_release(c); c->mx = st; return CL_OK; }
+    if (c->n == 0) { bal_release(c); c->mx.st = st; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
     bal_release(c);                                                             // (K25's state belongs to the earlier cells; every K25 call ends synchronised)
     int rc = agg_table(c, k24_cut(cut));
     if (rc == CL_OK) {
-        st.n_kept = c->ag_kept;
-        c->mx.ready = false;                                                    // (the buffers of the earlier cells are written from here on)
-        if (c->ag_kept > 0) rc = mat_cells(c, (int)res, fold != 0, st);
+        st.n_kept = c->ag.kept;
+        c->mx.st.ready = false;                                                    // (the buffers of the earlier cells are written from here on)
+        if (c->ag.kept > 0) rc = mat_cells(c, (int)res, fold != 0, st);
     }
     if (rc != CL_OK) {
         (void)hipStreamSynchronize(c->stream);
         mat_release(c);
         return rc;
     }
-    c->mx = st;
+    c->mx.st = st;
     *n_cells = st.n_cells; *n_kept = st.n_kept; *max_count = st.max_count;
     return CL_OK;
 }
@@ -467,15 +459,15 @@ extern "C" int cl_mat_cells(cl_chrom* c, int64_t cut, int64_t res, int32_t fold,
 extern "C" int cl_mat_cells_get(cl_chrom* c, int64_t first, int64_t count, int32_t* bx, int32_t* by, uint32_t* cnt)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (!c->mx.ready) return fail(CL_ERR_ARG, "cl_mat_cells_get: no cells on this handle (cl_mat_cells)");
-    if (!range_ok(first, count, c->mx.n_cells)) return fail(CL_ERR_ARG, "cl_mat_cells_get: range outside the cells");
+    if (!c->mx.st.ready) return fail(CL_ERR_ARG, "cl_mat_cells_get: no cells on this handle (cl_mat_cells)");
+    if (!range_ok(first, count, c->mx.st.n_cells)) return fail(CL_ERR_ARG, "cl_mat_cells_get: range outside the cells");
     if (count > 0 && (!bx || !by || !cnt)) return fail(CL_ERR_ARG, "cl_mat_cells_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_mat_cells_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)count * 4;
-    return read_back(c, "cl_mat_cells_get", {{bx, c->mx_bx.as<int>() + first, bytes}, {by, c->mx_by.as<int>() + first, bytes},
-                                             {cnt, c->mx_cnt.as<u32>() + first, bytes}});
+    return read_back(c, "cl_mat_cells_get", {{bx, c->mx.bx.as<int>() + first, bytes}, {by, c->mx.by.as<int>() + first, bytes},
+                                             {cnt, c->mx.cnt.as<u32>() + first, bytes}});
 }
 
 extern "C" int cl_mat_free(cl_chrom* c) { return unit_free(c, "cl_mat_free", mat_release); }

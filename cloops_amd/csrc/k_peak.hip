@@ -32,7 +32,7 @@
 //                             at the smallest position; a segmented scan in the wave (the points are sorted, so an interval's points
 //                             are consecutive), the segments that reach a wave's edge merged across the workgroup through LDS, then
 //                             one 64-bit atomicMax per workgroup and interval; k21_summit_out unpacks the keys
-// Only vector stores and ordinary HIP atomics.  Scratch (c->pk_*) is the handle's own, apart from the sweep's layouts, q index, count
+// Only vector stores and ordinary HIP atomics.  Scratch (c->pk) is the handle's own, apart from the sweep's layouts, q index, count
 // cache and the K8 / K13 / K14 / K19 / K20 state.
 #define K21_TILE 1024                   // elements of S per workgroup of k21_core and k21_summit (4 per thread)
 #define K21_HALO 1024                   // elements staged in LDS on either side of the tile of k21_core
@@ -41,7 +41,7 @@
 #define K21_RUNS (K21_U * (TPB / 64))   // stretches of 64 consecutive elements per workgroup
 #define K21_MAXW (1ll << 29)            // eps and w lie in [1, 2^29)
 
-enum { K21_NENDS = 0, K21_CLUST = 1, K21_CTRS = 2 };                    // c->pk_ctr, u64 each
+enum { K21_NENDS = 0, K21_CLUST = 1, K21_CTRS = 2 };                    // c->pk.ctr, u64 each
 static_assert(K21_NENDS == K20_NENDS, "k20_keys counts into slot K20_NENDS");
 
 __global__ void __launch_bounds__(TPB)
@@ -233,18 +233,9 @@ k21_summit_out(const u64* __restrict__ best, const long long* __restrict__ ivs, 
 // ---- K21 host side ------------------------------------------------------------------------------
 static int k21_grid(long long work) { return (int)std::max(1ll, std::min<long long>(4096, (work + TPB - 1) / TPB)); }
 
-void peak_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->pk_kin, &c->pk_key, &c->pk_tmp, &c->pk_lo, &c->pk_hi, &c->pk_flag, &c->pk_C, &c->pk_head, &c->pk_H, &c->pk_a,
-                      &c->pk_b, &c->pk_start, &c->pk_end, &c->pk_np, &c->pk_nc, &c->pk_ctr, &c->pk_ivs, &c->pk_ive, &c->pk_best,
-                      &c->pk_opos, &c->pk_ocnt})
-        b->release();
-    c->pk = cl_chrom::PeakState();
-}
-
 static int peak_scan(cl_chrom* c, const u32* in, u32* out, size_t n, const char* what)
 {
-    return prim_run(c->pk_tmp, what, [&](void* tmp, size_t& bytes) {
+    return prim_run(c->pk.tmp, what, [&](void* tmp, size_t& bytes) {
         return rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<u32>(), c->stream);
     });
 }
@@ -257,29 +248,29 @@ static int peak_sort(cl_chrom* c, long long cut, int ends, int64_t* n_ends, int6
     const int base = std::min(c->st.xmin, c->st.ymin), pmax = std::max(c->st.xmax, c->st.ymax);
     const int ebit = std::max(1, bits_for((u32)(pmax - base)));
     int rc;
-    if ((rc = c->pk_ctr.ensure(K21_CTRS * 8)) || (rc = c->pk_kin.ensure((size_t)n * ne * 4)) || (rc = c->pk_key.ensure((size_t)n * ne * 4))) return rc;
-    u64* ctr = c->pk_ctr.as<u64>();
+    if ((rc = c->pk.ctr.ensure(K21_CTRS * 8)) || (rc = c->pk.kin.ensure((size_t)n * ne * 4)) || (rc = c->pk.key.ensure((size_t)n * ne * 4))) return rc;
+    u64* ctr = c->pk.ctr.as<u64>();
     HIP_TRY(hipMemsetAsync(ctr, 0, K21_CTRS * 8, c->stream));
     hipLaunchKernelGGL(k20_keys, dim3((unsigned)(((long long)n + K20_ROWS - 1) / K20_ROWS)), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, cut, ends,
-                       0, base, c->pk_kin.as<u32>(), ctr);
+                       0, base, c->pk.kin.as<u32>(), ctr);
     HIP_TRY(hipGetLastError());
     u64 hm = 0;
     HIP_TRY(hipMemcpyAsync(&hm, ctr + K21_NENDS, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const long long m = (long long)hm;
     if (m > (long long)n * ne) return fail(CL_ERR_HIP, "cl_peak_sort: the key pass counted more end points than rows allow");
-    c->pk.base = base;
-    if (m == 0) { c->pk.sorted = true; return CL_OK; }
-    if ((rc = prim_run(c->pk_tmp, "radix_sort_keys(peaks)", [&](void* tmp, size_t& bytes) {
-            return rocprim::radix_sort_keys(tmp, bytes, c->pk_kin.as<u32>(), c->pk_key.as<u32>(), (size_t)m, 0, ebit, c->stream);
+    c->pk.st.base = base;
+    if (m == 0) { c->pk.st.sorted = true; return CL_OK; }
+    if ((rc = prim_run(c->pk.tmp, "radix_sort_keys(peaks)", [&](void* tmp, size_t& bytes) {
+            return rocprim::radix_sort_keys(tmp, bytes, c->pk.kin.as<u32>(), c->pk.key.as<u32>(), (size_t)m, 0, ebit, c->stream);
         })))
         return rc;
     u32 k0 = 0, k1 = 0;
-    HIP_TRY(hipMemcpyAsync(&k0, c->pk_key.as<u32>(), 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&k1, c->pk_key.as<u32>() + (m - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&k0, c->pk.key.as<u32>(), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&k1, c->pk.key.as<u32>() + (m - 1), 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->pk.m = m;
-    c->pk.sorted = true;
+    c->pk.st.m = m;
+    c->pk.st.sorted = true;
     *n_ends = m;
     *vmin = (long long)base + k0;
     *vmax = (long long)base + k1;
@@ -296,8 +287,8 @@ extern "C" int cl_peak_sort(cl_chrom* c, int64_t cut, int32_t ends, int64_t* n_e
     if (ends < 1 || ends > 3) return fail(CL_ERR_ARG, "cl_peak_sort: ends outside 1..3");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_peak_sort: asynchronous runs still in flight");
     HIP_TRY(hipSetDevice(c->device));
-    c->pk = cl_chrom::PeakState();                                      // (the buffers stay: the next sort reuses their memory, not their content)
-    if (c->n == 0) { c->pk.sorted = true; return CL_OK; }
+    c->pk.st = cl_chrom::Peak::State();                                      // (the buffers stay: the next sort reuses their memory, not their content)
+    if (c->n == 0) { c->pk.st.sorted = true; return CL_OK; }
     const int rc = peak_sort(c, cut, ends, n_ends, vmin, vmax);
     if (rc != CL_OK) {
         (void)hipStreamSynchronize(c->stream);                          // no copy to the stack may still be pending
@@ -309,56 +300,56 @@ extern "C" int cl_peak_sort(cl_chrom* c, int64_t cut, int32_t ends, int64_t* n_e
 // lo / hi of every element for the half-width `width`, and the core flags if `flags`
 static int peak_ranks(cl_chrom* c, int width, long long min_pts, bool flags)
 {
-    const long long m = c->pk.m;
+    const long long m = c->pk.st.m;
     int rc;
-    if ((rc = c->pk_lo.ensure((size_t)m * 4)) || (rc = c->pk_hi.ensure((size_t)m * 4))) return rc;
-    if (flags && (rc = c->pk_flag.ensure(((size_t)m + 1) * 4))) return rc;
-    if (flags) HIP_TRY(hipMemsetAsync(c->pk_flag.as<u32>() + m, 0, 4, c->stream));
-    hipLaunchKernelGGL(k21_core, dim3((unsigned)((m + K21_TILE - 1) / K21_TILE)), dim3(TPB), 0, c->stream, c->pk_key.as<u32>(), (int)m, c->pk.base,
-                       width, min_pts, c->pk_lo.as<u32>(), c->pk_hi.as<u32>(), flags ? c->pk_flag.as<u32>() : (u32*)nullptr);
+    if ((rc = c->pk.lo.ensure((size_t)m * 4)) || (rc = c->pk.hi.ensure((size_t)m * 4))) return rc;
+    if (flags && (rc = c->pk.flag.ensure(((size_t)m + 1) * 4))) return rc;
+    if (flags) HIP_TRY(hipMemsetAsync(c->pk.flag.as<u32>() + m, 0, 4, c->stream));
+    hipLaunchKernelGGL(k21_core, dim3((unsigned)((m + K21_TILE - 1) / K21_TILE)), dim3(TPB), 0, c->stream, c->pk.key.as<u32>(), (int)m, c->pk.st.base,
+                       width, min_pts, c->pk.lo.as<u32>(), c->pk.hi.as<u32>(), flags ? c->pk.flag.as<u32>() : (u32*)nullptr);
     HIP_TRY(hipGetLastError());
     return CL_OK;
 }
 
 static int peak_call(cl_chrom* c, int eps, long long min_pts, int64_t* n_peaks, int64_t* n_cores, int64_t* n_clustered)
 {
-    const long long m = c->pk.m;
+    const long long m = c->pk.st.m;
     int rc;
     if ((rc = peak_ranks(c, eps, min_pts, true))) return rc;
-    if ((rc = c->pk_C.ensure(((size_t)m + 1) * 4)) || (rc = c->pk_head.ensure(((size_t)m + 1) * 4)) || (rc = c->pk_H.ensure(((size_t)m + 1) * 4)))
+    if ((rc = c->pk.C.ensure(((size_t)m + 1) * 4)) || (rc = c->pk.head.ensure(((size_t)m + 1) * 4)) || (rc = c->pk.H.ensure(((size_t)m + 1) * 4)))
         return rc;
-    if ((rc = peak_scan(c, c->pk_flag.as<u32>(), c->pk_C.as<u32>(), (size_t)m + 1, "exclusive_scan(peaks, cores)"))) return rc;
-    HIP_TRY(hipMemsetAsync(c->pk_head.as<u32>() + m, 0, 4, c->stream));
-    hipLaunchKernelGGL(k21_heads, dim3(k21_grid(m)), dim3(TPB), 0, c->stream, c->pk_flag.as<u32>(), c->pk_C.as<u32>(), c->pk_lo.as<u32>(), (int)m,
-                       c->pk_head.as<u32>());
+    if ((rc = peak_scan(c, c->pk.flag.as<u32>(), c->pk.C.as<u32>(), (size_t)m + 1, "exclusive_scan(peaks, cores)"))) return rc;
+    HIP_TRY(hipMemsetAsync(c->pk.head.as<u32>() + m, 0, 4, c->stream));
+    hipLaunchKernelGGL(k21_heads, dim3(k21_grid(m)), dim3(TPB), 0, c->stream, c->pk.flag.as<u32>(), c->pk.C.as<u32>(), c->pk.lo.as<u32>(), (int)m,
+                       c->pk.head.as<u32>());
     HIP_TRY(hipGetLastError());
-    if ((rc = peak_scan(c, c->pk_head.as<u32>(), c->pk_H.as<u32>(), (size_t)m + 1, "exclusive_scan(peaks, heads)"))) return rc;
+    if ((rc = peak_scan(c, c->pk.head.as<u32>(), c->pk.H.as<u32>(), (size_t)m + 1, "exclusive_scan(peaks, heads)"))) return rc;
     u32 hC = 0, hP = 0;
-    u64* ctr = c->pk_ctr.as<u64>();
+    u64* ctr = c->pk.ctr.as<u64>();
     HIP_TRY(hipMemsetAsync(ctr + K21_CLUST, 0, 8, c->stream));
-    HIP_TRY(hipMemcpyAsync(&hC, c->pk_C.as<u32>() + m, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&hP, c->pk_H.as<u32>() + m, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hC, c->pk.C.as<u32>() + m, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hP, c->pk.H.as<u32>() + m, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const long long P = hP;
     u64 hclust = 0;
     if (P > 0) {
-        if ((rc = c->pk_a.ensure((size_t)P * 4)) || (rc = c->pk_b.ensure((size_t)P * 4)) || (rc = c->pk_start.ensure((size_t)P * 4)) ||
-            (rc = c->pk_end.ensure((size_t)P * 4)) || (rc = c->pk_np.ensure((size_t)P * 4)) || (rc = c->pk_nc.ensure((size_t)P * 4)))
+        if ((rc = c->pk.a.ensure((size_t)P * 4)) || (rc = c->pk.b.ensure((size_t)P * 4)) || (rc = c->pk.start.ensure((size_t)P * 4)) ||
+            (rc = c->pk.end.ensure((size_t)P * 4)) || (rc = c->pk.np.ensure((size_t)P * 4)) || (rc = c->pk.nc.ensure((size_t)P * 4)))
             return rc;
-        HIP_TRY(hipMemsetAsync(c->pk_a.p, 0xff, (size_t)P * 4, c->stream));                  // (an index no element has: refused by k21_extents)
-        HIP_TRY(hipMemsetAsync(c->pk_b.p, 0xff, (size_t)P * 4, c->stream));
-        hipLaunchKernelGGL(k21_chains, dim3(k21_grid(m)), dim3(TPB), 0, c->stream, c->pk_C.as<u32>(), c->pk_H.as<u32>(), c->pk_hi.as<u32>(), (int)m,
-                           (u32)P, c->pk_a.as<u32>(), c->pk_b.as<u32>());
+        HIP_TRY(hipMemsetAsync(c->pk.a.p, 0xff, (size_t)P * 4, c->stream));                  // (an index no element has: refused by k21_extents)
+        HIP_TRY(hipMemsetAsync(c->pk.b.p, 0xff, (size_t)P * 4, c->stream));
+        hipLaunchKernelGGL(k21_chains, dim3(k21_grid(m)), dim3(TPB), 0, c->stream, c->pk.C.as<u32>(), c->pk.H.as<u32>(), c->pk.hi.as<u32>(), (int)m,
+                           (u32)P, c->pk.a.as<u32>(), c->pk.b.as<u32>());
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k21_extents, dim3((unsigned)((P + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->pk_key.as<u32>(), (int)m, c->pk.base,
-                           c->pk_C.as<u32>(), c->pk_lo.as<u32>(), c->pk_hi.as<u32>(), c->pk_a.as<u32>(), c->pk_b.as<u32>(), (u32)P,
-                           c->pk_start.as<int>(), c->pk_end.as<int>(), c->pk_np.as<u32>(), c->pk_nc.as<u32>(), ctr);
+        hipLaunchKernelGGL(k21_extents, dim3((unsigned)((P + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->pk.key.as<u32>(), (int)m, c->pk.st.base,
+                           c->pk.C.as<u32>(), c->pk.lo.as<u32>(), c->pk.hi.as<u32>(), c->pk.a.as<u32>(), c->pk.b.as<u32>(), (u32)P,
+                           c->pk.start.as<int>(), c->pk.end.as<int>(), c->pk.np.as<u32>(), c->pk.nc.as<u32>(), ctr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&hclust, ctr + K21_CLUST, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->pk.P = P;
-    c->pk.called = true;
+    c->pk.st.P = P;
+    c->pk.st.called = true;
     *n_peaks = P;
     *n_cores = hC;
     *n_clustered = (int64_t)hclust;
@@ -374,10 +365,10 @@ extern "C" int cl_peak_call(cl_chrom* c, int64_t eps, int64_t min_pts, int64_t* 
     if (!n_peaks || !n_cores || !n_clustered) return fail(CL_ERR_ARG, "cl_peak_call: bad arguments");
     if (eps < 1 || eps >= K21_MAXW) return fail(CL_ERR_ARG, "cl_peak_call: eps outside [1, 2^29)");
     if (min_pts < 1) return fail(CL_ERR_ARG, "cl_peak_call: min_pts below 1");
-    if (!c->pk.sorted) return fail(CL_ERR_ARG, "cl_peak_call: no sorted end points on this handle (cl_peak_sort)");
+    if (!c->pk.st.sorted) return fail(CL_ERR_ARG, "cl_peak_call: no sorted end points on this handle (cl_peak_sort)");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_peak_call: asynchronous runs still in flight");
-    c->pk.called = false; c->pk.P = 0;
-    if (c->pk.m == 0) { c->pk.called = true; return CL_OK; }
+    c->pk.st.called = false; c->pk.st.P = 0;
+    if (c->pk.st.m == 0) { c->pk.st.called = true; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
     const int rc = peak_call(c, (int)eps, min_pts, n_peaks, n_cores, n_clustered);
     if (rc != CL_OK) (void)hipStreamSynchronize(c->stream);             // no copy to the stack may still be pending
@@ -387,35 +378,35 @@ extern "C" int cl_peak_call(cl_chrom* c, int64_t eps, int64_t min_pts, int64_t* 
 extern "C" int cl_peak_get(cl_chrom* c, int64_t first, int64_t count, int32_t* start, int32_t* end, uint32_t* n_points, uint32_t* n_cores)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (!c->pk.sorted || !c->pk.called) return fail(CL_ERR_ARG, "cl_peak_get: no peaks called on this handle (cl_peak_sort, cl_peak_call)");
-    if (!range_ok(first, count, c->pk.P)) return fail(CL_ERR_ARG, "cl_peak_get: range outside the peaks");
+    if (!c->pk.st.sorted || !c->pk.st.called) return fail(CL_ERR_ARG, "cl_peak_get: no peaks called on this handle (cl_peak_sort, cl_peak_call)");
+    if (!range_ok(first, count, c->pk.st.P)) return fail(CL_ERR_ARG, "cl_peak_get: range outside the peaks");
     if (count > 0 && (!start || !end || !n_points || !n_cores)) return fail(CL_ERR_ARG, "cl_peak_get: bad arguments");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_peak_get: asynchronous runs still in flight");
     if (count == 0) return CL_OK;
     HIP_TRY(hipSetDevice(c->device));
     const size_t nb = (size_t)count * 4;
-    return read_back(c, "cl_peak_get", {{start, c->pk_start.as<int>() + first, nb}, {end, c->pk_end.as<int>() + first, nb},
-                                        {n_points, c->pk_np.as<u32>() + first, nb}, {n_cores, c->pk_nc.as<u32>() + first, nb}});
+    return read_back(c, "cl_peak_get", {{start, c->pk.start.as<int>() + first, nb}, {end, c->pk.end.as<int>() + first, nb},
+                                        {n_points, c->pk.np.as<u32>() + first, nb}, {n_cores, c->pk.nc.as<u32>() + first, nb}});
 }
 
-// the n intervals of a count / summit call on the device (c->pk_ivs, c->pk_ive)
+// the n intervals of a count / summit call on the device (c->pk.ivs, c->pk.ive)
 static int peak_intervals(cl_chrom* c, const int64_t* starts, const int64_t* ends, long long n)
 {
     int rc;
-    if ((rc = c->pk_ivs.ensure((size_t)n * 8)) || (rc = c->pk_ive.ensure((size_t)n * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->pk_ivs.p, starts, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->pk_ive.p, ends, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = c->pk.ivs.ensure((size_t)n * 8)) || (rc = c->pk.ive.ensure((size_t)n * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->pk.ivs.p, starts, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->pk.ive.p, ends, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     return CL_OK;
 }
 
 static int peak_count(cl_chrom* c, const int64_t* starts, const int64_t* ends, long long n, uint32_t* counts)
 {
     int rc;
-    if ((rc = peak_intervals(c, starts, ends, n)) || (rc = c->pk_ocnt.ensure((size_t)n * 4))) return rc;
-    hipLaunchKernelGGL(k21_count, dim3(k21_grid(n)), dim3(TPB), 0, c->stream, c->pk_key.as<u32>(), (int)c->pk.m, c->pk.base,
-                       c->pk_ivs.as<long long>(), c->pk_ive.as<long long>(), n, c->pk_ocnt.as<u32>());
+    if ((rc = peak_intervals(c, starts, ends, n)) || (rc = c->pk.ocnt.ensure((size_t)n * 4))) return rc;
+    hipLaunchKernelGGL(k21_count, dim3(k21_grid(n)), dim3(TPB), 0, c->stream, c->pk.key.as<u32>(), (int)c->pk.st.m, c->pk.st.base,
+                       c->pk.ivs.as<long long>(), c->pk.ive.as<long long>(), n, c->pk.ocnt.as<u32>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(counts, c->pk_ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(counts, c->pk.ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CL_OK;
 }
@@ -424,10 +415,10 @@ extern "C" int cl_peak_count(cl_chrom* c, const int64_t* starts, const int64_t* 
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n < 0 || n > K20_LIMIT || (n > 0 && (!starts || !ends || !counts))) return fail(CL_ERR_ARG, "cl_peak_count: bad arguments");
-    if (!c->pk.sorted) return fail(CL_ERR_ARG, "cl_peak_count: no sorted end points on this handle (cl_peak_sort)");
+    if (!c->pk.st.sorted) return fail(CL_ERR_ARG, "cl_peak_count: no sorted end points on this handle (cl_peak_sort)");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_peak_count: asynchronous runs still in flight");
     if (n == 0) return CL_OK;
-    if (c->pk.m == 0) { std::memset(counts, 0, (size_t)n * 4); return CL_OK; }
+    if (c->pk.st.m == 0) { std::memset(counts, 0, (size_t)n * 4); return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
     const int rc = peak_count(c, starts, ends, n, counts);
     if (rc != CL_OK) (void)hipStreamSynchronize(c->stream);             // no copy from or to the caller's arrays may still be pending
@@ -436,21 +427,21 @@ extern "C" int cl_peak_count(cl_chrom* c, const int64_t* starts, const int64_t* 
 
 static int peak_summits(cl_chrom* c, const int64_t* starts, const int64_t* ends, long long n, int w, int32_t* pos, uint32_t* cnt)
 {
-    const long long m = c->pk.m;
+    const long long m = c->pk.st.m;
     int rc;
-    if ((rc = peak_intervals(c, starts, ends, n)) || (rc = c->pk_best.ensure((size_t)n * 8)) || (rc = c->pk_opos.ensure((size_t)n * 4)) ||
-        (rc = c->pk_ocnt.ensure((size_t)n * 4)))
+    if ((rc = peak_intervals(c, starts, ends, n)) || (rc = c->pk.best.ensure((size_t)n * 8)) || (rc = c->pk.opos.ensure((size_t)n * 4)) ||
+        (rc = c->pk.ocnt.ensure((size_t)n * 4)))
         return rc;
     if ((rc = peak_ranks(c, w, 1, false))) return rc;
-    HIP_TRY(hipMemsetAsync(c->pk_best.p, 0, (size_t)n * 8, c->stream));
-    hipLaunchKernelGGL(k21_summit, dim3((unsigned)((m + K21_TILE - 1) / K21_TILE)), dim3(TPB), 0, c->stream, c->pk_key.as<u32>(), (int)m, c->pk.base,
-                       c->pk_lo.as<u32>(), c->pk_hi.as<u32>(), c->pk_ivs.as<long long>(), c->pk_ive.as<long long>(), (int)n, c->pk_best.as<u64>());
+    HIP_TRY(hipMemsetAsync(c->pk.best.p, 0, (size_t)n * 8, c->stream));
+    hipLaunchKernelGGL(k21_summit, dim3((unsigned)((m + K21_TILE - 1) / K21_TILE)), dim3(TPB), 0, c->stream, c->pk.key.as<u32>(), (int)m, c->pk.st.base,
+                       c->pk.lo.as<u32>(), c->pk.hi.as<u32>(), c->pk.ivs.as<long long>(), c->pk.ive.as<long long>(), (int)n, c->pk.best.as<u64>());
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k21_summit_out, dim3(k21_grid(n)), dim3(TPB), 0, c->stream, c->pk_best.as<u64>(), c->pk_ivs.as<long long>(), n, c->pk.base,
-                       c->pk_opos.as<int>(), c->pk_ocnt.as<u32>());
+    hipLaunchKernelGGL(k21_summit_out, dim3(k21_grid(n)), dim3(TPB), 0, c->stream, c->pk.best.as<u64>(), c->pk.ivs.as<long long>(), n, c->pk.st.base,
+                       c->pk.opos.as<int>(), c->pk.ocnt.as<u32>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(pos, c->pk_opos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(cnt, c->pk_ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(pos, c->pk.opos.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(cnt, c->pk.ocnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CL_OK;
 }
@@ -460,13 +451,13 @@ extern "C" int cl_peak_summits(cl_chrom* c, const int64_t* starts, const int64_t
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n < 0 || n > K20_LIMIT || (n > 0 && (!starts || !ends || !pos || !cnt))) return fail(CL_ERR_ARG, "cl_peak_summits: bad arguments");
     if (w < 1 || w >= K21_MAXW) return fail(CL_ERR_ARG, "cl_peak_summits: w outside [1, 2^29)");
-    if (!c->pk.sorted) return fail(CL_ERR_ARG, "cl_peak_summits: no sorted end points on this handle (cl_peak_sort)");
+    if (!c->pk.st.sorted) return fail(CL_ERR_ARG, "cl_peak_summits: no sorted end points on this handle (cl_peak_sort)");
     for (int64_t k = 0; k < n; ++k)
         if (ends[k] < starts[k] || (k > 0 && starts[k] < ends[k - 1]))
             return fail(CL_ERR_ARG, "cl_peak_summits: the intervals must be ascending and disjoint");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_peak_summits: asynchronous runs still in flight");
     if (n == 0) return CL_OK;
-    if (c->pk.m == 0) {
+    if (c->pk.st.m == 0) {
         for (int64_t k = 0; k < n; ++k) { pos[k] = -1; cnt[k] = 0; }
         return CL_OK;
     }

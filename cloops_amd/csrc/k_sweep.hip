@@ -785,7 +785,7 @@ extern "C" int cl_kde_array(int device, const int32_t* d_host, int64_t n, double
     if (device < 0 || device >= ndev) return fail(CL_ERR_ARG, "cl_kde_array: no such device");
     if (n == 0) return CL_OK;
     HIP_TRY(hipSetDevice(device));
-    struct Tmp { DevBuf d, part; ~Tmp() { d.release(); part.release(); } } tmp;
+    struct { DevBuf d, part; } tmp;
     if ((rc = tmp.d.ensure((size_t)n * 4))) return rc;
     HIP_TRY(hipMemcpy(tmp.d.p, d_host, (size_t)n * 4, hipMemcpyHostToDevice));
     if ((rc = k17_evaluate((hipStream_t)nullptr, tmp.part, (const u64*)nullptr, tmp.d.as<int>(), (long long)n, lo, step, inv_h, gridsize, sums))) return rc;
@@ -894,7 +894,7 @@ static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out)
     // the sort buffers of the handle are sized for its PETs; a sweep of many steps on a strongly clustered chromosome can
     // leave more candidates than that: then the dedup sorts in buffers of its own (released at the end), and rocPRIM's
     // temporary storage is sized from N with the configuration the sort below uses
-    struct Tmp { DevBuf kin, kout, vin, vout; ~Tmp() { kin.release(); kout.release(); vin.release(); vout.release(); } } tmp;
+    struct { DevBuf kin, kout, vin, vout; } tmp;
     u64 *kin = c->keys_in.as<u64>(), *kout = c->keys_out.as<u64>();
     u32 *vin = c->vals_in.as<u32>(), *vout = c->vals_out.as<u32>();
     if (N > c->n) {

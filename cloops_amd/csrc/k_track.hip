@@ -25,7 +25,7 @@
 //                             (byte stores only in the two words it shares with its neighbours)
 // k14_bounds, the tile bounds and span flush of k14_render and the host side of the text (running sum, chunks, copy-out) are
 // cl_textout.h's, shared with K20 and K15.
-// Scratch (c->tk_*, the text in c->tk_txt) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables:
+// Scratch (c->tk, the text in c->tk.txt) is the handle's own, apart from the sweep's layouts, q index, count cache and K8 tables:
 // it lives from cl_track_build to the next build, cl_track_free or the handle's destruction.
 #define K14_ITEMS 8                     // rows per thread of the filter passes
 #define K14_ROWS (TPB * K14_ITEMS)      // rows per tile: 2048
@@ -208,62 +208,54 @@ k14_render(K14Tpl t, long long r0, long long r1, long long b0, const long long* 
 // ---- K14 host side ------------------------------------------------------------------------------
 static int k14_lcap(const cl_chrom* c)                                   // longest line the template allows
 {
-    return c->tk.la + c->tk.lb + (c->tk.kind == CL_TRACK_WASHU ? 11 + 5 * K14_FIELD : 12 + 2 * K14_FIELD);
+    return c->tk.st.la + c->tk.st.lb + (c->tk.st.kind == CL_TRACK_WASHU ? 11 + 5 * K14_FIELD : 12 + 2 * K14_FIELD);
 }
 
 static K14Tpl k14_tpl(cl_chrom* c)
 {
     K14Tpl t;
-    t.krow = c->tk_row.as<u32>();
-    t.keys = c->tk.kind == CL_TRACK_WASHU ? c->tk_sorted.as<u64>() : nullptr;
+    t.krow = c->tk.row.as<u32>();
+    t.keys = c->tk.st.kind == CL_TRACK_WASHU ? c->tk.sorted.as<u64>() : nullptr;
     t.X = c->d_x; t.Y = c->d_y;
-    t.ids = c->tk.ids ? c->tk_ids.as<long long>() : nullptr;
-    t.names = c->tk_names.as<char>();
-    t.ext = c->tk.ext;
-    t.gmask = c->tk.gbits >= 64 ? ~0ull : ((1ull << c->tk.gbits) - 1);
-    t.kind = c->tk.kind; t.la = c->tk.la; t.lb = c->tk.lb;
+    t.ids = c->tk.st.ids ? c->tk.ids.as<long long>() : nullptr;
+    t.names = c->tk.names.as<char>();
+    t.ext = c->tk.st.ext;
+    t.gmask = c->tk.st.gbits >= 64 ? ~0ull : ((1ull << c->tk.st.gbits) - 1);
+    t.kind = c->tk.st.kind; t.la = c->tk.st.la; t.lb = c->tk.st.lb;
     return t;
 }
 
 static int k14_grid(long long work) { return (int)std::max(1ll, std::min<long long>(4096, (work + TPB - 1) / TPB)); }
 
-void track_release(cl_chrom* c)
-{
-    for (DevBuf* b : {&c->tk_tcnt, &c->tk_toff, &c->tk_row, &c->tk_keys, &c->tk_sorted, &c->tk_tmp, &c->tk_ids, &c->tk_names})
-        b->release();
-    text_release(c->tk_txt);
-    c->tk = cl_chrom::TrackState();
-}
-
 // hn: host staging of the names, owned by the caller so that it outlives the stream synchronisation after an error return
 static int track_build(cl_chrom* c, const int64_t* ids, std::vector<char>& hn, int64_t* n_records, int64_t* n_bytes)
 {
     const int n = (int)c->n;
-    cl_chrom::TrackState& s = c->tk;
+    cl_chrom::Track::State& s = c->tk.st;
     int rc;
-    if ((rc = c->tk_names.ensure(2 * K14_NAME_MAX))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->tk_names.p, hn.data(), 2 * K14_NAME_MAX, hipMemcpyHostToDevice, c->stream));
+    if ((rc = c->tk.names.ensure(2 * K14_NAME_MAX))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->tk.names.p, hn.data(), 2 * K14_NAME_MAX, hipMemcpyHostToDevice, c->stream));
     if (ids) {
-        if ((rc = c->tk_ids.ensure((size_t)n * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->tk_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = c->tk.ids.ensure((size_t)n * 8))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->tk.ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     }
     // rows passing the cut, ascending
     const long long tiles = ((long long)n + K14_ROWS - 1) / K14_ROWS;
-    if ((rc = c->tk_tcnt.ensure((size_t)(tiles + 1) * 4)) || (rc = c->tk_toff.ensure((size_t)(tiles + 1) * 4)) ||
-        (rc = c->tk_row.ensure((size_t)n * 4)))
+    if ((rc = c->tk.tcnt.ensure((size_t)(tiles + 1) * 4)) || (rc = c->tk.toff.ensure((size_t)(tiles + 1) * 4)) ||
+        (rc = c->tk.row.ensure((size_t)n * 4)))
         return rc;
-    HIP_TRY(hipMemsetAsync(c->tk_tcnt.as<u32>() + tiles, 0, 4, c->stream));
-    hipLaunchKernelGGL(k14_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, (long long)s.cut, c->tk_tcnt.as<u32>());
+    HIP_TRY(hipMemsetAsync(c->tk.tcnt.as<u32>() + tiles, 0, 4, c->stream));
+    hipLaunchKernelGGL(k14_count, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, (long long)s.cut, c->tk.tcnt.as<u32>());
     HIP_TRY(hipGetLastError());
-    if ((rc = prim_run(c->tk_tmp, "exclusive_scan(tiles)", [&](void* tmp, size_t& bytes) {
-            return rocprim::exclusive_scan(tmp, bytes, c->tk_tcnt.as<u32>(), c->tk_toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
+    if ((rc = prim_run(c->tk.tmp, "exclusive_scan(tiles)", [&](void* tmp, size_t& bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, c->tk.tcnt.as<u32>(), c->tk.toff.as<u32>(), 0u, (size_t)tiles + 1, rocprim::plus<u32>(), c->stream);
         })))
         return rc;
-    hipLaunchKernelGGL(k14_compact, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, (long long)s.cut, c->tk_toff.as<u32>(),
-                       c->tk_row.as<u32>());
+    hipLaunchKernelGGL(k14_compact, dim3((unsigned)tiles), dim3(TPB), 0, c->stream, c->d_x, c->d_y, n, (long long)s.cut, c->tk.toff.as<u32>(),
+                       c->tk.row.as<u32>());
     HIP_TRY(hipGetLastError());
     u32 m = 0;
-    HIP_TRY(hipMemcpyAsync(&m, c->tk_toff.as<u32>() + tiles, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&m, c->tk.toff.as<u32>() + tiles, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const long long R = s.kind == CL_TRACK_WASHU ? 2ll * m : (long long)m;
     if (R == 0) { s.built = true; *n_records = 0; *n_bytes = 0; return CL_OK; }
@@ -272,24 +264,24 @@ static int track_build(cl_chrom* c, const int64_t* ids, std::vector<char>& hn, i
         const int pmin = std::min(c->st.xmin, c->st.ymin), pmax = std::max(c->st.xmax, c->st.ymax);
         s.gbits = std::max(1, bits_for((unsigned)(R - 1)));
         const int ebit = bits_for((u32)(pmax - pmin)) + s.gbits;
-        if ((rc = c->tk_keys.ensure((size_t)R * 8)) || (rc = c->tk_sorted.ensure((size_t)R * 8))) return rc;
-        hipLaunchKernelGGL(k14_keys, dim3(k14_grid(m)), dim3(TPB), 0, c->stream, c->tk_row.as<u32>(), (long long)m, c->d_x, c->d_y, pmin,
-                           s.gbits, c->tk_keys.as<u64>());
+        if ((rc = c->tk.keys.ensure((size_t)R * 8)) || (rc = c->tk.sorted.ensure((size_t)R * 8))) return rc;
+        hipLaunchKernelGGL(k14_keys, dim3(k14_grid(m)), dim3(TPB), 0, c->stream, c->tk.row.as<u32>(), (long long)m, c->d_x, c->d_y, pmin,
+                           s.gbits, c->tk.keys.as<u64>());
         HIP_TRY(hipGetLastError());
-        if ((rc = prim_run(c->tk_tmp, "radix_sort_keys(track)", [&](void* tmp, size_t& bytes) {
-                return rocprim::radix_sort_keys(tmp, bytes, c->tk_keys.as<u64>(), c->tk_sorted.as<u64>(), (size_t)R, 0, ebit, c->stream);
+        if ((rc = prim_run(c->tk.tmp, "radix_sort_keys(track)", [&](void* tmp, size_t& bytes) {
+                return rocprim::radix_sort_keys(tmp, bytes, c->tk.keys.as<u64>(), c->tk.sorted.as<u64>(), (size_t)R, 0, ebit, c->stream);
             })))
             return rc;
     }
     // line lengths and their running sum
-    TextOut& txt = c->tk_txt;
+    TextOut& txt = c->tk.txt;
     if ((rc = txt.len.ensure((size_t)R * 8)) || (rc = txt.end.ensure((size_t)R * 8))) return rc;
     if (s.kind == CL_TRACK_WASHU)
         hipLaunchKernelGGL(k14_lens<CL_TRACK_WASHU>, dim3(k14_grid(R)), dim3(TPB), 0, c->stream, k14_tpl(c), R, txt.len.as<long long>());
     else
         hipLaunchKernelGGL(k14_lens<CL_TRACK_JUICE>, dim3(k14_grid(R)), dim3(TPB), 0, c->stream, k14_tpl(c), R, txt.len.as<long long>());
     HIP_TRY(hipGetLastError());
-    if ((rc = text_scan(txt, c->tk_tmp, R, c->stream)) || (rc = text_total(txt, R, c->stream))) return rc;
+    if ((rc = text_scan(txt, c->tk.tmp, R, c->stream)) || (rc = text_total(txt, R, c->stream))) return rc;
     s.built = true;
     *n_records = R;
     *n_bytes = txt.total;
@@ -310,7 +302,7 @@ extern "C" int cl_track_build(cl_chrom* c, int32_t kind, int64_t cut, int64_t ex
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_track_build: asynchronous runs still in flight");
     HIP_TRY(hipSetDevice(c->device));
     track_release(c);
-    cl_chrom::TrackState& s = c->tk;
+    cl_chrom::Track::State& s = c->tk.st;
     s.kind = kind; s.cut = cut; s.ext = ext; s.la = (int)la; s.lb = (int)lb; s.ids = ids != nullptr;
     if (c->n == 0) { s.built = true; return CL_OK; }
     std::vector<char> hn(2 * K14_NAME_MAX, 0);
@@ -329,11 +321,11 @@ extern "C" int cl_track_chunks(cl_chrom* c, int64_t budget, int64_t cap, int64_t
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n_chunks) *n_chunks = 0;
     if (!n_chunks || (!rec_bounds) != (!byte_bounds)) return fail(CL_ERR_ARG, "cl_track_chunks: bad arguments");
-    if (!c->tk.built) return fail(CL_ERR_ARG, "cl_track_chunks: no track built on this handle");
+    if (!c->tk.st.built) return fail(CL_ERR_ARG, "cl_track_chunks: no track built on this handle");
     if (budget < k14_lcap(c)) return fail(CL_ERR_ARG, "cl_track_chunks: budget below the longest line the template allows");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_track_chunks: asynchronous runs still in flight");
-    if (c->tk_txt.R > 0) HIP_TRY(hipSetDevice(c->device));
-    return text_chunks(c->tk_txt, c->stream, budget, k14_lcap(c), cap, rec_bounds, byte_bounds, n_chunks, "cl_track_chunks");
+    if (c->tk.txt.R > 0) HIP_TRY(hipSetDevice(c->device));
+    return text_chunks(c->tk.txt, c->stream, budget, k14_lcap(c), cap, rec_bounds, byte_bounds, n_chunks, "cl_track_chunks");
 }
 
 extern "C" int cl_track_render(cl_chrom* c, int64_t chunk, char* out, int64_t cap, int64_t* n_bytes)
@@ -341,8 +333,8 @@ extern "C" int cl_track_render(cl_chrom* c, int64_t chunk, char* out, int64_t ca
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (n_bytes) *n_bytes = 0;
     if (!out || !n_bytes) return fail(CL_ERR_ARG, "cl_track_render: bad arguments");
-    cl_chrom::TrackState& s = c->tk;
-    TextOut& txt = c->tk_txt;
+    cl_chrom::Track::State& s = c->tk.st;
+    TextOut& txt = c->tk.txt;
     if (!s.built || txt.crec.empty()) return fail(CL_ERR_ARG, "cl_track_render: no chunks made on this handle (cl_track_chunks)");
     if (chunk < 0 || chunk + 1 >= (int64_t)txt.crec.size()) return fail(CL_ERR_ARG, "cl_track_render: chunk index out of range");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_track_render: asynchronous runs still in flight");
