@@ -1,7 +1,19 @@
-// cl_chrom.h -- host side shared by the translation units: the chromosome handle (device buffers, result slots, sweep
-// state), the structures the step tail exchanges with the K7 / K10 kernels, and the functions / kernels one unit uses
-// from another.  A __global__ function may be launched from a unit that only sees its declaration: the launch goes
-// through the defining unit's host stub.
+// cl_chrom.h -- host side shared by the translation units: what one call asks for (RunRequest), the chromosome handle (device
+// buffers, result slots, sweep state), the structures the step tail exchanges with the K7 / K10 kernels, and the functions /
+// kernels one unit uses from another.  A __global__ function may be launched from a unit that only sees its declaration: the
+// launch goes through the defining unit's host stub.
+//
+// Three kinds of thing, kept apart:
+//   RunRequest      what the caller of ONE run asked for.  The entry point builds it, enqueue() and the run functions take it by
+//                   reference; nothing of it is stored in the handle (the result slot notes where the run's output goes).
+//   cl_chrom::Run   the working set of the run BEING ENQUEUED (c->run): where its sorted arrays and K2 words live, its traversal
+//                   level, what its kernels have done already.  Assigned fresh by run_begin() at the start of every run, read by
+//                   nobody after the enqueue (the developer build's cl_debug_time_lists aside).
+//   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K26
+//                   state that outlives a run: one struct each, the buffers together with the flags that say what they hold, and
+//                   one invalidate() where several flags fall together.
+// What reports on the LAST run (last_k2_mode, dbg_g / dbg_nm, refused_labelled, the slots) stays in the handle: callers read it
+// after the enqueue.
 #pragma once
 #include "cl_common.h"
 #include "cl_table.h"
@@ -55,6 +67,20 @@ struct K7Src {
 
 struct K7Part { double sx[2]; double sxx[2]; long long n_all[2]; long long n_pos[2]; };
 
+// What one call asks of the handle.  cl_cluster, cl_cluster_async, cl_cluster_pairs_async, cl_cluster_rowmask_async,
+// cl_cluster_step_async and cl_cluster_weighted each build one and hand it to enqueue() (cloops_hip.hip)
+struct RunRequest {
+    int variant = CL_VARIANT_CDBSCAN1, eps = 0, minPts = 0, cut = 0;
+    int32_t* labels_out = nullptr;    // row-aligned labels to the host (pinned or pageable), or null
+    int2* pairs_out = nullptr;        // cl_cluster_pairs_async: (row, label) of every labelled PET, staged by the label kernel in the slot's
+    long long pairs_cap = 0;          // device buffer and copied by cl_wait into the caller's page-locked buffer (their count: header word 6)
+    void* mask_out = nullptr;         // cl_cluster_rowmask_async: one bit per row + the labels of the set rows in row order, made on the device from the
+    long long mask_cap = 0;           // row-aligned labels (k_rowmask_count / k_rowmask_write) in the slot's `pairs` buffer, copied out by cl_wait like the pairs
+    int step = -1;                    // >= 0: the run is step `step` of a sweep (cl_cluster_step_async), -1: it is not
+    long long fine_lo = -1;           // >= 0: the step's summary also histograms the self group's [fine_lo, fine_lo + 2048) exactly
+    int wx = 0, wy = 0;               // cl_cluster_weighted: the metric's weights (0: not the weighted form)
+};
+
 struct cl_chrom {
     long long tmp_n = -1;             // n the rocPRIM temporary storage was last sized for
     DevBuf arena;                     // ONE allocation behind the per-PET workspace of the handle (ensure_workspace): the first
@@ -71,11 +97,14 @@ struct cl_chrom {
     DevBuf keys_in, keys_out, vals_in, vals_out, sort_tmp, scan_tmp;
     DevBuf qb_key, qb_val;            // the q index (k_make_qkeys): rows sorted by q, persistent
     int qindex_layout = -1;           // layout the q index was built for (-1: none)
-    // the fine layout (cl_set_eps_list): rows sorted by (strip of width fine_w, q) once; the layout of an eps = k fine_w is a per-strip merge of it
-    DevBuf fq, fsp, frow, fstrip;
-    int fine_w = 0;                   // announced common divisor of the sweep's eps values (0: none)
-    int fine_valid_w = 0, fine_layout = -1;       // what the fine buffers hold
-    GridParams fine_g;
+    // the fine layout (cl_set_eps_list): rows sorted by (strip of width w, q) once; the layout of an eps = k w is a per-strip merge of it
+    struct Fine {
+        DevBuf q, sp, row, strip;
+        int w = 0;                    // announced common divisor of the sweep's eps values (0: none)
+        int valid_w = 0, layout = -1; // what the buffers hold
+        GridParams g;
+        void invalidate() { valid_w = 0; layout = -1; }
+    } fine;
     int sort_index_mode = 0;          // cl_set_sort_index: 0 = build at the second sort, 1 = at the first, -1 = never
     long long n_sorts = 0;            // layouts sorted on this handle so far
     DevBuf sv, sa, strip, cnt, parent, root, head, headidx, cellfirst, compkey, ncore, bsize, owner, state;
@@ -83,31 +112,60 @@ struct cl_chrom {
     int* h_pinned = nullptr;          // small pinned staging (stats, block scalars)
     struct StripPlan { int layout, eps, maxlen; };
     std::vector<StripPlan> plans;     // longest strip over all rows per (layout, eps): picks the sort path
-    u32* srow = nullptr;              // sorted position -> input row of the run being enqueued
-    // working set of the run being enqueued: sorted (q, sp), strip table, tile table.  They alias either the
-    // workspace buffers (sv, sa, strip, tile_s0) or, for a run without cut filter, the base layout itself.
-    int *w_sv = nullptr, *w_sa = nullptr, *w_strip = nullptr, *w_tile = nullptr;
+    // Working set of the run being enqueued.  run_begin() assigns a fresh one first thing in run_rotated, run_block, run_weighted and
+    // cl_neighbor_counts: no run sees what an earlier one -- of whatever kind, finished or failed half-way -- left here.
+    struct Run {
+        u32* srow = nullptr;          // sorted position -> input row
+        // sorted (q, sp), strip table, tile table: they alias either the workspace buffers (sv, sa, strip, tile_s0) or, for a run
+        // without cut filter, the base layout itself
+        int *sv = nullptr, *sa = nullptr, *strip = nullptr, *tile = nullptr;
+        int* cnt = nullptr;           // where K2 writes the run's words (the work buffer or the count cache)
+        WordSrc ws{};                 // where their consumers read them
+        int init_nclr = 0;            // > 0: the run has not cleared its key bitmap / counters yet (words to clear)
+        int level = 0;                // traversal level (run_sort_and_count decides: level 4 needs the count cache's tables)
+        const int* dM = nullptr;      // device: PETs that entered DBSCAN
+        int m = 0;                    // ... on the host (exact when m_exact, else n)
+        bool m_exact = false;
+        bool rows = true;             // the run produces row-aligned labels
+        bool l4_make_base = false;    // level 4: the run makes the words of its eps -- K2 on the base layout, launched behind the band query
+        bool l4_cut = false;          // level 4: the run has a cut (the per-strip tables of k_cut_strips apply)
+        bool l4_band = false;         // ... and re-uses counts under another cut (the band's words are fresh: c->cnt, by run position)
+        bool k2_make = false;         // the run made the words itself (level 4 under a cut: on the base layout, then its band)
+        const int* k_total = nullptr; // device: where the run left the number of ids handed out (null: rankscan[n])
+        bool hdr_packed = false;      // the run's own kernels have written the slot header (no k_pack_header)
+    } run;
     // Base layout: the sorted arrays of ALL rows (cut = 0) for one (variant layout, eps), kept until eps changes.
     // The sort order does not depend on minPts and a cut only REMOVES rows, so every further run of a sweep at this
     // eps is one stable stream compaction of the base layout instead of five radix passes (cLoops/pipe.py:241-281
     // walks eps in the outer loop).  Nothing of a result is kept: neighbour counts, components, labels are redone.
-    DevBuf bq, bsp, brow, bstrip, btile, sel_tmp;
-    struct BaseLayout { bool valid = false; int layout = -1, eps = 0; } base;
+    // ... and variant 2's cell minima of it (key: traversal level 4, once per eps)
+    struct Base {
+        DevBuf q, sp, row, strip, tile, key;
+        bool valid = false; int layout = -1, eps = 0;
+        bool key_valid = false;       // `key` belongs to the layout
+        void invalidate() { valid = false; key_valid = false; }
+    } base;
+    DevBuf sel_tmp;
     // Count cache: the K2 words (cl_common.h "K2W") of the FIRST run on a base layout, kept while the layout lives.  A word
     // holds the PET's neighbour count (saturated at `cap`, exact as far as the minPts values of `tmask` need it: GridParams::tmask) and does not depend on minPts otherwise;
     // a cut removes a prefix of every strip (q IS the distance), so between two runs of one eps the count of a PET changes
     // only if q - eps < max(the two cuts): every later run with a minPts of the set takes the words of the PETs beyond that
     // band as they are (k_cut_copy<true> carries them through its compaction) and runs K2 on the band alone.  Results are
     // identical with the cache switched off (cl_set_count_reuse); cLoops/pipe.py:247-250 walks minPts inside eps, descending.
-    struct CountCache { bool valid = false; bool cut_on_base = false /* made on the base layout by a run under a cut: the PETs within eps above thr counted removed neighbours -- every run under a cut re-queries its band */; bool base_space = false /* level 4: words by base position, hints in base positions (k_lists.hip) */; int layout = -1, eps = 0, thr = 0 /* q threshold of the run's cut, 0 = none */, cap = 0; u32 tmask[4] = {0, 0, 0, 0} /* the minPts values the words serve, bit t - 1 */; } rc;
-    DevBuf rc_cnt, rc_pre, rc_poff, rc_dpre, rc_D, rc_blen;   // the words in the sorted order of the run that made them; per strip: PETs its cut removed
+    struct Counts {
+        bool valid = false;
+        bool cut_on_base = false;     // made on the base layout by a run under a cut: the PETs within eps above thr counted removed
+                                      // neighbours -- every run under a cut re-queries its band
+        bool base_space = false;      // level 4: words by base position, hints in base positions (k_lists.hip)
+        int layout = -1, eps = 0, thr = 0 /* q threshold of the run's cut, 0 = none */, cap = 0;
+        u32 tmask[4] = {0, 0, 0, 0};  // the minPts values the words serve, bit t - 1
+        DevBuf cnt, pre, poff, dpre, D, blen;   // the words in the sorted order of the run that made them; per strip: PETs its cut removed
                                       // from the strip / from all strips up to and including it
+        void invalidate() { valid = false; }
+    } rc;
     bool reuse_counts = true;         // cl_set_count_reuse
     int count_floor = 0;              // cl_set_count_floor: smallest minPts later runs of this eps will ask for (0 = unknown)
     u32 count_tmask[4] = {0, 0, 0, 0}; // cl_set_count_thresholds: the minPts values themselves (bit t - 1; all zero = not announced)
-    int* w_cnt = nullptr;             // where K2 writes the words of the run being enqueued (cnt or rc_cnt)
-    WordSrc ws{};                     // where its consumers read them
-    int init_nclr = 0;                // > 0: the run being enqueued has not cleared its key bitmap / counters yet (words to clear)
     DevBuf blk_tmp;                   // block sums / offsets of the in-kernel scan over the key bitmap (k_rank_scan)
     DevBuf rootlist, cflag8;          // K3: the components' roots (k_flatten); per PET: core / opens a chain / ends one (k_chain_flags)
     // List form of a run (k_lists.hip): the run's CORES and its WALKERS (non-core PETs with a neighbour: the only ones a border
@@ -117,36 +175,20 @@ struct cl_chrom {
     DevBuf l_mask, l_rank, l_blk, l_cstrip, l_wpos, l_wenc, l_dist, l_aux;
     // ... built straight from the BASE layout (traversal level 4): a cut removes a prefix of every strip, so the list kernels
     // apply it by index (per strip: first kept base index, end of the cut band, PETs removed: l_tab) and a re-using run
-    // copies nothing at all; variant 2's cell minima are a property of the base layout (bkey, once per eps) except in the one
+    // copies nothing at all; variant 2's cell minima are a property of the base layout (base.key, once per eps) except in the one
     // cell per strip the cut goes through (l_fix, per run)
-    DevBuf l_tab, l_fix, bkey;
-    bool bkey_valid = false;          // bkey belongs to the current base layout
-    int run_level = 0;                // traversal level of the run being enqueued (run_sort_and_count decides: level 4 needs the count cache's tables)
-    const int* w_dM = nullptr;        // device: PETs that entered DBSCAN in the run being enqueued
-    bool run_rows = true;             // the run being enqueued produces row-aligned labels
-    int2* pairs_out = nullptr;        // cl_cluster_pairs_async: (row, label) of every labelled PET, staged by the label kernel in the slot's
-    long long pairs_cap = 0;          // device buffer and copied by cl_wait into the caller's page-locked buffer (their count: header word 6)
+    DevBuf l_tab, l_fix;
     bool pairs_defer = false, pairs_copy_pending = false;      // cl_set_pairs_defer / cl_pairs_sync
-    void* mask_out = nullptr;         // cl_cluster_rowmask_async: one bit per row + the labels of the set rows in row order, made on the device from the
-    long long mask_cap = 0;           // row-aligned labels (k_rowmask_count / k_rowmask_write) in the slot's `pairs` buffer, copied out by cl_wait like the pairs
-    bool l4_make_base = false;        // level 4: the run makes the words of its eps -- K2 on the base layout, launched behind the band query
-    bool l4_cut = false;              // level 4: the run has a cut (the per-strip tables of k_cut_strips apply)
-    bool l4_band = false;             // ... and re-uses counts under another cut (the band's words are fresh: c->cnt, by run position)
     bool fuse_chains = true;          // the chains of a run are made inside k_union_c (false: k_chain_c, a kernel of its own -- developer A/B)
     bool l_sup_dirty = false;         // k_classify's superblock sums may be non-zero (a run that failed between k_classify and k_chain_c)
     GridParams dbg_g{}; int dbg_nm = 0;   // the last rotated run's grid and size (developer build: kernels timed on their own)
     int traversal = 4;                // cl_set_traversal: 0 = tile kernels over every PET (rounds 1-4), 1 = K3 on the core list,
                                       // 2 = + border rule on the walker list, 3 = + labels / table / statistics from the lists,
                                       // 4 = + the lists built from the base layout (no copy of the layout for a run that re-uses counts)
-    bool last_k2_mode_make = false;   // the run being enqueued made the words itself (level 4 under a cut: on the base layout, then its band)
     int last_k2_mode = 0;             // 0 = full K2, 1 = words re-used as they are (same cut), 2 = remapped + K2 on the band
     std::vector<long long> dcum;      // dcum[k] = number of PETs with Y - X < k, k = 0 .. 65536 (empty: unknown)
-    const int* k_total = nullptr;     // device: where the run left the number of ids handed out (null: rankscan[n])
-    bool hdr_packed = false;          // the run's own kernels have written the slot header (no k_pack_header)
     DevBuf dhist;                     // device: number of PETs with Y - X == d, d = 0 .. 65535 (+ one slot for d < 0)
     long long n_neg = 0;              // PETs with Y - X < 0
-    int run_m = 0;                    // PETs that enter DBSCAN in the run being enqueued (exact when run_m_exact, else n)
-    bool run_m_exact = false;
     bool reuse_layout = true;
     // Result slots: two runs may be in flight (cl_cluster_async) -- the labels / table / header of
     // run k live in slot k & 1, so the D2H copy of run k (copy stream) overlaps the kernels of run k+1.
@@ -184,19 +226,19 @@ struct cl_chrom {
     } slot[2];
     bool device_labels = true;        // produce row-order device labels even without a host destination (cl_set_device_labels)
     bool export_table = true;         // copy the cluster table to pinned host memory at the end of a run (cl_set_table_export)
-    int pending_step = -1;            // >= 0: the run being enqueued is step `pending_step` of a sweep (cl_cluster_step_async)
-    int pending_cut = 0;
-    long long pending_fine_lo = -1;   // >= 0: the step's summary also histograms the self group's [fine_lo, fine_lo + 2048) exactly
-    DevBuf cand_box, cand_step, cand_keep, cand_out;   // K10: candidate loops of the running sweep
-    long long cand_n = 0, cand_cap = 0;
+    // K10: candidate loops of the running sweep (boxes, their steps, the keep flags and the output of cl_cand_finish)
+    struct Cand { DevBuf box, step, keep, out; long long n = 0, cap = 0; } cand;
     DevBuf hdr;                       // device result headers, 16 ints per slot
     DevBuf k7_cls, k7_parts;          // K7: class per cluster id, per-workgroup partials
     // K17 (k_sweep.hip): the (|d|, weight) entries of the two distance groups as cl_dist_collect appended them (group 0 from the
-    // front, group 1 from the back of ONE buffer of kde_cap entries) and sorted, counters, sort scratch, the evaluation's partials
-    DevBuf kde_ent, kde_sorted, kde_ctr, kde_tmp, kde_part;
-    int kde_run = -1;                 // `deq` at the cl_dist_collect that filled them (-1: none): valid while no further run completes
-    long long kde_cap = 0, kde_cnt[2] = {0, 0};
-    DevBuf sig_tx, sig_ty, sig_tmp, sig_sorttmp, sig_m, sig_win, sig_out;   // K8: sorted PET tables, windows, counts
+    // front, group 1 from the back of ONE buffer of `cap` entries) and sorted, counters, sort scratch, the evaluation's partials
+    struct Kde {
+        DevBuf ent, sorted, ctr, tmp, part;
+        int run = -1;                 // `deq` at the cl_dist_collect that filled them (-1: none): valid while no further run completes
+        long long cap = 0, cnt[2] = {0, 0};
+    } kde;
+    // K8: sorted PET tables (built for `cut` when ready), sort scratch, their number, windows, counts
+    struct Sig { DevBuf tx, ty, tmp, sorttmp, m, win, out; bool ready = false; int cut = 0; } sig;
     // ---- the analysis units: one struct each, released by assigning a fresh one (the unit's *_release) ----
     // K12 (k_fingerprint.hip): scratch of one call, freed when it returns
     struct Fp { DevBuf small, keys, sorted, tmp, pairs; } fp;
@@ -307,7 +349,6 @@ struct cl_chrom {
             long long nd = 0, n_used = 0;
         } st;
     } ex;
-    bool sig_ready = false; int sig_cut = 0;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
     int copy_mode = 0;                // 0: the D2H copies of a run go through copy_stream, 1: they are issued in `stream` (caller's stream),
@@ -330,6 +371,25 @@ struct cl_chrom {
 
 #define LAUNCH(kernel, nthreads, ...) \
     hipLaunchKernelGGL(kernel, dim3(nblocks(nthreads)), dim3(TPB), 0, c->stream, __VA_ARGS__)
+
+// first thing of every run (run_rotated, run_block, run_weighted, cl_neighbor_counts): a fresh working set
+static inline void run_begin(cl_chrom* c) { c->run = cl_chrom::Run(); }
+
+// A run that fails half-way (allocation, a HIP error between two launches) must not leave state behind that a later run would
+// trust: the count cache it may have marked valid before its words were written, the tickets of the in-kernel scans and the
+// superblock sums of the list kernels (all "zero between kernels").  Disarmed by the run that reaches its end.
+struct RunGuard {
+    cl_chrom* c; bool armed = true;
+    explicit RunGuard(cl_chrom* cc) : c(cc) {}
+    ~RunGuard()
+    {
+        if (!armed) return;
+        c->rc.invalidate();
+        c->l_sup_dirty = true;
+        if (c->counters.p) (void)hipMemsetAsync(c->counters.as<int>() + CTR_TICKET_A, 0, 8, c->stream);
+        (void)hipGetLastError();
+    }
+};
 
 // ---- ranged read-back of a unit's results (the cl_*_get entry points) ----
 // [first, first + count) lies inside [0, size)
@@ -357,7 +417,7 @@ int ensure_cand_capacity(cl_chrom* c, long long need);
 Table make_table_slot(cl_chrom* c, int slot);
 Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
-int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_out);
+int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* d_M);
 // A unit drops its buffers and its state by assigning a fresh struct, and with them what was made from them: K25's marginals and
 // weights belong to K24's cells, K26's diagonals to K25's marginals and weights.  Called by the units' entry points; the handle's
 // destruction needs none of them
@@ -380,8 +440,8 @@ static inline int unit_free(cl_chrom* c, const char* who, void (*release)(cl_chr
     return CL_OK;
 }
 // k_block.hip, k_weighted.hip
-int run_block(cl_chrom* c, int eps, int minPts, int cut, int32_t* labels_out);
-int run_weighted(cl_chrom* c, int eps, int minPts, int wx, int wy, int32_t* labels_out);
+int run_block(cl_chrom* c, const RunRequest& req);
+int run_weighted(cl_chrom* c, const RunRequest& req);
 
 // kernels of cloops_hip.hip that k_block.hip / k_weighted.hip launch
 __global__ void k_init_table(Table t, const int* __restrict__ rankscan, int n);
@@ -424,8 +484,8 @@ int lists_scatter_root(cl_chrom* c, int nm, const ListRun& L);
 int lists_border(cl_chrom* c, const GridParams& g, int nm, const ListRun& L);
 int lists_emit_records(cl_chrom* c, const GridParams& g, int nm, const ListRun& L);
 int lists_scatter_owner(cl_chrom* c, int nm, const ListRun& L);
-int lists_final(cl_chrom* c, const GridParams& g, int nm, const ListRun& L, bool rows, int* pair_count);
-int lists_rowmask(cl_chrom* c, int* total);
+int lists_final(cl_chrom* c, const RunRequest& req, const GridParams& g, int nm, const ListRun& L, bool rows, int* pair_count);
+int lists_rowmask(cl_chrom* c, const RunRequest& req, int* total);
 
 // kernels of k_sweep.hip that the step tail (finish_enqueue) launches
 __global__ void __launch_bounds__(256)
@@ -459,7 +519,7 @@ __device__ __forceinline__ int k8_ub(const u64* __restrict__ t, int m, long long
 {
     return k8_lb(t, m, v + 1);
 }
-// builds the tables of (chromosome, cut) unless the handle holds them already (c->sig_tx / sig_ty; c->sig_m[0] on the device = the
+// builds the tables of (chromosome, cut) unless the handle holds them already (c->sig.tx / sig.ty; c->sig.m[0] on the device = the
 // number of valid entries); enqueued on c->stream, c->n > 0
 int sig_tables(cl_chrom* c, int cut);
 // K19's table (k_agg.hip), shared with K22 (k_domain.hip), K23 (k_kdis.hip) and K24 (k_matrix.hip): the rows with Y - X >= cut sorted by X (c->ag.sx: X + 2^30 as u32, c->ag.sy:

@@ -2112,18 +2112,18 @@ k_final_labels(GridParams g, const int* __restrict__ strip_start, const int* __r
 // before a step is enqueued it has room for all the boxes the step can produce (one per cluster id, at most n / minPts).
 int ensure_cand_capacity(cl_chrom* c, long long need)
 {
-    if (need <= c->cand_cap) return CL_OK;
-    const long long cap = std::max<long long>(std::max<long long>(need, 2 * c->cand_cap), 1 << 20);
+    if (need <= c->cand.cap) return CL_OK;
+    const long long cap = std::max<long long>(std::max<long long>(need, 2 * c->cand.cap), 1 << 20);
     DevBuf nb, ns;
     int rc;
     if ((rc = nb.ensure((size_t)cap * 16)) || (rc = ns.ensure((size_t)cap * 4))) return rc;
-    if (c->cand_n > 0) {
-        HIP_TRY(hipMemcpyAsync(nb.p, c->cand_box.p, (size_t)c->cand_n * 16, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(ns.p, c->cand_step.p, (size_t)c->cand_n * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (c->cand.n > 0) {
+        HIP_TRY(hipMemcpyAsync(nb.p, c->cand.box.p, (size_t)c->cand.n * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(ns.p, c->cand.step.p, (size_t)c->cand.n * 4, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->cand_box = std::move(nb); c->cand_step = std::move(ns);
-    c->cand_cap = cap;
+    c->cand.box = std::move(nb); c->cand.step = std::move(ns);
+    c->cand.cap = cap;
     return CL_OK;
 }
 
@@ -2152,9 +2152,9 @@ static void free_chrom(cl_chrom* c)
 extern "C" void cl_chrom_destroy(cl_chrom* c) { free_chrom(c); }
 extern "C" int64_t cl_chrom_size(const cl_chrom* c) { return c ? c->n : -1; }
 extern "C" void cl_set_profiling(cl_chrom* c, int enabled) { if (c) c->profiling = enabled != 0; }
-extern "C" void cl_set_layout_reuse(cl_chrom* c, int enabled) { if (c) { c->reuse_layout = enabled != 0; c->base.valid = false; c->rc.valid = false; } }
-extern "C" void cl_set_count_reuse(cl_chrom* c, int enabled) { if (c) { c->reuse_counts = enabled != 0; c->rc.valid = false; } }
-extern "C" void cl_set_traversal(cl_chrom* c, int level) { if (c) { c->traversal = level < 0 ? 0 : (level > 4 ? 4 : level); c->rc.valid = false; } }
+extern "C" void cl_set_layout_reuse(cl_chrom* c, int enabled) { if (c) { c->reuse_layout = enabled != 0; c->base.invalidate(); c->rc.invalidate(); } }
+extern "C" void cl_set_count_reuse(cl_chrom* c, int enabled) { if (c) { c->reuse_counts = enabled != 0; c->rc.invalidate(); } }
+extern "C" void cl_set_traversal(cl_chrom* c, int level) { if (c) { c->traversal = level < 0 ? 0 : (level > 4 ? 4 : level); c->rc.invalidate(); } }
 extern "C" int cl_last_region_mode(const cl_chrom* c) { return c ? c->last_k2_mode : 0; }
 // Forget everything the handle has DERIVED from its rows -- the q index, the fine layout, the base layout of the last eps, the
 // cached neighbour counts -- and keep every allocation: the next run pays what the first run on a freshly uploaded dataset pays
@@ -2164,9 +2164,9 @@ extern "C" int cl_chrom_drop_indexes(cl_chrom* c)
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (c->slot[0].pending || c->slot[1].pending) return fail(CL_ERR_ARG, "cl_chrom_drop_indexes: a run is in flight");
     c->qindex_layout = -1;
-    c->fine_valid_w = 0; c->fine_layout = -1;
-    c->base.valid = false;
-    c->rc.valid = false;
+    c->fine.invalidate();
+    c->base.invalidate();
+    c->rc.invalidate();
     return CL_OK;
 }
 extern "C" void cl_set_count_floor(cl_chrom* c, int32_t min_pts)
@@ -2203,7 +2203,7 @@ extern "C" void cl_set_eps_list(cl_chrom* c, const int32_t* eps, int32_t n)
         gcd = a; mx = std::max<long long>(mx, eps[k]);
     }
     // worth a layout of its own: several eps values, strips of the common width not absurdly narrow, at most CL_FINE_KMAX runs per strip
-    c->fine_w = (distinct >= 2 && gcd >= 16 && mx / gcd <= CL_FINE_KMAX) ? (int)gcd : 0;
+    c->fine.w = (distinct >= 2 && gcd >= 16 && mx / gcd <= CL_FINE_KMAX) ? (int)gcd : 0;
 }
 
 extern "C" void cl_set_count_thresholds(cl_chrom* c, const int32_t* min_pts, int32_t n)
@@ -2627,9 +2627,9 @@ __global__ void k_store_m(int S, const int* __restrict__ sloc, const int* __rest
         {&c->slot[1].labels, n * 4}, {&c->slot[1].table, (n + 1) * sizeof(cl_box)}, {&c->slot[1].slab, n * 4}, \
         {&c->ulist, n * 4}, {&c->lo, n * 4}, {&c->hi, n * 4}, {&c->recs, n * sizeof(Rec)}, \
         {&c->chainflag, n * 4}, {&c->chainhead, n * 4}, {&c->usize, n * 4}, {&c->tile_s0, (n / 256 + 2) * 4}, \
-        {&c->bq, (n + 2 * SORT_PAD) * 4}, {&c->bsp, (n + 2 * SORT_PAD) * 4}, {&c->brow, n * 4}, {&c->btile, (n / 256 + 2) * 4}, \
-        {&c->fq, n * 4}, {&c->fsp, n * 4}, {&c->frow, n * 4}, \
-        {&c->qb_key, n * 4}, {&c->qb_val, n * 8}, {&c->k7_cls, n + 16}, {&c->rc_cnt, n * 4}, {&c->rootlist, n * 4}, {&c->cflag8, n + 16}, \
+        {&c->base.q, (n + 2 * SORT_PAD) * 4}, {&c->base.sp, (n + 2 * SORT_PAD) * 4}, {&c->base.row, n * 4}, {&c->base.tile, (n / 256 + 2) * 4}, \
+        {&c->fine.q, n * 4}, {&c->fine.sp, n * 4}, {&c->fine.row, n * 4}, \
+        {&c->qb_key, n * 4}, {&c->qb_val, n * 8}, {&c->k7_cls, n + 16}, {&c->rc.cnt, n * 4}, {&c->rootlist, n * 4}, {&c->cflag8, n + 16}, \
         {&c->slot[0].d_step, 16 + sizeof(K7Part) + K7_LOGBINS * 8 + K7_FINE * 8 + K7_BLOCKS * sizeof(K7Part)}, \
         {&c->slot[1].d_step, 16 + sizeof(K7Part) + K7_LOGBINS * 8 + K7_FINE * 8 + K7_BLOCKS * sizeof(K7Part)}, \
     };
@@ -2689,9 +2689,9 @@ static int reserve_workspace(cl_chrom* c)
         const long long cand0 = std::max<long long>((long long)n / 8, std::min<long long>(1 << 20, (long long)n + 1024));   // (small handles stay small)
         std::vector<Want> all(std::begin(wants), std::end(wants));
         all.push_back({&c->sort_tmp, sort_bytes}); all.push_back({&c->scan_tmp, scan_bytes});
-        all.push_back({&c->strip, (s_guess + 2) * 4}); all.push_back({&c->bstrip, (s_guess + 2) * 4}); all.push_back({&c->sel_tmp, (s_guess + 2) * 8 + (s_guess / 256 + 4) * 8 + 64});
+        all.push_back({&c->strip, (s_guess + 2) * 4}); all.push_back({&c->base.strip, (s_guess + 2) * 4}); all.push_back({&c->sel_tmp, (s_guess + 2) * 8 + (s_guess / 256 + 4) * 8 + 64});
         all.push_back({&c->blk_tmp, (n / 32 / 1024 + 4) * 8});     // (block sums / offsets of the in-kernel scans ride in sel_tmp / blk_tmp)
-        all.push_back({&c->cand_box, (size_t)cand0 * 16}); all.push_back({&c->cand_step, (size_t)cand0 * 4});
+        all.push_back({&c->cand.box, (size_t)cand0 * 16}); all.push_back({&c->cand.step, (size_t)cand0 * 4});
         bool untouched = true;
         size_t total = 0;
         for (const Want& w : all) { untouched = untouched && w.b->p == nullptr; total += ((w.bytes + 255) / 256) * 256 + 256; }
@@ -2700,7 +2700,7 @@ static int reserve_workspace(cl_chrom* c)
         else if (untouched) {
             char* at = (char*)c->arena.p;
             for (const Want& w : all) { const size_t sz = ((w.bytes + 255) / 256) * 256 + 256; w.b->adopt(at, sz); at += sz; }
-            c->cand_cap = cand0;
+            c->cand.cap = cand0;
         }
     }
     return CL_OK;
@@ -2713,8 +2713,8 @@ int ensure_workspace(cl_chrom* c, int S)
     WORKSPACE_WANTS(c, n);
     if (!c->arena.p) (void)reserve_workspace(c);
     const cl_chrom::Slot* other = &c->slot[1 - c->cur];
-    for (const Want& w : wants) if (w.b != &other->labels && w.b != &other->table && w.b != &other->slab && w.b != &c->slot[0].d_step && w.b != &c->slot[1].d_step && w.b != &c->bq && w.b != &c->bsp && w.b != &c->brow && w.b != &c->btile && w.b != &c->qb_key &&
-                                    w.b != &c->qb_val && w.b != &c->fq && w.b != &c->fsp && w.b != &c->frow && w.b != &c->k7_cls && w.b != &c->rc_cnt && w.b != &c->rootlist && w.b != &c->cflag8 && (rc = w.b->ensure(w.bytes))) return rc;
+    for (const Want& w : wants) if (w.b != &other->labels && w.b != &other->table && w.b != &other->slab && w.b != &c->slot[0].d_step && w.b != &c->slot[1].d_step && w.b != &c->base.q && w.b != &c->base.sp && w.b != &c->base.row && w.b != &c->base.tile && w.b != &c->qb_key &&
+                                    w.b != &c->qb_val && w.b != &c->fine.q && w.b != &c->fine.sp && w.b != &c->fine.row && w.b != &c->k7_cls && w.b != &c->rc.cnt && w.b != &c->rootlist && w.b != &c->cflag8 && (rc = w.b->ensure(w.bytes))) return rc;
     if ((rc = c->strip.ensure(((size_t)S + 2) * 4)) || (rc = c->counters.ensure(256))) return rc;      // (counters: allocated at upload)
     if (c->sv.fresh || c->sa.fresh) {
         // sentinel pads around the sorted arrays (k_region_core stages its windows without bounds checks)
@@ -2809,7 +2809,7 @@ static int strip_maxlen(cl_chrom* c, const GridParams& g, int* out)
 
 // K0 + K1: keys, sort, strip table, decoded sorted arrays for the rows that pass `g.cut`, written to the given
 // destination buffers (sorted arrays with their sentinel pads already in place)
-static int sort_layout(cl_chrom* c, const GridParams& g, int* dsv, int* dsa, u32* drow /* or null: c->srow aliases a sort buffer */,
+static int sort_layout(cl_chrom* c, const GridParams& g, int* dsv, int* dsa, u32* drow /* or null: c->run.srow aliases a sort buffer */,
                        int* dstrip, int* dtile)
 {
     const int n = (int)c->n;
@@ -2860,36 +2860,36 @@ static int sort_layout(cl_chrom* c, const GridParams& g, int* dsv, int* dsa, u32
                 LAUNCH(k_strip_table32, gx.S + 2, (const u32*)osa, n, gx.S, gx.rbits, ostrip, otile);
                 return CL_OK;
             };
-            const int fw = c->fine_w;
+            const int fw = c->fine.w;
             if (fw > 0 && g.eps % fw == 0 && g.eps / fw <= CL_FINE_KMAX) {
                 // the eps values of the sweep share the divisor fw (cl_set_eps_list): the layout comes from the fine one
-                if (c->fine_valid_w != fw || c->fine_layout != layout) {
+                if (c->fine.valid_w != fw || c->fine.layout != layout) {
                     GridParams gf;
-                    if (make_grid(c, g.variant, fw, 1, 0, &gf) != CL_OK) c->fine_w = 0;      // (too many strips of that width: sort as before)
+                    if (make_grid(c, g.variant, fw, 1, 0, &gf) != CL_OK) c->fine.w = 0;      // (too many strips of that width: sort as before)
                     else {
                         gf.dbg = g.dbg; gf.dbg2 = g.dbg2;
-                        if ((rc = c->fq.ensure((size_t)n * 4)) || (rc = c->fsp.ensure((size_t)n * 4)) || (rc = c->frow.ensure((size_t)n * 4)) ||
-                            (rc = c->fstrip.ensure(((size_t)gf.S + 2) * 4))) return rc;
-                        if ((rc = strip_sort(gf, c->fsp.as<int>(), c->fq.as<int>(), c->frow.as<u32>(), c->fstrip.as<int>(), (int*)nullptr))) return rc;
-                        c->fine_g = gf; c->fine_valid_w = fw; c->fine_layout = layout;
+                        if ((rc = c->fine.q.ensure((size_t)n * 4)) || (rc = c->fine.sp.ensure((size_t)n * 4)) || (rc = c->fine.row.ensure((size_t)n * 4)) ||
+                            (rc = c->fine.strip.ensure(((size_t)gf.S + 2) * 4))) return rc;
+                        if ((rc = strip_sort(gf, c->fine.sp.as<int>(), c->fine.q.as<int>(), c->fine.row.as<u32>(), c->fine.strip.as<int>(), (int*)nullptr))) return rc;
+                        c->fine.g = gf; c->fine.valid_w = fw; c->fine.layout = layout;
                     }
                 }
-                if (c->fine_w > 0) {
-                    const GridParams& gf = c->fine_g;
+                if (c->fine.w > 0) {
+                    const GridParams& gf = c->fine.g;
                     const int k = g.eps / fw;
-                    LAUNCH(k_strips_from_fine, g.S + 2, g.S, g.s0, k, gf.S, gf.s0, (const int*)c->fstrip.as<int>(), n, dstrip);
+                    LAUNCH(k_strips_from_fine, g.S + 2, g.S, g.s0, k, gf.S, gf.s0, (const int*)c->fine.strip.as<int>(), n, dstrip);
                     // (q + 1 -- the tie-break key -- must fit the q field of the sorted keys: qb bits; 0 = the field would leave no room for runs)
                     int qb = bits_for((unsigned)std::min<long long>((long long)gf.qtop + 1, 0x7fffffffLL));
                     if (qb > 28) qb = 0;
-                    hipLaunchKernelGGL(k_layout_from_fine, dim3(nblocks(n, LFF_T)), dim3(256), 0, c->stream, n, g, gf, k, (unsigned)(((1ull << 32) + (unsigned)k - 1ull) / (unsigned)k), qb, (const int*)c->fq.as<int>(),
-                                       (const int*)c->fsp.as<int>(), (const u32*)c->frow.as<u32>(), (const int*)c->fstrip.as<int>(), dsv, dsa, rows, dtile);
+                    hipLaunchKernelGGL(k_layout_from_fine, dim3(nblocks(n, LFF_T)), dim3(256), 0, c->stream, n, g, gf, k, (unsigned)(((1ull << 32) + (unsigned)k - 1ull) / (unsigned)k), qb, (const int*)c->fine.q.as<int>(),
+                                       (const int*)c->fine.sp.as<int>(), (const u32*)c->fine.row.as<u32>(), (const int*)c->fine.strip.as<int>(), dsv, dsa, rows, dtile);
                     HIP_TRY(hipGetLastError());
-                    c->srow = rows;
+                    c->run.srow = rows;
                     return CL_OK;
                 }
             }
             if ((rc = strip_sort(g, dsa, dsv, rows, dstrip, dtile))) return rc;
-            c->srow = rows;
+            c->run.srow = rows;
             return CL_OK;
         }
         LAUNCH(k_make_spkeys, n, n, g, (const u32*)c->qb_key.as<u32>(), (const u64*)c->qb_val.as<u64>(), k32_in, v64_in);
@@ -2900,7 +2900,7 @@ static int sort_layout(cl_chrom* c, const GridParams& g, int* dsv, int* dsa, u32
         LAUNCH(k_strip_table32, g.S + 2, (const u32*)k32_out, n, g.S, g.rbits, dstrip, (int*)nullptr);
         u32* rows = drow ? drow : k32_in;                 // the unsorted keys are dead after the sort
         LAUNCH(k_decode_sp, n, n, g, (const u32*)k32_out, (const u64*)v64_out, dsv, dsa, dtile, rows);
-        c->srow = rows;
+        c->run.srow = rows;
         return CL_OK;
     }
     ev_record(c, 0);
@@ -2916,54 +2916,53 @@ static int sort_layout(cl_chrom* c, const GridParams& g, int* dsv, int* dsa, u32
         u32* rows = drow ? drow : c->vals_in.as<u32>();  // the unsorted row ids are dead after the sort
         hipLaunchKernelGGL(k_strip_sort, dim3(nblocks(n, HS_TPB)), dim3(HS_TPB), 0, c->stream, n, g, c->keys_out.as<u64>(),
                            c->vals_out.as<u32>(), dstrip, dsv, dsa, rows, dtile, c->counters.as<int>());
-        c->srow = rows;
+        c->run.srow = rows;
     } else {
         LAUNCH(k_decode_sorted, n, n, g, c->keys_out.as<u64>(), dsv, dsa, dtile, c->vals_out.as<u32>(), drow);
-        c->srow = drow ? drow : c->vals_out.as<u32>();
+        c->run.srow = drow ? drow : c->vals_out.as<u32>();
     }
     return CL_OK;
 }
 
 // K0 + K1 + K2: sorted working set of the run (keys / sort, or a compaction of the base layout), then the neighbour
-// counts.  Leaves c->w_sv, w_sa, srow, w_strip, w_tile pointing at the sorted arrays of this run.
-static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact)
+// counts.  Leaves c->run.sv, sa, srow, strip, tile pointing at the sorted arrays of this run (a fresh c->run: run_begin).  level_cap:
+// the highest traversal level the run may take (cl_set_traversal, or 0 for the developer tile shapes).
+static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int level_cap)
 {
     const int n = (int)c->n;
     int rc;
     // M = PETs that pass the cut, from the distance histogram of the upload (exact for cut <= 65536)
-    c->run_m = n; c->run_m_exact = g.cut <= 0;
-    if (g.cut > 0 && g.cut < DCUM_BINS && !c->dcum.empty()) { c->run_m = (int)(n - c->dcum[g.cut]); c->run_m_exact = true; }
+    c->run.m = n; c->run.m_exact = g.cut <= 0;
+    if (g.cut > 0 && g.cut < DCUM_BINS && !c->dcum.empty()) { c->run.m = (int)(n - c->dcum[g.cut]); c->run.m_exact = true; }
     int* wsv = c->sv.as<int>() + SORT_PAD;
     int* wsa = c->sa.as<int>() + SORT_PAD;
-    c->w_cnt = c->cnt.as<int>();
-    c->last_k2_mode = 0; c->last_k2_mode_make = false;
+    c->run.cnt = c->cnt.as<int>();
+    c->last_k2_mode = 0;
     GridParams gk = g;                                    // what K2 sees: the minPts values its words serve, filled in below
     bool k2_band = false, k2_skip = false;
-    c->ws = WordSrc{c->cnt.as<int>(), nullptr, nullptr, nullptr, 0, g.rbits};
-    c->run_level = exact ? 0 : std::min(c->traversal, 3);
-    c->w_dM = nullptr; c->l4_cut = false; c->l4_band = false; c->l4_make_base = false;
+    c->run.ws = WordSrc{c->cnt.as<int>(), nullptr, nullptr, nullptr, 0, g.rbits};
+    c->run.level = exact ? 0 : std::min(level_cap, 3);
     c->slot[c->cur].band_timed = false; c->slot[c->cur].n_queried = 0;
     if (!c->reuse_layout) {
         // every run sorts for itself (the cut filter rides in the keys: filtered rows go behind the last strip)
         if ((rc = sort_layout(c, g, wsv, wsa, nullptr, c->strip.as<int>(), c->tile_s0.as<int>()))) return rc;
-        c->w_sv = wsv; c->w_sa = wsa; c->w_strip = c->strip.as<int>(); c->w_tile = c->tile_s0.as<int>();
+        c->run.sv = wsv; c->run.sa = wsa; c->run.strip = c->strip.as<int>(); c->run.tile = c->tile_s0.as<int>();
     } else {
         const int layout = (g.variant == CL_VARIANT_CDBSCAN2 ? 2 : 0) | (g.swap ? 1 : 0);
         if (!c->base.valid || c->base.layout != layout || c->base.eps != g.eps) {
-            c->base.valid = false;
-            if ((rc = c->bq.ensure(((size_t)n + 2 * SORT_PAD) * 4)) || (rc = c->bsp.ensure(((size_t)n + 2 * SORT_PAD) * 4)) ||
-                (rc = c->brow.ensure((size_t)n * 4)) || (rc = c->bstrip.ensure(((size_t)g.S + 2) * 4)) ||
-                (rc = c->btile.ensure(((size_t)n / 256 + 2) * 4))) return rc;
-            if (c->bq.fresh || c->bsp.fresh) {
-                hipLaunchKernelGGL(k_init_pads, dim3(nblocks(2 * SORT_PAD)), dim3(TPB), 0, c->stream, c->bq.as<int>(), c->bsp.as<int>(), (long long)n);
-                c->bq.fresh = c->bsp.fresh = false;
+            c->base.invalidate();                         // (with variant 2's cell minima)
+            c->rc.invalidate();                           // the cached words belong to the layout that is being replaced
+            if ((rc = c->base.q.ensure(((size_t)n + 2 * SORT_PAD) * 4)) || (rc = c->base.sp.ensure(((size_t)n + 2 * SORT_PAD) * 4)) ||
+                (rc = c->base.row.ensure((size_t)n * 4)) || (rc = c->base.strip.ensure(((size_t)g.S + 2) * 4)) ||
+                (rc = c->base.tile.ensure(((size_t)n / 256 + 2) * 4))) return rc;
+            if (c->base.q.fresh || c->base.sp.fresh) {
+                hipLaunchKernelGGL(k_init_pads, dim3(nblocks(2 * SORT_PAD)), dim3(TPB), 0, c->stream, c->base.q.as<int>(), c->base.sp.as<int>(), (long long)n);
+                c->base.q.fresh = c->base.sp.fresh = false;
             }
             GridParams g0 = g;
             g0.cut = 0;
-            c->rc.valid = false;                          // the cached words belong to the layout that is being replaced
-            c->bkey_valid = false;                        // ... and so do variant 2's cell minima
-            if ((rc = sort_layout(c, g0, c->bq.as<int>() + SORT_PAD, c->bsp.as<int>() + SORT_PAD, c->brow.as<u32>(),
-                                  c->bstrip.as<int>(), c->btile.as<int>()))) return rc;
+            if ((rc = sort_layout(c, g0, c->base.q.as<int>() + SORT_PAD, c->base.sp.as<int>() + SORT_PAD, c->base.row.as<u32>(),
+                                  c->base.strip.as<int>(), c->base.tile.as<int>()))) return rc;
             c->base.valid = true; c->base.layout = layout; c->base.eps = g.eps;
         } else {
             ev_record(c, 0);
@@ -2982,22 +2981,22 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact)
         enum { RC_NONE, RC_MAKE, RC_SAME, RC_REMAP } rcmode = RC_NONE;
         // traversal level 4 (lists from the base layout, count cache in base-position space) needs the cache: a run it does not take
         // (exact counts, minPts outside 2 .. 128, cache switched off) works on a copy of the layout as before
-        const bool want4 = c->traversal >= 4 && cacheable;
+        const bool want4 = level_cap >= 4 && cacheable;
         if (cacheable) {
             const bool serves = c->rc.valid && c->rc.layout == layout && c->rc.eps == g.eps && g.minPts <= c->rc.cap &&
                                 ((c->rc.tmask[m1 >> 5] >> (m1 & 31)) & 1u) && c->rc.base_space == want4;
             if (serves && thr_new == c->rc.thr && !(c->rc.cut_on_base && thr_new != 0)) rcmode = RC_SAME;
             else if (serves && !on_base && (long long)g.S <= 8LL * n) rcmode = RC_REMAP;      // (the band kernel works strip by strip)
             else rcmode = RC_MAKE;
-            if ((rc = c->rc_cnt.ensure((size_t)n * 4)) || (rc = c->rc_pre.ensure(((size_t)g.S + 2) * 4)) ||
-                (rc = c->rc_poff.ensure(((size_t)g.S + 2) * 4)) || (rc = c->rc_dpre.ensure(((size_t)g.S + 2) * 4)) ||
-                (rc = c->rc_D.ensure(((size_t)g.S + 2) * 4)) || (rc = c->rc_blen.ensure(((size_t)g.S + 2) * 8))) return rc;
+            if ((rc = c->rc.cnt.ensure((size_t)n * 4)) || (rc = c->rc.pre.ensure(((size_t)g.S + 2) * 4)) ||
+                (rc = c->rc.poff.ensure(((size_t)g.S + 2) * 4)) || (rc = c->rc.dpre.ensure(((size_t)g.S + 2) * 4)) ||
+                (rc = c->rc.D.ensure(((size_t)g.S + 2) * 4)) || (rc = c->rc.blen.ensure(((size_t)g.S + 2) * 8))) return rc;
         }
-        c->run_level = want4 ? 4 : std::min(c->traversal, 3);
-        if (exact) c->run_level = 0;
-        if (c->run_level == 4 && g.variant == CL_VARIANT_CDBSCAN2 && !c->bkey_valid) {
+        c->run.level = want4 ? 4 : std::min(level_cap, 3);
+        if (exact) c->run.level = 0;
+        if (c->run.level == 4 && g.variant == CL_VARIANT_CDBSCAN2 && !c->base.key_valid) {
             if ((rc = lists_base_keys(c, g))) return rc;
-            c->bkey_valid = true;
+            c->base.key_valid = true;
         }
         if (rcmode == RC_MAKE) {
             c->rc.valid = true; c->rc.layout = layout; c->rc.eps = g.eps; c->rc.thr = thr_new; c->rc.cap = g.minPts; c->rc.base_space = want4;
@@ -3014,14 +3013,14 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact)
             gk.tgap = 0;
             for (int t = 2, prev = 1; t <= g.minPts; ++t)
                 if ((c->rc.tmask[(t - 1) >> 5] >> ((t - 1) & 31)) & 1u) { gk.tgap = std::max(gk.tgap, t - prev); prev = t; }
-            c->w_cnt = c->rc_cnt.as<int>();
+            c->run.cnt = c->rc.cnt.as<int>();
             // (level 4 under a cut: K2 queries the compact copy into the work buffer, lists_words_to_base moves the words to their
             //  base positions in the cache)
-            if (want4 && !on_base) c->w_cnt = c->cnt.as<int>();
-            c->ws.rc = c->w_cnt;
+            if (want4 && !on_base) c->run.cnt = c->cnt.as<int>();
+            c->run.ws.rc = c->run.cnt;
             if (on_base) {
-                HIP_TRY(hipMemsetAsync(c->rc_pre.p, 0, ((size_t)g.S + 2) * 4, c->stream));
-                HIP_TRY(hipMemsetAsync(c->rc_poff.p, 0, ((size_t)g.S + 2) * 4, c->stream));
+                HIP_TRY(hipMemsetAsync(c->rc.pre.p, 0, ((size_t)g.S + 2) * 4, c->stream));
+                HIP_TRY(hipMemsetAsync(c->rc.poff.p, 0, ((size_t)g.S + 2) * 4, c->stream));
             }
             if (want4 && !on_base && (long long)g.S <= 8LL * n) {
                 // Level 4: the words of an eps are ALWAYS made on the base layout itself (threshold 0: every row), also when the first
@@ -3029,33 +3028,33 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact)
                 // cached ones beyond it).  One region query over all rows (213 us on chr1) instead of a copy of the layout, the
                 // query on the copy and the move of its words to base positions (54 + 146 + 77 us) -- and no copy of the layout is
                 // ever made (cLoops/pipe.py:59-63: the cut only removes a prefix of every strip).
-                HIP_TRY(hipMemsetAsync(c->rc_pre.p, 0, ((size_t)g.S + 2) * 4, c->stream));
-                HIP_TRY(hipMemsetAsync(c->rc_poff.p, 0, ((size_t)g.S + 2) * 4, c->stream));
-                c->l4_make_base = true;                      // (launched in the region-query bracket, below)
+                HIP_TRY(hipMemsetAsync(c->rc.pre.p, 0, ((size_t)g.S + 2) * 4, c->stream));
+                HIP_TRY(hipMemsetAsync(c->rc.poff.p, 0, ((size_t)g.S + 2) * 4, c->stream));
+                c->run.l4_make_base = true;                      // (launched in the region-query bracket, below)
                 // (the PETs this run's cut removes get no word: a later run under a smaller cut finds them in its cut band, which
                 //  reaches up to the larger of the two thresholds + eps)
                 c->rc.thr = thr_new;
                 c->rc.cut_on_base = true;
-                c->w_cnt = c->rc_cnt.as<int>();
+                c->run.cnt = c->rc.cnt.as<int>();
                 rcmode = RC_REMAP;
-                c->last_k2_mode_make = true;
+                c->run.k2_make = true;
             }
         }
         if (rcmode == RC_SAME) {
-            c->w_cnt = c->rc_cnt.as<int>();
-            c->ws.rc = c->w_cnt;
+            c->run.cnt = c->rc.cnt.as<int>();
+            c->run.ws.rc = c->run.cnt;
             k2_skip = true;
             c->last_k2_mode = 1;
         } else if (rcmode == RC_REMAP) {
             // the two cuts differ in the PETs with q in [min, max) of the thresholds: a PET keeps its count iff q - eps >= max
-            c->ws = WordSrc{c->rc_cnt.as<int>(), c->cnt.as<int>(), c->rc_D.as<int>(), c->rc_dpre.as<int>(), std::max(thr_new, c->rc.thr) + g.eps, g.rbits};
+            c->run.ws = WordSrc{c->rc.cnt.as<int>(), c->cnt.as<int>(), c->rc.D.as<int>(), c->rc.dpre.as<int>(), std::max(thr_new, c->rc.thr) + g.eps, g.rbits};
             k2_band = true;
-            c->last_k2_mode = c->last_k2_mode_make ? 0 : 2;
+            c->last_k2_mode = c->run.k2_make ? 0 : 2;
         }
         if (on_base) {
             // no row is filtered: the run works on the base layout itself
-            c->w_sv = c->bq.as<int>() + SORT_PAD; c->w_sa = c->bsp.as<int>() + SORT_PAD; c->srow = c->brow.as<u32>();
-            c->w_strip = c->bstrip.as<int>(); c->w_tile = c->btile.as<int>();
+            c->run.sv = c->base.q.as<int>() + SORT_PAD; c->run.sa = c->base.sp.as<int>() + SORT_PAD; c->run.srow = c->base.row.as<u32>();
+            c->run.strip = c->base.strip.as<int>(); c->run.tile = c->base.tile.as<int>();
         } else {
             if (!g.swap) return fail(CL_ERR_ARG, "internal: layout reuse needs the v-band layout");
             // stable compaction of the base layout by d = q + V0 >= cut (pipe.py:59-62): same order as sorting the
@@ -3069,65 +3068,65 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact)
             int* sboffs = bsum + nblk + 2;
             int* d_M = c->counters.as<int>() + CTR_M;
             const int thr = g.cut - g.V0;
-            const int* bq = c->bq.as<int>() + SORT_PAD;
-            const bool l4 = c->run_level == 4;
-            c->l4_cut = true; c->l4_band = rcmode == RC_REMAP;
+            const int* bq = c->base.q.as<int>() + SORT_PAD;
+            const bool l4 = c->run.level == 4;
+            c->run.l4_cut = true; c->run.l4_band = rcmode == RC_REMAP;
             if (l4 && ((rc = c->l_tab.ensure(((size_t)g.S + 2) * 16)) || (rc = c->l_fix.ensure(((size_t)g.S + 2) * 8)))) return rc;
-            LAUNCH(k_cut_strips, g.S + 1, g.S, thr, (const int*)c->bstrip.as<int>(), bq, sloc, bsum, sboffs, c->counters.as<int>() + CTR_TICKET_A, src0,
-                   rcmode == RC_MAKE ? c->rc_pre.as<int>() : (int*)nullptr,
-                   rcmode == RC_REMAP ? (const int*)c->rc_pre.as<int>() : (const int*)nullptr,
-                   rcmode == RC_REMAP ? c->rc_dpre.as<int>() : (int*)nullptr, rcmode == RC_REMAP ? c->rc_blen.as<int2>() : (int2*)nullptr,
-                   c->ws.bandq, g.eps, c->init_nclr > 0 ? c->flag.as<int>() : (int*)nullptr, c->init_nclr, c->counters.as<int>(),
-                   l4 ? c->l_tab.as<int4>() : (int4*)nullptr, (const u32*)c->brow.as<u32>(), g,
+            LAUNCH(k_cut_strips, g.S + 1, g.S, thr, (const int*)c->base.strip.as<int>(), bq, sloc, bsum, sboffs, c->counters.as<int>() + CTR_TICKET_A, src0,
+                   rcmode == RC_MAKE ? c->rc.pre.as<int>() : (int*)nullptr,
+                   rcmode == RC_REMAP ? (const int*)c->rc.pre.as<int>() : (const int*)nullptr,
+                   rcmode == RC_REMAP ? c->rc.dpre.as<int>() : (int*)nullptr, rcmode == RC_REMAP ? c->rc.blen.as<int2>() : (int2*)nullptr,
+                   c->run.ws.bandq, g.eps, c->run.init_nclr > 0 ? c->flag.as<int>() : (int*)nullptr, c->run.init_nclr, c->counters.as<int>(),
+                   l4 ? c->l_tab.as<int4>() : (int4*)nullptr, (const u32*)c->base.row.as<u32>(), g,
                    (l4 && g.variant == CL_VARIANT_CDBSCAN2) ? c->l_fix.as<int2>() : (int2*)nullptr);
-            c->init_nclr = 0;
+            c->run.init_nclr = 0;
             // (the kernel that opens a clustering run also clears its key bitmap and counters: init_nclr > 0)
             if (l4 && rcmode == RC_REMAP) {
                 // no copy of the layout: the band query alone (it reads the base layout and writes its words at the PETs' places in the
                 // run's -- virtual -- layout); the list kernels apply the cut by index
                 const int nbb = nblocks(nblocks(g.S, KB_SB), CMP_TPB / 64);
                 if (c->profiling) { (void)hipEventRecord(c->slot[c->cur].ev[8], c->stream); c->slot[c->cur].band_timed = true; }
-                hipLaunchKernelGGL(k_band, dim3(nbb), dim3(CMP_TPB), 0, c->stream, g.S, g.rbits, g.eps, g.minPts, bq, (const int*)(c->bsp.as<int>() + SORT_PAD),
-                                   (const int*)src0, (const int*)sloc, (const int*)sboffs, (const int2*)c->rc_blen.as<int2>(), c->cnt.as<int>(), d_M,
-                                   c->run_m_exact ? c->run_m : -1, c->counters.as<int>(), g.dbg);
+                hipLaunchKernelGGL(k_band, dim3(nbb), dim3(CMP_TPB), 0, c->stream, g.S, g.rbits, g.eps, g.minPts, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
+                                   (const int*)src0, (const int*)sloc, (const int*)sboffs, (const int2*)c->rc.blen.as<int2>(), c->cnt.as<int>(), d_M,
+                                   c->run.m_exact ? c->run.m : -1, c->counters.as<int>(), g.dbg);
                 if (c->profiling) (void)hipEventRecord(c->slot[c->cur].ev[9], c->stream);
-                c->w_dM = d_M;
+                c->run.dM = d_M;
             } else if (l4 && rcmode == RC_SAME) {
-                hipLaunchKernelGGL(k_store_m, dim3(1), dim3(1), 0, c->stream, g.S, (const int*)sloc, (const int*)sboffs, d_M, c->run_m_exact ? c->run_m : -1, c->counters.as<int>());
-                c->w_dM = d_M;
+                hipLaunchKernelGGL(k_store_m, dim3(1), dim3(1), 0, c->stream, g.S, (const int*)sloc, (const int*)sboffs, d_M, c->run.m_exact ? c->run.m : -1, c->counters.as<int>());
+                c->run.dM = d_M;
             } else
             if (rcmode == RC_REMAP) {
                 const int nbb = nblocks(nblocks(g.S, KB_SB), CMP_TPB / 64);      // workgroups that do K2 on the cut band (four waves of KB_SB strips each)
-                hipLaunchKernelGGL(k_cut_copy<true>, dim3(nbb + nb), dim3(CMP_TPB), 0, c->stream, n, g.S, g.rbits, thr, bq, (const int*)(c->bsp.as<int>() + SORT_PAD),
-                                   (const u32*)c->brow.as<u32>(), (const int*)src0, (const int*)sloc, (const int*)sboffs, c->strip.as<int>(), wsv, wsa, c->vals_out.as<u32>(), c->tile_s0.as<int>(),
-                                   d_M, c->run_m_exact ? c->run_m : -1, c->counters.as<int>(), (int*)nullptr, (const int*)c->rc_poff.as<int>(), c->rc_D.as<int>(),
-                                   nbb, (const int2*)c->rc_blen.as<int2>(), c->cnt.as<int>(), g.eps, g.minPts, g.dbg);
+                hipLaunchKernelGGL(k_cut_copy<true>, dim3(nbb + nb), dim3(CMP_TPB), 0, c->stream, n, g.S, g.rbits, thr, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
+                                   (const u32*)c->base.row.as<u32>(), (const int*)src0, (const int*)sloc, (const int*)sboffs, c->strip.as<int>(), wsv, wsa, c->vals_out.as<u32>(), c->tile_s0.as<int>(),
+                                   d_M, c->run.m_exact ? c->run.m : -1, c->counters.as<int>(), (int*)nullptr, (const int*)c->rc.poff.as<int>(), c->rc.D.as<int>(),
+                                   nbb, (const int2*)c->rc.blen.as<int2>(), c->cnt.as<int>(), g.eps, g.minPts, g.dbg);
             } else
-            hipLaunchKernelGGL(k_cut_copy<false>, dim3(nb), dim3(CMP_TPB), 0, c->stream, n, g.S, g.rbits, thr, bq, (const int*)(c->bsp.as<int>() + SORT_PAD),
-                               (const u32*)c->brow.as<u32>(), (const int*)src0, (const int*)sloc, (const int*)sboffs, c->strip.as<int>(), wsv, wsa, c->vals_out.as<u32>(), c->tile_s0.as<int>(),
-                               d_M, c->run_m_exact ? c->run_m : -1, c->counters.as<int>(), rcmode == RC_MAKE ? c->rc_poff.as<int>() : (int*)nullptr,
+            hipLaunchKernelGGL(k_cut_copy<false>, dim3(nb), dim3(CMP_TPB), 0, c->stream, n, g.S, g.rbits, thr, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
+                               (const u32*)c->base.row.as<u32>(), (const int*)src0, (const int*)sloc, (const int*)sboffs, c->strip.as<int>(), wsv, wsa, c->vals_out.as<u32>(), c->tile_s0.as<int>(),
+                               d_M, c->run.m_exact ? c->run.m : -1, c->counters.as<int>(), rcmode == RC_MAKE ? c->rc.poff.as<int>() : (int*)nullptr,
                                (const int*)nullptr, (int*)nullptr, 0, (const int2*)nullptr, (int*)nullptr, 0, 0, 0);
-            c->w_sv = wsv; c->w_sa = wsa; c->srow = c->vals_out.as<u32>();
-            c->w_strip = c->strip.as<int>(); c->w_tile = c->tile_s0.as<int>();
-            if (!c->w_dM) c->w_dM = d_M;
+            c->run.sv = wsv; c->run.sa = wsa; c->run.srow = c->vals_out.as<u32>();
+            c->run.strip = c->strip.as<int>(); c->run.tile = c->tile_s0.as<int>();
+            if (!c->run.dM) c->run.dM = d_M;
         }
     }
     ev_record(c, 2);
     rc = CL_OK;
-    if (c->l4_make_base) {
+    if (c->run.l4_make_base) {
         // level 4: the words of the eps, on the base layout itself (every row), whatever this run's cut is
         GridParams g0 = gk;
         g0.cut = 0;
         g0.qmin = c->rc.thr;
-        rc = cl_launch_region(c->stream, g0, n, n, false, c->bq.as<int>() + SORT_PAD, c->bsp.as<int>() + SORT_PAD, c->bstrip.as<int>(), c->btile.as<int>(),
-                              c->rc_cnt.as<int>());
-        c->slot[c->cur].n_queried = c->run_m;             // (the PETs that got a word: those the cut keeps)
+        rc = cl_launch_region(c->stream, g0, n, n, false, c->base.q.as<int>() + SORT_PAD, c->base.sp.as<int>() + SORT_PAD, c->base.strip.as<int>(), c->base.tile.as<int>(),
+                              c->rc.cnt.as<int>());
+        c->slot[c->cur].n_queried = c->run.m;             // (the PETs that got a word: those the cut keeps)
     } else if (!k2_skip && !k2_band && !SKIP(256)) {
-        rc = cl_launch_region(c->stream, gk, n, c->run_m, exact, c->w_sv, c->w_sa, c->w_strip, c->w_tile, c->w_cnt);
-        c->slot[c->cur].n_queried = c->run_m;
+        rc = cl_launch_region(c->stream, gk, n, c->run.m, exact, c->run.sv, c->run.sa, c->run.strip, c->run.tile, c->run.cnt);
+        c->slot[c->cur].n_queried = c->run.m;
     }
     if (rc) return rc;
-    if (c->run_level == 4 && c->l4_cut && !k2_skip && !k2_band && (rc = lists_words_to_base(c, g))) return rc;
+    if (c->run.level == 4 && c->run.l4_cut && !k2_skip && !k2_band && (rc = lists_words_to_base(c, g))) return rc;
     ev_record(c, 3);
     HIP_TRY(hipGetLastError());
     return CL_OK;
@@ -3175,13 +3174,14 @@ extern "C" int cl_neighbor_counts(cl_chrom* c, int32_t eps, int32_t cut, int32_t
     if (!counts_out) return fail(CL_ERR_ARG, "counts_out is null");
     HIP_TRY(hipSetDevice(c->device));
     GridParams g;
+    run_begin(c);
     if ((rc = make_grid(c, CL_VARIANT_CDBSCAN1, eps, 1, cut, &g))) return rc;
     if ((rc = ensure_workspace(c, g.S))) return rc;
     if ((rc = ensure_events(c))) return rc;
-    if ((rc = run_sort_and_count(c, g, true))) return rc;
+    if ((rc = run_sort_and_count(c, g, true, c->traversal))) return rc;
     const int n = (int)c->n;
     HIP_TRY(hipMemsetAsync(c->slot[c->cur].labels.p, 0xFF, (size_t)n * 4, c->stream));
-    LAUNCH(k_scatter_counts, n, c->w_strip, g.S, c->srow, c->cnt.as<int>(), c->slot[c->cur].labels.as<int>());
+    LAUNCH(k_scatter_counts, n, c->run.strip, g.S, c->run.srow, c->cnt.as<int>(), c->slot[c->cur].labels.as<int>());
     HIP_TRY(hipMemcpyAsync(counts_out, c->slot[c->cur].labels.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->profiling) {
@@ -3253,38 +3253,38 @@ const int* k7_hist_for(cl_chrom* c, int cut)
     return (cut > 0 && cut < DCUM_BINS && c->n_neg == 0 && !c->dcum.empty() && c->dhist.p) ? c->dhist.as<int>() : (const int*)nullptr;
 }
 
-int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_out)
+int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* d_M)
 {
     const int n = (int)c->n;
+    int32_t* const labels_out = req.labels_out;
     cl_chrom::Slot& sl = c->slot[c->cur];
     int* dh = c->hdr.as<int>() + 16 * c->cur;
     // the pinned host rows of the cluster table: only a run that exports its table needs them (a sweep step does not, and
     // page-locking (n / 16 + 65 536) rows per result slot was most of the first sweep's overhead: 1 .. 10 ms per handle and slot)
-    if (sl.h_boxes_cap == 0 && c->export_table && c->pending_step < 0) {
+    if (sl.h_boxes_cap == 0 && c->export_table && req.step < 0) {
         const size_t cap = (size_t)n / 16 + 65536;
         HIP_TRY(hipHostMalloc((void**)&sl.h_boxes, cap * sizeof(cl_box), hipHostMallocDefault));
         sl.h_boxes_cap = cap;
     }
-    if (!c->hdr_packed)
-        hipLaunchKernelGGL(k_pack_header, dim3(1), dim3(64), 0, c->stream, dh, c->k_total ? c->k_total : c->rankscan.as<int>() + n, c->counters.as<int>(), d_M);
-    c->k_total = nullptr; c->hdr_packed = false;
+    if (!c->run.hdr_packed)
+        hipLaunchKernelGGL(k_pack_header, dim3(1), dim3(64), 0, c->stream, dh, c->run.k_total ? c->run.k_total : c->rankscan.as<int>() + n, c->counters.as<int>(), d_M);
     // (without export the kernel still counts the non-empty ids for the header; cap 0 = no row is stored)
     // (a sweep step reads neither the rows nor n_clusters / max_label: its header keeps the values of k_pack_header)
-    const bool exported = c->export_table && c->pending_step < 0;
-    if (c->pending_step < 0)
+    const bool exported = c->export_table && req.step < 0;
+    if (req.step < 0)
         hipLaunchKernelGGL(k_export_table, dim3(256), dim3(TPB), 0, c->stream, dh, make_table(c), sl.h_boxes,
                            exported ? (int)std::min<size_t>(sl.h_boxes_cap, 0x7fffffff) : -1);
     sl.exported = exported;
     sl.step_valid = false;
     sl.host_written = false;
-    if (c->pending_step >= 0) {
+    if (req.step >= 0) {
         // sweep-step tail, still inside the run's stream: classify the table (pipe.py:83-97), append the inter-ligation
         // boxes to the chromosome's candidate buffer, reduce the distance statistics -- the host gets everything with
         // the run's own completion (one wait per chromosome and step)
         int rc;
         if ((rc = c->k7_cls.ensure((size_t)n + 16))) return rc;
         const int kmax = std::max(1, std::min(sl.kmax, n));     // the number of ids K is only known on the device: K <= kmax
-        if ((rc = ensure_cand_capacity(c, c->cand_n + kmax))) return rc;
+        if ((rc = ensure_cand_capacity(c, c->cand.n + kmax))) return rc;
         // step output (device and pinned host): 16 B box totals | the reduced statistics (one K7Part) | log histogram | fine window;
         // the workgroup partials live behind it on the device only
         const size_t out_bytes = 16 + sizeof(K7Part) + K7_LOGBINS * 8 + K7_FINE * 8;
@@ -3300,12 +3300,12 @@ int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_ou
                            lh, K7_LOGBINS + K7_FINE);                                       // + log histogram and the fine window behind it cleared
         // (no scan over the nb block counts: every append block sums the few counts in front of it itself)
         hipLaunchKernelGGL(k_cand_append, dim3(nb), dim3(256), 0, c->stream, (const int*)dh, cls, t, (const int*)nullptr, (const int*)bcount,
-                           (int)c->cand_n, c->pending_step, (int)std::min<long long>(c->cand_cap, INT_MAX), c->cand_box.as<int4>(), c->cand_step.as<int>());
+                           (int)c->cand.n, req.step, (int)std::min<long long>(c->cand.cap, INT_MAX), c->cand.box.as<int4>(), c->cand.step.as<int>());
         K7Part* parts = (K7Part*)(ds + out_bytes);
         K7Src src{};
         src.sorted = sl.sorted_src ? (sl.k7_lcnt ? 2 : 1) : 0; src.n = n; src.M = 0; src.v0 = sl.k7_v0; src.dM = sl.k7_lcnt ? sl.k7_lcnt : d_M;
         src.X = c->d_x; src.Y = c->d_y; src.labels = sl.labels.as<int>(); src.sv = sl.k7_sv; src.slab = sl.slab.as<int>();
-        src.dh = k7_hist_for(c, c->pending_cut);
+        src.dh = k7_hist_for(c, req.cut);
         int k7b = K7_STEP_BLOCKS;
 #ifdef CLOOPS_DEVEL
         int k7t = K7_STEP_THREADS;
@@ -3313,8 +3313,8 @@ int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_ou
 #else
         const int k7t = K7_STEP_THREADS;
 #endif
-        if (!SKIP(16)) hipLaunchKernelGGL(k7_summary, dim3(k7b), dim3(k7t), 0, c->stream, src, c->pending_cut, cls, parts, lh,
-                           (unsigned)c->pending_fine_lo, c->pending_fine_lo >= 0 ? lh + K7_LOGBINS : (unsigned long long*)nullptr);
+        if (!SKIP(16)) hipLaunchKernelGGL(k7_summary, dim3(k7b), dim3(k7t), 0, c->stream, src, req.cut, cls, parts, lh,
+                           (unsigned)req.fine_lo, req.fine_lo >= 0 ? lh + K7_LOGBINS : (unsigned long long*)nullptr);
         static_assert((16 + sizeof(K7Part)) % 8 == 0, "step output in 8-byte words");
         hipLaunchKernelGGL(k7_reduce_parts, dim3(1), dim3(256), 0, c->stream, (const K7Part*)parts, k7b, (K7Part*)(ds + 16),
                            (const int*)bcount, nb, (long long*)ds, (const unsigned long long*)ds, (int)(out_bytes / 8),
@@ -3330,7 +3330,7 @@ int finish_enqueue(cl_chrom* c, int n_strips, const int* d_M, int32_t* labels_ou
         }
 #endif
         sl.host_written = labels_out == nullptr;        // nothing left for the copy stream
-        sl.fine_lo = c->pending_fine_lo;
+        sl.fine_lo = req.fine_lo;
         sl.step_valid = true;
     }
     HIP_TRY(hipGetLastError());
@@ -3456,8 +3456,8 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
     c->k7_classified = sl.step_valid;                    // the step tail has classified this run's table already
     if (sl.step_valid) {
         const long long ni = ((const long long*)sl.h_step)[0];
-        if (c->cand_n + ni > c->cand_cap) return fail(CL_ERR_GRID, "internal: candidate buffer overrun");
-        c->cand_n += ni;
+        if (c->cand.n + ni > c->cand.cap) return fail(CL_ERR_GRID, "internal: candidate buffer overrun");
+        c->cand.n += ni;
     }
     if (c->profiling) {
         cl_timing& tm = c->timing;
@@ -3482,10 +3482,27 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
 }
 
 
-static int run_rotated(cl_chrom* c, int variant, int eps, int minPts, int cut, int32_t* labels_out);
+static int run_rotated(cl_chrom* c, const RunRequest& req);
 
-
-
+// Every public form of a run ends here with the request it has built: the checks of an asynchronous run, then the run function of
+// the request's kind.  Nothing of the request stays in the handle.
+static int enqueue(cl_chrom* c, const RunRequest& req)
+{
+    int rc = check_args(c, req.eps, req.minPts, req.cut);
+    if (rc) return rc;
+    if (req.variant != CL_VARIANT_CDBSCAN1 && req.variant != CL_VARIANT_CDBSCAN2 && req.variant != CL_VARIANT_BLOCK)
+        return fail(CL_ERR_ARG, "unknown variant");
+    if (c->enq - c->deq >= 2) return fail(CL_ERR_ARG, "cl_cluster_async: two runs already in flight, call cl_wait first");
+    if (c->n == 0) {
+        // cDBSCAN.py:77 / blockDBSCAN.py:74: mat[0] on an empty mat raises; cDBSCAN2 returns {}
+        if (req.variant != CL_VARIANT_CDBSCAN2 && req.cut <= 0) return fail(CL_ERR_EMPTY, "empty input (reference raises IndexError)");
+        return fail(CL_ERR_ARG, "cl_cluster_async: empty chromosome (use cl_cluster)");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (req.wx > 0) return run_weighted(c, req);
+    if (req.variant == CL_VARIANT_BLOCK) return run_block(c, req);
+    return run_rotated(c, req);
+}
 
 extern "C" int cl_cluster_weighted(cl_chrom* c, int32_t eps, int32_t min_pts, int32_t wx, int32_t wy, int32_t* labels_out,
                                    int32_t* n_clusters, int32_t* max_label)
@@ -3498,25 +3515,17 @@ extern "C" int cl_cluster_weighted(cl_chrom* c, int32_t eps, int32_t min_pts, in
     HIP_TRY(hipSetDevice(c->device));
     c->have_result = false;
     c->last_K = 0;
-    if ((rc = run_weighted(c, eps, min_pts, wx, wy, labels_out))) return rc;
+    RunRequest req;
+    req.eps = eps; req.minPts = min_pts; req.wx = wx; req.wy = wy; req.labels_out = labels_out;
+    if ((rc = enqueue(c, req))) return rc;
     return finish_wait(c, n_clusters, max_label);
 }
 
 extern "C" int cl_cluster_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, int32_t* labels_out)
 {
-    int rc = check_args(c, eps, min_pts, cut);
-    if (rc) return rc;
-    if (variant != CL_VARIANT_CDBSCAN1 && variant != CL_VARIANT_CDBSCAN2 && variant != CL_VARIANT_BLOCK)
-        return fail(CL_ERR_ARG, "unknown variant");
-    if (c->enq - c->deq >= 2) return fail(CL_ERR_ARG, "cl_cluster_async: two runs already in flight, call cl_wait first");
-    if (c->n == 0) {
-        // cDBSCAN.py:77 / blockDBSCAN.py:74: mat[0] on an empty mat raises; cDBSCAN2 returns {}
-        if (variant != CL_VARIANT_CDBSCAN2 && cut <= 0) return fail(CL_ERR_EMPTY, "empty input (reference raises IndexError)");
-        return fail(CL_ERR_ARG, "cl_cluster_async: empty chromosome (use cl_cluster)");
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    if (variant == CL_VARIANT_BLOCK) return run_block(c, eps, min_pts, cut, labels_out);
-    return run_rotated(c, variant, eps, min_pts, cut, labels_out);
+    RunRequest req;
+    req.variant = variant; req.eps = eps; req.minPts = min_pts; req.cut = cut; req.labels_out = labels_out;
+    return enqueue(c, req);
 }
 
 extern "C" int cl_cluster_pairs_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, int32_t* pinned_pairs_out, int64_t capacity_pairs)
@@ -3525,11 +3534,10 @@ extern "C" int cl_cluster_pairs_async(cl_chrom* c, int variant, int32_t eps, int
     if (!pinned_pairs_out || capacity_pairs <= 0) return fail(CL_ERR_ARG, "cl_cluster_pairs_async: no pair buffer");
     if (variant != CL_VARIANT_CDBSCAN1 && variant != CL_VARIANT_CDBSCAN2) return fail(CL_ERR_ARG, "cl_cluster_pairs_async: rotated variants only");
     if (c->traversal < 3 || min_pts < 2 || min_pts > 128) return fail(CL_ERR_ARG, "cl_cluster_pairs_async: needs the list form of the run (traversal level >= 3, minPts 2 .. 128)");
-    c->pairs_out = (int2*)pinned_pairs_out;
-    c->pairs_cap = capacity_pairs;
-    const int rc = cl_cluster_async(c, variant, eps, min_pts, cut, nullptr);
-    c->pairs_out = nullptr; c->pairs_cap = 0;
-    return rc;
+    RunRequest req;
+    req.variant = variant; req.eps = eps; req.minPts = min_pts; req.cut = cut;
+    req.pairs_out = (int2*)pinned_pairs_out; req.pairs_cap = capacity_pairs;
+    return enqueue(c, req);
 }
 extern "C" int cl_cluster_rowmask_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, void* pinned_out, int64_t capacity_labels)
 {
@@ -3537,11 +3545,10 @@ extern "C" int cl_cluster_rowmask_async(cl_chrom* c, int variant, int32_t eps, i
     if (!pinned_out || capacity_labels <= 0) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: no output buffer");
     if (variant != CL_VARIANT_CDBSCAN1 && variant != CL_VARIANT_CDBSCAN2) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: rotated variants only");
     if (c->traversal < 3 || min_pts < 2 || min_pts > 128) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: needs the list form of the run (traversal level >= 3, minPts 2 .. 128)");
-    c->mask_out = pinned_out;
-    c->mask_cap = capacity_labels;
-    const int rc = cl_cluster_async(c, variant, eps, min_pts, cut, nullptr);
-    c->mask_out = nullptr; c->mask_cap = 0;
-    return rc;
+    RunRequest req;
+    req.variant = variant; req.eps = eps; req.minPts = min_pts; req.cut = cut;
+    req.mask_out = pinned_out; req.mask_cap = capacity_labels;
+    return enqueue(c, req);
 }
 extern "C" void cl_set_pairs_defer(cl_chrom* c, int enabled) { if (c) c->pairs_defer = enabled != 0; }
 extern "C" int cl_pairs_sync(cl_chrom* c)
@@ -3567,12 +3574,10 @@ extern "C" int cl_cluster_step_async(cl_chrom* c, int variant, int32_t eps, int3
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
     if (step < 0) return fail(CL_ERR_ARG, "cl_cluster_step_async: step must be >= 0");
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cluster_step_async: one sweep step in flight per chromosome");
-    c->pending_step = step;
-    c->pending_cut = cut;
-    c->pending_fine_lo = (fine_lo >= 0 && fine_lo < (1LL << 31)) ? fine_lo : -1;
-    const int rc = cl_cluster_async(c, variant, eps, min_pts, cut, nullptr);
-    c->pending_step = -1;
-    return rc;
+    RunRequest req;
+    req.variant = variant; req.eps = eps; req.minPts = min_pts; req.cut = cut;
+    req.step = step; req.fine_lo = (fine_lo >= 0 && fine_lo < (1LL << 31)) ? fine_lo : -1;
+    return enqueue(c, req);
 }
 
 extern "C" int cl_step_result(cl_chrom* c, int64_t* n_inter, int64_t* n_self, cl_dsummary* out)
@@ -3620,32 +3625,19 @@ extern "C" int cl_cluster(cl_chrom* c, int variant, int32_t eps, int32_t min_pts
     }
     c->have_result = false;
     c->last_K = 0;
-    rc = cl_cluster_async(c, variant, eps, min_pts, cut, labels_out);
-    if (rc) return rc;
+    RunRequest req;
+    req.variant = variant; req.eps = eps; req.minPts = min_pts; req.cut = cut; req.labels_out = labels_out;
+    if ((rc = enqueue(c, req))) return rc;
     return finish_wait(c, n_clusters, max_label);
 }
 
-// A run that fails half-way (allocation, a HIP error between two launches) must not leave state behind that a later run would
-// trust: the count cache it may have marked valid before its words were written, the tickets of the in-kernel scans and the
-// superblock sums of the list kernels (all "zero between kernels").
-struct RunGuard {
-    cl_chrom* c; bool armed = true;
-    explicit RunGuard(cl_chrom* cc) : c(cc) {}
-    ~RunGuard()
-    {
-        if (!armed) return;
-        c->rc.valid = false;
-        c->l_sup_dirty = true;
-        if (c->counters.p) (void)hipMemsetAsync(c->counters.as<int>() + CTR_TICKET_A, 0, 8, c->stream);
-        (void)hipGetLastError();
-    }
-};
-
-static int run_rotated(cl_chrom* c, int variant, int eps, int minPts, int cut, int32_t* labels_out)
+static int run_rotated(cl_chrom* c, const RunRequest& req)
 {
     int rc;
     GridParams g;
+    run_begin(c);
     RunGuard guard(c);
+    const int variant = req.variant, minPts = req.minPts, cut = req.cut;
 #ifdef CLOOPS_DEVEL
     // developer build: host time of the enqueue, by section (CLOOPS_TRACE_ENQ=<ms> prints the calls above that)
     static const double trace_ms = getenv("CLOOPS_TRACE_ENQ") ? atof(getenv("CLOOPS_TRACE_ENQ")) : -1.0;
@@ -3659,7 +3651,7 @@ static int run_rotated(cl_chrom* c, int variant, int eps, int minPts, int cut, i
 #else
 #define ENQ_MARK() do { } while (0)
 #endif
-    if ((rc = make_grid(c, variant, eps, minPts, cut, &g))) return rc;
+    if ((rc = make_grid(c, variant, req.eps, minPts, cut, &g))) return rc;
     if ((rc = ensure_workspace(c, g.S))) return rc;
     if ((rc = ensure_events(c))) return rc;
     ENQ_MARK();
@@ -3686,41 +3678,37 @@ static int run_rotated(cl_chrom* c, int variant, int eps, int minPts, int cut, i
     const int nw = (n + 31) / 32;                       // words of the key bitmap (K5); one more word takes the scan's total
     // the bitmap and the counters are cleared by the first kernel of the cut compaction (k_cut_strips); a run without one clears
     // them in a launch of its own
-    c->init_nclr = nw + 1;
+    c->run.init_nclr = nw + 1;
     // row-aligned labels only when somebody reads them: k_final_labels then writes the label (or -1) of every PET that
     // entered DBSCAN and only the rows removed by the cut filter need the -1 fill
-    const bool rows = labels_out != nullptr || c->device_labels || c->pairs_out != nullptr || c->mask_out != nullptr;
+    const bool rows = req.labels_out != nullptr || c->device_labels || req.pairs_out != nullptr || req.mask_out != nullptr;
     // how far the run works on lists (k_lists.hip; cl_set_traversal): 0 = tile kernels over every PET, 1 = K3 on the core list,
     // 2 = + the border rule on the walker list, 3 = + labels / table / distance list from the lists (only labelled PETs are
     // written: the row-aligned array is filled with -1 first)
-    if (rows && !c->pairs_out && (cut > 0 || (wide == 0 && c->traversal >= 3))) HIP_TRY(hipMemsetAsync(c->slot[c->cur].labels.p, 0xFF, (size_t)n * 4, c->stream));
-    c->run_rows = rows;
-    const int trav_saved = c->traversal;
-    if (wide != 0) c->traversal = 0;                    // (developer tile shapes: the tile kernels)
-    rc = run_sort_and_count(c, g, false);
-    c->traversal = trav_saved;
-    if (rc) return rc;
-    const int level = c->run_level;
+    if (rows && !req.pairs_out && (cut > 0 || (wide == 0 && c->traversal >= 3))) HIP_TRY(hipMemsetAsync(c->slot[c->cur].labels.p, 0xFF, (size_t)n * 4, c->stream));
+    c->run.rows = rows;
+    if ((rc = run_sort_and_count(c, g, false, wide != 0 ? 0 /* developer tile shapes: the tile kernels */ : c->traversal))) return rc;
+    const int level = c->run.level;
     // (a level-3 default that fell to the tile kernels for this run -- exact counts are not a clustering run -- cannot happen here)
-    if (c->init_nclr > 0) { LAUNCH(k_init_flags, nw + 1, nw, c->flag.as<int>(), counters); c->init_nclr = 0; }
-    const WordSrc ws = c->ws;                           // where the K2 words of this run live (the handle's count cache / the work buffer)
+    if (c->run.init_nclr > 0) { LAUNCH(k_init_flags, nw + 1, nw, c->flag.as<int>(), counters); c->run.init_nclr = 0; }
+    const WordSrc ws = c->run.ws;                           // where the K2 words of this run live (the handle's count cache / the work buffer)
     if ((rc = c->rootlist.ensure((size_t)n * 4)) || (rc = c->cflag8.ensure((size_t)n + 16))) return rc;
     unsigned char* cflag = c->cflag8.as<unsigned char>();
     ENQ_MARK();
     {
         cl_chrom::Slot& sl = c->slot[c->cur];
-        sl.rows_valid = rows && !c->pairs_out; sl.sorted_src = g.swap != 0; sl.k7_sv = c->w_sv; sl.k7_v0 = g.V0; sl.k7_lcnt = nullptr;
+        sl.rows_valid = rows && !req.pairs_out; sl.sorted_src = g.swap != 0; sl.k7_sv = c->run.sv; sl.k7_v0 = g.V0; sl.k7_lcnt = nullptr;
         // variant 2 hands an id only to a live cluster, which has >= minPts members (cDBSCAN2.py:180-185): K <= n / minPts;
         // variant 1 numbers every component, dropped ones included (cDBSCAN.py:136-152): K <= n
         sl.kmax = (variant == CL_VARIANT_CDBSCAN2 && minPts >= 1) ? n / minPts + 1 : n;
     }
-    int* strip = c->w_strip;
-    int* sv = c->w_sv;
-    int* sa = c->w_sa;
-    const u32* srow = c->srow;
+    int* strip = c->run.strip;
+    int* sv = c->run.sv;
+    int* sa = c->run.sa;
+    const u32* srow = c->run.srow;
     // everything behind the sort works on the nm = M PETs that passed the cut (known on the host from the upload's distance
     // histogram; nm = n when it is not): grids, tiles and scans are sized by it
-    const int nm = std::max(1, c->run_m);
+    const int nm = std::max(1, c->run.m);
     ntiles = nblocks(nm, tile_nt);
     tgrid = tile_grid(ntiles);
 
@@ -3770,7 +3758,7 @@ static int run_rotated(cl_chrom* c, int variant, int eps, int minPts, int cut, i
     if (level >= 2) { if ((rc = lists_border(c, g, nm, L))) return rc; }
     else if (wide == 0) {
         // 1024 PETs per workgroup of 256 threads (4 per thread in the first pass, the walkers of the whole tile in one list)
-        const int nt_b = nblocks(std::max(1, c->run_m), 1024);
+        const int nt_b = nblocks(std::max(1, c->run.m), 1024);
         if (!SKIP(1)) hipLaunchKernelGGL((k_border<1024, 128, TPB>), dim3(tile_grid(nt_b)), dim3(TPB), 0, c->stream, g, nt_b, sv, sa, strip, c->root.as<int>(),
                            c->compkey.as<int>(), c->ncore.as<int>(), srow, c->owner.as<int>(), c->bsize.as<int>(), c->usize.as<int>(), ws, clist, counters);
     } else
@@ -3798,33 +3786,33 @@ static int run_rotated(cl_chrom* c, int variant, int eps, int minPts, int cut, i
     int* wboff = wbsum + nblkw + 1;
     hipLaunchKernelGGL(k_rank_scan, dim3(nblkw), dim3(256), 0, c->stream, nw, (const unsigned*)c->flag.as<unsigned>(), c->rankscan.as<int>(), wbsum, wboff,
                        counters + CTR_TICKET_B);
-    c->k_total = wboff + nblkw;
+    c->run.k_total = wboff + nblkw;
     Table t = make_table(c);
     // rlabel reuses the chainhead buffer (free after k_chain_parent); the kernel also resets the table rows of the ids handed out
     hipLaunchKernelGGL(k_root_labels_bits_l, dim3(512), dim3(TPB), 0, c->stream, g, rootlist, counters, c->compkey.as<int>(), c->ncore.as<int>(), c->bsize.as<int>(),
                        c->state.as<int>(), c->flag.as<unsigned>(), (const int*)c->rankscan.as<int>(), (const int*)wboff, c->chainhead.as<int>(), t, nblkw,
-                       c->hdr.as<int>() + 16 * c->cur, c->w_dM ? c->w_dM : (const int*)(strip + g.S));
-    c->hdr_packed = true;
+                       c->hdr.as<int>() + 16 * c->cur, c->run.dM ? c->run.dM : (const int*)(strip + g.S));
+    c->run.hdr_packed = true;
     if (level >= 3) {
-        c->slot[c->cur].pairs_host = c->pairs_out;
-        c->slot[c->cur].pairs_host_cap = c->pairs_cap;
-        if (c->pairs_out && (rc = c->slot[c->cur].pairs.ensure((size_t)std::max<long long>(c->pairs_cap, 1) * 8))) return rc;
-        if ((rc = lists_final(c, g, nm, L, rows, c->hdr.as<int>() + 16 * c->cur + 6))) return rc;
+        c->slot[c->cur].pairs_host = req.pairs_out;
+        c->slot[c->cur].pairs_host_cap = req.pairs_cap;
+        if (req.pairs_out && (rc = c->slot[c->cur].pairs.ensure((size_t)std::max<long long>(req.pairs_cap, 1) * 8))) return rc;
+        if ((rc = lists_final(c, req, g, nm, L, rows, c->hdr.as<int>() + 16 * c->cur + 6))) return rc;
         cl_chrom::Slot& sl = c->slot[c->cur];
-        sl.mask_host = c->mask_out; sl.mask_host_cap = c->mask_cap;
+        sl.mask_host = req.mask_out; sl.mask_host_cap = req.mask_cap;
         // (cl_cluster_rowmask_async: the row-aligned labels the kernel above has just written -> mask words + labels in row order,
         //  their number in header word 6 like the pairs')
-        if (c->mask_out && (rc = lists_rowmask(c, c->hdr.as<int>() + 16 * c->cur + 6))) return rc;
+        if (req.mask_out && (rc = lists_rowmask(c, req, c->hdr.as<int>() + 16 * c->cur + 6))) return rc;
         sl.k7_lcnt = L.lcnt; sl.k7_sv = c->l_dist.as<int>();      // the distance statistics read the run's lists (K7Src::sorted == 2)
     } else {
-        if (c->mask_out) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: this run did not take the list form");
+        if (req.mask_out) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: this run did not take the list form");
         if (level == 2 && (rc = lists_scatter_owner(c, nm, L))) return rc;
         if (!SKIP(8)) hipLaunchKernelGGL(k_final_labels, dim3(nblocks(nm, BIGTPB * FINAL_CHUNKS)), dim3(BIGTPB), 0, c->stream, g, strip, sv, sa, srow,
                        level == 2 ? c->l_aux.as<int>() : c->owner.as<int>(),
                        c->chainhead.as<int>(), rows ? c->slot[c->cur].labels.as<int>() : (int*)nullptr, c->slot[c->cur].slab.as<int>(), t);
     }
     HIP_TRY(hipGetLastError());
-    rc = finish_enqueue(c, g.S + 2, c->w_dM ? c->w_dM : strip + g.S, labels_out);
+    rc = finish_enqueue(c, req, g.S + 2, c->run.dM ? c->run.dM : strip + g.S);
     guard.armed = rc != CL_OK;
     return rc;
 }

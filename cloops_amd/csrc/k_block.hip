@@ -350,10 +350,12 @@ k_blk_point_labels(BlkParams p, const BlkScalars* __restrict__ sc, const int* __
 
 
 // ---- variant 3 host driver -----------------------------------------------------------------
-int run_block(cl_chrom* c, int eps, int minPts, int cut, int32_t* labels_out)
+int run_block(cl_chrom* c, const RunRequest& req)
 {
     int rc;
-    const int n = (int)c->n;
+    run_begin(c);
+    RunGuard guard(c);
+    const int n = (int)c->n, eps = req.eps, minPts = req.minPts, cut = req.cut;
     long long R = ((long long)c->st.xmax - c->st.xmin) / eps + 1;
     if (R > (1LL << 28)) return fail(CL_ERR_GRID, "eps too small for the coordinate extent (cell-row table > 2^28 rows)");
     if ((rc = ensure_workspace(c, (int)R))) return rc;
@@ -446,5 +448,7 @@ int run_block(cl_chrom* c, int eps, int minPts, int cut, int32_t* labels_out)
     // blockDBSCAN.py:74: an empty (fully filtered) mat raises only when the class is called
     // on it; pipe.py:64-65 returns before that, so cut > 0 with no survivors is just empty.
     { cl_chrom::Slot& sl = c->slot[c->cur]; sl.rows_valid = true; sl.sorted_src = false; sl.kmax = n; }      // ids <= cells <= n
-    return finish_enqueue(c, p.R + 1, &sc->M, labels_out);
+    rc = finish_enqueue(c, req, p.R + 1, &sc->M);
+    guard.armed = rc != CL_OK;
+    return rc;
 }

@@ -2014,14 +2014,14 @@ static int list_bufs(cl_chrom* c, const GridParams& g, int nm, ListBufs* b)
 
 static void launch_classify(cl_chrom* c, const GridParams& g, int nblk, const ListBufs& b)
 {
-#define LA_ARGS g, (const int*)c->w_sv, (const int*)c->w_sa, (const int*)c->w_strip, c->ws, (const u32*)c->srow, b.cmask, b.wmask, b.hmask, b.cgloc, b.wgloc, b.bsum, b.sup, c->cellfirst.as<int>()
+#define LA_ARGS g, (const int*)c->run.sv, (const int*)c->run.sa, (const int*)c->run.strip, c->run.ws, (const u32*)c->run.srow, b.cmask, b.wmask, b.hmask, b.cgloc, b.wgloc, b.bsum, b.sup, c->cellfirst.as<int>()
     if (g.variant == CL_VARIANT_CDBSCAN2) hipLaunchKernelGGL(k_classify<true>, dim3(nblk), dim3(256), 0, c->stream, LA_ARGS);
     else hipLaunchKernelGGL(k_classify<false>, dim3(nblk), dim3(256), 0, c->stream, LA_ARGS);
 #undef LA_ARGS
 }
 static void launch_make_lists(cl_chrom* c, const GridParams& g, int nblk, const ListBufs& b, const ListRun& L)
 {
-#define LM_ARGS g, (const int*)c->w_sv, (const int*)c->w_sa, (const int*)c->w_strip, c->ws, (const u32*)c->srow, (const unsigned long long*)b.cmask,                   \
+#define LM_ARGS g, (const int*)c->run.sv, (const int*)c->run.sa, (const int*)c->run.strip, c->run.ws, (const u32*)c->run.srow, (const unsigned long long*)b.cmask,                   \
                 (const unsigned long long*)b.wmask, (const unsigned long long*)b.hmask, (const int*)b.cgloc, (const int*)b.wgloc, (const int*)b.bsum, (const int*)b.sup,  \
                 (const int*)c->cellfirst.as<int>(), b.cgrank, b.wgrank, L.cpair, L.cpos, L.ckey, L.wpair, L.wpos, L.wenc, b.lcnt
     if (g.variant == CL_VARIANT_CDBSCAN2) hipLaunchKernelGGL(k_make_lists<true>, dim3(nblk), dim3(256), 0, c->stream, LM_ARGS);
@@ -2062,17 +2062,17 @@ int lists_build(cl_chrom* c, const GridParams& g, int nm, ListRun* out)
     // chains (the core count is only known on the device: the grids are sized by the PETs of the run)
     fuse_knob(c);
     if (c->fuse_chains)
-        hipLaunchKernelGGL(k_prep_c, dim3(nblocks(std::max(std::max(nm, g.S + 2), b.nsup2))), dim3(TPB), 0, c->stream, g, (const int*)L.lcnt, (const int*)c->w_strip,
+        hipLaunchKernelGGL(k_prep_c, dim3(nblocks(std::max(std::max(nm, g.S + 2), b.nsup2))), dim3(TPB), 0, c->stream, g, (const int*)L.lcnt, (const int*)c->run.strip,
                            (const unsigned long long*)L.cmask, (const int*)L.cgrank, L.cstrip, b.sup, b.nsup2, c->parent.as<int>());
 #ifdef CLOOPS_DEVEL
     else
     hipLaunchKernelGGL(k_chain_c, dim3(nblocks(nm, 256 * CH_PER)), dim3(256), 0, c->stream, g, L.lcnt, (const int2*)L.cpair, c->chainflag.as<int>(),
                        c->parent.as<int>(), c->compkey.as<int>(), c->ncore.as<int>(), c->bsize.as<int>(), c->usize.as<int>(), c->state.as<int>(),
-                       c->cellfirst.as<int>() /* cskip */, (const int*)c->w_strip, L.cmask, L.cgrank, L.cstrip, b.sup, b.nsup2, (int*)nullptr);
+                       c->cellfirst.as<int>() /* cskip */, (const int*)c->run.strip, L.cmask, L.cgrank, L.cstrip, b.sup, b.nsup2, (int*)nullptr);
 #else
     { }
 #endif
-    L.npos = nm; L.pstrip = c->w_strip;
+    L.npos = nm; L.pstrip = c->run.strip;
     *out = L;
     HIP_TRY(hipGetLastError());
     c->l_sup_dirty = false;
@@ -2082,10 +2082,10 @@ int lists_build(cl_chrom* c, const GridParams& g, int nm, ListRun* out)
 int lists_base_keys(cl_chrom* c, const GridParams& g)
 {
     const int n = (int)c->n;
-    int rc = c->bkey.ensure((size_t)n * 4);
+    int rc = c->base.key.ensure((size_t)n * 4);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_base_keys, dim3(nblocks(n, LT)), dim3(256), 0, c->stream, g, n, (const int*)(c->bq.as<int>() + SORT_PAD),
-                       (const int*)(c->bsp.as<int>() + SORT_PAD), (const u32*)c->brow.as<u32>(), c->bkey.as<int>());
+    hipLaunchKernelGGL(k_base_keys, dim3(nblocks(n, LT)), dim3(256), 0, c->stream, g, n, (const int*)(c->base.q.as<int>() + SORT_PAD),
+                       (const int*)(c->base.sp.as<int>() + SORT_PAD), (const u32*)c->base.row.as<u32>(), c->base.key.as<int>());
     HIP_TRY(hipGetLastError());
     return CL_OK;
 }
@@ -2101,33 +2101,33 @@ int lists_build_base(cl_chrom* c, const GridParams& g, int nm, ListRun* out)
     const bool v2 = g.variant == CL_VARIANT_CDBSCAN2;
     ListRun L{};
     list_views(c, b, &L);
-    L.npos = n; L.pstrip = c->bstrip.as<int>();
+    L.npos = n; L.pstrip = c->base.strip.as<int>();
     unsigned long long* sup64 = (unsigned long long*)b.sup;
     const int nsup_ints = 2 * (nblk / 16 + 2);
     if (c->l_sup_dirty) HIP_TRY(hipMemsetAsync(b.sup, 0, (size_t)std::max(nsup_ints, b.nsup2) * 4, c->stream));
     c->l_sup_dirty = true;
-    const int* bq = c->bq.as<int>() + SORT_PAD;
-    const int* bsp = c->bsp.as<int>() + SORT_PAD;
-    const u32* brow = c->brow.as<u32>();
-    c->srow = c->brow.as<u32>();                         // positions are base positions: their input rows
-    const int* words = c->rc_cnt.as<int>();              // the handle's count cache, base-position space
+    const int* bq = c->base.q.as<int>() + SORT_PAD;
+    const int* bsp = c->base.sp.as<int>() + SORT_PAD;
+    const u32* brow = c->base.row.as<u32>();
+    c->run.srow = c->base.row.as<u32>();                         // positions are base positions: their input rows
+    const int* words = c->rc.cnt.as<int>();              // the handle's count cache, base-position space
     const int* band = c->cnt.as<int>();                  // fresh words of the cut band (k_band), base positions
-    const int thr = c->l4_cut ? g.cut - g.V0 : INT_MIN;
-    const int bandq = c->ws.bandq;
+    const int thr = c->run.l4_cut ? g.cut - g.V0 : INT_MIN;
+    const int bandq = c->run.ws.bandq;
 #define LCQ_ARGS g, n, thr, bandq, bq, words, band, b.cmask, b.wmask, b.cgloc, b.wgloc, b.bsum, sup64
-    if (!c->l4_cut) hipLaunchKernelGGL((k_classify_q<false, false>), dim3(nblk), dim3(256), 0, c->stream, LCQ_ARGS);
-    else if (c->l4_band) hipLaunchKernelGGL((k_classify_q<true, true>), dim3(nblk), dim3(256), 0, c->stream, LCQ_ARGS);
+    if (!c->run.l4_cut) hipLaunchKernelGGL((k_classify_q<false, false>), dim3(nblk), dim3(256), 0, c->stream, LCQ_ARGS);
+    else if (c->run.l4_band) hipLaunchKernelGGL((k_classify_q<true, true>), dim3(nblk), dim3(256), 0, c->stream, LCQ_ARGS);
     else hipLaunchKernelGGL((k_classify_q<true, false>), dim3(nblk), dim3(256), 0, c->stream, LCQ_ARGS);
 #undef LCQ_ARGS
-#define LMQ_ARGS g, n, bandq, bq, bsp, brow, (const int*)c->bkey.as<int>(), (const int2*)c->l_fix.as<int2>(), words, band, (const unsigned long long*)b.cmask,                  \
+#define LMQ_ARGS g, n, bandq, bq, bsp, brow, (const int*)c->base.key.as<int>(), (const int2*)c->l_fix.as<int2>(), words, band, (const unsigned long long*)b.cmask,                  \
                  (const unsigned long long*)b.wmask, (const int*)b.cgloc, (const int*)b.wgloc, (const int*)b.bsum, (const unsigned long long*)sup64, b.cgrank, b.wgrank, L.cpair,  \
-                 c->run_rows ? L.cpos : (int*)nullptr, L.ckey, L.wpair, L.wpos, L.wenc, b.lcnt, c->fuse_chains ? c->parent.as<int>() : (int*)nullptr
+                 c->run.rows ? L.cpos : (int*)nullptr, L.ckey, L.wpair, L.wpos, L.wenc, b.lcnt, c->fuse_chains ? c->parent.as<int>() : (int*)nullptr
     if (v2) {
-        if (!c->l4_cut) hipLaunchKernelGGL((k_make_lists_q<true, false, false>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
-        else if (c->l4_band) hipLaunchKernelGGL((k_make_lists_q<true, true, true>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
+        if (!c->run.l4_cut) hipLaunchKernelGGL((k_make_lists_q<true, false, false>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
+        else if (c->run.l4_band) hipLaunchKernelGGL((k_make_lists_q<true, true, true>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
         else hipLaunchKernelGGL((k_make_lists_q<true, true, false>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
     } else {
-        if (c->l4_band) hipLaunchKernelGGL((k_make_lists_q<false, true, true>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
+        if (c->run.l4_band) hipLaunchKernelGGL((k_make_lists_q<false, true, true>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
         else hipLaunchKernelGGL((k_make_lists_q<false, false, false>), dim3(nblk), dim3(256), 0, c->stream, LMQ_ARGS);
     }
 #undef LMQ_ARGS
@@ -2154,14 +2154,14 @@ int lists_build_base(cl_chrom* c, const GridParams& g, int nm, ListRun* out)
 int lists_words_to_base(cl_chrom* c, const GridParams& g)
 {
     const int n = (int)c->n;
-    LAUNCH(k_words_to_base, n, g, n, (const int*)(c->bsp.as<int>() + SORT_PAD), (const int4*)c->l_tab.as<int4>(), (const int*)c->rc_poff.as<int>(),
-           (const int*)c->cnt.as<int>(), c->rc_cnt.as<int>());
+    LAUNCH(k_words_to_base, n, g, n, (const int*)(c->base.sp.as<int>() + SORT_PAD), (const int4*)c->l_tab.as<int4>(), (const int*)c->rc.poff.as<int>(),
+           (const int*)c->cnt.as<int>(), c->rc.cnt.as<int>());
     HIP_TRY(hipGetLastError());
     return CL_OK;
 }
 
 // croot: c->root (levels >= 2) or, while the tile kernels still read roots by position (level 1), the distance-list buffer
-static int* croot_of(cl_chrom* c) { return c->run_level >= 2 ? c->root.as<int>() : c->l_aux.as<int>(); }
+static int* croot_of(cl_chrom* c) { return c->run.level >= 2 ? c->root.as<int>() : c->l_aux.as<int>(); }
 
 int lists_union_flatten(cl_chrom* c, const GridParams& g, int nm, const ListRun& L)
 {
@@ -2169,7 +2169,7 @@ int lists_union_flatten(cl_chrom* c, const GridParams& g, int nm, const ListRun&
     const int nt = nblocks(nm, UNT);
     // the union walk looks one strip back, i.e. about one strip's cores in front of the core: the halo follows the mean strip population
     const HeadReset hr{c->compkey.as<int>(), c->ncore.as<int>(), c->bsize.as<int>(), c->usize.as<int>(), c->state.as<int>()};
-    int* prune = (c->run_level >= 4 && g.variant == CL_VARIANT_CDBSCAN2) ? L.ckey : (int*)nullptr;
+    int* prune = (c->run.level >= 4 && g.variant == CL_VARIANT_CDBSCAN2) ? L.ckey : (int*)nullptr;
 #define LU_ARGS g, nt, L.lcnt, (const int2*)L.cpair, c->chainflag.as<int>(), (const int*)L.cstrip, c->cellfirst.as<int>() /* cskip: the cell minima are in the keys */, \
                 c->parent.as<int>(), hr, prune, c->ulist.as<int>() /* the overflow list: free until k_mark_uncertain_l */, c->counters.as<int>()
     // UK: the neighbours on either side that k_union_c's domination test looks at
@@ -2261,13 +2261,13 @@ int lists_scatter_owner(cl_chrom* c, int nm, const ListRun& L)
     return CL_OK;
 }
 
-int lists_final(cl_chrom* c, const GridParams& g, int nm, const ListRun& L, bool rows, int* pair_count)
+int lists_final(cl_chrom* c, const RunRequest& req, const GridParams& g, int nm, const ListRun& L, bool rows, int* pair_count)
 {
     cl_chrom::Slot& sl = c->slot[c->cur];
     hipLaunchKernelGGL(k_final_lists, dim3(nblocks(nm, LF_TPB * LF_CHUNKS)), dim3(LF_TPB), 0, c->stream, g, L.lcnt, (const int2*)L.cpair, (const int*)L.cpos,
                        (const int*)croot_of(c), (const int2*)L.wpair, (const int*)L.wpos, (const int*)c->owner.as<int>(), (const int*)c->chainhead.as<int>(),
-                       (const u32*)c->srow, (rows && !c->pairs_out) ? sl.labels.as<int>() : (int*)nullptr, sl.slab.as<int>(), c->l_dist.as<int>(), make_table(c),
-                       c->pairs_out ? sl.pairs.as<int2>() : (int2*)nullptr, (int)std::min<long long>(c->pairs_cap, INT_MAX), pair_count);
+                       (const u32*)c->run.srow, (rows && !req.pairs_out) ? sl.labels.as<int>() : (int*)nullptr, sl.slab.as<int>(), c->l_dist.as<int>(), make_table(c),
+                       req.pairs_out ? sl.pairs.as<int2>() : (int2*)nullptr, (int)std::min<long long>(req.pairs_cap, INT_MAX), pair_count);
     HIP_TRY(hipGetLastError());
     return CL_OK;
 }
@@ -2347,12 +2347,12 @@ k_rowmask_write(int n, const int* __restrict__ labels, const unsigned long long*
     }
 }
 // the slot's `pairs` buffer in this form: mask words | labels (capacity) | tile sums | superblock sums
-int lists_rowmask(cl_chrom* c, int* total)
+int lists_rowmask(cl_chrom* c, const RunRequest& req, int* total)
 {
     cl_chrom::Slot& sl = c->slot[c->cur];
     const long long n = c->n;
     const size_t nw = (size_t)((n + 63) / 64), ntile = (size_t)((n + RM_T - 1) / RM_T), nsup = ntile / 16 + 1;
-    const size_t cap = (size_t)std::max<long long>(c->mask_cap, 1);
+    const size_t cap = (size_t)std::max<long long>(req.mask_cap, 1);
     const size_t o_lab = nw * 8, o_tsum = ((o_lab + cap * 4 + 255) / 256) * 256, o_sup = ((o_tsum + ntile * 4 + 255) / 256) * 256;
     int rc = sl.pairs.ensure(o_sup + nsup * 8 + 256);
     if (rc) return rc;
@@ -2361,7 +2361,7 @@ int lists_rowmask(cl_chrom* c, int* total)
     hipLaunchKernelGGL(k_rowmask_count, dim3((unsigned)ntile), dim3(256), 0, c->stream, (int)n, (const int*)sl.labels.as<int>(), (unsigned long long*)p,
                        (int*)(p + o_tsum), (unsigned long long*)(p + o_sup));
     hipLaunchKernelGGL(k_rowmask_write, dim3((unsigned)ntile), dim3(256), 0, c->stream, (int)n, (const int*)sl.labels.as<int>(), (const unsigned long long*)p,
-                       (const int*)(p + o_tsum), (const unsigned long long*)(p + o_sup), (int*)(p + o_lab), (long long)c->mask_cap, total);
+                       (const int*)(p + o_tsum), (const unsigned long long*)(p + o_sup), (int*)(p + o_lab), (long long)req.mask_cap, total);
     HIP_TRY(hipGetLastError());
     return CL_OK;
 }
@@ -2400,15 +2400,15 @@ extern "C" int cl_debug_time_lists(cl_chrom* c, int which, int reps, float* ms_o
             if ((rc = list_bufs(c, g, n, &bb))) return rc;
             const int nb4 = nblocks(n, LT);
             unsigned long long* sup64 = (unsigned long long*)bb.sup;
-            const int* bq = c->bq.as<int>() + SORT_PAD; const int* bsp = c->bsp.as<int>() + SORT_PAD;
-            const int thr = g.cut - g.V0, bandq = c->ws.bandq;
+            const int* bq = c->base.q.as<int>() + SORT_PAD; const int* bsp = c->base.sp.as<int>() + SORT_PAD;
+            const int thr = g.cut - g.V0, bandq = c->run.ws.bandq;
             if (which == 6) {
                 HIP_TRY(hipMemsetAsync(bb.sup, 0, (size_t)2 * (nb4 / 16 + 2) * 4, c->stream));
-                hipLaunchKernelGGL((k_classify_q<true, true>), dim3(nb4), dim3(256), 0, c->stream, g, n, thr, bandq, bq, (const int*)c->rc_cnt.as<int>(), (const int*)c->cnt.as<int>(),
+                hipLaunchKernelGGL((k_classify_q<true, true>), dim3(nb4), dim3(256), 0, c->stream, g, n, thr, bandq, bq, (const int*)c->rc.cnt.as<int>(), (const int*)c->cnt.as<int>(),
                                    bb.cmask, bb.wmask, bb.cgloc, bb.wgloc, bb.bsum, sup64);
             } else {
-                hipLaunchKernelGGL((k_make_lists_q<true, true, true>), dim3(nb4), dim3(256), 0, c->stream, g, n, bandq, bq, bsp, (const u32*)c->brow.as<u32>(), (const int*)c->bkey.as<int>(),
-                                   (const int2*)c->l_fix.as<int2>(), (const int*)c->rc_cnt.as<int>(), (const int*)c->cnt.as<int>(), (const unsigned long long*)bb.cmask,
+                hipLaunchKernelGGL((k_make_lists_q<true, true, true>), dim3(nb4), dim3(256), 0, c->stream, g, n, bandq, bq, bsp, (const u32*)c->base.row.as<u32>(), (const int*)c->base.key.as<int>(),
+                                   (const int2*)c->l_fix.as<int2>(), (const int*)c->rc.cnt.as<int>(), (const int*)c->cnt.as<int>(), (const unsigned long long*)bb.cmask,
                                    (const unsigned long long*)bb.wmask, (const int*)bb.cgloc, (const int*)bb.wgloc, (const int*)bb.bsum, (const unsigned long long*)sup64, bb.cgrank, bb.wgrank,
                                    L.cpair, (int*)nullptr, L.ckey, L.wpair, L.wpos, L.wenc, bb.lcnt, (int*)nullptr);
             }
@@ -2416,13 +2416,13 @@ extern "C" int cl_debug_time_lists(cl_chrom* c, int which, int reps, float* ms_o
             // k_border_w / k_union_c + k_flatten_c / k_final_lists of the last run once more (their inputs are in place; the per-component
             // counters they add to are garbage afterwards)
             ListRun L2 = L;
-            c->run_level = c->traversal >= 4 ? 4 : 3;
-            if (c->run_level == 4) { ListBufs bb; if ((rc = list_bufs(c, g, (int)c->n, &bb))) return rc; list_views(c, bb, &L2); L2.npos = (int)c->n; L2.pstrip = c->bstrip.as<int>(); }
-            else { L2.npos = nm; L2.pstrip = c->w_strip; }
+            c->run.level = c->traversal >= 4 ? 4 : 3;
+            if (c->run.level == 4) { ListBufs bb; if ((rc = list_bufs(c, g, (int)c->n, &bb))) return rc; list_views(c, bb, &L2); L2.npos = (int)c->n; L2.pstrip = c->base.strip.as<int>(); }
+            else { L2.npos = nm; L2.pstrip = c->run.strip; }
             if (which == 4) { if ((rc = lists_border(c, g, nm, L2))) return rc; }
             else if (which == 3) {
                 // (the chain kernel resets the forest and the per-head accumulators first -- timed with it)
-                ListBufs bb; if ((rc = list_bufs(c, g, c->run_level == 4 ? (int)c->n : nm, &bb))) return rc;
+                ListBufs bb; if ((rc = list_bufs(c, g, c->run.level == 4 ? (int)c->n : nm, &bb))) return rc;
                 fuse_knob(c);
                 if (c->fuse_chains)
                     hipLaunchKernelGGL(k_prep_c, dim3(nblocks(std::max(nm, g.S + 2))), dim3(TPB), 0, c->stream, g, (const int*)L2.lcnt, (const int*)L2.pstrip,
@@ -2437,7 +2437,7 @@ extern "C" int cl_debug_time_lists(cl_chrom* c, int which, int reps, float* ms_o
 #endif
                 HIP_TRY(hipMemsetAsync(c->counters.p, 0, 64, c->stream));
                 if ((rc = lists_union_flatten(c, g, nm, L2))) return rc;
-            } else { if ((rc = lists_final(c, g, nm, L2, false, c->counters.as<int>() + 40))) return rc; }
+            } else { if ((rc = lists_final(c, RunRequest(), g, nm, L2, false, c->counters.as<int>() + 40))) return rc; }
         } else return fail(CL_ERR_ARG, "cl_debug_time_lists: kernel not supported on its own");
     }
     HIP_TRY(hipEventRecord(e1, c->stream));

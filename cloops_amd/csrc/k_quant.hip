@@ -95,14 +95,14 @@ extern "C" int cl_quant_counts(cl_chrom* c, int32_t cut, int32_t n_records, cons
     int rc;
     if ((rc = sig_tables(c, cut))) return rc;                          // K8's sorted tables of (chromosome, cut), shared
     int hm = 0;
-    HIP_TRY(hipMemcpyAsync(&hm, c->sig_m.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hm, c->sig.m.p, 4, hipMemcpyDeviceToHost, c->stream));
     if (n_records > 0) {
-        if ((rc = c->sig_win.ensure((size_t)n_records * sizeof(SigWin))) || (rc = c->sig_out.ensure((size_t)n_records * QNT_OUT * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->sig_win.p, windows, (size_t)n_records * sizeof(SigWin), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k11_quant, dim3(n_records), dim3(TPB), 0, c->stream, c->sig_tx.as<u64>(), c->sig_ty.as<u64>(), c->sig_m.as<int>(),
-                           n_records, c->sig_win.as<SigWin>(), c->sig_out.as<int>());
+        if ((rc = c->sig.win.ensure((size_t)n_records * sizeof(SigWin))) || (rc = c->sig.out.ensure((size_t)n_records * QNT_OUT * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->sig.win.p, windows, (size_t)n_records * sizeof(SigWin), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k11_quant, dim3(n_records), dim3(TPB), 0, c->stream, c->sig.tx.as<u64>(), c->sig.ty.as<u64>(), c->sig.m.as<int>(),
+                           n_records, c->sig.win.as<SigWin>(), c->sig.out.as<int>());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, c->sig_out.p, (size_t)n_records * QNT_OUT * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out, c->sig.out.p, (size_t)n_records * QNT_OUT * 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n_pets) *n_pets = hm;

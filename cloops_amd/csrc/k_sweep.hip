@@ -716,18 +716,18 @@ extern "C" int cl_dist_collect(cl_chrom* c, int32_t cut, int64_t* n_pos, int64_t
     int rc = k7_prepare(c);
     if (rc) return rc;
     if (!c->slot[c->last_slot].sorted_src && !c->slot[c->last_slot].rows_valid) return fail(CL_ERR_ARG, "cl_dist_collect: the last run left no labels");
-    c->kde_run = -1;
+    c->kde.run = -1;
     // one entry per PET of the run at most, plus one per distance below the cut when those come from the distance histogram
     const long long cap = c->n + 65536;
     if (cap > (long long)UINT_MAX) return fail(CL_ERR_GRID, "cl_dist_collect: more than 2^32 entries");
-    if ((rc = c->kde_ent.ensure((size_t)cap * 8)) || (rc = c->kde_sorted.ensure((size_t)cap * 8)) || (rc = c->kde_ctr.ensure(sizeof(K17Ctr)))) return rc;
+    if ((rc = c->kde.ent.ensure((size_t)cap * 8)) || (rc = c->kde.sorted.ensure((size_t)cap * 8)) || (rc = c->kde.ctr.ensure(sizeof(K17Ctr)))) return rc;
     K17Ctr h{};
     h.dmin[0] = h.dmin[1] = ~0u;
-    HIP_TRY(hipMemcpyAsync(c->kde_ctr.p, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->kde.ctr.p, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k17_collect, dim3(K7_BLOCKS), dim3(TPB), 0, c->stream, k7_source(c, cut), (int)cut, c->k7_cls.as<signed char>(),
-                       c->kde_ent.as<u64>(), (unsigned)cap, c->kde_ctr.as<K17Ctr>());
+                       c->kde.ent.as<u64>(), (unsigned)cap, c->kde.ctr.as<K17Ctr>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h, c->kde_ctr.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&h, c->kde.ctr.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if ((long long)h.cnt[0] + (long long)h.cnt[1] > cap) return fail(CL_ERR_GRID, "internal: distance entry buffer overrun");
     // each list sorted by (|d|, weight): equal keys are equal entries, so the sorted lists -- and every sum over them -- are the
@@ -737,23 +737,23 @@ extern "C" int cl_dist_collect(cl_chrom* c, int32_t cut, int64_t* n_pos, int64_t
         size_t need = 0;
         e = rocprim::radix_sort_keys(nullptr, need, (u64*)nullptr, (u64*)nullptr, std::max<size_t>(h.cnt[g], 1), 0, 64, c->stream);
         if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query (kde)", hipGetErrorString(e));
-        if ((rc = c->kde_tmp.ensure(std::max<size_t>(need, 16)))) return rc;
+        if ((rc = c->kde.tmp.ensure(std::max<size_t>(need, 16)))) return rc;
     }
     for (int g = 0; g < 2; ++g) {
         if (!h.cnt[g]) continue;
         const size_t off = g ? (size_t)cap - h.cnt[g] : 0;
-        size_t bytes = c->kde_tmp.bytes;
-        e = rocprim::radix_sort_keys(c->kde_tmp.p, bytes, c->kde_ent.as<u64>() + off, c->kde_sorted.as<u64>() + off, (size_t)h.cnt[g], 0, 64, c->stream);
+        size_t bytes = c->kde.tmp.bytes;
+        e = rocprim::radix_sort_keys(c->kde.tmp.p, bytes, c->kde.ent.as<u64>() + off, c->kde.sorted.as<u64>() + off, (size_t)h.cnt[g], 0, 64, c->stream);
         if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(kde)", hipGetErrorString(e));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int g = 0; g < 2; ++g) {
-        c->kde_cnt[g] = h.cnt[g];
+        c->kde.cnt[g] = h.cnt[g];
         n_pos[g] = (int64_t)h.n_pos[g];
         if (h.cnt[g]) { dmin[g] = h.dmin[g]; dmax[g] = h.dmax[g]; }
     }
-    c->kde_cap = cap;
-    c->kde_run = c->deq;
+    c->kde.cap = cap;
+    c->kde.run = c->deq;
     return CL_OK;
 }
 
@@ -765,11 +765,11 @@ extern "C" int cl_dist_kde(cl_chrom* c, int group, double lo, double step, doubl
     if (group != 0 && group != 1) return fail(CL_ERR_ARG, "cl_dist_kde: group must be 0 (inter-ligation) or 1 (self-ligation)");
     if (c && c->n == 0) return CL_OK;
     if ((rc = k7_prepare(c))) return rc;
-    if (c->kde_run != c->deq) return fail(CL_ERR_ARG, "cl_dist_kde: call cl_dist_collect for the last completed run first");
-    const long long m = c->kde_cnt[group];
+    if (c->kde.run != c->deq) return fail(CL_ERR_ARG, "cl_dist_kde: call cl_dist_collect for the last completed run first");
+    const long long m = c->kde.cnt[group];
     if (m == 0) return CL_OK;
-    const u64* ent = c->kde_sorted.as<u64>() + (group ? (size_t)(c->kde_cap - m) : 0);
-    if ((rc = k17_evaluate(c->stream, c->kde_part, ent, (const int*)nullptr, m, lo, step, inv_h, gridsize, sums))) return rc;
+    const u64* ent = c->kde.sorted.as<u64>() + (group ? (size_t)(c->kde.cap - m) : 0);
+    if ((rc = k17_evaluate(c->stream, c->kde.part, ent, (const int*)nullptr, m, lo, step, inv_h, gridsize, sums))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CL_OK;
 }
@@ -797,7 +797,7 @@ extern "C" int cl_kde_array(int device, const int32_t* d_host, int64_t n, double
 extern "C" int cl_cand_reset(cl_chrom* c)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    c->cand_n = 0;
+    c->cand.n = 0;
     return CL_OK;
 }
 
@@ -811,7 +811,7 @@ extern "C" int cl_cand_append(cl_chrom* c, int32_t step, int64_t* n_inter, int64
     cl_chrom::Slot& sl = c->slot[c->last_slot];
     const int K = sl.h_hdr[0];
     if (K <= 0) return CL_OK;
-    if ((rc = ensure_cand_capacity(c, c->cand_n + K))) return rc;
+    if ((rc = ensure_cand_capacity(c, c->cand.n + K))) return rc;
     const int nb = nblocks(K, CAND_BLOCK);
     if ((rc = c->sel_tmp.ensure((size_t)nb * 12 + 64))) return rc;
     int* bcount = c->sel_tmp.as<int>();
@@ -822,20 +822,20 @@ extern "C" int cl_cand_append(cl_chrom* c, int32_t step, int64_t* n_inter, int64
     hipError_t e = rocprim::exclusive_scan(c->scan_tmp.p, tb, bcount, boff, 0, (size_t)nb, rocprim::plus<int>(), c->stream);
     if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(cand)", hipGetErrorString(e));
     hipLaunchKernelGGL(k_cand_append, dim3(nb), dim3(256), 0, c->stream, dK, c->k7_cls.as<signed char>(), make_table_slot(c, c->last_slot),
-                       (const int*)boff, (const int*)bcount, (int)c->cand_n, (int)step, (int)std::min<long long>(c->cand_cap, INT_MAX), c->cand_box.as<int4>(), c->cand_step.as<int>());
+                       (const int*)boff, (const int*)bcount, (int)c->cand.n, (int)step, (int)std::min<long long>(c->cand.cap, INT_MAX), c->cand.box.as<int4>(), c->cand.step.as<int>());
     std::vector<int> h(2 * nb);
     HIP_TRY(hipMemcpyAsync(h.data(), bcount, (size_t)2 * nb * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     long long ni = 0, ns = 0;
     for (int k = 0; k < nb; ++k) { ni += h[k]; ns += h[nb + k]; }
-    if (c->cand_n + ni > c->cand_cap) return fail(CL_ERR_GRID, "internal: candidate buffer overrun");
-    c->cand_n += ni;
+    if (c->cand.n + ni > c->cand.cap) return fail(CL_ERR_GRID, "internal: candidate buffer overrun");
+    c->cand.n += ni;
     if (n_inter) *n_inter = ni;
     if (n_self) *n_self = ns;
     return CL_OK;
 }
 
-// combineTwice + filterClusterByDis over the chromosome's candidate buffer -> the surviving boxes in c->cand_out (device), *kept of them
+// combineTwice + filterClusterByDis over the chromosome's candidate buffer -> the surviving boxes in c->cand.out (device), *kept of them
 static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out);
 
 extern "C" int cl_cand_finish(cl_chrom* c, int32_t final_cut, int32_t* boxes_out, int64_t capacity, int64_t* n_out)
@@ -849,7 +849,7 @@ extern "C" int cl_cand_finish(cl_chrom* c, int32_t final_cut, int32_t* boxes_out
     if (kept > capacity) return fail(CL_ERR_ARG, "cl_cand_finish: boxes_out too small");
     if (kept > 0) {
         if (!boxes_out) return fail(CL_ERR_ARG, "cl_cand_finish: boxes_out is null");
-        HIP_TRY(hipMemcpyAsync(boxes_out, c->cand_out.p, (size_t)kept * 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(boxes_out, c->cand.out.p, (size_t)kept * 16, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return CL_OK;
@@ -863,14 +863,14 @@ extern "C" int cl_cand_finish_device(cl_chrom* c, int32_t final_cut, const int32
     int rc = cand_finish_core(c, final_cut, &kept);
     if (rc) return rc;
     *n_out = kept;
-    *dev_rows_out = kept > 0 ? (const int32_t*)c->cand_out.p : nullptr;      // valid until the handle's next sweep finishes (or it is destroyed)
+    *dev_rows_out = kept > 0 ? (const int32_t*)c->cand.out.p : nullptr;      // valid until the handle's next sweep finishes (or it is destroyed)
     return CL_OK;
 }
 
 static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out)
 {
     *kept_out = 0;
-    const long long N = c->cand_n;
+    const long long N = c->cand.n;
     if (N == 0) return CL_OK;
     if (c->enq != c->deq) return fail(CL_ERR_ARG, "cl_cand_finish: asynchronous runs still in flight");
     if (N > INT_MAX - 1024) return fail(CL_ERR_GRID, "cl_cand_finish: more than 2^31 candidates");
@@ -888,7 +888,7 @@ static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out)
 #define CF_MARK() do { } while (0)
 #endif
     if ((rc = ensure_workspace(c, 1))) return rc;
-    if ((rc = c->cand_keep.ensure((size_t)N + 64)) || (rc = c->cand_out.ensure((size_t)N * 16))) return rc;
+    if ((rc = c->cand.keep.ensure((size_t)N + 64)) || (rc = c->cand.out.ensure((size_t)N * 16))) return rc;
     CF_MARK();
     const int n = (int)N;
     // the sort buffers of the handle are sized for its PETs; a sweep of many steps on a strongly clustered chromosome can
@@ -915,12 +915,12 @@ static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out)
     int hflag = 0;
     for (int attempt = 0; attempt < 4; ++attempt) {
         HIP_TRY(hipMemsetAsync(flags, 0, 4, c->stream));
-        LAUNCH(k_cand_hash, n, n, c->cand_box.as<int4>(), (u64)attempt * 0x9FB21C651E98DF25ull, kin, vin);
+        LAUNCH(k_cand_hash, n, n, c->cand.box.as<int4>(), (u64)attempt * 0x9FB21C651E98DF25ull, kin, vin);
         size_t tmp_bytes = c->sort_tmp.bytes;
         hipError_t e = rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, kin, kout, vin, vout, (size_t)n, 0, 64, c->stream);
         if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_pairs(cand)", hipGetErrorString(e));
-        LAUNCH(k_cand_mark, n, n, (const u64*)kout, (const u32*)vout, c->cand_box.as<int4>(), c->cand_step.as<int>(), (int)final_cut,
-               c->cand_keep.as<unsigned char>(), flags);
+        LAUNCH(k_cand_mark, n, n, (const u64*)kout, (const u32*)vout, c->cand.box.as<int4>(), c->cand.step.as<int>(), (int)final_cut,
+               c->cand.keep.as<unsigned char>(), flags);
         HIP_TRY(hipMemcpyAsync(&hflag, flags, 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (hflag == 0) break;
@@ -932,11 +932,11 @@ static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out)
     if ((rc = c->sel_tmp.ensure((size_t)nb * 8 + 64))) return rc;
     int* bcount = c->sel_tmp.as<int>();
     int* boff = bcount + nb;
-    hipLaunchKernelGGL(k_flag_count, dim3(nb), dim3(256), 0, c->stream, n, c->cand_keep.as<unsigned char>(), bcount);
+    hipLaunchKernelGGL(k_flag_count, dim3(nb), dim3(256), 0, c->stream, n, c->cand.keep.as<unsigned char>(), bcount);
     size_t tb = c->scan_tmp.bytes;
     e = rocprim::exclusive_scan(c->scan_tmp.p, tb, bcount, boff, 0, (size_t)nb, rocprim::plus<int>(), c->stream);
     if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan(cand out)", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_cand_emit, dim3(nb), dim3(256), 0, c->stream, n, c->cand_keep.as<unsigned char>(), c->cand_box.as<int4>(), (const int*)boff, c->cand_out.as<int4>());
+    hipLaunchKernelGGL(k_cand_emit, dim3(nb), dim3(256), 0, c->stream, n, c->cand.keep.as<unsigned char>(), c->cand.box.as<int4>(), (const int*)boff, c->cand.out.as<int4>());
     int tail[2];
     HIP_TRY(hipMemcpyAsync(&tail[0], boff + nb - 1, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&tail[1], bcount + nb - 1, 4, hipMemcpyDeviceToHost, c->stream));
@@ -949,26 +949,26 @@ static int cand_finish_core(cl_chrom* c, int32_t final_cut, long long* kept_out)
 // ---- K8 host entry point ------------------------------------------------------------------------
 int sig_tables(cl_chrom* c, int cut)
 {
-    if (c->sig_ready && c->sig_cut == cut) return CL_OK;
+    if (c->sig.ready && c->sig.cut == cut) return CL_OK;
     const int n = (int)c->n;
     int rc;
     // X-sorted and Y-sorted tables of the PETs that pass parseJd(f, cut); built once per (chromosome, cut)
-    if ((rc = c->sig_tx.ensure((size_t)n * 8)) || (rc = c->sig_ty.ensure((size_t)n * 8)) ||
-        (rc = c->sig_tmp.ensure((size_t)n * 8)) || (rc = c->sig_m.ensure(64))) return rc;
-    LAUNCH(k8_split, n, c->d_x, c->d_y, n, cut, c->sig_tmp.as<u64>(), c->sig_ty.as<u64>());
+    if ((rc = c->sig.tx.ensure((size_t)n * 8)) || (rc = c->sig.ty.ensure((size_t)n * 8)) ||
+        (rc = c->sig.tmp.ensure((size_t)n * 8)) || (rc = c->sig.m.ensure(64))) return rc;
+    LAUNCH(k8_split, n, c->d_x, c->d_y, n, cut, c->sig.tmp.as<u64>(), c->sig.ty.as<u64>());
     size_t bytes = 0;
     hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, (u64*)nullptr, (u64*)nullptr, (size_t)n, 0, 64, c->stream);
     if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys size query", hipGetErrorString(e));
-    if ((rc = c->sig_sorttmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
-    bytes = c->sig_sorttmp.bytes;
-    e = rocprim::radix_sort_keys(c->sig_sorttmp.p, bytes, c->sig_tmp.as<u64>(), c->sig_tx.as<u64>(), (size_t)n, 0, 64, c->stream);
+    if ((rc = c->sig.sorttmp.ensure(std::max<size_t>(bytes, 16)))) return rc;
+    bytes = c->sig.sorttmp.bytes;
+    e = rocprim::radix_sort_keys(c->sig.sorttmp.p, bytes, c->sig.tmp.as<u64>(), c->sig.tx.as<u64>(), (size_t)n, 0, 64, c->stream);
     if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(X)", hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(c->sig_tmp.p, c->sig_ty.p, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
-    bytes = c->sig_sorttmp.bytes;
-    e = rocprim::radix_sort_keys(c->sig_sorttmp.p, bytes, c->sig_tmp.as<u64>(), c->sig_ty.as<u64>(), (size_t)n, 0, 64, c->stream);
+    HIP_TRY(hipMemcpyAsync(c->sig.tmp.p, c->sig.ty.p, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+    bytes = c->sig.sorttmp.bytes;
+    e = rocprim::radix_sort_keys(c->sig.sorttmp.p, bytes, c->sig.tmp.as<u64>(), c->sig.ty.as<u64>(), (size_t)n, 0, 64, c->stream);
     if (e != hipSuccess) return fail(CL_ERR_HIP, "radix_sort_keys(Y)", hipGetErrorString(e));
-    hipLaunchKernelGGL(k8_count_valid, dim3(1), dim3(64), 0, c->stream, c->sig_tx.as<u64>(), n, c->sig_m.as<int>());
-    c->sig_ready = true; c->sig_cut = cut;
+    hipLaunchKernelGGL(k8_count_valid, dim3(1), dim3(64), 0, c->stream, c->sig.tx.as<u64>(), n, c->sig.m.as<int>());
+    c->sig.ready = true; c->sig.cut = cut;
     return CL_OK;
 }
 
@@ -984,14 +984,14 @@ extern "C" int cl_sig_counts(cl_chrom* c, int32_t cut, int32_t n_records, const 
     int rc;
     if ((rc = sig_tables(c, cut))) return rc;
     int hm = 0;
-    HIP_TRY(hipMemcpyAsync(&hm, c->sig_m.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&hm, c->sig.m.p, 4, hipMemcpyDeviceToHost, c->stream));
     if (n_records > 0) {
-        if ((rc = c->sig_win.ensure((size_t)n_records * sizeof(SigWin))) || (rc = c->sig_out.ensure((size_t)n_records * SIG_OUT * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->sig_win.p, windows, (size_t)n_records * sizeof(SigWin), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k8_counts, dim3(n_records), dim3(TPB), 0, c->stream, c->sig_tx.as<u64>(), c->sig_ty.as<u64>(), c->sig_m.as<int>(),
-                           n_records, c->sig_win.as<SigWin>(), c->sig_out.as<int>());
+        if ((rc = c->sig.win.ensure((size_t)n_records * sizeof(SigWin))) || (rc = c->sig.out.ensure((size_t)n_records * SIG_OUT * 4))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->sig.win.p, windows, (size_t)n_records * sizeof(SigWin), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k8_counts, dim3(n_records), dim3(TPB), 0, c->stream, c->sig.tx.as<u64>(), c->sig.ty.as<u64>(), c->sig.m.as<int>(),
+                           n_records, c->sig.win.as<SigWin>(), c->sig.out.as<int>());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, c->sig_out.p, (size_t)n_records * SIG_OUT * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out, c->sig.out.p, (size_t)n_records * SIG_OUT * 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n_pets) *n_pets = hm;

@@ -143,10 +143,12 @@ k64_final(int n, const int* __restrict__ X, const int* __restrict__ Y, const u32
 
 
 // ---- variant 1 under the weighted metric (K9) ------------------------------------------------
-int run_weighted(cl_chrom* c, int eps, int minPts, int wx, int wy, int32_t* labels_out)
+int run_weighted(cl_chrom* c, const RunRequest& req)
 {
     int rc;
-    const int n = (int)c->n;
+    run_begin(c);
+    RunGuard guard(c);
+    const int n = (int)c->n, eps = req.eps, minPts = req.minPts, wx = req.wx, wy = req.wy;
     G64 g; g.eps = eps; g.minPts = minPts; g.wx = wx; g.wy = wy;
     // bounds of U = wx*X + wy*Y and W = wy*Y - wx*X from the upload statistics
     const long long umin = (long long)wx * c->st.xmin + (long long)wy * c->st.ymin, umax = (long long)wx * c->st.xmax + (long long)wy * c->st.ymax;
@@ -180,7 +182,7 @@ int run_weighted(cl_chrom* c, int eps, int minPts, int wx, int wy, int32_t* labe
     }
     const u64* sk = c->keys_out.as<u64>();
     const u32* srow = c->vals_out.as<u32>();
-    c->srow = c->vals_out.as<u32>();
+    c->run.srow = c->vals_out.as<u32>();
     long long* p64 = c->keys_in.as<long long>();         // the unsorted keys are dead after the sort
     LAUNCH(k_strip_table, g.S + 2, sk, n, g.S, qbits, strip);
     LAUNCH(k64_p, n, n, g, c->d_x, c->d_y, srow, p64);
@@ -209,5 +211,7 @@ int run_weighted(cl_chrom* c, int eps, int minPts, int wx, int wy, int32_t* labe
                        c->chainhead.as<int>(), c->slot[c->cur].labels.as<int>(), t);
     HIP_TRY(hipGetLastError());
     { cl_chrom::Slot& sl = c->slot[c->cur]; sl.rows_valid = true; sl.sorted_src = false; }
-    return finish_enqueue(c, g.S + 2, strip + g.S, labels_out);
+    rc = finish_enqueue(c, req, g.S + 2, strip + g.S);
+    guard.armed = rc != CL_OK;
+    return rc;
 }
