@@ -39,6 +39,9 @@ CL_KDIS_BINS = 3968          # 31 octaves x 128 log bins: d < 2^31
 CL_MAT_WMAX = 8192           # bins a side of a dense window
 CL_MAT_CELLS_MAX = 16777216  # 2^24 cells of a dense window
 CL_BAL_BINS_MAX = 16777216   # 2^24 bins of a balanced chromosome
+CL_EIG_MAX = 6               # eigenpairs of a cl_eig_iterate
+CL_EIG_BLOCK = 8             # columns of the iteration's block, vectors of a cl_eig_apply
+CL_EIG_BINS_MAX = 1048576    # 2^20 bins of a chromosome's compartments
 
 
 class ClBox(ctypes.Structure):
@@ -148,6 +151,11 @@ PROTOTYPES = {
     "cl_exp_set": (_int, [_vp, _vp, _i64]),
     "cl_exp_cells_get": (_int, [_vp, _i64, _i64, _vp]),
     "cl_exp_free": (_int, [_vp]),
+    "cl_eig_build": (_int, [_vp, _f64, _i64, _i64p, _i64p]),
+    "cl_eig_apply": (_int, [_vp, _vp, _i32, _vp]),
+    "cl_eig_iterate": (_int, [_vp, _i32, _i32, _f64, _i32p, _i32p, _vp, _vp]),
+    "cl_eig_vectors_get": (_int, [_vp, _i32, _i64, _i64, _vp]),
+    "cl_eig_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

@@ -935,6 +935,53 @@ class Chromosome(_Handle):
         _lib.check(self._lib.cl_exp_free(self._h))
         self._exp_diags = 0
 
+    def eig_build(self, clip=float("inf"), dmax=None):
+        """K27: describes M = min(O/E, clip) - 1 over the valid bin pairs with ignore_diags <= |i - j| < dmax (0 elsewhere; O/E is 0
+        where there is no cell) from the cells, weights and expected values of the last exp_set, kept on the device for eig_apply /
+        eig_iterate.  dmax None: all diagonals (nb).  Refused when a diagonal of the band with valid pairs has no finite positive
+        expected value -> (n_valid, n_in: the cells inside the band)  (cl_eig_build)"""
+        nv, ni = ctypes.c_int64(0), ctypes.c_int64(0)
+        dmax = getattr(self, "_bal_bins", 0) if dmax is None else int(dmax)
+        _lib.check(self._lib.cl_eig_build(self._h, float(clip), dmax, ctypes.byref(nv), ctypes.byref(ni)))
+        return int(nv.value), int(ni.value)
+
+    def eig_apply(self, x):
+        """y = M x for the vectors x: float64 [nb] or [n_vec, nb], 1 <= n_vec <= CL_EIG_BLOCK; the invalid bins of x read as 0 -> y of
+        the same shape  (cl_eig_apply)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        nb = getattr(self, "_bal_bins", 0)
+        if x.ndim not in (1, 2) or x.shape[-1] != nb:
+            raise ValueError("eig_apply: the vectors need one entry per bin (%d), got shape %s" % (nb, x.shape))
+        n_vec = 1 if x.ndim == 1 else x.shape[0]
+        if not 1 <= n_vec <= _lib.CL_EIG_BLOCK:
+            raise ValueError("eig_apply: needs 1 .. %d vectors, got %d" % (_lib.CL_EIG_BLOCK, n_vec))
+        y = np.zeros_like(x)
+        _lib.check(self._lib.cl_eig_apply(self._h, _vp(x), n_vec, _vp(y)))
+        return y
+
+    def eig_iterate(self, n_eigs=3, max_iters=1000, tol=1e-8):
+        """K27: subspace iteration for the n_eigs (1 .. CL_EIG_MAX) eigenpairs of M of largest |lambda|, until every residual |M v -
+        lambda v| is at most tol |lambda_0| or max_iters iterations are done -> (iters, converged, eigvals float64 [n_eigs] by |lambda|
+        descending, resid float64 [n_eigs]); NaN where there are fewer valid bins than n_eigs.  The vectors stay on the device for
+        eig_vectors  (cl_eig_iterate)"""
+        n_eigs = int(n_eigs)
+        if not 1 <= n_eigs <= _lib.CL_EIG_MAX:
+            raise ValueError("eig_iterate: n_eigs must lie in [1, %d], got %d" % (_lib.CL_EIG_MAX, n_eigs))
+        it, cv = ctypes.c_int32(0), ctypes.c_int32(0)
+        lam, res = np.full(n_eigs, np.nan), np.full(n_eigs, np.nan)
+        _lib.check(self._lib.cl_eig_iterate(self._h, n_eigs, int(max_iters), float(tol), ctypes.byref(it), ctypes.byref(cv), _vp(lam), _vp(res)))
+        return int(it.value), bool(cv.value), lam, res
+
+    def eig_vectors(self, which=0, first=0, count=None):
+        """entries [first, first + count) of vector `which` of the last eig_iterate (all from `first` on by default) -> float64: unit
+        2-norm over the valid bins, NaN on the others, the entry of largest magnitude positive  (cl_eig_vectors_get)"""
+        return self._get(self._lib.cl_eig_vectors_get, "_bal_bins", first, count, (np.float64,), int(which))[0]
+
+    def eig_free(self):
+        """releases the matrix, the vectors and the device scratch of the eig_* calls; everything up to the expected values stays
+        (cl_eig_free)"""
+        _lib.check(self._lib.cl_eig_free(self._h))
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

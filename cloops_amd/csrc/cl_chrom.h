@@ -9,7 +9,7 @@
 //   cl_chrom::Run   the working set of the run BEING ENQUEUED (c->run): where its sorted arrays and K2 words live, its traversal
 //                   level, what its kernels have done already.  Assigned fresh by run_begin() at the start of every run, read by
 //                   nobody after the enqueue (the developer build's cl_debug_time_lists aside).
-//   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K26
+//   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K27
 //                   state that outlives a run: one struct each, the buffers together with the flags that say what they hold, and
 //                   one invalidate() where several flags fall together.
 // What reports on the LAST run (last_k2_mode, dbg_g / dbg_nm, refused_labelled, the slots) stays in the handle: callers read it
@@ -349,6 +349,21 @@ struct cl_chrom {
             long long nd = 0, n_used = 0;
         } st;
     } ex;
+    // K27 (k_eig.hip): the value of every cell inside the band in both orders (min(O/E, clip), 0 outside), the row pointers of both
+    // orders, the prefix sums of a block inside the scan's tiles, the tile totals and their exclusive sums, the counter of the cells
+    // inside the band; the blocks of the iteration (Q, Z, Y, the first pass of an orthonormalisation, the Ritz vectors), the partial
+    // sums of its reductions, the 8 x 8 coefficients and the loop's record, the result vectors; the staging and the two blocks of a
+    // cl_eig_apply.  Kept from cl_eig_build to the next one, cl_eig_free, anything that releases or rebuilds K26's state (exp_release,
+    // cl_exp_diagonals, cl_exp_set) or destruction
+    struct Eig {
+        DevBuf val, rows, pl, tot, ctr, q, part, sm, vec, io, ax;
+        struct State {
+            bool built = false, iterated = false;                        // M is described; cl_eig_iterate has run since
+            double clip = 0.0;
+            long long dmax = 0, n_valid = 0, n_in = 0;
+            int n_eigs = 0;                                              // the vectors cl_eig_vectors_get serves
+        } st;
+    } eg;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
     int copy_mode = 0;                // 0: the D2H copies of a run go through copy_stream, 1: they are issued in `stream` (caller's stream),
@@ -419,14 +434,15 @@ Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
 int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* d_M);
 // A unit drops its buffers and its state by assigning a fresh struct, and with them what was made from them: K25's marginals and
-// weights belong to K24's cells, K26's diagonals to K25's marginals and weights.  Called by the units' entry points; the handle's
-// destruction needs none of them
+// weights belong to K24's cells, K26's diagonals to K25's marginals and weights, K27's matrix to K26's expected values.  Called by
+// the units' entry points; the handle's destruction needs none of them
 static inline void track_release(cl_chrom* c) { c->tk = cl_chrom::Track(); }
 static inline void cov_release(cl_chrom* c) { c->cv = cl_chrom::Cov(); }
 static inline void peak_release(cl_chrom* c) { c->pk = cl_chrom::Peak(); }
 static inline void dom_release(cl_chrom* c) { c->dm = cl_chrom::Dom(); }
 static inline void kdis_release(cl_chrom* c) { c->kd = cl_chrom::Kdis(); }
-static inline void exp_release(cl_chrom* c) { c->ex = cl_chrom::Exp(); }
+static inline void eig_release(cl_chrom* c) { c->eg = cl_chrom::Eig(); }
+static inline void exp_release(cl_chrom* c) { eig_release(c); c->ex = cl_chrom::Exp(); }
 static inline void bal_release(cl_chrom* c) { exp_release(c); c->bl = cl_chrom::Bal(); }
 static inline void mat_release(cl_chrom* c) { c->mx = cl_chrom::Mat(); bal_release(c); }
 // what a unit's cl_*_free entry point does around its release function

@@ -637,6 +637,65 @@ int cl_exp_cells_get(cl_chrom* c, int64_t first, int64_t count, double* oe);
 int cl_exp_free(cl_chrom* c);
 
 /*
+ * Compartments (K27): the leading eigenpairs of the chromosome's O/E matrix minus one -- the A/B compartment track, what `cooltools
+ * eigs-cis` computes -- by subspace iteration over the cells resident on the device.  The reference has no counterpart, so these
+ * definitions are the specification (tests/compartments_cases.py restates them in numpy); the orientation of the vectors, the clip's
+ * percentile, the texts and the files stay on the host (cloops_amd/compartments.py).
+ *
+ * Input: the state after cl_mat_cells(fold = 1), cl_bal_marginals, cl_exp_diagonals (either mode) and cl_exp_set: the cells (bx, by,
+ * cnt), the bins b0 .. b0 + nb - 1, K26's validity of a bin and its w, ign = ignore_diags and expected[d].  From the caller: clip (fp64,
+ * > 0, or +inf) and dmax, ign <= dmax <= nb; the diagonals at or beyond dmax take no part.
+ * The symmetric matrix M (nb x nb):
+ *   M[i][j] = min(oe(i, j), clip) - 1   where both bins are valid and ign <= |i - j| < dmax,
+ *   M[i][j] = 0                         everywhere else;
+ *   oe(i, j) is K26's O/E of the cell of the two bins, ((w[bx] cnt) w[by]) / expected[by - bx], in that order of operations, and 0
+ *   without a cell (the entry is then -1).  A diagonal cell counts once.
+ * M is never stored densely.  M = S - B: S the sparse matrix of min(oe, clip) over the used cells inside the band, B the 0/1 matrix of
+ * the valid pairs inside the band; (B x)[i] is a difference of prefix sums of valid x, at most four look-ups per bin.
+ * cl_eig_build refuses expected values that are NaN, infinite or <= 0 on a diagonal ign <= d < dmax that holds at least one valid pair:
+ * the host picks dmax so that there is none.
+ *
+ * Result of cl_eig_iterate, 1 <= n_eigs <= CL_EIG_MAX: the n_eigs eigenpairs of M of largest |lambda|, ordered by |lambda| descending,
+ * the sign of lambda kept.  A vector has unit 2-norm over the valid bins and NaN on the others; its sign makes its entry of largest
+ * magnitude positive (the lowest bin on a tie).  resid[k] = |M v_k - lambda_k v_k|_2; *converged iff every resid[k] <= tol |lambda_0|.
+ * With fewer than n_eigs valid bins there are n_valid pairs and the others are NaN (values, residuals and vectors).  Without a valid
+ * bin, and with max_iters = 0: 0 iterations, not converged, everything NaN.
+ * Method: subspace iteration on a block Q of CL_EIG_BLOCK orthonormal columns (n_valid of them when there are fewer valid bins).  An
+ * iteration is Z = M Q; H = Q^T Z; the Ritz pairs (lambda, W) of the 8 x 8 H by cyclic Jacobi; v = Q W with the residuals |Z W - Q W
+ * lambda|; Q = the orthonormalised Z W (Gram-Schmidt, twice).  The start block is a fixed integer hash of (column, bin); a column that
+ * vanishes under the projections (its remainder below 2^-40 of its squared norm) is replaced by the next hash vector and
+ * orthogonalised.  M = 0 gives eigenvalues 0, orthonormal vectors and *converged after one iteration.  Every sum is taken in an order
+ * that depends on the cells, nb and the block alone: two calls on the same input give the same bytes; no fp64 atomics.
+ *
+ * cl_eig_build -- the values of the cells inside the band in both orders and their row pointers -> *n_valid, *n_in (the cells inside
+ * the band: used, ign <= by - bx < dmax).
+ * cl_eig_apply -- y = M x for n_vec vectors, x and y n_vec x nb row-major, 1 <= n_vec <= CL_EIG_BLOCK; the invalid bins of x read as 0,
+ * those of y are 0.  Leaves the result of cl_eig_iterate alone.
+ * cl_eig_iterate -- at most max_iters iterations -> *iters, *converged, eigval and resid (n_eigs values each); the vectors stay on
+ * the device.  May be repeated with other arguments.
+ * cl_eig_vectors_get -- entries [first, first + count) inside [0, nb] of vector `which`, 0 <= which < the n_eigs of the last
+ * cl_eig_iterate.
+ * cl_eig_free -- releases the state (cells, marginals, weights, diagonals and expected values stay).  The next cl_eig_build,
+ * cl_exp_set, cl_exp_diagonals, cl_exp_free and everything that releases K26's state release it as well.
+ *
+ * nb == 0 is not an error (dmax must then be 0): n_valid = n_in = 0, 0 iterations, NaN values, and calls of count 0 succeed with NULL
+ * arrays.  Errors:
+ * CL_ERR_ARG, found on the host before any launch, scalar outputs zeroed and the earlier state left usable, for a NULL handle or NULL
+ * outputs, any call before cl_exp_set, clip not above 0 or NaN, dmax outside [ign, nb], the rule on the expected values, nb >
+ * CL_EIG_BINS_MAX, n_eigs or n_vec out of range, max_iters < 0, tol < 0 or NaN, cl_eig_apply, cl_eig_iterate or cl_eig_vectors_get
+ * before cl_eig_build, cl_eig_vectors_get before cl_eig_iterate, `which` or a range outside, or runs in flight.
+ */
+#define CL_EIG_MAX 6
+#define CL_EIG_BLOCK 8
+#define CL_EIG_BINS_MAX 1048576
+int cl_eig_build(cl_chrom* c, double clip, int64_t dmax, int64_t* n_valid, int64_t* n_in);
+int cl_eig_apply(cl_chrom* c, const double* x, int32_t n_vec, double* y);
+int cl_eig_iterate(cl_chrom* c, int32_t n_eigs, int32_t max_iters, double tol, int32_t* iters, int32_t* converged, double* eigval,
+                   double* resid);
+int cl_eig_vectors_get(cl_chrom* c, int32_t which, int64_t first, int64_t count, double* v);
+int cl_eig_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
