@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import golden_util as G
+import sig_cases as S
 from test_quant import GOLD, QUANT_GOLD, brute_counts, _read
 
 pytestmark = pytest.mark.gpu
@@ -131,6 +132,26 @@ def test_between_sweep_steps():
         ch.close()
         return out
     assert sweep(True) == sweep(False)
+
+
+SIG_CASE_CUTS = [(name, k) for name in S.QUANT_NAMES for k in range(3)]
+
+
+@pytest.mark.parametrize("name_k", SIG_CASE_CUTS, ids=lambda p: "%s-%s" % (p[0], ("cut0", "part", "none")[p[1]]))
+def test_cases_of_sig_counts(name_k):
+    """K8's edge cases through K11: the Y-side halves of ra and rb meet reversed rows, negative coordinates, the ends of int32 and
+    slices around the workgroup's stride; at the cut that keeps no row the table is all zero"""
+    from cloops_amd import api
+    c = S.case(name_k[0])
+    cut = S.cuts_of(c)[name_k[1]]
+    ch = api.Chromosome(c.X, c.Y)
+    got = _check(ch, c.X, c.Y, c.windows, cut)
+    if name_k[1] == 2:
+        assert not got.any() and ch.quant_counts(c.windows, cut)[1] == 0
+    else:
+        k8, n8 = ch.sig_counts(c.windows, cut)                              # same handle, same sorted tables
+        assert np.array_equal(got[:, 0], k8[:, 0]) and np.array_equal(got[:, 1], k8[:, 11]) and np.array_equal(got[:, 2], k8[:, 22])
+    ch.close()
 
 
 def _io_dirs(root):
