@@ -97,6 +97,7 @@ PROTOTYPES = {
     "cl_last_n_labelled": (_i64, [_vp]),
     "cl_last_n_in": (_i64, [_vp]),
     "cl_last_region_mode": (_int, [_vp]),
+    "cl_base_rows": (_i64, [_vp]),
     "cl_get_boxes": (_int, [_vp, _vp]),
     "cl_boxes_host": (_vp, [_vp]),
     "cl_labels_device": (_vp, [_vp]),

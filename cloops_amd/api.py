@@ -256,6 +256,11 @@ class Chromosome(_Handle):
         """0 = the last enqueued run did a full region query, 1 = re-used the kept words, 2 = re-used them outside the cut band"""
         return int(self._lib.cl_last_region_mode(self._h))
 
+    def base_rows(self):
+        """rows of the handle's current base layout (cl_base_rows): fewer than len(self) while a sweep's layout leaves out the rows far
+        below the chain's cut, len(self) otherwise"""
+        return int(self._lib.cl_base_rows(self._h))
+
     def set_layout_reuse(self, on=True):
         """keep the sorted arrays of the last eps and start further runs at that eps from a compaction by the cut
         (default on; results identical either way -- cl_set_layout_reuse of include/cloops_hip.h)"""

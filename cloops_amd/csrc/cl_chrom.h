@@ -100,6 +100,7 @@ struct cl_chrom {
     // the fine layout (cl_set_eps_list): rows sorted by (strip of width w, q) once; the layout of an eps = k w is a per-strip merge of it
     struct Fine {
         DevBuf q, sp, row, strip;
+        DevBuf dead;                  // a layout with a floor: per fine strip the rows below it, and their exclusive sums
         int w = 0;                    // announced common divisor of the sweep's eps values (0: none)
         int valid_w = 0, layout = -1; // what the buffers hold
         GridParams g;
@@ -139,12 +140,20 @@ struct cl_chrom {
     // eps is one stable stream compaction of the base layout instead of five radix passes (cLoops/pipe.py:241-281
     // walks eps in the outer loop).  Nothing of a result is kept: neighbour counts, components, labels are redone.
     // ... and variant 2's cell minima of it (key: traversal level 4, once per eps)
+    // Inside an announced sweep a layout that is built for a run under a cut leaves out the rows far below that cut (floor_q > 0:
+    // the rows with q < floor_q, a prefix of every strip -- exactly what a cut removes): every later run of the eps whose
+    // threshold is >= floor_q treats those rows as absent anyway, and no pass over base positions reads them again.  A run below
+    // the floor (a cut that fell, no cut, exact counts) rebuilds the layout with floor 0 (run_sort_and_count).
     struct Base {
         DevBuf q, sp, row, strip, tile, key;
         bool valid = false; int layout = -1, eps = 0;
         bool key_valid = false;       // `key` belongs to the layout
-        void invalidate() { valid = false; key_valid = false; }
+        int floor_q = 0;              // the layout holds the rows with q >= floor_q only (0: all rows)
+        int rows = 0;                 // ... their number: the base positions are [0, rows)
+        long long pad_rows = -1;      // `rows` the sentinel pads behind q / sp were last written for (-1: never)
+        void invalidate() { valid = false; key_valid = false; floor_q = 0; }
     } base;
+    bool sweep_planned = false;       // cl_sweep_plan announced a sweep (a non-empty eps list): its layouts may carry a floor
     DevBuf sel_tmp;
     // Count cache: the K2 words (cl_common.h "K2W") of the FIRST run on a base layout, kept while the layout lives.  A word
     // holds the PET's neighbour count (saturated at `cap`, exact as far as the minPts values of `tmask` need it: GridParams::tmask) and does not depend on minPts otherwise;
@@ -389,6 +398,12 @@ struct cl_chrom {
 
 // first thing of every run (run_rotated, run_block, run_weighted, cl_neighbor_counts): a fresh working set
 static inline void run_begin(cl_chrom* c) { c->run = cl_chrom::Run(); }
+// base positions of the current base layout (all rows, or those above its floor)
+static inline int base_rows(const cl_chrom* c) { return c->base.valid ? c->base.rows : (int)c->n; }
+// the floor of a layout built under cut `c` is the distance c * CL_FLOOR_NUM / CL_FLOOR_DEN: the chained cuts of a sweep never
+// fell below 0.6 of an earlier one (docs/history_r1-r4.md), and nearly all rows below a Hi-C cut lie below half of it too
+#define CL_FLOOR_NUM 1
+#define CL_FLOOR_DEN 2
 
 // A run that fails half-way (allocation, a HIP error between two launches) must not leave state behind that a later run would
 // trust: the count cache it may have marked valid before its words were written, the tickets of the in-kernel scans and the

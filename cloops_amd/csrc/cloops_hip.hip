@@ -306,12 +306,34 @@ struct SplitOut {                                       // output iterator: valu
 // distances of one strip (by run instead of by input row: no kernel reads that order).  One pass of 12 B/PET in, 12 B/PET out instead of two
 // radix passes + histogram + the sort's own resets.
 // ------------------------------------------------------------------------------------------
-__global__ void k_strips_from_fine(int S, int s0, int k, int F, int f0, const int* __restrict__ fstrip, int n, int* __restrict__ strip_start)
+//
+// A layout with a FLOOR (cl_chrom::Base::floor_q > 0) holds the rows with q >= floor_q only.  Inside a fine strip the rows are in q
+// order, so the floor removes a prefix of every fine strip: k_fine_dead finds its length by a lower bound inside the strip, an
+// exclusive scan over the fine strips gives deadpre[f] = rows below the floor in the fine strips in front of f (deadpre[F]: all of
+// them), and both kernels below subtract it -- the strip table counts kept rows only, and a kept PET's place is its place among
+// all rows minus the removed rows of its own and of all earlier strips (every one of them has q' < floor_q <= q: they were all
+// counted in front of it).  `rows` = n - deadpre[F], known on the host from the upload's distance histogram.  deadpre == null
+// (floor_q == 0): every row, as before.
+__global__ void k_fine_dead(int F, int floor_q, const int* __restrict__ fstrip, const int* __restrict__ fq, int* __restrict__ dead)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f > F) return;
+    int lo = 0, b = 0;
+    if (f < F) {
+        b = lo = fstrip[f];
+        int hi = fstrip[f + 1];
+        while (lo < hi) { const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1); if (fq[mid] < floor_q) lo = mid + 1; else hi = mid; }
+    }
+    dead[f] = lo - b;                                     // (dead[F] = 0: the scan leaves the total there)
+}
+__global__ void k_strips_from_fine(int S, int s0, int k, int F, int f0, const int* __restrict__ fstrip, int rows, int* __restrict__ strip_start,
+                                   const int* __restrict__ deadpre /* or null */)
 {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s > S + 1) return;
     const long long f = (long long)k * ((long long)s + s0) - f0;
-    strip_start[s] = s >= S ? n : fstrip[(int)std::min<long long>(std::max<long long>(f, 0), F)];
+    const int fc = (int)std::min<long long>(std::max<long long>(f, 0), F);
+    strip_start[s] = s >= S ? rows : fstrip[fc] - (deadpre ? deadpre[fc] : 0);
 }
 #define LFF_T 1024               // PETs of the fine layout per workgroup
 #define LFF_CAP 4096             // staged entries: the strips a tile's PETs belong to, whole (a tile + one strip on either side)
@@ -319,7 +341,8 @@ __global__ void k_strips_from_fine(int S, int s0, int k, int F, int f0, const in
 #define LFF_PAD 512              // keys of all ones behind them: unclamped probes of searches up to 9 steps deep
 __global__ void __launch_bounds__(256)
 k_layout_from_fine(int n, GridParams g, GridParams gf, int k, unsigned kmagic, int qb, const int* __restrict__ fq, const int* __restrict__ fsp, const u32* __restrict__ frow,
-                   const int* __restrict__ fstrip, int* __restrict__ dq, int* __restrict__ dsp, u32* __restrict__ drow, int* __restrict__ dtile)
+                   const int* __restrict__ fstrip, int* __restrict__ dq, int* __restrict__ dsp, u32* __restrict__ drow, int* __restrict__ dtile,
+                   int floor_q, const int* __restrict__ deadpre /* or null: no floor */)
 {
     __shared__ int lq[LFF_CAP + LFF_PAD];
     const int t0 = blockIdx.x * LFF_T, t1 = min(n, t0 + LFF_T);
@@ -336,6 +359,7 @@ k_layout_from_fine(int n, GridParams g, GridParams gf, int k, unsigned kmagic, i
         in[e] = i < t1;
         const int ic = in[e] ? i : t0;
         q[e] = fq[ic]; row[e] = frow[ic]; spf[e] = fsp[ic];
+        in[e] = in[e] && q[e] >= floor_q;                 // (a row below the layout's floor has no place in it: it searches and stores nothing)
     }
     // the strips (of width eps) the tile's first and last PET belong to are contiguous in the fine layout: [a, b) holds every run
     // any PET of the tile has to be ranked in
@@ -374,6 +398,8 @@ k_layout_from_fine(int n, GridParams g, GridParams gf, int k, unsigned kmagic, i
         r[e] = fabs - sabs * k;                          // ... and the PET's run inside it
         fbase[e] = sabs * k - gf.s0;                     // table row of the strip's first run (< 0: runs in front of the chromosome's first strip)
         dst[e] = in[e] ? fst(max(fbase[e], 0)) + (i - fst(f)) : 0;
+        // (the rows the floor removes from the fine strips up to the end of the PET's strip: fbase + k > f >= 0)
+        if (deadpre && in[e]) dst[e] -= deadpre[min(fbase[e] + k, gf.S)];
     }
 #ifdef CLOOPS_DEVEL
     const int kk_abl = (g.dbg2 & (1 << 12)) ? 0 : k;      // (ablation: no searches)
@@ -2156,6 +2182,7 @@ extern "C" void cl_set_layout_reuse(cl_chrom* c, int enabled) { if (c) { c->reus
 extern "C" void cl_set_count_reuse(cl_chrom* c, int enabled) { if (c) { c->reuse_counts = enabled != 0; c->rc.invalidate(); } }
 extern "C" void cl_set_traversal(cl_chrom* c, int level) { if (c) { c->traversal = level < 0 ? 0 : (level > 4 ? 4 : level); c->rc.invalidate(); } }
 extern "C" int cl_last_region_mode(const cl_chrom* c) { return c ? c->last_k2_mode : 0; }
+extern "C" int64_t cl_base_rows(const cl_chrom* c) { return c ? (int64_t)base_rows(c) : -1; }
 // Forget everything the handle has DERIVED from its rows -- the q index, the fine layout, the base layout of the last eps, the
 // cached neighbour counts -- and keep every allocation: the next run pays what the first run on a freshly uploaded dataset pays
 // for its orders, without the allocations of a new handle (bench.py `cold_sweep_s`: a dataset is swept once, pipe.py:247-275).
@@ -2228,6 +2255,7 @@ extern "C" int cl_sweep_plan(cl_chrom* c, const int32_t* eps, int32_t n_eps, con
     // (layout reuse, count reuse and the traversal level are left as they are: all three are on / 4 by default, and a caller that
     //  switched one off -- the tests of the older levels, the measurements without re-use -- meant it)
     cl_set_count_thresholds(c, min_pts, n_min_pts);
+    c->sweep_planned = n_eps > 0;                         // (its layouts may leave out the rows far below the chain's cut: Base::floor_q)
     int distinct = 0;
     for (int k = 0; k < n_eps; ++k) { bool seen = false; for (int j = 0; j < k; ++j) seen |= eps[j] == eps[k]; distinct += seen ? 0 : 1; }
     if (distinct > 1) { cl_set_sort_index(c, 1); cl_set_eps_list(c, eps, n_eps); }
@@ -2520,7 +2548,7 @@ k_cut_strips(int S, int thr, const int* __restrict__ bstrip, const int* __restri
 // PETs, hidden behind the copy instead of a launch of its own) -- each of their four waves takes KB_SB strips.
 template <bool BAND>
 __global__ void __launch_bounds__(CMP_TPB)
-k_cut_copy(int n, int S, int rbits, int thr, const int* __restrict__ bq, const int* __restrict__ bsp, const u32* __restrict__ brow,
+k_cut_copy(int n /* rows of the handle: what the run's arrays are sized for */, int nbase /* positions of the base layout */, int S, int rbits, int thr, const int* __restrict__ bq, const int* __restrict__ bsp, const u32* __restrict__ brow,
            const int* __restrict__ src0, const int* __restrict__ sloc, const int* __restrict__ sboffs /* the new strip table, two-level (k_cut_strips) */,
            int* __restrict__ strip_start /* [0..S+1]: the table in one piece, written here for everything that follows */,
            int* __restrict__ sv, int* __restrict__ sa, u32* __restrict__ srow, int* __restrict__ tile_s0, int* __restrict__ d_M,
@@ -2546,8 +2574,8 @@ k_cut_copy(int n, int S, int rbits, int thr, const int* __restrict__ bq, const i
 #pragma unroll
     for (int k = 0; k < CMP_PER; ++k) {
         const int i = base + k * CMP_TPB + (int)threadIdx.x;
-        q[k] = i < n ? bq[i] : INT_MIN;
-        keep[k] = i < n && q[k] >= thr;
+        q[k] = i < nbase ? bq[i] : INT_MIN;
+        keep[k] = i < nbase && q[k] >= thr;
     }
 #pragma unroll
     for (int k = 0; k < CMP_PER; ++k) {
@@ -2574,7 +2602,7 @@ k_cut_copy(int n, int S, int rbits, int thr, const int* __restrict__ bq, const i
         const int st = sloc[u] + sboffs[u >> 8];
         strip_start[u] = st;
         if (poff_out || poff_ref) {
-            const int po = (u < S ? src0[u] : n) - st;
+            const int po = (u < S ? src0[u] : nbase) - st;
             if (poff_out) poff_out[u] = po; else D_out[u] = po - poff_ref[u];
         }
     }
@@ -2809,9 +2837,12 @@ static int strip_maxlen(cl_chrom* c, const GridParams& g, int* out)
 
 // K0 + K1: keys, sort, strip table, decoded sorted arrays for the rows that pass `g.cut`, written to the given
 // destination buffers (sorted arrays with their sentinel pads already in place)
+// floor_q > 0 (with g.cut == 0): the caller would like the layout without the floor_rows rows with q >= floor_q only; *floored says
+// whether it got that (the merge from the fine layout can leave rows out, a sort cannot)
 static int sort_layout(cl_chrom* c, const GridParams& g, int* dsv, int* dsa, u32* drow /* or null: c->run.srow aliases a sort buffer */,
-                       int* dstrip, int* dtile)
+                       int* dstrip, int* dtile, int floor_q = 0, int floor_rows = 0, bool* floored = nullptr)
 {
+    if (floored) *floored = false;
     const int n = (int)c->n;
     const int sh = g.qbits + g.rbits, strip_bits = std::max(1, bits_for((unsigned)g.S));
     // the q index: built at the handle's second sort (or its first, if the caller announced several: cl_set_sort_index)
@@ -2877,12 +2908,30 @@ static int sort_layout(cl_chrom* c, const GridParams& g, int* dsv, int* dsa, u32
                 if (c->fine.w > 0) {
                     const GridParams& gf = c->fine.g;
                     const int k = g.eps / fw;
-                    LAUNCH(k_strips_from_fine, g.S + 2, g.S, g.s0, k, gf.S, gf.s0, (const int*)c->fine.strip.as<int>(), n, dstrip);
+                    int rows_kept = n;
+                    const int* deadpre = nullptr;
+                    if (floor_q > 0 && floored) {
+                        // the rows below the floor, per fine strip and summed in front of every fine strip
+                        const size_t nf = (size_t)gf.S + 1;
+                        if ((rc = c->fine.dead.ensure(2 * nf * 4))) return rc;
+                        int* dead = c->fine.dead.as<int>();
+                        int* dpre = dead + nf;
+                        size_t need = 0;
+                        hipError_t e = rocprim::exclusive_scan(nullptr, need, dead, dpre, 0, nf, rocprim::plus<int>(), c->stream);
+                        if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan size query (layout floor)", hipGetErrorString(e));
+                        if (need > c->scan_tmp.bytes && (rc = c->scan_tmp.ensure(need))) return rc;
+                        LAUNCH(k_fine_dead, gf.S + 1, gf.S, floor_q, (const int*)c->fine.strip.as<int>(), (const int*)c->fine.q.as<int>(), dead);
+                        size_t tb = c->scan_tmp.bytes;
+                        e = rocprim::exclusive_scan(c->scan_tmp.p, tb, dead, dpre, 0, nf, rocprim::plus<int>(), c->stream);
+                        if (e != hipSuccess) return fail(CL_ERR_HIP, "exclusive_scan (layout floor)", hipGetErrorString(e));
+                        deadpre = dpre; rows_kept = floor_rows; *floored = true;
+                    }
+                    LAUNCH(k_strips_from_fine, g.S + 2, g.S, g.s0, k, gf.S, gf.s0, (const int*)c->fine.strip.as<int>(), rows_kept, dstrip, deadpre);
                     // (q + 1 -- the tie-break key -- must fit the q field of the sorted keys: qb bits; 0 = the field would leave no room for runs)
                     int qb = bits_for((unsigned)std::min<long long>((long long)gf.qtop + 1, 0x7fffffffLL));
                     if (qb > 28) qb = 0;
                     hipLaunchKernelGGL(k_layout_from_fine, dim3(nblocks(n, LFF_T)), dim3(256), 0, c->stream, n, g, gf, k, (unsigned)(((1ull << 32) + (unsigned)k - 1ull) / (unsigned)k), qb, (const int*)c->fine.q.as<int>(),
-                                       (const int*)c->fine.sp.as<int>(), (const u32*)c->fine.row.as<u32>(), (const int*)c->fine.strip.as<int>(), dsv, dsa, rows, dtile);
+                                       (const int*)c->fine.sp.as<int>(), (const u32*)c->fine.row.as<u32>(), (const int*)c->fine.strip.as<int>(), dsv, dsa, rows, dtile, deadpre ? floor_q : 0, deadpre);
                     HIP_TRY(hipGetLastError());
                     c->run.srow = rows;
                     return CL_OK;
@@ -2949,27 +2998,46 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
         c->run.sv = wsv; c->run.sa = wsa; c->run.strip = c->strip.as<int>(); c->run.tile = c->tile_s0.as<int>();
     } else {
         const int layout = (g.variant == CL_VARIANT_CDBSCAN2 ? 2 : 0) | (g.swap ? 1 : 0);
-        if (!c->base.valid || c->base.layout != layout || c->base.eps != g.eps) {
+        const long long dmin = g.swap ? c->st.amin : 0;   // swap == 0 is a developer layout: always compacts
+        const bool on_base = g.cut <= 0 || (g.swap && (long long)g.cut <= dmin);
+        const int thr_new = on_base ? 0 : g.cut - g.V0;   // q >= 0 everywhere: threshold 0 removes nothing
+        const bool same_base = c->base.valid && c->base.layout == layout && c->base.eps == g.eps;
+        // (a run whose threshold lies below the layout's floor needs rows the layout does not hold: rebuilt, with every row)
+        if (!same_base || thr_new < c->base.floor_q) {
             c->base.invalidate();                         // (with variant 2's cell minima)
             c->rc.invalidate();                           // the cached words belong to the layout that is being replaced
             if ((rc = c->base.q.ensure(((size_t)n + 2 * SORT_PAD) * 4)) || (rc = c->base.sp.ensure(((size_t)n + 2 * SORT_PAD) * 4)) ||
                 (rc = c->base.row.ensure((size_t)n * 4)) || (rc = c->base.strip.ensure(((size_t)g.S + 2) * 4)) ||
                 (rc = c->base.tile.ensure(((size_t)n / 256 + 2) * 4))) return rc;
-            if (c->base.q.fresh || c->base.sp.fresh) {
-                hipLaunchKernelGGL(k_init_pads, dim3(nblocks(2 * SORT_PAD)), dim3(TPB), 0, c->stream, c->base.q.as<int>(), c->base.sp.as<int>(), (long long)n);
-                c->base.q.fresh = c->base.sp.fresh = false;
+            // The floor: only a layout that a sweep's run under a cut builds from the fine layout gets one -- the later runs of the eps
+            // then come with cuts of the same chain.  A one-off run, and the rebuild for a run below the floor, keep every row.
+            int floor_q = 0, floor_rows = n;
+            const long long fd = (long long)g.cut * CL_FLOOR_NUM / CL_FLOOR_DEN;      // floor distance
+            const int fw = c->fine.w;
+            if (!same_base && !on_base && !exact && c->sweep_planned && g.swap && fw > 0 && g.eps % fw == 0 && g.eps / fw <= CL_FINE_KMAX &&
+                fd < DCUM_BINS && !c->dcum.empty() && fd - g.V0 > 0) {
+                floor_q = (int)(fd - g.V0);
+                floor_rows = (int)(n - c->dcum[(size_t)fd]);      // (from the upload's distance histogram, like run.m)
             }
             GridParams g0 = g;
             g0.cut = 0;
+            bool floored = false;
             if ((rc = sort_layout(c, g0, c->base.q.as<int>() + SORT_PAD, c->base.sp.as<int>() + SORT_PAD, c->base.row.as<u32>(),
-                                  c->base.strip.as<int>(), c->base.tile.as<int>()))) return rc;
+                                  c->base.strip.as<int>(), c->base.tile.as<int>(), floor_q, floor_rows, &floored))) return rc;
+            c->base.floor_q = floored ? floor_q : 0;
+            c->base.rows = floored ? floor_rows : n;
+            if (c->base.q.fresh || c->base.sp.fresh || c->base.pad_rows != c->base.rows) {
+                // the sentinels stand right behind the layout's last row: rewritten whenever that place moves
+                hipLaunchKernelGGL(k_init_pads, dim3(nblocks(2 * SORT_PAD)), dim3(TPB), 0, c->stream, c->base.q.as<int>(), c->base.sp.as<int>(), (long long)c->base.rows);
+                c->base.q.fresh = c->base.sp.fresh = false;
+                c->base.pad_rows = c->base.rows;
+            }
             c->base.valid = true; c->base.layout = layout; c->base.eps = g.eps;
         } else {
             ev_record(c, 0);
             ev_record(c, 1);
         }
-        const long long dmin = g.swap ? c->st.amin : 0;   // swap == 0 is a developer layout: always compacts
-        const bool on_base = g.cut <= 0 || (g.swap && (long long)g.cut <= dmin);
+        const int nbase = c->base.rows;                   // base positions (n, or the rows above the layout's floor)
         // ---- count cache (cl_chrom::rc): what this run does about its K2 words -------------------------------------
         //   make : the run's K2 writes the cache (first clustering run on this layout, or one the cached words cannot serve)
         //   same : same cut as the run that made the words -- nothing to do, the consumers read the cache
@@ -2977,7 +3045,6 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
         //          its place in the layout the words were made on (WordSrc)
         const int m1 = g.minPts - 1;
         const bool cacheable = !exact && c->reuse_counts && g.swap && m1 >= 1 && m1 <= 127;
-        const int thr_new = on_base ? 0 : g.cut - g.V0;   // q >= 0 everywhere: threshold 0 removes nothing
         enum { RC_NONE, RC_MAKE, RC_SAME, RC_REMAP } rcmode = RC_NONE;
         // traversal level 4 (lists from the base layout, count cache in base-position space) needs the cache: a run it does not take
         // (exact counts, minPts outside 2 .. 128, cache switched off) works on a copy of the layout as before
@@ -3059,8 +3126,8 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
             if (!g.swap) return fail(CL_ERR_ARG, "internal: layout reuse needs the v-band layout");
             // stable compaction of the base layout by d = q + V0 >= cut (pipe.py:59-62): same order as sorting the
             // filtered rows, one pass over 12 B/PET
-            const int nb = nblocks(n, CMP_BLOCK);
-            const int nblk = nblocks(g.S + 1, 256);       // workgroups of k_cut_strips = blocks of the two-level strip table
+            const int nb = nblocks(std::max(1, nbase), CMP_BLOCK);
+            const int nblk = nblocks(g.S + 1, 256);     // workgroups of k_cut_strips = blocks of the two-level strip table
             if ((rc = c->sel_tmp.ensure(((size_t)g.S + 2) * 8 + ((size_t)nblk + 2) * 8 + 64))) return rc;
             int* sloc = c->sel_tmp.as<int>();
             int* src0 = sloc + g.S + 2;
@@ -3097,12 +3164,12 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
             } else
             if (rcmode == RC_REMAP) {
                 const int nbb = nblocks(nblocks(g.S, KB_SB), CMP_TPB / 64);      // workgroups that do K2 on the cut band (four waves of KB_SB strips each)
-                hipLaunchKernelGGL(k_cut_copy<true>, dim3(nbb + nb), dim3(CMP_TPB), 0, c->stream, n, g.S, g.rbits, thr, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
+                hipLaunchKernelGGL(k_cut_copy<true>, dim3(nbb + nb), dim3(CMP_TPB), 0, c->stream, n, nbase, g.S, g.rbits, thr, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
                                    (const u32*)c->base.row.as<u32>(), (const int*)src0, (const int*)sloc, (const int*)sboffs, c->strip.as<int>(), wsv, wsa, c->vals_out.as<u32>(), c->tile_s0.as<int>(),
                                    d_M, c->run.m_exact ? c->run.m : -1, c->counters.as<int>(), (int*)nullptr, (const int*)c->rc.poff.as<int>(), c->rc.D.as<int>(),
                                    nbb, (const int2*)c->rc.blen.as<int2>(), c->cnt.as<int>(), g.eps, g.minPts, g.dbg);
             } else
-            hipLaunchKernelGGL(k_cut_copy<false>, dim3(nb), dim3(CMP_TPB), 0, c->stream, n, g.S, g.rbits, thr, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
+            hipLaunchKernelGGL(k_cut_copy<false>, dim3(nb), dim3(CMP_TPB), 0, c->stream, n, nbase, g.S, g.rbits, thr, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
                                (const u32*)c->base.row.as<u32>(), (const int*)src0, (const int*)sloc, (const int*)sboffs, c->strip.as<int>(), wsv, wsa, c->vals_out.as<u32>(), c->tile_s0.as<int>(),
                                d_M, c->run.m_exact ? c->run.m : -1, c->counters.as<int>(), rcmode == RC_MAKE ? c->rc.poff.as<int>() : (int*)nullptr,
                                (const int*)nullptr, (int*)nullptr, 0, (const int2*)nullptr, (int*)nullptr, 0, 0, 0);
@@ -3118,8 +3185,10 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
         GridParams g0 = gk;
         g0.cut = 0;
         g0.qmin = c->rc.thr;
-        rc = cl_launch_region(c->stream, g0, n, n, false, c->base.q.as<int>() + SORT_PAD, c->base.sp.as<int>() + SORT_PAD, c->base.strip.as<int>(), c->base.tile.as<int>(),
-                              c->rc.cnt.as<int>());
+        const int nbase = c->base.rows;
+        if (nbase > 0)                                    // (a floor above every row: nothing to query)
+            rc = cl_launch_region(c->stream, g0, nbase, nbase, false, c->base.q.as<int>() + SORT_PAD, c->base.sp.as<int>() + SORT_PAD, c->base.strip.as<int>(),
+                                  c->base.tile.as<int>(), c->rc.cnt.as<int>());
         c->slot[c->cur].n_queried = c->run.m;             // (the PETs that got a word: those the cut keeps)
     } else if (!k2_skip && !k2_band && !SKIP(256)) {
         rc = cl_launch_region(c->stream, gk, n, c->run.m, exact, c->run.sv, c->run.sa, c->run.strip, c->run.tile, c->run.cnt);

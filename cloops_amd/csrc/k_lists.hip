@@ -2081,10 +2081,10 @@ int lists_build(cl_chrom* c, const GridParams& g, int nm, ListRun* out)
 
 int lists_base_keys(cl_chrom* c, const GridParams& g)
 {
-    const int n = (int)c->n;
-    int rc = c->base.key.ensure((size_t)n * 4);
+    const int n = base_rows(c);                           // base positions
+    int rc = c->base.key.ensure((size_t)c->n * 4);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_base_keys, dim3(nblocks(n, LT)), dim3(256), 0, c->stream, g, n, (const int*)(c->base.q.as<int>() + SORT_PAD),
+    if (n > 0) hipLaunchKernelGGL(k_base_keys, dim3(nblocks(n, LT)), dim3(256), 0, c->stream, g, n, (const int*)(c->base.q.as<int>() + SORT_PAD),
                        (const int*)(c->base.sp.as<int>() + SORT_PAD), (const u32*)c->base.row.as<u32>(), c->base.key.as<int>());
     HIP_TRY(hipGetLastError());
     return CL_OK;
@@ -2093,11 +2093,11 @@ int lists_base_keys(cl_chrom* c, const GridParams& g)
 int lists_build_base(cl_chrom* c, const GridParams& g, int nm, ListRun* out)
 {
     fuse_knob(c);
-    const int n = (int)c->n;
+    const int n = base_rows(c);                           // base positions: the rows above the layout's floor
     ListBufs b;
-    int rc = list_bufs(c, g, n, &b);
+    int rc = list_bufs(c, g, std::max(1, n), &b);
     if (rc) return rc;
-    const int nblk = nblocks(n, LT);
+    const int nblk = nblocks(std::max(1, n), LT);         // (no position at all: one tile that finds nothing and leaves the counts)
     const bool v2 = g.variant == CL_VARIANT_CDBSCAN2;
     ListRun L{};
     list_views(c, b, &L);
@@ -2153,8 +2153,8 @@ int lists_build_base(cl_chrom* c, const GridParams& g, int nm, ListRun* out)
 // handle's cache, hints in base positions
 int lists_words_to_base(cl_chrom* c, const GridParams& g)
 {
-    const int n = (int)c->n;
-    LAUNCH(k_words_to_base, n, g, n, (const int*)(c->base.sp.as<int>() + SORT_PAD), (const int4*)c->l_tab.as<int4>(), (const int*)c->rc.poff.as<int>(),
+    const int n = base_rows(c);
+    if (n > 0) LAUNCH(k_words_to_base, n, g, n, (const int*)(c->base.sp.as<int>() + SORT_PAD), (const int4*)c->l_tab.as<int4>(), (const int*)c->rc.poff.as<int>(),
            (const int*)c->cnt.as<int>(), c->rc.cnt.as<int>());
     HIP_TRY(hipGetLastError());
     return CL_OK;
@@ -2216,7 +2216,7 @@ int lists_border(cl_chrom* c, const GridParams& g, int nm, const ListRun& L)
 #ifdef CLOOPS_DEVEL
     { const char* e = getenv("CLOOPS_BCAP"); if (e) kcap = atoi(e); queued = kcap > 0; e = getenv("CLOOPS_BQG"); if (e) bqg = atoi(e); }
 #endif
-    const int nt = nblocks(L.npos, (g.variant == CL_VARIANT_CDBSCAN1 || !queued) ? BNT : BNQ);
+    const int nt = nblocks(std::max(1, L.npos), (g.variant == CL_VARIANT_CDBSCAN1 || !queued) ? BNT : BNQ);      // (no position: one tile that returns at once)
 #define LB_ARGS g, nt, L.npos, L.lcnt, L.cmask, L.cgrank, L.wgrank, (const int2*)L.cpair, (const int*)croot_of(c), (const int*)c->cellfirst.as<int>(),    \
                 (const int*)L.ckey, (const int*)L.cstrip, (const int2*)L.wpair, (const int*)L.wpos, (const int*)L.wenc, (const int*)c->compkey.as<int>(),                    \
                 (const int*)c->ncore.as<int>(), c->owner.as<int>(), c->bsize.as<int>(), c->usize.as<int>(), c->chainflag.as<int>() /* clist: the chain ids are dead */,  \
@@ -2395,7 +2395,7 @@ extern "C" int cl_debug_time_lists(cl_chrom* c, int which, int reps, float* ms_o
             launch_make_lists(c, g, nblk, b, L);
         } else if (which == 6 || which == 7) {
             // level 4 (the last run must have been one with a cut that re-used counts): k_classify_q / k_make_lists_q
-            const int n = (int)c->n;
+            const int n = std::max(1, base_rows(c));
             ListBufs bb;
             if ((rc = list_bufs(c, g, n, &bb))) return rc;
             const int nb4 = nblocks(n, LT);
@@ -2417,12 +2417,12 @@ extern "C" int cl_debug_time_lists(cl_chrom* c, int which, int reps, float* ms_o
             // counters they add to are garbage afterwards)
             ListRun L2 = L;
             c->run.level = c->traversal >= 4 ? 4 : 3;
-            if (c->run.level == 4) { ListBufs bb; if ((rc = list_bufs(c, g, (int)c->n, &bb))) return rc; list_views(c, bb, &L2); L2.npos = (int)c->n; L2.pstrip = c->base.strip.as<int>(); }
+            if (c->run.level == 4) { ListBufs bb; if ((rc = list_bufs(c, g, std::max(1, base_rows(c)), &bb))) return rc; list_views(c, bb, &L2); L2.npos = base_rows(c); L2.pstrip = c->base.strip.as<int>(); }
             else { L2.npos = nm; L2.pstrip = c->run.strip; }
             if (which == 4) { if ((rc = lists_border(c, g, nm, L2))) return rc; }
             else if (which == 3) {
                 // (the chain kernel resets the forest and the per-head accumulators first -- timed with it)
-                ListBufs bb; if ((rc = list_bufs(c, g, c->run.level == 4 ? (int)c->n : nm, &bb))) return rc;
+                ListBufs bb; if ((rc = list_bufs(c, g, c->run.level == 4 ? std::max(1, base_rows(c)) : nm, &bb))) return rc;
                 fuse_knob(c);
                 if (c->fuse_chains)
                     hipLaunchKernelGGL(k_prep_c, dim3(nblocks(std::max(nm, g.S + 2))), dim3(TPB), 0, c->stream, g, (const int*)L2.lcnt, (const int*)L2.pstrip,

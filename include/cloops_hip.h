@@ -979,6 +979,11 @@ void cl_set_count_reuse(cl_chrom* c, int enabled);
 void cl_set_count_floor(cl_chrom* c, int32_t min_pts);
 void cl_set_count_thresholds(cl_chrom* c, const int32_t* min_pts, int32_t n);
 int cl_last_region_mode(const cl_chrom* c);
+/* cl_base_rows: the rows the handle's current base layout holds (read-only).  Inside an announced sweep (cl_sweep_plan) a layout
+ * that is built for a run under a cut leaves out the rows with Y - X below half of that cut -- every later run of the eps whose
+ * cut is not below that floor treats them as absent anyway; a run below it (a smaller cut, no cut, exact counts) rebuilds the
+ * layout with every row.  Results never depend on it.  n when the handle holds no layout or the layout holds every row. */
+int64_t cl_base_rows(const cl_chrom* c);
 
 /* How the part of a rotated run behind the region query (components, border rule, labels) walks the data.  The reference
  * expands clusters from core points only (cDBSCAN2.py:114-192 queryGrid, cDBSCAN.py:155-184 expandCluster); levels 3 and 4
