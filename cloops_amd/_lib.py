@@ -42,6 +42,8 @@ CL_BAL_BINS_MAX = 16777216   # 2^24 bins of a balanced chromosome
 CL_EIG_MAX = 6               # eigenpairs of a cl_eig_iterate
 CL_EIG_BLOCK = 8             # columns of the iteration's block, vectors of a cl_eig_apply
 CL_EIG_BINS_MAX = 1048576    # 2^20 bins of a chromosome's compartments
+CL_SCC_HMAX = 20             # largest half-width of the SCC's box
+CL_SCC_BAND_MAX = 268435456  # 2^28 entries nb (n_diags + 4 h) of a band array of cl_scc_moments
 
 
 class ClBox(ctypes.Structure):
@@ -157,6 +159,8 @@ PROTOTYPES = {
     "cl_eig_iterate": (_int, [_vp, _i32, _i32, _f64, _i32p, _i32p, _vp, _vp]),
     "cl_eig_vectors_get": (_int, [_vp, _i32, _i64, _i64, _vp]),
     "cl_eig_free": (_int, [_vp]),
+    "cl_scc_moments": (_int, [_vp, _vp, _i64, _i64, _i32, _i64, _i64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    "cl_scc_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

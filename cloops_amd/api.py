@@ -987,6 +987,33 @@ class Chromosome(_Handle):
         (cl_eig_free)"""
         _lib.check(self._lib.cl_eig_free(self._h))
 
+    def scc_moments(self, other, b0, nb, h=0, n_diags=None):
+        """K28: the moments of the stratum-adjusted correlation of this handle's and `other`'s contact matrix (both after
+        mat_cells(res, fold=True) at one res; `other` may be this handle) over the bins [b0, b0 + nb): both matrices under a (2h+1)^2
+        box sum, and per diagonal d < n_diags (None: nb) over the positions where either sum is non-zero -> (n int64, sx, sy, sxx, syy,
+        sxy uint64), n_diags entries each.  The scratch stays with this handle  (cl_scc_moments)"""
+        if not isinstance(other, Chromosome):
+            raise ValueError("scc_moments: the other sample must be a Chromosome, got %r" % (other,))
+        nb, h = int(nb), int(h)
+        D = nb if n_diags is None else int(n_diags)
+        if not 0 <= h <= _lib.CL_SCC_HMAX:
+            raise ValueError("scc_moments: h must lie in [0, %d], got %d" % (_lib.CL_SCC_HMAX, h))
+        if nb < 0 or not (1 <= D <= nb or D == nb == 0):
+            raise ValueError("scc_moments: needs nb >= 0 and 1 <= n_diags <= nb (0 with nb = 0), got nb %d, n_diags %d" % (nb, D))
+        if nb * (D + 4 * h) > _lib.CL_SCC_BAND_MAX:
+            raise ValueError("scc_moments: the band nb (n_diags + 4 h) = %d has more than %d entries: fewer diagonals, a smaller h or a "
+                             "larger res" % (nb * (D + 4 * h), _lib.CL_SCC_BAND_MAX))
+        n = np.zeros(D, dtype=np.int64)
+        m = [np.zeros(D, dtype=np.uint64) for _ in range(5)]
+        ptr = [a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if D else None for a in m]
+        _lib.check(self._lib.cl_scc_moments(self._h, other._h, int(b0), nb, h, D, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if D else None,
+                                            *ptr))
+        return (n,) + tuple(m)
+
+    def scc_free(self):
+        """releases the device scratch of scc_moments; the cells stay  (cl_scc_free)"""
+        _lib.check(self._lib.cl_scc_free(self._h))
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

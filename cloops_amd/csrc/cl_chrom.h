@@ -373,6 +373,12 @@ struct cl_chrom {
             int n_eigs = 0;                                              // the vectors cl_eig_vectors_get serves
         } st;
     } eg;
+    // K28 (k_scc.hip): the band forms of this handle's and the other handle's matrix (nb x (D + 4h) u32 each; tb unused when a sample is
+    // compared with itself) and the six accumulators per diagonal.  Scratch of the first handle of cl_scc_moments, reused when large
+    // enough; kept to cl_scc_free, the next cl_mat_cells, cl_mat_free or destruction.  Nothing is kept on the second handle
+    struct Scc {
+        DevBuf ta, tb, acc;
+    } sc;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
     int copy_mode = 0;                // 0: the D2H copies of a run go through copy_stream, 1: they are issued in `stream` (caller's stream),
@@ -459,7 +465,8 @@ static inline void kdis_release(cl_chrom* c) { c->kd = cl_chrom::Kdis(); }
 static inline void eig_release(cl_chrom* c) { c->eg = cl_chrom::Eig(); }
 static inline void exp_release(cl_chrom* c) { eig_release(c); c->ex = cl_chrom::Exp(); }
 static inline void bal_release(cl_chrom* c) { exp_release(c); c->bl = cl_chrom::Bal(); }
-static inline void mat_release(cl_chrom* c) { c->mx = cl_chrom::Mat(); bal_release(c); }
+static inline void scc_release(cl_chrom* c) { c->sc = cl_chrom::Scc(); }
+static inline void mat_release(cl_chrom* c) { c->mx = cl_chrom::Mat(); bal_release(c); scc_release(c); }
 // what a unit's cl_*_free entry point does around its release function
 static inline int unit_free(cl_chrom* c, const char* who, void (*release)(cl_chrom*))
 {

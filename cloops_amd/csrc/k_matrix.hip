@@ -437,9 +437,10 @@ extern "C" int cl_mat_cells(cl_chrom* c, int64_t cut, int64_t res, int32_t fold,
     cl_chrom::Mat::State st;
     st.ready = true;
     st.res = (int)res; st.fold = fold != 0;
-    if (c->n == 0) { bal_release(c); c->mx.st = st; return CL_OK; }
+    if (c->n == 0) { bal_release(c); scc_release(c); c->mx.st = st; return CL_OK; }
     HIP_TRY(hipSetDevice(c->device));
     bal_release(c);                                                             // (K25's state belongs to the earlier cells; every K25 call ends synchronised)
+    scc_release(c);                                                             // (K28's scratch was sized for them; cl_scc_moments ends synchronised)
     int rc = agg_table(c, k24_cut(cut));
     if (rc == CL_OK) {
         st.n_kept = c->ag.kept;

@@ -696,6 +696,46 @@ int cl_eig_vectors_get(cl_chrom* c, int32_t which, int64_t first, int64_t count,
 int cl_eig_free(cl_chrom* c);
 
 /*
+ * Two samples compared (K28): the integer moments of the stratum-adjusted correlation coefficient (SCC, HiCRep: Yang et al. 2017) of
+ * two contact matrices.  The reference has no counterpart, so these definitions are the specification (tests/similarity_cases.py
+ * restates them in numpy); the coefficients, the weights, the texts and the files stay on the host (cloops_amd/similarity.py).
+ *
+ * Input: two handles a and b on one device, each with the cells of a cl_mat_cells(c, cut, res, fold = 1) of the same res (the cuts may
+ * differ; a == b is allowed).  From the caller: the window of bins [b0, b0 + nb), h (0 <= h <= CL_SCC_HMAX) and n_diags = D (1 <= D <=
+ * nb, or D = 0 with nb = 0).
+ * For a sample s, A_s is the symmetric nb x nb matrix of its cells inside the window: A[u][v] = A[v][u] = cnt with u = bx - b0 and v =
+ * by - b0; a diagonal cell counts once; a cell with a bin outside the window takes no part; everything else is 0.
+ * Box sums (zero padding at the window's edge; sums, not means -- Pearson's coefficient does not tell them apart):
+ *   S_s[i][j] = the sum of A_s[u][v] over |u - i| <= h, |v - j| <= h, 0 <= u, v < nb.
+ * Strata: for d = 0 .. D - 1 the positions (i, i + d), 0 <= i < nb - d.  A position is counted iff S_a != 0 or S_b != 0.  Over the
+ * counted positions of d, with x = S_a and y = S_b:
+ *   n[d] (int64)                          = their number,
+ *   sx[d], sy[d] (uint64)                 = the sums of x and of y,
+ *   sxx[d], syy[d], sxy[d] (uint64)       = the sums of x x, y y and x y.
+ * Everything is an integer: two calls give the same bytes, and a test may ask for equality.
+ * Overflow rule, decided on the host in exact arithmetic before any launch: with Smax_s = min((2h+1)^2 max_count_s, 2 n_kept_s) of
+ * what cl_mat_cells recorded, the call is refused unless max(Smax_a, Smax_b)^2 nb < 2^64 -- no box sum then passes 2^32 and no sum
+ * of a diagonal 2^64.
+ * Memory: each matrix is held in band form, nb x (D + 4h) uint32; the call is refused unless nb (D + 4h) <= CL_SCC_BAND_MAX.
+ *
+ * cl_scc_moments -- synchronous: waits for both handles' streams before it reads either handle's cells, enqueues on a's stream and
+ * returns with the six arrays (D entries each) on the host.  Neither handle's cells, K25-K27 state, layouts or results are touched.
+ * The scratch (two band arrays, the accumulators) stays with a and is reused when large enough; nothing is kept on b.
+ * cl_scc_free -- releases the scratch.  The next cl_mat_cells, cl_mat_free and cl_chrom_destroy of a release it as well.
+ *
+ * nb == 0 gives CL_OK with NULL arrays.  A sample without cells (an empty handle, or a cut that removes every row) is a zero matrix.
+ * Errors: CL_ERR_ARG, found on the host before any launch, the earlier state left usable and the outputs zeroed (each non-NULL array
+ * must hold n_diags entries whenever 1 <= n_diags <= CL_SCC_BAND_MAX), for a NULL handle or NULL output, handles on different devices,
+ * no cells or unfolded cells on either handle, different res, h, n_diags or nb out of range (negative, or beyond the band limit), |b0| >
+ * 2^30, the overflow rule (the message says so), or runs in flight on either handle.
+ */
+#define CL_SCC_HMAX 20
+#define CL_SCC_BAND_MAX 268435456
+int cl_scc_moments(cl_chrom* a, cl_chrom* b, int64_t b0, int64_t nb, int32_t h, int64_t n_diags, int64_t* n, uint64_t* sx, uint64_t* sy,
+                   uint64_t* sxx, uint64_t* syy, uint64_t* sxy);
+int cl_scc_free(cl_chrom* a);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
