@@ -149,13 +149,22 @@ def labels_v1(X, Y, eps, minPts, stats=None):
     return out
 
 
-def labels_block(X, Y, eps, minPts):
+def labels_block(X, Y, eps, minPts, origin=None, cell_shift=0, centroid="le", pair_tail=True, border="max", rank_over="core",
+                 wrap_nyb=None):
+    """blockDBSCAN's closed form.  The keyword arguments are the rule under test of tests/test_block_cases.py, each
+    with today's rule as its default: `origin` (x, y) anchors the grid somewhere else than at the minimum of the set;
+    `cell_shift` moves every cell boundary by that many base pairs (a pair: along X, along Y); `centroid` "lt" makes the centroid test strict, "off" drops
+    it; `pair_tail` False walks the larger cell of a pair (on a tie the later one in cell order) in fours and leaves its last
+    len % 4 PETs out; `border` "min" gives a non-core cell the smallest adjacent rank; `rank_over` "all" takes a component's key
+    over its non-core cells as well; `wrap_nyb` k counts the cell (nx + 1, 0) as a same-row neighbour of (nx, 2^k - 1) too."""
     X = np.asarray(X, np.int64)
     Y = np.asarray(Y, np.int64)
     n = len(X)
     out = np.full(n, -1, np.int32)
-    nx = (X - X.min()) // eps + 1
-    ny = (Y - Y.min()) // eps + 1
+    ox, oy = (X.min(), Y.min()) if origin is None else origin
+    shx, shy = cell_shift if isinstance(cell_shift, tuple) else (cell_shift, cell_shift)
+    nx = (X - ox + shx) // eps + 1
+    ny = (Y - oy + shy) // eps + 1
     key = nx * (1 << 40) + ny
     order = np.argsort(key, kind="stable")
     uk, first_pos, inv_sorted, counts = np.unique(key[order], return_index=True, return_inverse=True, return_counts=True)
@@ -167,6 +176,13 @@ def labels_block(X, Y, eps, minPts):
     lut = {(int(a), int(b)): i for i, (a, b) in enumerate(zip(cnx, cny))}
     nbrs = [[lut[(int(cnx[c]) + dx, int(cny[c]) + dy)] for dx in (-1, 0, 1) for dy in (-1, 0, 1)
              if (dx or dy) and (int(cnx[c]) + dx, int(cny[c]) + dy) in lut] for c in range(C)]
+    if wrap_nyb is not None:
+        top = (1 << wrap_nyb)                             # (ny counts from 1 here)
+        for c in range(C):
+            q = lut.get((int(cnx[c]) + 1, 1)) if cny[c] == top else None
+            if q is not None:
+                nbrs[c].append(q)
+                nbrs[q].append(c)
     tot = np.array([counts[c] + sum(counts[q] for q in nbrs[c]) for c in range(C)])
     low = tot < minPts
     alive = np.array([not (low[c] and all(low[q] for q in nbrs[c])) for c in range(C)])
@@ -184,9 +200,16 @@ def labels_block(X, Y, eps, minPts):
         members = [so[bounds[c]:bounds[c + 1]] for c in range(C)]
 
     def linked(c, q):
-        if abs(cx[c] - cx[q]) + abs(cy[c] - cy[q]) <= float(eps):
+        dc = abs(cx[c] - cx[q]) + abs(cy[c] - cy[q])
+        if (centroid == "le" and dc <= float(eps)) or (centroid == "lt" and dc < float(eps)):
             return True
         pc, pq = members[c], members[q]
+        if not pair_tail:                                 # c < q in cell order: q is walked inside unless c is larger
+            if len(pc) > len(pq):
+                pc, pq = pq, pc
+            pq = pq[:len(pq) - len(pq) % 4]
+            if len(pq) == 0:
+                return False
         d = np.abs(X[pc][:, None] - X[pq][None, :]) + np.abs(Y[pc][:, None] - Y[pq][None, :])
         return bool((d <= eps).any())
 
@@ -216,14 +239,19 @@ def labels_block(X, Y, eps, minPts):
     compkey = np.full(ncomp, n, np.int64)
     np.minimum.at(compkey, comp[corec], cfirst[corec])
     present = np.unique(comp[corec])
-    rank = np.full(ncomp, -1, np.int64)
-    rank[present[np.argsort(compkey[present])]] = np.arange(len(present))
-    clab = np.full(C, -1, np.int64)
-    clab[corec] = rank[comp[corec]]
-    for c in range(C):
-        if alive[c] and not corec[c]:
-            r = [rank[comp[q]] for q in links[c] if corec[q]]
-            if r:
-                clab[c] = max(r)
+    pick = max if border == "max" else min
+    for again in ((False, True) if rank_over == "all" else (False,)):
+        rank = np.full(ncomp, -1, np.int64)
+        rank[present[np.argsort(compkey[present], kind="stable")]] = np.arange(len(present))
+        clab = np.full(C, -1, np.int64)
+        clab[corec] = rank[comp[corec]]
+        for c in range(C):
+            if alive[c] and not corec[c]:
+                r = [rank[comp[q]] for q in links[c] if corec[q]]
+                if r:
+                    clab[c] = pick(r)
+                    if rank_over == "all" and not again:  # the cell's first row counts for the component that took it
+                        k = int(np.flatnonzero(rank == clab[c])[0])
+                        compkey[k] = min(compkey[k], cfirst[c])
     out[:] = clab[cell_of]
     return out
