@@ -44,6 +44,10 @@ CL_EIG_BLOCK = 8             # columns of the iteration's block, vectors of a cl
 CL_EIG_BINS_MAX = 1048576    # 2^20 bins of a chromosome's compartments
 CL_SCC_HMAX = 20             # largest half-width of the SCC's box
 CL_SCC_BAND_MAX = 268435456  # 2^28 entries nb (n_diags + 4 h) of a band array of cl_scc_moments
+CL_DOT_WMAX = 16             # largest half-width of the donut's footprint
+CL_DOT_CHUNKS_MAX = 64       # chunks of la of a cl_dot_hist
+CL_DOT_CMAX = 4095           # counts at or above it share the histogram's last column
+CL_DOT_BAND_MAX = 134217728  # 2^27 entries nb (dmax + 4 w) of the value band of cl_dot_lambdas
 
 
 class ClBox(ctypes.Structure):
@@ -161,6 +165,13 @@ PROTOTYPES = {
     "cl_eig_free": (_int, [_vp]),
     "cl_scc_moments": (_int, [_vp, _vp, _i64, _i64, _i32, _i64, _i64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
     "cl_scc_free": (_int, [_vp]),
+    "cl_dot_lambdas": (_int, [_vp, _i32, _i32, _i64, _i64, _i64p, _i64p]),
+    "cl_dot_lambdas_get": (_int, [_vp, _i32, _i64, _i64, _vp]),
+    "cl_dot_cells_get": (_int, [_vp, _i64, _i64, _vp]),
+    "cl_dot_hist": (_int, [_vp, _vp, _i32, _vp, _u64p]),
+    "cl_dot_call": (_int, [_vp, _vp, _i64p]),
+    "cl_dot_sig_get": (_int, [_vp, _i64, _i64, _vp]),
+    "cl_dot_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

@@ -1014,6 +1014,78 @@ class Chromosome(_Handle):
         """releases the device scratch of scc_moments; the cells stay  (cl_scc_free)"""
         _lib.check(self._lib.cl_scc_free(self._h))
 
+    def dot_lambdas(self, p, w, dmin, dmax=None):
+        """K29: the four neighbourhood sums (donut, lower-left, horizontal, vertical; inner half-width p, outer w) of observed and
+        expected around every pixel (i, i + d), dmin <= d < dmax, of the matrix of the last exp_set, and the local expected counts la_k
+        they imply, kept on the device for dot_lambdas_get / dot_cells / dot_hist / dot_call.  dmin: at or above the
+        ignore_diags of bal_marginals; dmax None: all diagonals (nb) -> (n_cand, n_full)  (cl_dot_lambdas)"""
+        p, w = int(p), int(w)
+        if not 0 <= p < w <= _lib.CL_DOT_WMAX:
+            raise ValueError("dot_lambdas: needs 0 <= p < w <= %d, got p %d, w %d" % (_lib.CL_DOT_WMAX, p, w))
+        nb = getattr(self, "_bal_bins", 0)
+        dmax = nb if dmax is None else int(dmax)
+        nc, nf = ctypes.c_int64(0), ctypes.c_int64(0)
+        dmin = int(dmin)
+        if nb * (dmax + 4 * w) > _lib.CL_DOT_BAND_MAX:
+            raise ValueError("dot_lambdas: the band nb (dmax + 4 w) = %d has more than %d entries: fewer diagonals, a smaller w or a larger "
+                             "res" % (nb * (dmax + 4 * w), _lib.CL_DOT_BAND_MAX))
+        _lib.check(self._lib.cl_dot_lambdas(self._h, p, w, dmin, dmax, ctypes.byref(nc), ctypes.byref(nf)))
+        self._dot_bins, self._dot_nd, self._dot_chunks, self._dot_sig = nb, dmax - dmin, 0, 0
+        return int(nc.value), int(nf.value)
+
+    def dot_lambdas_get(self, kernel, first_bin=0, n_bins=None):
+        """la of neighbourhood `kernel` (0 donut, 1 lower-left, 2 horizontal, 3 vertical) for the bins [first_bin, first_bin + n_bins)
+        (all from `first_bin` on by default) -> float64 [n_bins, dmax - dmin]: row = bin i, column = d - dmin; NaN where the pixel is no
+        candidate or the neighbourhood's expected sum is 0  (cl_dot_lambdas_get)"""
+        first, count, n = self._range("_dot_bins", first_bin, n_bins)
+        out = np.zeros((n, getattr(self, "_dot_nd", 0)), dtype=np.float64)
+        _lib.check(self._lib.cl_dot_lambdas_get(self._h, int(kernel), first, count, _vp(out) if out.size else None))
+        return out
+
+    def dot_cells(self, first=0, count=None):
+        """the four la of the cells [first, first + count) of mat_cells, in their order -> float64 [count, 4], NaN where the cell's pixel
+        is no candidate  (cl_dot_cells_get)"""
+        first, count, n = self._range("_mat_cells", first, count)
+        out = np.zeros((n, 4), dtype=np.float64)
+        _lib.check(self._lib.cl_dot_cells_get(self._h, first, count, _vp(out) if n else None))
+        return out
+
+    def dot_hist(self, edges):
+        """K29: the histogram of the full pixels of the last dot_lambdas over the chunks of la (chunk(x) = the smallest l with x <=
+        edges[l]; edges finite, above 0, strictly ascending, at most CL_DOT_CHUNKS_MAX) and their raw counts, saturated at CL_DOT_CMAX
+        -> (uint64 [4, n_chunks, CL_DOT_CMAX + 1], n_beyond: the full pixels with a la above the last edge, left out)  (cl_dot_hist)"""
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+        if e.ndim != 1 or not 1 <= len(e) <= _lib.CL_DOT_CHUNKS_MAX:
+            raise ValueError("dot_hist: needs 1 .. %d edges, got shape %s" % (_lib.CL_DOT_CHUNKS_MAX, e.shape))
+        hist = np.zeros((4, len(e), _lib.CL_DOT_CMAX + 1), dtype=np.uint64)
+        nbey = ctypes.c_uint64(0)
+        _lib.check(self._lib.cl_dot_hist(self._h, _vp(e), len(e), _vp(hist), ctypes.byref(nbey)))
+        self._dot_chunks, self._dot_sig = len(e), 0
+        return hist, int(nbey.value)
+
+    def dot_call(self, thr):
+        """K29: the cells whose pixel is full, not beyond, and has cnt >= thr[k][chunk(la_k)] for all four k; thr: uint32 [4, n_chunks]
+        over the edges of the last dot_hist -> n_sig; the list stays on the device for dot_sig  (cl_dot_call)"""
+        t = np.ascontiguousarray(thr, dtype=np.uint32)
+        n = getattr(self, "_dot_chunks", 0)                                  # (0: no histogram; the library refuses before it reads thr)
+        if n and t.shape != (4, n):
+            raise ValueError("dot_call: the thresholds need shape (4, %d), got %s" % (n, t.shape))
+        ns = ctypes.c_int64(0)
+        _lib.check(self._lib.cl_dot_call(self._h, _vp(t), ctypes.byref(ns)))
+        self._dot_sig = int(ns.value)
+        return int(ns.value)
+
+    def dot_sig(self, first=0, count=None):
+        """entries [first, first + count) of the last dot_call's list (all from `first` on by default) -> int64, ascending: indices
+        into the order of mat_cells  (cl_dot_sig_get)"""
+        return self._get(self._lib.cl_dot_sig_get, "_dot_sig", first, count, (np.int64,))[0]
+
+    def dot_free(self):
+        """releases the band, the la, the histogram and the list of the dot_* calls; everything up to the expected values stays
+        (cl_dot_free)"""
+        _lib.check(self._lib.cl_dot_free(self._h))
+        self._dot_bins = self._dot_nd = self._dot_chunks = self._dot_sig = 0
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

@@ -9,7 +9,7 @@
 //   cl_chrom::Run   the working set of the run BEING ENQUEUED (c->run): where its sorted arrays and K2 words live, its traversal
 //                   level, what its kernels have done already.  Assigned fresh by run_begin() at the start of every run, read by
 //                   nobody after the enqueue (the developer build's cl_debug_time_lists aside).
-//   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K27
+//   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K29
 //                   state that outlives a run: one struct each, the buffers together with the flags that say what they hold, and
 //                   one invalidate() where several flags fall together.
 // What reports on the LAST run (last_k2_mode, dbg_g / dbg_nm, refused_labelled, the slots) stays in the handle: callers read it
@@ -379,6 +379,18 @@ struct cl_chrom {
     struct Scc {
         DevBuf ta, tb, acc;
     } sc;
+    // K29 (k_dots.hip): the value band (nb x (dmax + 4w) fp64), the four planes of la over the dense nb x (dmax - dmin) pixels and the
+    // plane of their raw counts, counters; the edges and the histogram of cl_dot_hist; the thresholds, the cells' flags, their scan (and
+    // its scratch) and the significant cells of cl_dot_call; the la of a cl_dot_cells_get.  Kept from cl_dot_lambdas to the next one,
+    // cl_dot_free, anything that releases or rebuilds K26's state (exp_release, cl_exp_diagonals, cl_exp_set) or destruction
+    struct Dot {
+        DevBuf band, la, pix, ctr, edges, hist, thr, flag, scan, tmp, sig, out;
+        struct State {
+            bool lambdas = false, hist = false, called = false;          // cl_dot_lambdas / cl_dot_hist / cl_dot_call have run since
+            int p = 0, w = 0, n_chunks = 0;
+            long long dmin = 0, dmax = 0, n_sig = 0;
+        } st;
+    } dt;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
     int copy_mode = 0;                // 0: the D2H copies of a run go through copy_stream, 1: they are issued in `stream` (caller's stream),
@@ -455,7 +467,7 @@ Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
 int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* d_M);
 // A unit drops its buffers and its state by assigning a fresh struct, and with them what was made from them: K25's marginals and
-// weights belong to K24's cells, K26's diagonals to K25's marginals and weights, K27's matrix to K26's expected values.  Called by
+// weights belong to K24's cells, K26's diagonals to K25's marginals and weights, K27's matrix and K29's lambdas to K26's expected values.  Called by
 // the units' entry points; the handle's destruction needs none of them
 static inline void track_release(cl_chrom* c) { c->tk = cl_chrom::Track(); }
 static inline void cov_release(cl_chrom* c) { c->cv = cl_chrom::Cov(); }
@@ -463,7 +475,8 @@ static inline void peak_release(cl_chrom* c) { c->pk = cl_chrom::Peak(); }
 static inline void dom_release(cl_chrom* c) { c->dm = cl_chrom::Dom(); }
 static inline void kdis_release(cl_chrom* c) { c->kd = cl_chrom::Kdis(); }
 static inline void eig_release(cl_chrom* c) { c->eg = cl_chrom::Eig(); }
-static inline void exp_release(cl_chrom* c) { eig_release(c); c->ex = cl_chrom::Exp(); }
+static inline void dot_release(cl_chrom* c) { c->dt = cl_chrom::Dot(); }
+static inline void exp_release(cl_chrom* c) { eig_release(c); dot_release(c); c->ex = cl_chrom::Exp(); }
 static inline void bal_release(cl_chrom* c) { exp_release(c); c->bl = cl_chrom::Bal(); }
 static inline void scc_release(cl_chrom* c) { c->sc = cl_chrom::Scc(); }
 static inline void mat_release(cl_chrom* c) { c->mx = cl_chrom::Mat(); bal_release(c); scc_release(c); }

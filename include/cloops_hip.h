@@ -736,6 +736,79 @@ int cl_scc_moments(cl_chrom* a, cl_chrom* b, int64_t b0, int64_t nb, int32_t h, 
 int cl_scc_free(cl_chrom* a);
 
 /*
+ * Loops from the contact matrix (K29): the local-enrichment ("donut") test of HiCCUPS (Rao et al. 2014; `cooltools dots` restates it)
+ * over every pixel of a band of the matrix -- four neighbourhood sums of observed and expected per pixel, the local expected count
+ * la_k they imply, the histogram of the raw counts per chunk of la_k, and the call against the caller's thresholds.  The reference has
+ * no counterpart, so these definitions are the specification (tests/dots_cases.py restates them in numpy); the thresholds from the
+ * histogram (FDR), the enrichment filter, the merging of pixels into loops, the texts and the files stay on the host
+ * (cloops_amd/dots.py).
+ *
+ * Input: the state after cl_mat_cells(fold = 1), cl_bal_marginals, cl_exp_diagonals (either mode) and cl_exp_set: the cells (bx, by,
+ * cnt), the bins b0 .. b0 + nb - 1, K26's validity of a bin and its w (1 on the valid bins in raw mode), ign = ignore_diags and
+ * expected[e].  From the caller: p and w, 0 <= p < w <= CL_DOT_WMAX, and dmin, dmax with ign <= dmin < dmax <= nb (dmin = dmax = 0
+ * with nb = 0).
+ * Two symmetric nb x nb matrices:
+ *   V[u][v] = (w[u] cnt) w[v], in K25's order of operations, where the pair has a cell, both bins are valid and |u - v| >= ign, and 0
+ *             everywhere else; a diagonal cell counts once;
+ *   E[u][v] = expected[|u - v|] where both bins are valid and |u - v| >= ign, and 0 everywhere else.
+ *   Positions outside [0, nb) read as 0 in both.
+ * Four neighbourhoods around a pixel (i, j), j = i + d, as offsets (a, b) added to (i, j); inner(a, b) = |a| <= p and |b| <= p:
+ *   k = 0  donut       |a| <= w, |b| <= w, a != 0, b != 0, not inner;
+ *   k = 1  lower-left  1 <= a <= w, -w <= b <= -1, not inner (the side towards the diagonal);
+ *   k = 2  horizontal  |a| <= 1, p < |b| <= w;
+ *   k = 3  vertical    |b| <= 1, p < |a| <= w.
+ * A footprint may cross the main diagonal: the matrices are symmetric.
+ * NO_k(i, j) / NE_k(i, j) = the sum of V / of E over neighbourhood k.  The local expected raw count of the pixel is
+ *   la_k = ((NO_k / NE_k) expected[d]) / (w[i] w[j]),   in that order of operations;
+ * la_k is NaN when the pixel is no candidate -- d outside [dmin, dmax), or i or j invalid (j >= nb included) -- or NE_k is 0.  A pixel
+ * is FULL when its four la_k are numbers; only full pixels take part in the histogram and the call.
+ * Summation rule: NO and NE are sums of at most T = (2w+1)^2 non-negative fp64 terms; the device adds terms or partial sums only and
+ * never subtracts one fp64 sum from another (no running sums, no summed-area differences in fp64; integers may be subtracted freely);
+ * the order of the additions is fixed by the geometry alone; no fp64 atomics: two calls give the same bytes.  Any two orders of
+ * adding at most T non-negative terms lie within 2 (T - 1) 2^-53 of each other, relatively.
+ * Chunks: edges[0 .. n_chunks), finite, above 0, strictly ascending, 1 <= n_chunks <= CL_DOT_CHUNKS_MAX; chunk(x) = the smallest l
+ * with x <= edges[l], by comparisons alone; a value above the last edge is in no chunk, and a full pixel with such a la_k is BEYOND.
+ * Histogram: hist[k][l][c] (uint64, 4 x n_chunks x (CL_DOT_CMAX + 1)) = the number of full pixels that are not beyond, have
+ * chunk(la_k) == l and min(cnt, CL_DOT_CMAX) == c, cnt the raw count of the pixel's cell and 0 without a cell (the zero-count pixels
+ * of the band are most of the tests an FDR corrects for); *n_beyond = the full pixels left out because they are beyond.
+ * Call: thr[k][l] (uint32, 4 x n_chunks, over the edges of the last cl_dot_hist); a cell is significant iff its pixel is full, is not
+ * beyond and cnt >= thr[k][chunk(la_k)] for all four k.  The result is the ascending list of the significant cells' indices into
+ * the order of cl_mat_cells.
+ * Memory: V is held in band form, nb x (dmax + 4w) fp64, the la in a dense array of nb x (dmax - dmin) x 4 fp64; the call is refused
+ * unless nb (dmax + 4w) <= CL_DOT_BAND_MAX.  E is never stored.
+ *
+ * cl_dot_lambdas -- the band, the four la of every pixel (i, d), 0 <= i < nb, dmin <= d < dmax -> *n_cand (the candidates), *n_full.
+ * cl_dot_lambdas_get -- la of kernel k for the bins [first_bin, first_bin + n_bins) inside [0, nb]: n_bins x (dmax - dmin), row-major,
+ * row = bin i, column = d - dmin.
+ * cl_dot_cells_get -- the four la of the cells [first, first + count) of cl_mat_cells: count x 4, NaN where the cell's pixel is no
+ * candidate.
+ * cl_dot_hist -- the histogram over the dense array -> hist, *n_beyond.  May be repeated with other edges.
+ * cl_dot_call -- -> *n_sig; the list stays on the device.  May be repeated with other thresholds.
+ * cl_dot_sig_get -- entries [first, first + count) inside [0, n_sig] of the list.
+ * cl_dot_free -- releases the state (cells and the K25-K27 state stay).  The next cl_dot_lambdas, cl_exp_set, cl_exp_diagonals,
+ * cl_exp_free and everything that releases K26's state release it as well.  K27's state and K29's do not touch each other.
+ *
+ * The calls are synchronous on the handle's stream.  nb == 0 is not an error: n_cand = n_full = n_beyond = n_sig = 0, a histogram of
+ * zeros, and the arrays may be NULL.  Errors: CL_ERR_ARG, found on the host before any launch, scalar outputs zeroed and the earlier
+ * state left usable, for a NULL handle or NULL output, any call before cl_exp_set, p, w, dmin or dmax outside the rules above, the
+ * band limit, an expected[e] that is NaN, infinite or negative on a diagonal ign <= e < min(nb, dmax + 2w) that holds a valid pair
+ * (zero is allowed), edges that are not finite, positive and strictly ascending, n_chunks out of range, cl_dot_hist or a get before
+ * cl_dot_lambdas, cl_dot_call before cl_dot_hist, cl_dot_sig_get before cl_dot_call, a kernel index outside [0, 3], a range outside
+ * its array, or runs in flight.
+ */
+#define CL_DOT_WMAX 16
+#define CL_DOT_CHUNKS_MAX 64
+#define CL_DOT_CMAX 4095
+#define CL_DOT_BAND_MAX 134217728
+int cl_dot_lambdas(cl_chrom* c, int32_t p, int32_t w, int64_t dmin, int64_t dmax, int64_t* n_cand, int64_t* n_full);
+int cl_dot_lambdas_get(cl_chrom* c, int32_t kernel, int64_t first_bin, int64_t n_bins, double* la);
+int cl_dot_cells_get(cl_chrom* c, int64_t first, int64_t count, double* la4);
+int cl_dot_hist(cl_chrom* c, const double* edges, int32_t n_chunks, uint64_t* hist, uint64_t* n_beyond);
+int cl_dot_call(cl_chrom* c, const uint32_t* thr, int64_t* n_sig);
+int cl_dot_sig_get(cl_chrom* c, int64_t first, int64_t count, int64_t* cell_index);
+int cl_dot_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
