@@ -5,15 +5,17 @@
 //
 // Three kinds of thing, kept apart:
 //   RunRequest      what the caller of ONE run asked for.  The entry point builds it, enqueue() and the run functions take it by
-//                   reference; nothing of it is stored in the handle (the result slot notes where the run's output goes).
+//                   reference; nothing of it is stored in the handle (the run's record notes where its output goes).
 //   cl_chrom::Run   the working set of the run BEING ENQUEUED (c->run): where its sorted arrays and K2 words live, its traversal
-//                   level, what its kernels have done already.  Assigned fresh by run_begin() at the start of every run, read by
-//                   nobody after the enqueue (the developer build's cl_debug_time_lists aside).
+//                   level, what its kernels have done already, and the record it will leave in its result slot (Run::held).  Assigned
+//                   fresh by run_begin() at the start of every run, read by nobody after the enqueue (the developer build's
+//                   cl_debug_time_lists aside).  finish_enqueue() commits the record to the slot in one assignment once the run is
+//                   completely enqueued; nothing else writes a slot's record (finish_wait() clears the destination it has served).
 //   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K29
 //                   state that outlives a run: one struct each, the buffers together with the flags that say what they hold, and
 //                   one invalidate() where several flags fall together.
-// What reports on the LAST run (last_k2_mode, dbg_g / dbg_nm, refused_labelled, the slots) stays in the handle: callers read it
-// after the enqueue.
+// What reports on the LAST run (last_k2_mode, dbg_g / dbg_nm, refused_labelled, the slots' records) stays in the handle: callers
+// read it after the enqueue.
 #pragma once
 #include "cl_common.h"
 #include "cl_table.h"
@@ -67,6 +69,13 @@ struct K7Src {
 
 struct K7Part { double sx[2]; double sxx[2]; long long n_all[2]; long long n_pos[2]; };
 
+// The header of a result slot, HDR_WORDS ints on the device (cl_chrom::hdr), the first eight copied to the slot's pinned h_hdr: ids
+// handed out, internal error (0: none), PETs that entered DBSCAN, non-empty ids and the largest of them (k_export_table; -1: none),
+// 1 = the pinned table rows were too few, labelled PETs handed out as pairs / under the row mask
+enum { HDR_K = 0, HDR_ERR = 1, HDR_M = 2, HDR_NCLUSTERS = 3, HDR_MAXLABEL = 4, HDR_TRUNC = 5, HDR_LABELLED = 6, HDR_WORDS = 16 };
+// values of HDR_ERR (the device counter CTR_OVERFLOW); any other non-zero value: the release records overflowed
+enum { HDR_ERR_STRIP = 4 /* strip longer than the hybrid sort accepts */, HDR_ERR_COUNT = 8 /* M differs from the host's count */ };
+
 // What one call asks of the handle.  cl_cluster, cl_cluster_async, cl_cluster_pairs_async, cl_cluster_rowmask_async,
 // cl_cluster_step_async and cl_cluster_weighted each build one and hand it to enqueue() (cloops_hip.hip)
 struct RunRequest {
@@ -113,6 +122,32 @@ struct cl_chrom {
     int* h_pinned = nullptr;          // small pinned staging (stats, block scalars)
     struct StripPlan { int layout, eps, maxlen; };
     std::vector<StripPlan> plans;     // longest strip over all rows per (layout, eps): picks the sort path
+    // The record of ONE run in its result slot (Slot::held, below); the defaults are those of a run that sets nothing
+    struct Held {
+        int32_t* labels_out = nullptr;
+        // the pairs (kp (row, label) of 8 bytes) or the row mask (ceil(n / 64) words, then kp labels): cl_wait copies `fixed` + kp * `per`
+        // bytes from the slot's `pairs` to the caller once the header tells the number kp of labelled PETs
+        struct Extra {
+            void* dst = nullptr;          // the caller's page-locked buffer (null: the run has no such output)
+            long long cap = 0;            // its capacity in labelled PETs: cl_wait refuses a run that labelled more
+            size_t fixed = 0; int per = 0;
+            bool copy_empty = false;      // kp == 0 still copies (the fixed part)
+            const char* refusal = nullptr;    // cl_wait's error text for a run that labelled more than `cap`
+        } extra;
+        int n_strips = 0;
+        bool band_timed = false;      // ev[8], ev[9] were recorded
+        long long n_queried = 0;      // PETs the run's region query covered (0: none)
+        bool exported = false;        // the table rows were stored to h_boxes
+        bool step_valid = false;      // the run carried the sweep-step tail (classification, candidate append, distance summary)
+        bool host_written = false;    // ... and its last kernel stored header + step output in pinned host memory itself
+        bool wait_done = false;       // cl_wait waits for ev_done (nothing went through the copy stream)
+        long long fine_lo = -1;       // fine window of that tail's summary (-1 = none)
+        bool rows_valid = false;      // `labels` (row order) was produced by the run
+        bool sorted_src = false;      // the run left sorted (q, label) arrays for the distance statistics
+        const int* k7_sv = nullptr;   // sorted q of the run (list form: q of every core and walker)
+        const int* k7_lcnt = nullptr; // list form (k_lists.hip): device {cores, walkers} -- slab / k7_sv hold one entry per core and walker
+        int k7_v0 = 0;                // d = q + k7_v0
+    };
     // Working set of the run being enqueued.  run_begin() assigns a fresh one first thing in run_rotated, run_block, run_weighted and
     // cl_neighbor_counts: no run sees what an earlier one -- of whatever kind, finished or failed half-way -- left here.
     struct Run {
@@ -134,6 +169,8 @@ struct cl_chrom {
         bool k2_make = false;         // the run made the words itself (level 4 under a cut: on the base layout, then its band)
         const int* k_total = nullptr; // device: where the run left the number of ids handed out (null: rankscan[n])
         bool hdr_packed = false;      // the run's own kernels have written the slot header (no k_pack_header)
+        int kmax = 0;                 // upper bound of the number of cluster ids of the run (host-known; the count itself is on the device)
+        Held held;                    // the record the run will leave in its slot (finish_enqueue completes and commits it)
     } run;
     // Base layout: the sorted arrays of ALL rows (cut = 0) for one (variant layout, eps), kept until eps changes.
     // The sort order does not depend on minPts and a cut only REMOVES rows, so every further run of a sweep at this
@@ -201,37 +238,24 @@ struct cl_chrom {
     bool reuse_layout = true;
     // Result slots: two runs may be in flight (cl_cluster_async) -- the labels / table / header of
     // run k live in slot k & 1, so the D2H copy of run k (copy stream) overlaps the kernels of run k+1.
+    // A slot is RESOURCES (buffers, events, pinned memory: they live as long as the handle and are used while a run is enqueued) and
+    // the RECORD `held` of the run it holds.  A run builds its record in c->run.held; finish_enqueue() commits it in ONE assignment,
+    // the last act of an enqueue that succeeded, and nothing else writes it (finish_wait() clears the host destination it has
+    // served): a run that fails leaves the slot describing the last run completely enqueued there, cl_neighbor_counts writes none.
     struct Slot {
-        DevBuf labels, table;
-        bool pending = false;
-        int n_strips = 0;
+        DevBuf labels, table;         // row-order labels and the cluster table of the run
+        DevBuf slab;                  // labels in sorted order (rotated variants)
+        DevBuf pairs;                 // the output a run's cl_wait copies to the caller (Held::Extra), staged on the device: its size is only
+                                      // known when the run has completed
+        DevBuf d_step;                // device: {n_inter, n_self} + K7 partials + log histogram of a sweep step's tail
         hipEvent_t ev_done = nullptr, ev_copied = nullptr;
         hipEvent_t ev[10]{};          // profiling marks of the run that used this slot (8, 9: around the band query of a level-4 run)
-        bool band_timed = false;      // ... which ran
-        long long n_queried = 0;      // PETs the run's region query covered (0: none)
-        int* h_hdr = nullptr;         // pinned: {K, overflow, M}
+        int* h_hdr = nullptr;         // pinned: the slot header (HDR_K ...)
+        char* h_step = nullptr;       // pinned host copy of d_step
         cl_box* h_boxes = nullptr;    // pinned host copy of the cluster table
         size_t h_boxes_cap = 0;
-        int32_t* labels_out = nullptr;
-        DevBuf slab;                  // labels in sorted order (rotated variants)
-        DevBuf pairs;                 // cl_cluster_pairs_async: (row, label) of the labelled PETs on the device (copied out by cl_wait: their number is
-        int2* pairs_host = nullptr;   //   only known when the run has completed)
-        long long pairs_host_cap = 0; //   the caller's capacity (pairs): cl_wait refuses a run that labelled more
-        void* mask_host = nullptr;    // cl_cluster_rowmask_async: the caller's buffer (mask words, then labels) and its capacity in labels
-        long long mask_host_cap = 0;
-        bool exported = true;         // the table rows were stored to h_boxes
-        bool step_valid = false;      // the run carried the sweep-step tail (classification, candidate append, distance summary)
-        bool host_written = false;    // ... and its last kernel stored header + step output in pinned host memory itself
-        bool wait_done = false;       // cl_wait waits for ev_done (nothing went through the copy stream)
-        long long fine_lo = -1;       // fine window of that tail's summary (-1 = none)
-        int kmax = 0;                 // upper bound of the number of cluster ids of the run (host-known; the count itself is on the device)
-        DevBuf d_step;                // device: {n_inter, n_self} + K7 partials + log histogram of that tail
-        char* h_step = nullptr;       // pinned host copy
-        bool rows_valid = false;      // `labels` (row order) was produced by the run
-        bool sorted_src = false;      // the run left sorted (q, label) arrays for the distance statistics
-        const int* k7_sv = nullptr;   // sorted q of the run (list form: q of every core and walker)
-        const int* k7_lcnt = nullptr; // list form (k_lists.hip): device {cores, walkers} -- slab / k7_sv hold one entry per core and walker
-        int k7_v0 = 0;                // d = q + k7_v0
+        bool pending = false;         // a run has been enqueued here and not been waited for
+        Held held;                    // what the run that the slot holds left here (cl_chrom::Held)
     } slot[2];
     bool device_labels = true;        // produce row-order device labels even without a host destination (cl_set_device_labels)
     bool export_table = true;         // copy the cluster table to pinned host memory at the end of a run (cl_set_table_export)
@@ -465,6 +489,7 @@ int ensure_cand_capacity(cl_chrom* c, long long need);
 Table make_table_slot(cl_chrom* c, int slot);
 Table make_table(cl_chrom* c);
 const int* k7_hist_for(cl_chrom* c, int cut);
+K7Src k7_src(cl_chrom* c, const cl_chrom::Held& r, cl_chrom::Slot& sl, int cut, int M, const int* dM);
 int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* d_M);
 // A unit drops its buffers and its state by assigning a fresh struct, and with them what was made from them: K25's marginals and
 // weights belong to K24's cells, K26's diagonals to K25's marginals and weights, K27's matrix and K29's lambdas to K26's expected values.  Called by

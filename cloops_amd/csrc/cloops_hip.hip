@@ -585,7 +585,7 @@ k_strip_sort(int n, GridParams g, const u64* __restrict__ keys, const u32* __res
         return;
     }
     const int b = strip_start[strip], e = strip_start[strip + 1];
-    if (e - b > HS_LMAX) { counters[CTR_OVERFLOW] = 4; return; }                  // cannot happen (strip_maxlen)
+    if (e - b > HS_LMAX) { counters[CTR_OVERFLOW] = HDR_ERR_STRIP; return; }                  // cannot happen (strip_maxlen)
     const u32 qi = lq[i - base];
     int rank = 0;
     for (int j = b; j < e; ++j) {
@@ -2064,7 +2064,8 @@ __global__ void k_root_labels_bits_l(GridParams g, const int* __restrict__ rootl
 {
     const int ids = wboff[nblkw];                        // total number of ids handed out
     if (blockIdx.x == 0 && threadIdx.x == 0) {          // k_pack_header rides along (nothing behind this kernel raises a flag)
-        hdr[0] = ids; hdr[1] = counters[CTR_OVERFLOW]; hdr[2] = d_M[0]; hdr[3] = 0; hdr[4] = -1; hdr[5] = 0; hdr[6] = 0;      // (6: labelled PETs handed out as pairs)
+        hdr[HDR_K] = ids; hdr[HDR_ERR] = counters[CTR_OVERFLOW]; hdr[HDR_M] = d_M[0]; hdr[HDR_NCLUSTERS] = 0; hdr[HDR_MAXLABEL] = -1; hdr[HDR_TRUNC] = 0;
+        hdr[HDR_LABELLED] = 0;
     }
     const int K = counters[CTR_NROOT];
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < K; k += gridDim.x * blockDim.x) {
@@ -2270,7 +2271,7 @@ extern "C" int cl_get_timing(const cl_chrom* c, cl_timing* out)
 }
 extern "C" const int32_t* cl_labels_device(const cl_chrom* c)
 {
-    return (c && c->last_slot >= 0 && c->slot[c->last_slot].rows_valid) ? (const int32_t*)c->slot[c->last_slot].labels.p : nullptr;
+    return (c && c->last_slot >= 0 && c->slot[c->last_slot].held.rows_valid) ? (const int32_t*)c->slot[c->last_slot].labels.p : nullptr;
 }
 extern "C" void cl_set_device_labels(cl_chrom* c, int enabled) { if (c) c->device_labels = enabled != 0; }
 extern "C" void cl_set_table_export(cl_chrom* c, int enabled) { if (c) c->export_table = enabled != 0; }
@@ -2613,7 +2614,7 @@ k_cut_copy(int n /* rows of the handle: what the run's arrays are sized for */, 
     if (t == 0) {
         d_M[0] = M;
         strip_start[S + 1] = n;
-        if (expect_m >= 0 && expect_m != M) counters[CTR_OVERFLOW] = 8;      // the host sized the run by a wrong M: fail loudly
+        if (expect_m >= 0 && expect_m != M) counters[CTR_OVERFLOW] = HDR_ERR_COUNT;      // the host sized the run by a wrong M: fail loudly
     }
 }
 
@@ -2629,7 +2630,7 @@ k_band(int S, int rbits, int eps, int minPts, const int* __restrict__ bq, const 
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const int M = sloc[S] + sboffs[S >> 8];
         d_M[0] = M;
-        if (expect_m >= 0 && expect_m != M) counters[CTR_OVERFLOW] = 8;      // the host sized the run by a wrong M: fail loudly
+        if (expect_m >= 0 && expect_m != M) counters[CTR_OVERFLOW] = HDR_ERR_COUNT;      // the host sized the run by a wrong M: fail loudly
     }
     band_wave<true>(blockIdx.x * (CMP_TPB / 64) + wv, threadIdx.x & 63, l_band[wv], S, eps, 1 << rbits, minPts, bq, bsp, src0, sloc, sboffs, blen, band_words, dbg);
 }
@@ -2637,7 +2638,7 @@ __global__ void k_store_m(int S, const int* __restrict__ sloc, const int* __rest
 {
     const int M = sloc[S] + sboffs[S >> 8];
     d_M[0] = M;
-    if (expect_m >= 0 && expect_m != M) counters[CTR_OVERFLOW] = 8;
+    if (expect_m >= 0 && expect_m != M) counters[CTR_OVERFLOW] = HDR_ERR_COUNT;
 }
 
 // workspace for a run over n rows
@@ -2991,7 +2992,6 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
     bool k2_band = false, k2_skip = false;
     c->run.ws = WordSrc{c->cnt.as<int>(), nullptr, nullptr, nullptr, 0, g.rbits};
     c->run.level = exact ? 0 : std::min(level_cap, 3);
-    c->slot[c->cur].band_timed = false; c->slot[c->cur].n_queried = 0;
     if (!c->reuse_layout) {
         // every run sorts for itself (the cut filter rides in the keys: filtered rows go behind the last strip)
         if ((rc = sort_layout(c, g, wsv, wsa, nullptr, c->strip.as<int>(), c->tile_s0.as<int>()))) return rc;
@@ -3152,7 +3152,7 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
                 // no copy of the layout: the band query alone (it reads the base layout and writes its words at the PETs' places in the
                 // run's -- virtual -- layout); the list kernels apply the cut by index
                 const int nbb = nblocks(nblocks(g.S, KB_SB), CMP_TPB / 64);
-                if (c->profiling) { (void)hipEventRecord(c->slot[c->cur].ev[8], c->stream); c->slot[c->cur].band_timed = true; }
+                if (c->profiling) { (void)hipEventRecord(c->slot[c->cur].ev[8], c->stream); c->run.held.band_timed = true; }
                 hipLaunchKernelGGL(k_band, dim3(nbb), dim3(CMP_TPB), 0, c->stream, g.S, g.rbits, g.eps, g.minPts, bq, (const int*)(c->base.sp.as<int>() + SORT_PAD),
                                    (const int*)src0, (const int*)sloc, (const int*)sboffs, (const int2*)c->rc.blen.as<int2>(), c->cnt.as<int>(), d_M,
                                    c->run.m_exact ? c->run.m : -1, c->counters.as<int>(), g.dbg);
@@ -3189,10 +3189,10 @@ static int run_sort_and_count(cl_chrom* c, const GridParams& g, bool exact, int 
         if (nbase > 0)                                    // (a floor above every row: nothing to query)
             rc = cl_launch_region(c->stream, g0, nbase, nbase, false, c->base.q.as<int>() + SORT_PAD, c->base.sp.as<int>() + SORT_PAD, c->base.strip.as<int>(),
                                   c->base.tile.as<int>(), c->rc.cnt.as<int>());
-        c->slot[c->cur].n_queried = c->run.m;             // (the PETs that got a word: those the cut keeps)
+        c->run.held.n_queried = c->run.m;             // (the PETs that got a word: those the cut keeps)
     } else if (!k2_skip && !k2_band && !SKIP(256)) {
         rc = cl_launch_region(c->stream, gk, n, c->run.m, exact, c->run.sv, c->run.sa, c->run.strip, c->run.tile, c->run.cnt);
-        c->slot[c->cur].n_queried = c->run.m;
+        c->run.held.n_queried = c->run.m;
     }
     if (rc) return rc;
     if (c->run.level == 4 && c->run.l4_cut && !k2_skip && !k2_band && (rc = lists_words_to_base(c, g))) return rc;
@@ -3272,12 +3272,12 @@ __global__ void k_pack_header(int* __restrict__ hdr, const int* __restrict__ ran
                               const int* __restrict__ d_M)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        hdr[0] = rankscan_total[0];          // K  = ids handed out
-        hdr[1] = counters[CTR_OVERFLOW];
-        hdr[2] = d_M[0];                     // M  = PETs that entered DBSCAN
-        hdr[3] = 0;                          // n_clusters (filled by k_export_table)
-        hdr[4] = -1;                         // max_label
-        hdr[5] = 0;                          // 1 = table truncated (host buffer too small)
+        hdr[HDR_K] = rankscan_total[0];
+        hdr[HDR_ERR] = counters[CTR_OVERFLOW];
+        hdr[HDR_M] = d_M[0];
+        hdr[HDR_NCLUSTERS] = 0;              // (filled by k_export_table, like the next)
+        hdr[HDR_MAXLABEL] = -1;
+        hdr[HDR_TRUNC] = 0;
     }
 }
 
@@ -3287,7 +3287,7 @@ __global__ void k_pack_header(int* __restrict__ hdr, const int* __restrict__ ran
 // would queue behind the kernels of the next run that is already executing.
 __global__ void k_export_table(int* __restrict__ hdr, Table t, cl_box* __restrict__ host_rows, int cap)
 {
-    const int K = hdr[0];
+    const int K = hdr[HDR_K];
     const bool store = cap >= 0;                        // cap < 0: count the non-empty ids only (the caller does not read the rows)
     const int lim = store ? min(K, cap) : K;
     int nc = 0, ml = -1;
@@ -3300,10 +3300,10 @@ __global__ void k_export_table(int* __restrict__ hdr, Table t, cl_box* __restric
     }
     for (int o = 32; o > 0; o >>= 1) { nc += __shfl_down(nc, o); ml = max(ml, __shfl_down(ml, o)); }
     if ((threadIdx.x & 63) == 0) {
-        if (nc) atomicAdd(&hdr[3], nc);
-        if (ml >= 0) atomicMax(&hdr[4], ml);
+        if (nc) atomicAdd(&hdr[HDR_NCLUSTERS], nc);
+        if (ml >= 0) atomicMax(&hdr[HDR_MAXLABEL], ml);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && store && K > cap) hdr[5] = 1;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && store && K > cap) hdr[HDR_TRUNC] = 1;
 }
 
 Table make_table_slot(cl_chrom* c, int slot)
@@ -3322,12 +3322,26 @@ const int* k7_hist_for(cl_chrom* c, int cut)
     return (cut > 0 && cut < DCUM_BINS && c->n_neg == 0 && !c->dcum.empty() && c->dhist.p) ? c->dhist.as<int>() : (const int*)nullptr;
 }
 
+// where K7 finds the (distance, label) pairs of the run with record `r` in slot `sl`.  The number of PETs that entered DBSCAN comes
+// from the device while the run has not been waited for (dM; the list form's own counts go first), from the header afterwards (M)
+K7Src k7_src(cl_chrom* c, const cl_chrom::Held& r, cl_chrom::Slot& sl, int cut, int M, const int* dM)
+{
+    K7Src s{};
+    s.sorted = r.sorted_src ? (r.k7_lcnt ? 2 : 1) : 0; s.n = (int)c->n; s.M = M; s.v0 = r.k7_v0; s.dM = r.k7_lcnt ? r.k7_lcnt : dM;
+    s.X = c->d_x; s.Y = c->d_y; s.labels = sl.labels.as<int>(); s.sv = r.k7_sv; s.slab = sl.slab.as<int>();
+    s.dh = k7_hist_for(c, cut);
+    return s;
+}
+
+// The run's record (c->run.held) is completed here and committed to the slot in the one assignment at the end: a return in front
+// of it leaves the slot describing the run that was last enqueued there completely
 int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* d_M)
 {
     const int n = (int)c->n;
     int32_t* const labels_out = req.labels_out;
     cl_chrom::Slot& sl = c->slot[c->cur];
-    int* dh = c->hdr.as<int>() + 16 * c->cur;
+    cl_chrom::Held& held = c->run.held;
+    int* dh = c->hdr.as<int>() + HDR_WORDS * c->cur;
     // the pinned host rows of the cluster table: only a run that exports its table needs them (a sweep step does not, and
     // page-locking (n / 16 + 65 536) rows per result slot was most of the first sweep's overhead: 1 .. 10 ms per handle and slot)
     if (sl.h_boxes_cap == 0 && c->export_table && req.step < 0) {
@@ -3343,16 +3357,14 @@ int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* 
     if (req.step < 0)
         hipLaunchKernelGGL(k_export_table, dim3(256), dim3(TPB), 0, c->stream, dh, make_table(c), sl.h_boxes,
                            exported ? (int)std::min<size_t>(sl.h_boxes_cap, 0x7fffffff) : -1);
-    sl.exported = exported;
-    sl.step_valid = false;
-    sl.host_written = false;
+    held.exported = exported;
     if (req.step >= 0) {
         // sweep-step tail, still inside the run's stream: classify the table (pipe.py:83-97), append the inter-ligation
         // boxes to the chromosome's candidate buffer, reduce the distance statistics -- the host gets everything with
         // the run's own completion (one wait per chromosome and step)
         int rc;
         if ((rc = c->k7_cls.ensure((size_t)n + 16))) return rc;
-        const int kmax = std::max(1, std::min(sl.kmax, n));     // the number of ids K is only known on the device: K <= kmax
+        const int kmax = std::max(1, std::min(c->run.kmax, n)); // the number of ids K is only known on the device: K <= kmax
         if ((rc = ensure_cand_capacity(c, c->cand.n + kmax))) return rc;
         // step output (device and pinned host): 16 B box totals | the reduced statistics (one K7Part) | log histogram | fine window;
         // the workgroup partials live behind it on the device only
@@ -3371,10 +3383,7 @@ int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* 
         hipLaunchKernelGGL(k_cand_append, dim3(nb), dim3(256), 0, c->stream, (const int*)dh, cls, t, (const int*)nullptr, (const int*)bcount,
                            (int)c->cand.n, req.step, (int)std::min<long long>(c->cand.cap, INT_MAX), c->cand.box.as<int4>(), c->cand.step.as<int>());
         K7Part* parts = (K7Part*)(ds + out_bytes);
-        K7Src src{};
-        src.sorted = sl.sorted_src ? (sl.k7_lcnt ? 2 : 1) : 0; src.n = n; src.M = 0; src.v0 = sl.k7_v0; src.dM = sl.k7_lcnt ? sl.k7_lcnt : d_M;
-        src.X = c->d_x; src.Y = c->d_y; src.labels = sl.labels.as<int>(); src.sv = sl.k7_sv; src.slab = sl.slab.as<int>();
-        src.dh = k7_hist_for(c, req.cut);
+        const K7Src src = k7_src(c, held, sl, req.cut, 0, d_M);
         int k7b = K7_STEP_BLOCKS;
 #ifdef CLOOPS_DEVEL
         int k7t = K7_STEP_THREADS;
@@ -3398,29 +3407,30 @@ int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* 
                                    (unsigned long long*)sl.h_step, (const int*)dh, sl.h_hdr);
         }
 #endif
-        sl.host_written = labels_out == nullptr;        // nothing left for the copy stream
-        sl.fine_lo = req.fine_lo;
-        sl.step_valid = true;
+        held.host_written = labels_out == nullptr;      // nothing left for the copy stream
+        held.fine_lo = req.fine_lo;
+        held.step_valid = true;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.ev_done, c->stream));
     ev_record(c, 6);
-    sl.wait_done = sl.host_written && !c->profiling;
-    if (sl.wait_done) {
+    held.wait_done = held.host_written && !c->profiling;
+    if (held.wait_done) {
         // sweep step: k7_reduce_parts has stored header and step output in pinned host memory; completion = the run's own event
     } else {
         if (c->copy_mode == 2 && !c->shared_copy && !(c->shared_copy = paired_copy_stream(c->stream))) return fail(CL_ERR_HIP, "hipStreamCreate(copy)");
         hipStream_t cs = c->copy_mode == 1 ? c->stream : (c->copy_mode == 2 ? c->shared_copy : c->copy_stream);
         if (cs != c->stream) HIP_TRY(hipStreamWaitEvent(cs, sl.ev_done, 0));
         HIP_TRY(hipMemcpyAsync(sl.h_hdr, dh, 32, hipMemcpyDeviceToHost, cs));
-        if (sl.step_valid) HIP_TRY(hipMemcpyAsync(sl.h_step, sl.d_step.p, 16 + sizeof(K7Part) + K7_LOGBINS * 8 + K7_FINE * 8, hipMemcpyDeviceToHost, cs));
+        if (held.step_valid) HIP_TRY(hipMemcpyAsync(sl.h_step, sl.d_step.p, 16 + sizeof(K7Part) + K7_LOGBINS * 8 + K7_FINE * 8, hipMemcpyDeviceToHost, cs));
         if (labels_out) HIP_TRY(hipMemcpyAsync(labels_out, sl.labels.p, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
         if (c->profiling) (void)hipEventRecord(sl.ev[7], cs);
         HIP_TRY(hipEventRecord(sl.ev_copied, cs));
     }
+    held.n_strips = n_strips;
+    held.labels_out = labels_out;
+    sl.held = held;                                     // the one place that writes a slot's record
     sl.pending = true;
-    sl.n_strips = n_strips;
-    sl.labels_out = labels_out;
     c->enq++;
     c->cur ^= 1;
     return CL_OK;
@@ -3431,6 +3441,7 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
     if (c->deq == c->enq) return fail(CL_ERR_ARG, "cl_wait: no run in flight");
     const int w = c->deq & 1;
     cl_chrom::Slot& sl = c->slot[w];
+    const cl_chrom::Held& held = sl.held;
 #ifdef CLOOPS_DEVEL
     static const bool dbg_wait = getenv("CLOOPS_DBG_WAIT") != nullptr;
 #else
@@ -3443,7 +3454,7 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
         fprintf(stderr, "[wait] run %d slot %d: compute_done=%d copied=%d next_done=%d\n", c->deq, w, q1 == hipSuccess, q2 == hipSuccess,
                 (int)(hipEventQuery(c->slot[w ^ 1].ev_done) == hipSuccess));
     }
-    HIP_TRY(hipEventSynchronize(sl.wait_done ? sl.ev_done : sl.ev_copied));
+    HIP_TRY(hipEventSynchronize(held.wait_done ? sl.ev_done : sl.ev_copied));
     if (dbg_wait) {
         clock_gettime(CLOCK_MONOTONIC, &ts1);
         fprintf(stderr, "[wait]   ev_copied after %.0f us; next_done=%d\n", (ts1.tv_sec - ts0.tv_sec) * 1e6 + (ts1.tv_nsec - ts0.tv_nsec) / 1e3,
@@ -3459,71 +3470,55 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
         fprintf(stderr, "[counters] n=%lld uncertain=%d records=%d overflow=%d roots=%d listed=%d\n", (long long)c->n, h[CTR_NU], h[CTR_NREC], h[CTR_OVERFLOW], h[CTR_NROOT], h[CTR_NFLAG]);
     }
 #endif
-    const int K = sl.h_hdr[0];
-    if (sl.pairs_host) {
-        // the (row, label) pairs of a cl_cluster_pairs_async run: their number is in the header that has just arrived
-        int2* dst = sl.pairs_host;
-        sl.pairs_host = nullptr;
-        const long long kp = sl.h_hdr[6];
+    const int K = sl.h_hdr[HDR_K];
+    if (held.extra.dst) {
+        // the pairs / the row mask and its labels of the run: the number of labelled PETs is in the header that has just arrived
+        const cl_chrom::Held::Extra x = held.extra;
+        sl.held.extra.dst = nullptr;                     // served (or refused) once
+        const long long kp = sl.h_hdr[HDR_LABELLED];
         // the kernel clamps its stores at the capacity but keeps counting: a run that labelled more PETs than the caller's
-        // buffer holds is an argument error, nothing is copied (the staging buffer holds `capacity` pairs, not kp)
-        if (kp > sl.pairs_host_cap) {
+        // buffer holds is an argument error, nothing is copied (the staging buffer holds `capacity` of them, not kp)
+        if (kp > x.cap) {
             c->refused_labelled = kp;                    // (cl_last_n_labelled: the capacity the caller needs)
-            return fail(CL_ERR_ARG, "cl_cluster_pairs_async: the run labelled more PETs than capacity_pairs (n always suffices)");
+            return fail(CL_ERR_ARG, x.refusal);
         }
-        if (kp > 0 && sl.h_hdr[1] == 0) {
-            HIP_TRY(hipMemcpyAsync(dst, sl.pairs.p, (size_t)kp * 8, hipMemcpyDeviceToHost, c->aux_stream));
+        if ((kp > 0 || x.copy_empty) && sl.h_hdr[HDR_ERR] == 0) {
+            HIP_TRY(hipMemcpyAsync(x.dst, sl.pairs.p, x.fixed + (size_t)kp * x.per, hipMemcpyDeviceToHost, c->aux_stream));
             // (cl_set_pairs_defer: the caller completes the copy with cl_pairs_sync -- a loop over many handles then has all their
             //  copies in flight together instead of one engine's worth at a time)
             if (c->pairs_defer) c->pairs_copy_pending = true;
             else HIP_TRY(hipStreamSynchronize(c->aux_stream));
         }
     }
-    if (sl.mask_host) {
-        // cl_cluster_rowmask_async: ceil(n / 64) mask words, then one label per set bit (their number: header word 6), one copy
-        void* dst = sl.mask_host;
-        sl.mask_host = nullptr;
-        const long long kp = sl.h_hdr[6];
-        if (kp > sl.mask_host_cap) {
-            c->refused_labelled = kp;
-            return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: the run labelled more PETs than capacity_labels (n always suffices)");
-        }
-        if (sl.h_hdr[1] == 0) {
-            const size_t nw = (size_t)((c->n + 63) / 64);
-            HIP_TRY(hipMemcpyAsync(dst, sl.pairs.p, nw * 8 + (size_t)kp * 4, hipMemcpyDeviceToHost, c->aux_stream));
-            if (c->pairs_defer) c->pairs_copy_pending = true;
-            else HIP_TRY(hipStreamSynchronize(c->aux_stream));
-        }
-    }
-    if (sl.h_hdr[1] != 0)
-        return fail(CL_ERR_HIP, sl.h_hdr[1] == 8 ? "internal: the number of PETs that passed the cut differs from the host's count"
-                                : sl.h_hdr[1] == 4 ? "internal: strip longer than the hybrid sort accepts"
+    if (sl.h_hdr[HDR_ERR] != 0)
+        return fail(CL_ERR_HIP, sl.h_hdr[HDR_ERR] == HDR_ERR_COUNT ? "internal: the number of PETs that passed the cut differs from the host's count"
+                                : sl.h_hdr[HDR_ERR] == HDR_ERR_STRIP ? "internal: strip longer than the hybrid sort accepts"
                                                  : "internal: release-record overflow (border point with > 4 adjacent components)");
     // the table rows are already in the slot's pinned cache (k_export_table); only if that cache was
     // too small (K > capacity, reported in the header) grow it and fetch the rows with a copy
-    int nc = sl.h_hdr[3], ml = sl.h_hdr[4];
-    if (sl.h_hdr[5] != 0) {
+    int nc = sl.h_hdr[HDR_NCLUSTERS], ml = sl.h_hdr[HDR_MAXLABEL];
+    if (sl.h_hdr[HDR_TRUNC] != 0) {
         if (sl.h_boxes) (void)hipHostFree(sl.h_boxes);
         sl.h_boxes = nullptr; sl.h_boxes_cap = 0;
         size_t cap = (size_t)K + (size_t)K / 4 + 1024;
         HIP_TRY(hipHostMalloc((void**)&sl.h_boxes, cap * sizeof(cl_box), hipHostMallocDefault));
         sl.h_boxes_cap = cap;
         // slow path (first run with very many clusters): export again into the larger buffer
-        int* dh = c->hdr.as<int>() + 16 * w;
+        int* dh = c->hdr.as<int>() + HDR_WORDS * w;
         int reset[3] = {0, -1, 0};
-        HIP_TRY(hipMemcpyAsync(dh + 3, reset, 12, hipMemcpyHostToDevice, c->aux_stream));
+        HIP_TRY(hipMemcpyAsync(dh + HDR_NCLUSTERS, reset, 12, hipMemcpyHostToDevice, c->aux_stream));
         hipLaunchKernelGGL(k_export_table, dim3(256), dim3(TPB), 0, c->aux_stream, dh, make_table_slot(c, w), sl.h_boxes, (int)std::min<size_t>(cap, 0x7fffffff));
         HIP_TRY(hipMemcpyAsync(sl.h_hdr, dh, 32, hipMemcpyDeviceToHost, c->aux_stream));
         HIP_TRY(hipStreamSynchronize(c->aux_stream));
-        nc = sl.h_hdr[3]; ml = sl.h_hdr[4];
+        nc = sl.h_hdr[HDR_NCLUSTERS]; ml = sl.h_hdr[HDR_MAXLABEL];
     }
     if (n_clusters) *n_clusters = nc;
     if (max_label) *max_label = ml;
     c->last_K = ml + 1;
     c->last_slot = w;
     c->have_result = true;
-    c->k7_classified = sl.step_valid;                    // the step tail has classified this run's table already
-    if (sl.step_valid) {
+    c->k7_classified = held.step_valid;                  // the step tail has classified this run's table already
+    if (held.step_valid) {
         const long long ni = ((const long long*)sl.h_step)[0];
         if (c->cand.n + ni > c->cand.cap) return fail(CL_ERR_GRID, "internal: candidate buffer overrun");
         c->cand.n += ni;
@@ -3540,12 +3535,12 @@ static int finish_wait(cl_chrom* c, int32_t* n_clusters, int32_t* max_label)
         (void)hipEventElapsedTime(&tm.ms_table, ev[5], ev[6]);
         (void)hipEventElapsedTime(&tm.ms_d2h, ev[6], ev[7]);
         (void)hipEventElapsedTime(&tm.ms_total, ev[0], ev[7]);
-        tm.n_in = sl.h_hdr[2];
-        tm.n_strips = sl.n_strips;
+        tm.n_in = sl.h_hdr[HDR_M];
+        tm.n_strips = held.n_strips;
         tm.ms_bracket = c->ev_bracket_ms;
         tm.ms_band = 0.f;
-        if (sl.band_timed) (void)hipEventElapsedTime(&tm.ms_band, ev[8], ev[9]);
-        tm.n_queried = sl.n_queried;
+        if (held.band_timed) (void)hipEventElapsedTime(&tm.ms_band, ev[8], ev[9]);
+        tm.n_queried = held.n_queried;
     }
     return CL_OK;
 }
@@ -3597,12 +3592,19 @@ extern "C" int cl_cluster_async(cl_chrom* c, int variant, int32_t eps, int32_t m
     return enqueue(c, req);
 }
 
-extern "C" int cl_cluster_pairs_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, int32_t* pinned_pairs_out, int64_t capacity_pairs)
+// the argument checks of the two forms whose output cl_wait copies out (pairs, row mask)
+static int check_extra_args(cl_chrom* c, const char* who, const char* no_buffer, int variant, int min_pts, const void* out, int64_t capacity)
 {
     if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (!pinned_pairs_out || capacity_pairs <= 0) return fail(CL_ERR_ARG, "cl_cluster_pairs_async: no pair buffer");
-    if (variant != CL_VARIANT_CDBSCAN1 && variant != CL_VARIANT_CDBSCAN2) return fail(CL_ERR_ARG, "cl_cluster_pairs_async: rotated variants only");
-    if (c->traversal < 3 || min_pts < 2 || min_pts > 128) return fail(CL_ERR_ARG, "cl_cluster_pairs_async: needs the list form of the run (traversal level >= 3, minPts 2 .. 128)");
+    if (!out || capacity <= 0) return fail_at(CL_ERR_ARG, who, no_buffer);
+    if (variant != CL_VARIANT_CDBSCAN1 && variant != CL_VARIANT_CDBSCAN2) return fail_at(CL_ERR_ARG, who, "rotated variants only");
+    if (c->traversal < 3 || min_pts < 2 || min_pts > 128) return fail_at(CL_ERR_ARG, who, "needs the list form of the run (traversal level >= 3, minPts 2 .. 128)");
+    return CL_OK;
+}
+
+extern "C" int cl_cluster_pairs_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, int32_t* pinned_pairs_out, int64_t capacity_pairs)
+{
+    if (int rc = check_extra_args(c, "cl_cluster_pairs_async", "no pair buffer", variant, min_pts, pinned_pairs_out, capacity_pairs)) return rc;
     RunRequest req;
     req.variant = variant; req.eps = eps; req.minPts = min_pts; req.cut = cut;
     req.pairs_out = (int2*)pinned_pairs_out; req.pairs_cap = capacity_pairs;
@@ -3610,10 +3612,7 @@ extern "C" int cl_cluster_pairs_async(cl_chrom* c, int variant, int32_t eps, int
 }
 extern "C" int cl_cluster_rowmask_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, void* pinned_out, int64_t capacity_labels)
 {
-    if (!c) return fail(CL_ERR_ARG, "null chromosome handle");
-    if (!pinned_out || capacity_labels <= 0) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: no output buffer");
-    if (variant != CL_VARIANT_CDBSCAN1 && variant != CL_VARIANT_CDBSCAN2) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: rotated variants only");
-    if (c->traversal < 3 || min_pts < 2 || min_pts > 128) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: needs the list form of the run (traversal level >= 3, minPts 2 .. 128)");
+    if (int rc = check_extra_args(c, "cl_cluster_rowmask_async", "no output buffer", variant, min_pts, pinned_out, capacity_labels)) return rc;
     RunRequest req;
     req.variant = variant; req.eps = eps; req.minPts = min_pts; req.cut = cut;
     req.mask_out = pinned_out; req.mask_cap = capacity_labels;
@@ -3635,7 +3634,7 @@ extern "C" int64_t cl_last_n_labelled(const cl_chrom* c)
     if (!c) return -1;
     if (c->refused_labelled >= 0) return c->refused_labelled;            // the run cl_wait has just refused with CL_ERR_ARG: more than its capacity
     if (!c->have_result || c->last_slot < 0) return -1;
-    return c->slot[c->last_slot].h_hdr[6];
+    return c->slot[c->last_slot].h_hdr[HDR_LABELLED];
 }
 
 extern "C" int cl_cluster_step_async(cl_chrom* c, int variant, int32_t eps, int32_t min_pts, int32_t cut, int32_t step, int64_t fine_lo)
@@ -3652,7 +3651,7 @@ extern "C" int cl_cluster_step_async(cl_chrom* c, int variant, int32_t eps, int3
 extern "C" int cl_step_result(cl_chrom* c, int64_t* n_inter, int64_t* n_self, cl_dsummary* out)
 {
     if (!c || !out) return fail(CL_ERR_ARG, "cl_step_result: null argument");
-    if (!c->have_result || c->last_slot < 0 || !c->slot[c->last_slot].step_valid)
+    if (!c->have_result || c->last_slot < 0 || !c->slot[c->last_slot].held.step_valid)
         return fail(CL_ERR_ARG, "cl_step_result: the last completed run was not a sweep step");
     const char* h = c->slot[c->last_slot].h_step;
     if (n_inter) *n_inter = ((const long long*)h)[0];
@@ -3662,7 +3661,7 @@ extern "C" int cl_step_result(cl_chrom* c, int64_t* n_inter, int64_t* n_self, cl
     const K7Part* part = (const K7Part*)(h + 16);           // reduced on the device in a fixed order (k7_reduce_block)
     for (int g = 0; g < 2; ++g) { out->sumx[g] = part->sx[g]; out->sumxx[g] = part->sxx[g]; out->n_all[g] = part->n_all[g]; out->n_pos[g] = part->n_pos[g]; }
     memcpy(out->loghist, h + 16 + sizeof(K7Part), K7_LOGBINS * 8);
-    out->fine_lo = c->slot[c->last_slot].fine_lo;
+    out->fine_lo = c->slot[c->last_slot].held.fine_lo;
     if (out->fine_lo >= 0) memcpy(out->fine, h + 16 + sizeof(K7Part) + K7_LOGBINS * 8, K7_FINE * 8);
     return CL_OK;
 }
@@ -3764,13 +3763,11 @@ static int run_rotated(cl_chrom* c, const RunRequest& req)
     if ((rc = c->rootlist.ensure((size_t)n * 4)) || (rc = c->cflag8.ensure((size_t)n + 16))) return rc;
     unsigned char* cflag = c->cflag8.as<unsigned char>();
     ENQ_MARK();
-    {
-        cl_chrom::Slot& sl = c->slot[c->cur];
-        sl.rows_valid = rows && !req.pairs_out; sl.sorted_src = g.swap != 0; sl.k7_sv = c->run.sv; sl.k7_v0 = g.V0; sl.k7_lcnt = nullptr;
-        // variant 2 hands an id only to a live cluster, which has >= minPts members (cDBSCAN2.py:180-185): K <= n / minPts;
-        // variant 1 numbers every component, dropped ones included (cDBSCAN.py:136-152): K <= n
-        sl.kmax = (variant == CL_VARIANT_CDBSCAN2 && minPts >= 1) ? n / minPts + 1 : n;
-    }
+    cl_chrom::Held& held = c->run.held;
+    held.rows_valid = rows && !req.pairs_out; held.sorted_src = g.swap != 0; held.k7_sv = c->run.sv; held.k7_v0 = g.V0;
+    // variant 2 hands an id only to a live cluster, which has >= minPts members (cDBSCAN2.py:180-185): K <= n / minPts;
+    // variant 1 numbers every component, dropped ones included (cDBSCAN.py:136-152): K <= n
+    c->run.kmax = (variant == CL_VARIANT_CDBSCAN2 && minPts >= 1) ? n / minPts + 1 : n;
     int* strip = c->run.strip;
     int* sv = c->run.sv;
     int* sa = c->run.sa;
@@ -3860,19 +3857,22 @@ static int run_rotated(cl_chrom* c, const RunRequest& req)
     // rlabel reuses the chainhead buffer (free after k_chain_parent); the kernel also resets the table rows of the ids handed out
     hipLaunchKernelGGL(k_root_labels_bits_l, dim3(512), dim3(TPB), 0, c->stream, g, rootlist, counters, c->compkey.as<int>(), c->ncore.as<int>(), c->bsize.as<int>(),
                        c->state.as<int>(), c->flag.as<unsigned>(), (const int*)c->rankscan.as<int>(), (const int*)wboff, c->chainhead.as<int>(), t, nblkw,
-                       c->hdr.as<int>() + 16 * c->cur, c->run.dM ? c->run.dM : (const int*)(strip + g.S));
+                       c->hdr.as<int>() + HDR_WORDS * c->cur, c->run.dM ? c->run.dM : (const int*)(strip + g.S));
     c->run.hdr_packed = true;
     if (level >= 3) {
-        c->slot[c->cur].pairs_host = req.pairs_out;
-        c->slot[c->cur].pairs_host_cap = req.pairs_cap;
-        if (req.pairs_out && (rc = c->slot[c->cur].pairs.ensure((size_t)std::max<long long>(req.pairs_cap, 1) * 8))) return rc;
-        if ((rc = lists_final(c, req, g, nm, L, rows, c->hdr.as<int>() + 16 * c->cur + 6))) return rc;
-        cl_chrom::Slot& sl = c->slot[c->cur];
-        sl.mask_host = req.mask_out; sl.mask_host_cap = req.mask_cap;
+        int* const labelled = c->hdr.as<int>() + HDR_WORDS * c->cur + HDR_LABELLED;
+        if (req.pairs_out) {
+            held.extra = {req.pairs_out, req.pairs_cap, 0, 8, false, "cl_cluster_pairs_async: the run labelled more PETs than capacity_pairs (n always suffices)"};
+            if ((rc = c->slot[c->cur].pairs.ensure((size_t)std::max<long long>(req.pairs_cap, 1) * 8))) return rc;
+        }
+        if ((rc = lists_final(c, req, g, nm, L, rows, labelled))) return rc;
         // (cl_cluster_rowmask_async: the row-aligned labels the kernel above has just written -> mask words + labels in row order,
-        //  their number in header word 6 like the pairs')
-        if (req.mask_out && (rc = lists_rowmask(c, req, c->hdr.as<int>() + 16 * c->cur + 6))) return rc;
-        sl.k7_lcnt = L.lcnt; sl.k7_sv = c->l_dist.as<int>();      // the distance statistics read the run's lists (K7Src::sorted == 2)
+        //  their number in the header like the pairs')
+        if (req.mask_out) {
+            held.extra = {req.mask_out, req.mask_cap, (size_t)((n + 63) / 64) * 8, 4, true, "cl_cluster_rowmask_async: the run labelled more PETs than capacity_labels (n always suffices)"};
+            if ((rc = lists_rowmask(c, req, labelled))) return rc;
+        }
+        held.k7_lcnt = L.lcnt; held.k7_sv = c->l_dist.as<int>();  // the distance statistics read the run's lists (K7Src::sorted == 2)
     } else {
         if (req.mask_out) return fail(CL_ERR_ARG, "cl_cluster_rowmask_async: this run did not take the list form");
         if (level == 2 && (rc = lists_scatter_owner(c, nm, L))) return rc;
@@ -3894,7 +3894,7 @@ extern "C" int cl_get_boxes(cl_chrom* c, cl_box* boxes_out)
     const int K = c->last_K;
     if (K <= 0) return CL_OK;
     if (!boxes_out) return fail(CL_ERR_ARG, "boxes_out is null");
-    if (c->last_slot >= 0 && !c->slot[c->last_slot].exported) return fail(CL_ERR_ARG, "cl_get_boxes: the run was made with the table export switched off");
+    if (c->last_slot >= 0 && !c->slot[c->last_slot].held.exported) return fail(CL_ERR_ARG, "cl_get_boxes: the run was made with the table export switched off");
     memcpy(boxes_out, c->slot[c->last_slot].h_boxes, (size_t)K * sizeof(cl_box));
     return CL_OK;
 }
@@ -3902,11 +3902,11 @@ extern "C" int cl_get_boxes(cl_chrom* c, cl_box* boxes_out)
 extern "C" int64_t cl_last_n_in(const cl_chrom* c)
 {
     if (!c || !c->have_result || c->last_slot < 0) return 0;
-    return c->slot[c->last_slot].h_hdr[2];
+    return c->slot[c->last_slot].h_hdr[HDR_M];
 }
 
 extern "C" const cl_box* cl_boxes_host(const cl_chrom* c)
 {
-    if (!c || !c->have_result || c->last_slot < 0 || c->last_K <= 0 || !c->slot[c->last_slot].exported) return nullptr;
+    if (!c || !c->have_result || c->last_slot < 0 || c->last_K <= 0 || !c->slot[c->last_slot].held.exported) return nullptr;
     return c->slot[c->last_slot].h_boxes;
 }

@@ -447,7 +447,7 @@ int run_block(cl_chrom* c, const RunRequest& req)
     HIP_TRY(hipGetLastError());
     // blockDBSCAN.py:74: an empty (fully filtered) mat raises only when the class is called
     // on it; pipe.py:64-65 returns before that, so cut > 0 with no survivors is just empty.
-    { cl_chrom::Slot& sl = c->slot[c->cur]; sl.rows_valid = true; sl.sorted_src = false; sl.kmax = n; }      // ids <= cells <= n
+    c->run.held.rows_valid = true; c->run.kmax = n;          // ids <= cells <= n
     rc = finish_enqueue(c, req, p.R + 1, &sc->M);
     guard.armed = rc != CL_OK;
     return rc;

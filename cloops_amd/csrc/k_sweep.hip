@@ -16,7 +16,7 @@
 // group 0 = inter, group 1 = self (+ short), -1 = in no group
 __global__ void k7_classify(const int* __restrict__ hdr, Table t, signed char* __restrict__ cls)
 {
-    const int K = hdr[0];
+    const int K = hdr[HDR_K];
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
     const cl_box b = t.get(k);
@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(256)
 k_cand_count(const int* __restrict__ dK, const signed char* __restrict__ cls, int* __restrict__ bcount /* [nb] inter, [nb] self */, int nb)
 {
     __shared__ int red[2][4];
-    const int K = dK[0];
+    const int K = dK[HDR_K];
     const int base = blockIdx.x * CAND_BLOCK;
     int ci = 0, cs = 0;
     for (int k = threadIdx.x; k < CAND_BLOCK; k += 256) {
@@ -277,7 +277,7 @@ k_step_classify_count(const int* __restrict__ dK, Table t, signed char* __restri
 {
     __shared__ int red[2][4];
     for (int k = blockIdx.x * 256 + threadIdx.x; k < nzero; k += gridDim.x * 256) zero[k] = 0ull;
-    const int K = dK[0];
+    const int K = dK[HDR_K];
     const int base = blockIdx.x * CAND_BLOCK;
     int ci = 0, cs = 0;
     for (int k = threadIdx.x; k < CAND_BLOCK; k += 256) {
@@ -338,7 +338,7 @@ __global__ void __launch_bounds__(256)
 k_cand_append(const int* __restrict__ dK, const signed char* __restrict__ cls, Table t, const int* __restrict__ boff /* or null: */,
               const int* __restrict__ bcount, int base, int step, int cap, int4* __restrict__ cbox, int* __restrict__ cstep)
 {
-    ordered_scatter_block(dK[0], boff, bcount, [&](int i) { return cls[i] == 0; },
+    ordered_scatter_block(dK[HDR_K], boff, bcount, [&](int i) { return cls[i] == 0; },
                           [&](int i, int r) { const int d = base + r; if (d < cap) { cbox[d] = make_int4(t.minx[i], t.maxx[i], t.miny[i], t.maxy[i]); cstep[d] = step; } });
 }
 __device__ __forceinline__ u64 box_hash(int4 b, u64 salt)
@@ -504,7 +504,7 @@ static int k7_prepare(cl_chrom* c)
     if ((rc = c->k7_cls.ensure((size_t)c->n + 16))) return rc;
     if ((rc = c->k7_parts.ensure(K7_BLOCKS * sizeof(K7Part) + K7_LOGBINS * 8 + 4096))) return rc;
     if (!c->k7_classified) {
-        int* dh = c->hdr.as<int>() + 16 * c->last_slot;
+        int* dh = c->hdr.as<int>() + HDR_WORDS * c->last_slot;
         LAUNCH(k7_classify, c->n + 1, dh, make_table_slot(c, c->last_slot), c->k7_cls.as<signed char>());
         c->k7_classified = true;
     }
@@ -514,12 +514,7 @@ static int k7_prepare(cl_chrom* c)
 static K7Src k7_source(cl_chrom* c, int cut)
 {
     cl_chrom::Slot& sl = c->slot[c->last_slot];
-    K7Src s{};
-    s.dh = k7_hist_for(c, cut);
-    s.sorted = sl.sorted_src ? (sl.k7_lcnt ? 2 : 1) : 0; s.n = (int)c->n; s.M = sl.h_hdr[2]; s.v0 = sl.k7_v0;
-    s.dM = sl.k7_lcnt;
-    s.X = c->d_x; s.Y = c->d_y; s.labels = sl.labels.as<int>(); s.sv = sl.k7_sv; s.slab = sl.slab.as<int>();
-    return s;
+    return k7_src(c, sl.held, sl, cut, sl.h_hdr[HDR_M], nullptr);      // the last completed run: M from its header
 }
 
 extern "C" int cl_dist_summary(cl_chrom* c, int32_t cut, cl_dsummary* out)
@@ -530,7 +525,7 @@ extern "C" int cl_dist_summary(cl_chrom* c, int32_t cut, cl_dsummary* out)
     if (c && c->n == 0) return CL_OK;
     int rc = k7_prepare(c);
     if (rc) return rc;
-    if (!c->slot[c->last_slot].sorted_src && !c->slot[c->last_slot].rows_valid) return fail(CL_ERR_ARG, "cl_dist_summary: the last run left no labels");
+    if (!c->slot[c->last_slot].held.sorted_src && !c->slot[c->last_slot].held.rows_valid) return fail(CL_ERR_ARG, "cl_dist_summary: the last run left no labels");
     unsigned long long* dh = (unsigned long long*)((char*)c->k7_parts.p + K7_BLOCKS * sizeof(K7Part));
     HIP_TRY(hipMemsetAsync(dh, 0, K7_LOGBINS * 8, c->stream));
     K7Part* dpart = (K7Part*)((char*)dh + K7_LOGBINS * 8);                  // behind the histogram (the buffer's spare 4 KB)
@@ -715,7 +710,7 @@ extern "C" int cl_dist_collect(cl_chrom* c, int32_t cut, int64_t* n_pos, int64_t
     if (c && c->n == 0) return CL_OK;
     int rc = k7_prepare(c);
     if (rc) return rc;
-    if (!c->slot[c->last_slot].sorted_src && !c->slot[c->last_slot].rows_valid) return fail(CL_ERR_ARG, "cl_dist_collect: the last run left no labels");
+    if (!c->slot[c->last_slot].held.sorted_src && !c->slot[c->last_slot].held.rows_valid) return fail(CL_ERR_ARG, "cl_dist_collect: the last run left no labels");
     c->kde.run = -1;
     // one entry per PET of the run at most, plus one per distance below the cut when those come from the distance histogram
     const long long cap = c->n + 65536;
@@ -809,14 +804,14 @@ extern "C" int cl_cand_append(cl_chrom* c, int32_t step, int64_t* n_inter, int64
     int rc = k7_prepare(c);                              // classifies the table of the last completed run (pipe.py:83-97)
     if (rc) return rc;
     cl_chrom::Slot& sl = c->slot[c->last_slot];
-    const int K = sl.h_hdr[0];
+    const int K = sl.h_hdr[HDR_K];
     if (K <= 0) return CL_OK;
     if ((rc = ensure_cand_capacity(c, c->cand.n + K))) return rc;
     const int nb = nblocks(K, CAND_BLOCK);
     if ((rc = c->sel_tmp.ensure((size_t)nb * 12 + 64))) return rc;
     int* bcount = c->sel_tmp.as<int>();
     int* boff = bcount + 2 * nb;
-    const int* dK = c->hdr.as<int>() + 16 * c->last_slot;
+    const int* dK = c->hdr.as<int>() + HDR_WORDS * c->last_slot;
     hipLaunchKernelGGL(k_cand_count, dim3(nb), dim3(256), 0, c->stream, dK, c->k7_cls.as<signed char>(), bcount, nb);
     size_t tb = c->scan_tmp.bytes;
     hipError_t e = rocprim::exclusive_scan(c->scan_tmp.p, tb, bcount, boff, 0, (size_t)nb, rocprim::plus<int>(), c->stream);

@@ -210,7 +210,7 @@ int run_weighted(cl_chrom* c, const RunRequest& req)
     hipLaunchKernelGGL(k64_final, dim3(nblocks(n, BIGTPB)), dim3(BIGTPB), 0, c->stream, n, c->d_x, c->d_y, srow, c->owner.as<int>(),
                        c->chainhead.as<int>(), c->slot[c->cur].labels.as<int>(), t);
     HIP_TRY(hipGetLastError());
-    { cl_chrom::Slot& sl = c->slot[c->cur]; sl.rows_valid = true; sl.sorted_src = false; }
+    c->run.held.rows_valid = true;
     rc = finish_enqueue(c, req, g.S + 2, strip + g.S);
     guard.armed = rc != CL_OK;
     return rc;

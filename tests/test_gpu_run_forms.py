@@ -129,21 +129,40 @@ def _leak(ch):
 
 
 # ---- two runs in flight, of different forms ---------------------------------------------------------
+def _check_last(ch, res, form, variant, eps, m, cut, tag):
+    """what the handle answers from the record of the last completed run, against the form that was waited for last"""
+    want = _oracle(variant, eps, m, cut)["labels"]
+    # the labelled PETs: counted by the pairs and the row-mask form only
+    assert int(ch._lib.cl_last_n_labelled(ch._h)) == (0 if form == "plain" else int((want >= 0).sum())), tag
+    # row labels on the device: every form but the pairs, which replace them
+    assert bool(ch._lib.cl_labels_device(ch._h)) == (form != "pairs"), tag
+    assert np.array_equal(_get_boxes(ch, res.max_label), res.boxes), tag
+    with pytest.raises(_lib.CloopsHipError) as ei:                                  # none of them was a sweep step
+        ch.step_result()
+    assert ei.value.code == _lib.CL_ERR_ARG, tag
+
+
 def _in_flight(ch):
     ch.cluster_async("v2", EPS, M, 0)
     ch.cluster_pairs_async("v2", EPS, M, 300)
     _check_plain(ch.wait(copy=True), "v2", EPS, M, 0, "plain in front of pairs")
-    _check_pairs(*ch.wait_pairs(copy=True), "v2", EPS, M, 300, "pairs behind plain")
+    res, pairs = ch.wait_pairs(copy=True)
+    _check_pairs(res, pairs, "v2", EPS, M, 300, "pairs behind plain")
+    _check_last(ch, res, "pairs", "v2", EPS, M, 300, "record behind plain, pairs")
 
     ch.cluster_pairs_async("v1", EPS, M, 300)
     ch.cluster_rowmask_async("v2", EPS, M, 150)
     _check_pairs(*ch.wait_pairs(copy=True), "v1", EPS, M, 300, "pairs in front of rowmask")
-    _check_rowmask(ch, *ch.wait_rowmask(copy=True), "v2", EPS, M, 150, "rowmask behind pairs")
+    res, mask, labels = ch.wait_rowmask(copy=True)
+    _check_rowmask(ch, res, mask, labels, "v2", EPS, M, 150, "rowmask behind pairs")
+    _check_last(ch, res, "rowmask", "v2", EPS, M, 150, "record behind pairs, rowmask")
 
     ch.cluster_rowmask_async("v2", EPS, M, 0)
     ch.cluster_async("v1", EPS, M, 300)
     _check_rowmask(ch, *ch.wait_rowmask(copy=True), "v2", EPS, M, 0, "rowmask in front of plain")
-    _check_plain(ch.wait(copy=True), "v1", EPS, M, 300, "plain behind rowmask")
+    res = ch.wait(copy=True)
+    _check_plain(res, "v1", EPS, M, 300, "plain behind rowmask")
+    _check_last(ch, res, "plain", "v1", EPS, M, 300, "record behind rowmask, plain")
 
 
 # ---- the working set across the kinds of run --------------------------------------------------------
@@ -210,6 +229,73 @@ def test_working_set_across_run_kinds():
         ch.close()
     print("last_region_mode:", modes)
     assert modes == MODES
+
+
+def _block_and_weighted_timing(ch):
+    """one block and one weighted run, labels against the oracle -> [(ms_band, n_queried)] of the two"""
+    out = []
+    _check_plain(ch.cluster("block", EPS, M, 0), "block", EPS, M, 0, "block, timed")
+    out.append((ch.timing()["ms_band"], ch.timing()["n_queried"]))
+    got = ch.cluster_weighted(EPS, M, WX, WY)
+    assert np.array_equal(got.labels, _weighted()), "weighted, timed"
+    out.append((ch.timing()["ms_band"], ch.timing()["n_queried"]))
+    return out
+
+
+def test_timing_record_does_not_outlive_its_run():
+    """the band time and the queried PETs that cl_get_timing reports belong to the run that was waited for: a block or a weighted run
+    has neither, whatever the slot held before.
+
+    The first FOUR runs of ROTATED, not five: a run that re-uses the counts of its eps (cl_last_region_mode 2: runs 3 and 4) queries
+    its cut band only and reports n_queried == 0 by definition (include/cloops_hip.h: "0 = none ran"), so after five runs neither slot
+    would hold a count to inherit.  Run 2 makes the words of its eps under a cut: the whole layout (n_queried > 0) and its band
+    (ms_band > 0).  After four runs slot 0 holds run 2 and slot 1 holds run 3 (ms_band > 0); the block run then takes slot 0 and the
+    weighted run slot 1, so each of the two figures has a slot it could be inherited from."""
+    fresh = _handle(None)
+    try:
+        fresh.set_profiling(True)
+        first = _block_and_weighted_timing(fresh)
+    finally:
+        fresh.close()
+    assert first == [(0.0, 0), (0.0, 0)]
+    ch = _handle(None)
+    try:
+        ch.set_profiling(True)
+        for k, (variant, eps, cut) in enumerate(ROTATED[:4]):
+            _check_plain(ch.cluster(variant, eps, M, cut), variant, eps, M, cut, ("rotated, timed", k))
+            tm = ch.timing()
+            if k == 2:                                                              # not vacuous: slot 0 holds both figures
+                assert ch.last_region_mode() == 0 and tm["ms_band"] > 0 and 0 < tm["n_queried"] <= N
+            if k == 3:                                                              # ... and slot 1 a band query's time
+                assert ch.last_region_mode() == 2 and tm["ms_band"] > 0 and tm["n_queried"] == 0
+        behind = _block_and_weighted_timing(ch)
+    finally:
+        ch.close()
+    assert behind == [(0.0, 0), (0.0, 0)]
+
+
+def test_exact_counts_write_no_slot():
+    """cl_neighbor_counts enqueues no run and writes no result slot.  The handle has no result behind it, as ever (the workspace the
+    distance statistics would read holds the counts' layout: cl_dist_summary refuses), so the slot is read through the next runs:
+    the block run that takes the slot the counts worked in, and the weighted run behind it, report nothing of a region query, and the
+    next plain run has the statistics of the one in front of the counts."""
+    ch = _handle(None)
+    try:
+        ch.set_profiling(True)
+        ch.cluster_async("v2", EPS, M, 0)
+        _check_plain(ch.wait(copy=True), "v2", EPS, M, 0, "plain in front of exact counts")
+        before = ch.dist_summary(0)
+        assert np.array_equal(ch.neighbor_counts(EPS, 300), _counts(EPS, 300)), "exact counts"
+        with pytest.raises(_lib.CloopsHipError) as ei:
+            ch.dist_summary(0)
+        assert ei.value.code == _lib.CL_ERR_ARG
+        assert _block_and_weighted_timing(ch) == [(0.0, 0), (0.0, 0)]
+        ch.cluster_async("v2", EPS, M, 0)
+        _check_plain(ch.wait(copy=True), "v2", EPS, M, 0, "plain behind exact counts")
+        after = ch.dist_summary(0)
+        assert all(np.array_equal(before[k], after[k]) for k in ("n_all", "n_pos", "loghist")), "the same run, the same statistics"
+    finally:
+        ch.close()
 
 
 @pytest.mark.parametrize("switch", [None, "nocounts", "nolayout"], ids=["default", "nocounts", "nolayout"])
