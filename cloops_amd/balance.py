@@ -18,14 +18,13 @@ Definitions (include/cloops_hip.h, cl_bal_marginals; DESIGN.md, K25):
 - A chromosome that does not converge within max_iters is reported with a warning and `converged: false`, not dropped.
 """
 import argparse
-import json
+import collections
 import logging
 import sys
 
 import numpy as np
 
-from . import matrix
-from .matrix import CHUNK, bin_label, check_res, parse_region, region_bins, window_fits
+from .matrix import CHUNK, bin_label, cell_chunks, check_res, chrom_outputs, chroms_of, common, each_chrom, region_bins, region_records
 from .peaks import write_outputs
 
 logger = logging.getLogger("cloops_amd.balance")
@@ -54,8 +53,18 @@ def valid_bins(sum_, nnz, min_nnz=10, min_count=0, mad_max=5):
     return ok
 
 
-def check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters):
-    """-> the six as numbers; ValueError for one that cl_bal_* or the mask would refuse"""
+class BalanceArgs(collections.namedtuple("BalanceArgs", "ignore_diags min_nnz min_count mad_max tol max_iters")):
+    """the six balancing options; the fields are the keywords of the jd2* and the keys of the json's `args` (`_asdict`)"""
+    __slots__ = ()
+
+    @classmethod
+    def parsed(cls, op):
+        """of a namespace with the options of add_options, unchecked"""
+        return cls(op.ignorediags, op.minnnz, op.mincount, op.mad, op.tol, op.maxiters)
+
+
+def check_args(ignore_diags=2, min_nnz=10, min_count=0, mad_max=5, tol=1e-5, max_iters=200):
+    """-> BalanceArgs of the six as numbers; ValueError for one that cl_bal_* or the mask would refuse"""
     try:
         ignore_diags, min_nnz, min_count, max_iters = int(ignore_diags), int(min_nnz), int(min_count), int(max_iters)
         mad_max, tol = float(mad_max), float(tol)
@@ -71,7 +80,7 @@ def check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters):
         raise ValueError("tol must be a number at or above 0, got %r" % tol)
     if max_iters < 0 or max_iters >= (1 << 31):
         raise ValueError("maxiters must lie in [0, 2^31), got %d" % max_iters)
-    return ignore_diags, min_nnz, min_count, mad_max, tol, max_iters
+    return BalanceArgs(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters)
 
 
 def format_bins(chrom, res, b0, sum_, nnz, weight):
@@ -111,47 +120,61 @@ def _num(v):
     return None if v != v else float(FLOAT % v)
 
 
-def balance_chrom(ch, chrom, res, cut=0, ignore_diags=2, min_nnz=10, min_count=0, mad_max=5, tol=1e-5, max_iters=200, region=None,
-                  chunk=CHUNK):
-    """One chromosome on the device: `ch` has the mat_* and bal_* methods of api.Chromosome; region = (chrom, start, end) or None
-    -> dict(bins: text, cells: text, stats: the json's entry, matrix: text or None)"""
+Balanced = collections.namedtuple("Balanced", "n_cells b0 nb n_used sum nnz mask iters converged var scale")
+
+
+def balanced_state(ch, res, cut, bal, raw=False):
+    """The folded cells of a chromosome, their marginals, the mask of the bins and -- unless `raw` -- the iteration, left on the device
+    -> Balanced.  `bal`: BalanceArgs.  The weights are not fetched (bal_weights); the caller's `finally` has the mat_free."""
+    n_cells = ch.mat_cells(res, cut=cut, fold=True)[0]
+    b0, nb, n_used = ch.bal_marginals(bal.ignore_diags)
+    sum_, nnz = ch.bal_marginals_get(0, nb)
+    mask = valid_bins(sum_, nnz, bal.min_nnz, bal.min_count, bal.mad_max)
+    result = (0, False, float("nan"), float("nan")) if raw else ch.bal_iterate(mask, max_iters=bal.max_iters, tol=bal.tol)
+    return Balanced(n_cells, b0, nb, n_used, sum_, nnz, mask, *result)
+
+
+def not_converged(chrom, st, tol, raw=False, num=fmt):
+    """the warning of a chromosome whose iteration stopped at max_iters, None for any other; `num` writes its two floats"""
+    if raw or st.nb == 0 or st.converged:
+        return None
+    return "%s did not converge in %d iterations (variance %s, tol %s)" % (chrom, st.iters, num(st.var), num(tol))
+
+
+def balance_stats(st):
+    """the four statistics of the iteration in a chromosome's entry of the json"""
+    return {"iters": int(st.iters), "converged": bool(st.converged), "var": _num(st.var), "scale": _num(st.scale)}
+
+
+def balance_chrom(ch, chrom, res, cut=0, region=None, chunk=CHUNK, bal=None, **options):
+    """One chromosome on the device: `ch` has the mat_* and bal_* methods of api.Chromosome; region = (chrom, start, end) or None;
+    `bal`: BalanceArgs, or its fields as keywords -> dict(bins: text, cells: text, stats: the json's entry, matrix: text or None)"""
+    bal = check_args(**options) if bal is None else bal
     try:
-        n_cells = ch.mat_cells(res, cut=cut, fold=True)[0]
-        b0, nb, n_used = ch.bal_marginals(ignore_diags)
-        sum_, nnz = ch.bal_marginals_get(0, nb)
-        valid = valid_bins(sum_, nnz, min_nnz, min_count, mad_max)
-        iters, converged, var, scale = ch.bal_iterate(valid, max_iters=max_iters, tol=tol)
-        weight = ch.bal_weights(0, nb)
-        cells = []
-        for first in range(0, int(n_cells), int(chunk)):
-            k = min(int(chunk), int(n_cells) - first)
-            bx, by, cnt = ch.mat_cells_get(first, k)
-            cells.append(format_cells(chrom, res, bx, by, cnt, ch.bal_cells_get(first, k)))
+        st = balanced_state(ch, res, cut, bal)
+        weight = ch.bal_weights(0, st.nb)
+        cells, first = [], 0
+        for bx, by, cnt in cell_chunks(ch, st.n_cells, chunk):
+            cells.append(format_cells(chrom, res, bx, by, cnt, ch.bal_cells_get(first, len(bx))))
+            first += len(bx)
         mat_text = None
         if region is not None:
             rb0, rn = region_bins(region[1], region[2], res)
             mat = ch.mat_window(res, rb0, rb0, rn, rn, cut=cut, mirror=True)[0]
-            wr = weights_over(b0, weight, rb0, rn)
+            wr = weights_over(st.b0, weight, rb0, rn)
             mat_text = format_balanced_matrix(chrom, res, rb0, rb0, np.asarray(mat, np.float64) * np.outer(wr, wr))
     finally:
         ch.mat_free()
-    if nb > 0 and not converged:
-        logger.warning("WARNING: %s did not converge in %d iterations (variance %s, tol %s)" % (chrom, iters, fmt(var), fmt(tol)))
-    stats = {"b0": int(b0), "nb": int(nb), "n_used": int(n_used), "n_valid": int(np.count_nonzero(valid)), "iters": int(iters),
-             "converged": bool(converged), "var": _num(var), "scale": _num(scale)}
-    return {"bins": format_bins(chrom, res, b0, sum_, nnz, weight), "cells": "".join(cells), "stats": stats, "matrix": mat_text}
+    msg = not_converged(chrom, st, bal.tol)
+    if msg is not None:
+        logger.warning("WARNING: " + msg)
+    stats = dict(balance_stats(st), b0=int(st.b0), nb=int(st.nb), n_used=int(st.n_used), n_valid=int(np.count_nonzero(st.mask)))
+    return {"bins": format_bins(chrom, res, st.b0, st.sum, st.nnz, weight), "cells": "".join(cells), "stats": stats, "matrix": mat_text}
 
 
 def balance_outputs(per_chrom, args):
     """{suffix: text} of the files from {chrom: balance_chrom's dict}, and the json's content"""
-    names = sorted(per_chrom)
-    js = {"args": args, "chroms": {n: per_chrom[n]["stats"] for n in names}}
-    texts = {SUFFIXES[0]: "".join(per_chrom[n]["bins"] for n in names), SUFFIXES[1]: "".join(per_chrom[n]["cells"] for n in names),
-             SUFFIXES[2]: json.dumps(js, indent=1, sort_keys=True) + "\n"}
-    mats = [per_chrom[n]["matrix"] for n in names if per_chrom[n]["matrix"] is not None]
-    if mats:
-        texts[SUFFIXES[3]] = mats[0]
-    return texts, js
+    return chrom_outputs(per_chrom, ((SUFFIXES[0], "bins"), (SUFFIXES[1], "cells")), SUFFIXES[2], {"args": args}, SUFFIXES[3])
 
 
 def jd2balance(jd, fout, res=10000, cut=0, chroms=(), ignore_diags=2, min_nnz=10, min_count=0, mad_max=5, tol=1e-5, max_iters=200,
@@ -159,46 +182,35 @@ def jd2balance(jd, fout, res=10000, cut=0, chroms=(), ignore_diags=2, min_nnz=10
     """The weights and balanced cells of every cis chromosome of `jd` -> `<fout>_balance.txt`, `<fout>_balanced_cells.txt`,
     `<fout>_balance.json` and, with `region`, `<fout>_balanced_matrix.txt`; returns the json's content."""
     res, cut = check_res(res), int(cut)
-    ignore_diags, min_nnz, min_count, mad_max, tol, max_iters = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters)
-    rg = None if region is None else parse_region(region)
-    if rg is not None and not window_fits(rg, rg, res):
-        raise ValueError("the region needs more than %d bins a side or %d cells at -res %d; the smallest -res that fits is %d"
-                         % (matrix.WMAX, matrix.CELLS_MAX, res, matrix.smallest_res(rg, rg)))
-    recs = matrix._records(jd, chroms)
-    if rg is not None and rg[0] not in [c for c, _ in recs]:
-        raise ValueError("no cis .jd file of chromosome %s among those to balance" % rg[0])
-    per_chrom = {}
-    for chrom, r in recs:
-        logger.info("balancing the contact matrix of %s" % chrom)
-        with r.lock:
-            per_chrom[chrom] = balance_chrom(r.chrom, chrom, res, cut, ignore_diags, min_nnz, min_count, mad_max, tol, max_iters,
-                                             region=rg if rg is not None and rg[0] == chrom else None)
-    args = {"res": res, "cut": cut, "ignore_diags": ignore_diags, "min_nnz": min_nnz, "min_count": min_count, "mad_max": mad_max, "tol": tol,
-            "max_iters": max_iters, "region": None if rg is None else "%s:%d-%d" % rg}
+    bal = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters)
+    rg, recs = region_records(jd, chroms, region, res, "balance")
+    per_chrom = each_chrom(recs, logger, "balancing the contact matrix of %s",
+                           lambda ch, chrom: balance_chrom(ch, chrom, res, cut, region=rg if rg is not None and rg[0] == chrom else None, bal=bal))
+    args = dict(bal._asdict(), res=res, cut=cut, region=None if rg is None else "%s:%d-%d" % rg)
     texts, js = balance_outputs(per_chrom, args)
     write_outputs(fout, texts)
     return js
 
 
-def help(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m cloops_amd.balance",
-                                 description="Balanced contact matrices (iterative correction) on MI355X. "
-                                             "For example: python -m cloops_amd.balance -d hic -o hic -res 10000")
-    ap.add_argument("-d", dest="d", required=True, type=str, help="The directory of cis .jd files.")
-    ap.add_argument("-o", dest="output", required=True, type=str, help="Output prefix.")
-    ap.add_argument("-res", dest="res", required=False, default=10000, type=int, help="Bin size in bp, default 10000.")
-    ap.add_argument("-cut", dest="cut", required=False, default=0, type=int, help="Distance cutoff to filter PETs, default 0.")
-    ap.add_argument("-c", dest="chroms", required=False, default="", type=str,
-                    help="Whether to process limited chroms, specify it as chr1,chr2,chr3, default is all.")
+def add_options(ap):
+    """the six options of BalanceArgs.parsed"""
     ap.add_argument("-ignorediags", dest="ignorediags", required=False, default=2, type=int,
-                    help="Cells nearer the diagonal than this many bins take no part in the balancing, default 2.")
+                    help="Cells nearer the diagonal than this many bins take no part, default 2.")
     ap.add_argument("-minnnz", dest="minnnz", required=False, default=10, type=int, help="A bin needs this many non-empty cells, default 10.")
     ap.add_argument("-mincount", dest="mincount", required=False, default=0, type=int, help="A bin needs this many contacts, default 0.")
     ap.add_argument("-mad", dest="mad", required=False, default=5.0, type=float,
                     help="Bins whose log marginal lies more than this many median absolute deviations below the median are left out; "
                          "0 switches the filter off. Default 5.")
     ap.add_argument("-tol", dest="tol", required=False, default=1e-5, type=float, help="Variance of the marginals to stop at, default 1e-5.")
-    ap.add_argument("-maxiters", dest="maxiters", required=False, default=200, type=int, help="Most iterations, default 200.")
+    ap.add_argument("-maxiters", dest="maxiters", required=False, default=200, type=int, help="Most iterations of the balancing, default 200.")
+
+
+def help(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cloops_amd.balance",
+                                 description="Balanced contact matrices (iterative correction) on MI355X. "
+                                             "For example: python -m cloops_amd.balance -d hic -o hic -res 10000")
+    common(ap, 10000, chroms=True)
+    add_options(ap)
     ap.add_argument("-r", dest="region", required=False, default=None, type=str,
                     help="Also write the balanced matrix of this region, chrom:start-end, into <o>_balanced_matrix.txt.")
     return ap.parse_args(argv)
@@ -206,9 +218,7 @@ def help(argv=None):
 
 def main(argv=None):
     op = help(argv)
-    jd2balance(op.d, op.output, res=op.res, cut=op.cut, chroms=[] if op.chroms == "" else set(op.chroms.split(",")),
-               ignore_diags=op.ignorediags, min_nnz=op.minnnz, min_count=op.mincount, mad_max=op.mad, tol=op.tol, max_iters=op.maxiters,
-               region=op.region)
+    jd2balance(op.d, op.output, res=op.res, cut=op.cut, chroms=chroms_of(op), region=op.region, **BalanceArgs.parsed(op)._asdict())
     return 0
 
 

@@ -20,16 +20,15 @@ Definitions (include/cloops_hip.h, cl_eig_build; DESIGN.md, K27):
   (the correlations) and the balance statistics iters, converged, var, scale, and the arguments.  Floats as %.10g, NaN as nan.
 """
 import argparse
-import json
 import logging
 import sys
 
 import numpy as np
 
 from . import matrix
-from .balance import _num, check_args, fmt, valid_bins
-from .expected import check_perdecade, expected_of
-from .matrix import CHUNK, check_res
+from .balance import _num, balance_stats, balanced_state, check_args, fmt, not_converged
+from .expected import add_options, check_exp_args, expected_state, options_of, parsed_options
+from .matrix import CHUNK, check_res, chrom_outputs, chroms_of, common, each_chrom
 from .peaks import write_outputs
 
 logger = logging.getLogger("cloops_amd.compartments")
@@ -163,31 +162,20 @@ def format_runs(chrom, res, b0, valid, e1):
     return "".join("%s\t%d\t%d\t%s\t%s\n" % (chrom, (b0 + s) * res, (b0 + e) * res, name, fmt(m)) for s, e, name, m in compartment_runs(valid, e1))
 
 
-def compartments_chrom(ch, chrom, res, cut=0, n_eigs=3, clip=99.9, eig_tol=1e-8, eig_iters=1000, phase=None, ignore_diags=2, min_nnz=10,
-                       min_count=0, mad_max=5, tol=1e-5, max_iters=200, raw=False, per_decade=10, nosmooth=False, chunk=CHUNK):
+def compartments_chrom(ch, chrom, res, cut=0, n_eigs=3, clip=99.9, eig_tol=1e-8, eig_iters=1000, phase=None, chunk=CHUNK, **options):
     """One chromosome on the device: `ch` has the mat_*, bal_*, exp_* and eig_* methods of api.Chromosome; phase = (starts, ends,
-    values) of the chromosome's track or None -> dict(eigs: text, bedgraph: text, runs: text, stats: the json's entry, vectors: the
-    oriented scaled vectors [n_eigs, nb])"""
+    values) of the chromosome's track or None; `options`: the records bal= and exp= (expected.options_of), or their fields as keywords
+    -> dict(eigs: text, bedgraph: text, runs: text, stats: the json's entry, vectors: the oriented scaled vectors [n_eigs, nb])"""
+    bal, exp = options_of(**options)
     try:
-        n_cells = ch.mat_cells(res, cut=cut, fold=True)[0]
-        b0, nb, _ = ch.bal_marginals(ignore_diags)
-        sum_, nnz = ch.bal_marginals_get(0, nb)
-        mask = valid_bins(sum_, nnz, min_nnz, min_count, mad_max)
-        if raw:
-            iters, converged, var, scale = 0, False, float("nan"), float("nan")
-            valid = np.asarray(mask, bool)
-            nd, _ = ch.exp_diagonals(valid=mask, balanced=False)
-        else:
-            iters, converged, var, scale = ch.bal_iterate(mask, max_iters=max_iters, tol=tol)
-            valid = ~np.isnan(ch.bal_weights(0, nb))
-            nd, _ = ch.exp_diagonals()
-        n_pairs, _, val_sum = ch.exp_diagonals_get(0, nd)
-        exp, _ = expected_of(n_pairs, val_sum, ignore_diags, per_decade, nosmooth)
-        ch.exp_set(exp)
-        oe = [ch.exp_cells_get(first, min(int(chunk), int(n_cells) - first)) for first in range(0, int(n_cells), int(chunk))]
+        st = balanced_state(ch, res, cut, bal, exp.raw)
+        nb, n_cells = st.nb, int(st.n_cells)
+        valid = np.asarray(st.mask, bool) if exp.raw else ~np.isnan(ch.bal_weights(0, nb))
+        ex = expected_state(ch, st, bal, exp)
+        oe = [ch.exp_cells_get(first, min(int(chunk), n_cells - first)) for first in range(0, n_cells, int(chunk))]
         clip_value = clip_of(np.concatenate(oe) if oe else np.zeros(0), clip)
-        dmax = pick_dmax(n_pairs, exp, ignore_diags)
-        no_band = 0 < nb < ignore_diags                                     # fewer bins than ignored diagonals: no band, no matrix
+        dmax = pick_dmax(ex.n_pairs, ex.expected, bal.ignore_diags)
+        no_band = 0 < nb < bal.ignore_diags                                 # fewer bins than ignored diagonals: no band, no matrix
         if no_band:
             n_valid, n_in, eig_it, eig_cv = int(np.count_nonzero(valid)), 0, 0, False
             lam, resid, vecs = np.full(n_eigs, np.nan), np.full(n_eigs, np.nan), np.full((n_eigs, nb), np.nan)
@@ -197,13 +185,14 @@ def compartments_chrom(ch, chrom, res, cut=0, n_eigs=3, clip=99.9, eig_tol=1e-8,
             vecs = np.stack([ch.eig_vectors(k, 0, nb) for k in range(n_eigs)]) if nb > 0 else np.zeros((n_eigs, 0))
     finally:
         ch.mat_free()
-    if not raw and nb > 0 and not converged:
-        logger.warning("WARNING: %s did not converge in %d iterations (variance %s, tol %s)" % (chrom, iters, fmt(var), fmt(tol)))
+    msg = not_converged(chrom, st, bal.tol, exp.raw)
+    if msg is not None:
+        logger.warning("WARNING: " + msg)
     if no_band:
-        logger.warning("WARNING: %s has %d bins, fewer than the %d ignored diagonals: no eigenvectors" % (chrom, nb, ignore_diags))
+        logger.warning("WARNING: %s has %d bins, fewer than the %d ignored diagonals: no eigenvectors" % (chrom, nb, bal.ignore_diags))
     elif nb > 0 and not eig_cv:
         logger.warning("WARNING: the eigenvectors of %s did not converge in %d iterations (tol %s)" % (chrom, eig_it, fmt(eig_tol)))
-    track = np.asarray(sum_, np.float64) if phase is None else bin_track(phase[0], phase[1], phase[2], b0, nb, res)
+    track = np.asarray(st.sum, np.float64) if phase is None else bin_track(phase[0], phase[1], phase[2], st.b0, nb, res)
     track = np.where(valid, track, np.nan) if nb > 0 else track
     E, flipped, corr = np.full((n_eigs, nb), np.nan), [], []
     for k in range(n_eigs):
@@ -211,21 +200,16 @@ def compartments_chrom(ch, chrom, res, cut=0, n_eigs=3, clip=99.9, eig_tol=1e-8,
         E[k] = v * np.sqrt(np.abs(lam[k]))
         flipped.append(flip)
         corr.append(_num(r))
-    stats = {"b0": int(b0), "nb": int(nb), "n_valid": int(n_valid), "n_in": int(n_in), "dmax": int(dmax), "clip": _num(clip_value),
-             "eigvals": [_num(x) for x in np.asarray(lam).tolist()], "resid": [_num(x) for x in np.asarray(resid).tolist()],
-             "eig_iters": int(eig_it), "eig_converged": bool(eig_cv), "flipped": flipped, "phase_corr": corr,
-             "iters": int(iters), "converged": bool(converged), "var": _num(var), "scale": _num(scale)}
-    return {"eigs": format_eigs(chrom, res, b0, valid, E), "bedgraph": format_bedgraph(chrom, res, b0, valid, E[0]),
-            "runs": format_runs(chrom, res, b0, valid, E[0]), "stats": stats, "vectors": E}
+    stats = dict(balance_stats(st), b0=int(st.b0), nb=int(nb), n_valid=int(n_valid), n_in=int(n_in), dmax=int(dmax), clip=_num(clip_value),
+                 eigvals=[_num(x) for x in np.asarray(lam).tolist()], resid=[_num(x) for x in np.asarray(resid).tolist()],
+                 eig_iters=int(eig_it), eig_converged=bool(eig_cv), flipped=flipped, phase_corr=corr)
+    return {"eigs": format_eigs(chrom, res, st.b0, valid, E), "bedgraph": format_bedgraph(chrom, res, st.b0, valid, E[0]),
+            "runs": format_runs(chrom, res, st.b0, valid, E[0]), "stats": stats, "vectors": E}
 
 
 def compartments_outputs(per_chrom, args):
     """{suffix: text} of the files from {chrom: compartments_chrom's dict}, and the json's content"""
-    names = sorted(per_chrom)
-    js = {"args": args, "chroms": {n: per_chrom[n]["stats"] for n in names}}
-    texts = {SUFFIXES[0]: "".join(per_chrom[n]["eigs"] for n in names), SUFFIXES[1]: "".join(per_chrom[n]["bedgraph"] for n in names),
-             SUFFIXES[2]: "".join(per_chrom[n]["runs"] for n in names), SUFFIXES[3]: json.dumps(js, indent=1, sort_keys=True) + "\n"}
-    return texts, js
+    return chrom_outputs(per_chrom, ((SUFFIXES[0], "eigs"), (SUFFIXES[1], "bedgraph"), (SUFFIXES[2], "runs")), SUFFIXES[3], {"args": args})
 
 
 def jd2compartments(jd, fout, res=100000, cut=0, chroms=(), n_eigs=3, clip=99.9, eig_tol=1e-8, eig_iters=1000, phase=None, raw=False,
@@ -233,23 +217,14 @@ def jd2compartments(jd, fout, res=100000, cut=0, chroms=(), n_eigs=3, clip=99.9,
     """The compartment vectors of every cis chromosome of `jd` -> `<fout>_eigs.txt`, `<fout>_E1.bedGraph`, `<fout>_compartments.bed`
     and `<fout>_eigs.json`; `phase`: the path of a bedGraph to orient the vectors by; returns the json's content."""
     res, cut = check_res(res), int(cut)
-    ignore_diags, min_nnz, min_count, mad_max, tol, max_iters = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters)
-    per_decade = check_perdecade(per_decade)
+    bal, exp = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters), check_exp_args(raw, per_decade, nosmooth)
     n_eigs, clip, eig_tol, eig_iters = check_eig_args(n_eigs, clip, eig_tol, eig_iters)
     tracks = None if phase is None else read_bedgraph(phase)
-    recs = matrix._records(jd, chroms)
-    per_chrom = {}
-    for chrom, r in recs:
-        logger.info("compartments of %s" % chrom)
-        ph = None
-        if tracks is not None:
-            ph = tracks.get(chrom, (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0)))
-        with r.lock:
-            per_chrom[chrom] = compartments_chrom(r.chrom, chrom, res, cut, n_eigs, clip, eig_tol, eig_iters, ph, ignore_diags, min_nnz,
-                                                  min_count, mad_max, tol, max_iters, bool(raw), per_decade, bool(nosmooth))
-    args = {"res": res, "cut": cut, "raw": bool(raw), "per_decade": per_decade, "nosmooth": bool(nosmooth), "ignore_diags": ignore_diags,
-            "min_nnz": min_nnz, "min_count": min_count, "mad_max": mad_max, "tol": tol, "max_iters": max_iters, "n_eigs": n_eigs,
-            "clip": clip, "eig_tol": eig_tol, "eig_iters": eig_iters, "phase": phase}
+    no_track = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0))
+    per_chrom = each_chrom(matrix._records(jd, chroms), logger, "compartments of %s",
+                           lambda ch, chrom: compartments_chrom(ch, chrom, res, cut, n_eigs, clip, eig_tol, eig_iters,
+                                                                None if tracks is None else tracks.get(chrom, no_track), bal=bal, exp=exp))
+    args = dict(bal._asdict(), res=res, cut=cut, n_eigs=n_eigs, clip=clip, eig_tol=eig_tol, eig_iters=eig_iters, phase=phase, **exp._asdict())
     texts, js = compartments_outputs(per_chrom, args)
     write_outputs(fout, texts)
     return js
@@ -259,12 +234,7 @@ def help(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cloops_amd.compartments",
                                  description="A/B compartments: the leading eigenvectors of the O/E contact matrix on MI355X. "
                                              "For example: python -m cloops_amd.compartments -d hic -o hic -res 100000")
-    ap.add_argument("-d", dest="d", required=True, type=str, help="The directory of cis .jd files.")
-    ap.add_argument("-o", dest="output", required=True, type=str, help="Output prefix.")
-    ap.add_argument("-res", dest="res", required=False, default=100000, type=int, help="Bin size in bp, default 100000.")
-    ap.add_argument("-cut", dest="cut", required=False, default=0, type=int, help="Distance cutoff to filter PETs, default 0.")
-    ap.add_argument("-c", dest="chroms", required=False, default="", type=str,
-                    help="Whether to process limited chroms, specify it as chr1,chr2,chr3, default is all.")
+    common(ap, 100000, chroms=True)
     ap.add_argument("-neigs", dest="neigs", required=False, default=3, type=int, help="Eigenvectors per chromosome, 1 to 6, default 3.")
     ap.add_argument("-clip", dest="clip", required=False, default=99.9, type=float,
                     help="Percentile of the O/E values the matrix is clipped at, default 99.9; 100 switches the clip off.")
@@ -273,30 +243,14 @@ def help(argv=None):
     ap.add_argument("-eigiters", dest="eigiters", required=False, default=1000, type=int, help="Most iterations of the eigensolver, default 1000.")
     ap.add_argument("-phase", dest="phase", required=False, default=None, type=str,
                     help="A bedGraph (GC content, gene density ..) whose per-bin mean orients the vectors; default: the bins' coverage.")
-    ap.add_argument("-raw", dest="raw", required=False, action="store_true",
-                    help="O/E of the raw counts over the valid bins, without balancing.")
-    ap.add_argument("-perdecade", dest="perdecade", required=False, default=10, type=int,
-                    help="Groups of diagonals per decade of distance the expected value is averaged over, default 10.")
-    ap.add_argument("-nosmooth", dest="nosmooth", required=False, action="store_true",
-                    help="The expected value of a diagonal is its own average, not its group's.")
-    ap.add_argument("-ignorediags", dest="ignorediags", required=False, default=2, type=int,
-                    help="Cells nearer the diagonal than this many bins take no part, default 2.")
-    ap.add_argument("-minnnz", dest="minnnz", required=False, default=10, type=int, help="A bin needs this many non-empty cells, default 10.")
-    ap.add_argument("-mincount", dest="mincount", required=False, default=0, type=int, help="A bin needs this many contacts, default 0.")
-    ap.add_argument("-mad", dest="mad", required=False, default=5.0, type=float,
-                    help="Bins whose log marginal lies more than this many median absolute deviations below the median are left out; "
-                         "0 switches the filter off. Default 5.")
-    ap.add_argument("-tol", dest="tol", required=False, default=1e-5, type=float, help="Variance of the marginals to stop at, default 1e-5.")
-    ap.add_argument("-maxiters", dest="maxiters", required=False, default=200, type=int, help="Most iterations of the balancing, default 200.")
+    add_options(ap)
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     op = help(argv)
-    jd2compartments(op.d, op.output, res=op.res, cut=op.cut, chroms=[] if op.chroms == "" else set(op.chroms.split(",")), n_eigs=op.neigs,
-                    clip=op.clip, eig_tol=op.eigtol, eig_iters=op.eigiters, phase=op.phase, raw=op.raw, per_decade=op.perdecade,
-                    nosmooth=op.nosmooth, ignore_diags=op.ignorediags, min_nnz=op.minnnz, min_count=op.mincount, mad_max=op.mad, tol=op.tol,
-                    max_iters=op.maxiters)
+    jd2compartments(op.d, op.output, res=op.res, cut=op.cut, chroms=chroms_of(op), n_eigs=op.neigs, clip=op.clip, eig_tol=op.eigtol,
+                    eig_iters=op.eigiters, phase=op.phase, **parsed_options(op))
     return 0
 
 

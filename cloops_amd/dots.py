@@ -32,16 +32,15 @@ Definitions (include/cloops_hip.h, cl_dot_lambdas; DESIGN.md, K29):
   as nan.
 """
 import argparse
-import json
 import logging
 import sys
 
 import numpy as np
 
 from . import _lib, matrix
-from .balance import _num, check_args, valid_bins
-from .expected import check_perdecade, expected_of
-from .matrix import CHUNK, check_res
+from .balance import balance_stats, balanced_state, check_args, not_converged
+from .expected import add_options, check_exp_args, expected_state, options_of, parsed_options
+from .matrix import CHUNK, check_res, chrom_outputs, chroms_of, common, each_chrom
 from .peaks import write_outputs
 from .similarity import fnum
 
@@ -188,26 +187,16 @@ def format_thresholds(chrom, edges, n, thr):
 
 
 def dots_chrom(ch, chrom, res, cut=0, p=2, w=5, mindist=0, maxdist=2000000, fdr=0.1, chunks=40, merge=20000, minpix=1, enrich=DEFAULT_ENRICH,
-               ignore_diags=2, min_nnz=10, min_count=0, mad_max=5, tol=1e-5, max_iters=200, raw=False, per_decade=10, nosmooth=False,
-               chunk=CHUNK):
-    """One chromosome on the device: `ch` has the mat_*, bal_*, exp_* and dot_* methods of api.Chromosome -> dict(loops: text, pixels:
-    text, thresholds: text, stats: the json's entry, warnings: [str], called: [(bx, by)] of the loops)"""
-    warnings = []
+               chunk=CHUNK, **options):
+    """One chromosome on the device: `ch` has the mat_*, bal_*, exp_* and dot_* methods of api.Chromosome; `options`: the records bal=
+    and exp= (expected.options_of), or their fields as keywords -> dict(loops: text, pixels: text, thresholds: text, stats: the json's
+    entry, warnings: [str], called: [(bx, by)] of the loops)"""
+    bal, exp = options_of(**options)
     try:
-        n_cells = ch.mat_cells(res, cut=cut, fold=True)[0]
-        b0, nb, _ = ch.bal_marginals(ignore_diags)
-        sum_, nnz = ch.bal_marginals_get(0, nb)
-        mask = valid_bins(sum_, nnz, min_nnz, min_count, mad_max)
-        if raw:
-            iters, converged, var, scale = 0, False, float("nan"), float("nan")
-            nd, _ = ch.exp_diagonals(valid=mask, balanced=False)
-        else:
-            iters, converged, var, scale = ch.bal_iterate(mask, max_iters=max_iters, tol=tol)
-            nd, _ = ch.exp_diagonals()
-        n_pairs, _, val_sum = ch.exp_diagonals_get(0, nd)
-        exp, _ = expected_of(n_pairs, val_sum, ignore_diags, per_decade, nosmooth)
-        ch.exp_set(exp)
-        dmin, dmax = band_of(nb, ignore_diags, p, res, mindist, maxdist)
+        st = balanced_state(ch, res, cut, bal, exp.raw)
+        expected_state(ch, st, bal, exp)
+        nb, n_cells = st.nb, int(st.n_cells)
+        dmin, dmax = band_of(nb, bal.ignore_diags, p, res, mindist, maxdist)
         edges = default_edges(chunks)
         no_band = nb > 0 and dmin >= dmax                                   # fewer bins than the nearest tested diagonal
         thr, n_chunk = np.full((4, chunks), NO_THRESHOLD, np.uint32), np.zeros((4, chunks), np.int64)
@@ -222,8 +211,8 @@ def dots_chrom(ch, chrom, res, cut=0, p=2, w=5, mindist=0, maxdist=2000000, fdr=
             n_sig = ch.dot_call(thr)
             sig = ch.dot_sig(0, n_sig)
         sx, sy, sc, sla = [], [], [], []
-        for first in range(0, int(n_cells), int(chunk)):                    # the significant cells, chunk by chunk of the cells
-            k = min(int(chunk), int(n_cells) - first)
+        for first in range(0, n_cells, int(chunk)):                         # the significant cells, chunk by chunk of the cells
+            k = min(int(chunk), n_cells - first)
             mine = sig[(sig >= first) & (sig < first + k)] - first
             if len(mine) == 0:
                 continue
@@ -238,8 +227,8 @@ def dots_chrom(ch, chrom, res, cut=0, p=2, w=5, mindist=0, maxdist=2000000, fdr=
     passed = enrichment_pass(sc, sla, enrich)
     keep = np.flatnonzero(passed)
     loops = merge_pixels(sx[keep], sy[keep], sc[keep], max(1, merge // res), minpix)
-    if not raw and nb > 0 and not converged:
-        warnings.append("%s did not converge in %d iterations (variance %s, tol %s)" % (chrom, iters, fnum(var), fnum(tol)))
+    msg = not_converged(chrom, st, bal.tol, exp.raw, num=fnum)
+    warnings = [] if msg is None else [msg]
     if no_band:
         warnings.append("%s has %d bins, no diagonal in [%d, %d): no test" % (chrom, nb, dmin, dmax))
     if n_beyond > 0:
@@ -249,9 +238,8 @@ def dots_chrom(ch, chrom, res, cut=0, p=2, w=5, mindist=0, maxdist=2000000, fdr=
         warnings.append("%s has cells but no pixel with all four neighbourhoods: no test" % chrom)
     for msg in warnings:
         logger.warning("WARNING: " + msg)
-    stats = {"b0": int(b0), "nb": int(nb), "dmin": int(dmin), "dmax": int(dmax), "n_cells": int(n_cells), "n_cand": int(n_cand),
-             "n_full": int(n_full), "n_beyond": int(n_beyond), "n_sig": int(len(sig)), "n_kept": int(len(keep)), "n_loops": len(loops),
-             "iters": int(iters), "converged": bool(converged), "var": _num(var), "scale": _num(scale)}
+    stats = dict(balance_stats(st), b0=int(st.b0), nb=int(nb), dmin=int(dmin), dmax=int(dmax), n_cells=n_cells, n_cand=int(n_cand),
+                 n_full=int(n_full), n_beyond=int(n_beyond), n_sig=int(len(sig)), n_kept=int(len(keep)), n_loops=len(loops))
     return {"loops": format_loops(chrom, res, sx[keep], sy[keep], sc[keep], sla[keep], loops),
             "pixels": format_pixels(chrom, res, sx, sy, sc, sla, passed), "thresholds": format_thresholds(chrom, edges, n_chunk, thr),
             "stats": stats, "warnings": warnings, "called": [(int(sx[keep][a]), int(sy[keep][a])) for a, _, _, _ in loops]}
@@ -259,11 +247,8 @@ def dots_chrom(ch, chrom, res, cut=0, p=2, w=5, mindist=0, maxdist=2000000, fdr=
 
 def dots_outputs(per_chrom, args):
     """{suffix: text} of the files from {chrom: dots_chrom's dict}, and the json's content"""
-    names = sorted(per_chrom)
-    js = {"args": args, "chroms": {n: per_chrom[n]["stats"] for n in names}, "warnings": [m for n in names for m in per_chrom[n]["warnings"]]}
-    texts = {SUFFIXES[0]: "".join(per_chrom[n]["loops"] for n in names), SUFFIXES[1]: "".join(per_chrom[n]["pixels"] for n in names),
-             SUFFIXES[2]: "".join(per_chrom[n]["thresholds"] for n in names), SUFFIXES[3]: json.dumps(js, indent=1, sort_keys=True) + "\n"}
-    return texts, js
+    js = {"args": args, "warnings": [m for n in sorted(per_chrom) for m in per_chrom[n]["warnings"]]}
+    return chrom_outputs(per_chrom, ((SUFFIXES[0], "loops"), (SUFFIXES[1], "pixels"), (SUFFIXES[2], "thresholds")), SUFFIXES[3], js)
 
 
 def jd2dots(jd, fout, res=10000, cut=0, chroms=(), p=2, w=5, mindist=0, maxdist=2000000, fdr=0.1, chunks=40, merge=20000, minpix=1,
@@ -272,19 +257,13 @@ def jd2dots(jd, fout, res=10000, cut=0, chroms=(), p=2, w=5, mindist=0, maxdist=
     """The loops of every cis chromosome of `jd` by the donut test -> `<fout>_dots.bedpe`, `<fout>_dots_pixels.txt`,
     `<fout>_dots_thresholds.txt` and `<fout>_dots.json`; returns the json's content."""
     res, cut = check_res(res), int(cut)
-    ignore_diags, min_nnz, min_count, mad_max, tol, max_iters = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters)
-    per_decade = check_perdecade(per_decade)
+    bal, exp = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters), check_exp_args(raw, per_decade, nosmooth)
     p, w, mindist, maxdist, fdr, chunks, merge, minpix, enrich = check_dot_args(p, w, mindist, maxdist, fdr, chunks, merge, minpix, enrich)
-    recs = matrix._records(jd, chroms)
-    per_chrom = {}
-    for chrom, r in recs:
-        logger.info("dots of %s" % chrom)
-        with r.lock:
-            per_chrom[chrom] = dots_chrom(r.chrom, chrom, res, cut, p, w, mindist, maxdist, fdr, chunks, merge, minpix, enrich, ignore_diags,
-                                          min_nnz, min_count, mad_max, tol, max_iters, bool(raw), per_decade, bool(nosmooth))
-    args = {"res": res, "cut": cut, "p": p, "w": w, "mindist": mindist, "maxdist": maxdist, "fdr": fdr, "chunks": chunks, "merge": merge,
-            "minpix": minpix, "enrich": list(enrich), "raw": bool(raw), "per_decade": per_decade, "nosmooth": bool(nosmooth),
-            "ignore_diags": ignore_diags, "min_nnz": min_nnz, "min_count": min_count, "mad_max": mad_max, "tol": tol, "max_iters": max_iters}
+    per_chrom = each_chrom(matrix._records(jd, chroms), logger, "dots of %s",
+                           lambda ch, chrom: dots_chrom(ch, chrom, res, cut, p, w, mindist, maxdist, fdr, chunks, merge, minpix, enrich,
+                                                        bal=bal, exp=exp))
+    args = dict(bal._asdict(), res=res, cut=cut, p=p, w=w, mindist=mindist, maxdist=maxdist, fdr=fdr, chunks=chunks, merge=merge,
+                minpix=minpix, enrich=list(enrich), **exp._asdict())
     texts, js = dots_outputs(per_chrom, args)
     write_outputs(fout, texts)
     return js
@@ -294,9 +273,7 @@ def help(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cloops_amd.dots",
                                  description="Loops from the contact matrix by the donut enrichment test (HiCCUPS) on MI355X. "
                                              "For example: python -m cloops_amd.dots -d hic -o hic -res 10000")
-    ap.add_argument("-d", dest="d", required=True, type=str, help="The directory of cis .jd files.")
-    ap.add_argument("-o", dest="output", required=True, type=str, help="Output prefix.")
-    ap.add_argument("-res", dest="res", required=False, default=10000, type=int, help="Bin size in bp, default 10000.")
+    common(ap, 10000, chroms=True)
     ap.add_argument("-p", dest="p", required=False, default=2, type=int, help="Half-width of the inner square left out around a pixel, default 2.")
     ap.add_argument("-w", dest="w", required=False, default=5, type=int, help="Half-width of the neighbourhoods, at most 16, default 5.")
     ap.add_argument("-mindist", dest="mindist", required=False, default=0, type=int, help="Nearest tested distance in bp, default 0.")
@@ -310,32 +287,14 @@ def help(argv=None):
     ap.add_argument("-enrich", dest="enrich", required=False, default=",".join(repr(x) for x in DEFAULT_ENRICH), type=str,
                     help="Least count over la of the donut, lower-left, horizontal and vertical neighbourhoods, and of the larger of the "
                          "first two, default 1.75,1.75,1.5,1.5,2.0.")
-    ap.add_argument("-raw", dest="raw", required=False, action="store_true", help="The raw counts over the valid bins, without balancing.")
-    ap.add_argument("-cut", dest="cut", required=False, default=0, type=int, help="Distance cutoff to filter PETs, default 0.")
-    ap.add_argument("-c", dest="chroms", required=False, default="", type=str,
-                    help="Whether to process limited chroms, specify it as chr1,chr2,chr3, default is all.")
-    ap.add_argument("-perdecade", dest="perdecade", required=False, default=10, type=int,
-                    help="Groups of diagonals per decade of distance the expected value is averaged over, default 10.")
-    ap.add_argument("-nosmooth", dest="nosmooth", required=False, action="store_true",
-                    help="The expected value of a diagonal is its own average, not its group's.")
-    ap.add_argument("-ignorediags", dest="ignorediags", required=False, default=2, type=int,
-                    help="Cells nearer the diagonal than this many bins take no part, default 2.")
-    ap.add_argument("-minnnz", dest="minnnz", required=False, default=10, type=int, help="A bin needs this many non-empty cells, default 10.")
-    ap.add_argument("-mincount", dest="mincount", required=False, default=0, type=int, help="A bin needs this many contacts, default 0.")
-    ap.add_argument("-mad", dest="mad", required=False, default=5.0, type=float,
-                    help="Bins whose log marginal lies more than this many median absolute deviations below the median are left out; "
-                         "0 switches the filter off. Default 5.")
-    ap.add_argument("-tol", dest="tol", required=False, default=1e-5, type=float, help="Variance of the marginals to stop at, default 1e-5.")
-    ap.add_argument("-maxiters", dest="maxiters", required=False, default=200, type=int, help="Most iterations of the balancing, default 200.")
+    add_options(ap)
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     op = help(argv)
-    jd2dots(op.d, op.output, res=op.res, cut=op.cut, chroms=[] if op.chroms == "" else set(op.chroms.split(",")), p=op.p, w=op.w,
-            mindist=op.mindist, maxdist=op.maxdist, fdr=op.fdr, chunks=op.chunks, merge=op.merge, minpix=op.minpix, enrich=op.enrich, raw=op.raw,
-            per_decade=op.perdecade, nosmooth=op.nosmooth, ignore_diags=op.ignorediags, min_nnz=op.minnnz, min_count=op.mincount,
-            mad_max=op.mad, tol=op.tol, max_iters=op.maxiters)
+    jd2dots(op.d, op.output, res=op.res, cut=op.cut, chroms=chroms_of(op), p=op.p, w=op.w, mindist=op.mindist, maxdist=op.maxdist, fdr=op.fdr,
+            chunks=op.chunks, merge=op.merge, minpix=op.minpix, enrich=op.enrich, **parsed_options(op))
     return 0
 
 

@@ -23,15 +23,15 @@ Definitions (include/cloops_hip.h, cl_exp_diagonals; DESIGN.md, K26):
   expected[|i - j|].  Floats as %.10g, NaN as nan.
 """
 import argparse
-import json
+import collections
 import logging
 import sys
 
 import numpy as np
 
-from . import matrix
-from .balance import _num, check_args, fmt, format_balanced_matrix, valid_bins, weights_over
-from .matrix import CHUNK, check_res, parse_region, region_bins, window_fits
+from . import balance
+from .balance import BalanceArgs, balance_stats, balanced_state, check_args, fmt, format_balanced_matrix, not_converged, weights_over
+from .matrix import CHUNK, cell_chunks, check_res, chrom_outputs, chroms_of, common, each_chrom, region_bins, region_records
 from .peaks import write_outputs
 
 logger = logging.getLogger("cloops_amd.expected")
@@ -39,11 +39,37 @@ logger = logging.getLogger("cloops_amd.expected")
 SUFFIXES = ("_expected.txt", "_ps.txt", "_oe_cells.txt", "_expected.json", "_oe_matrix.txt")
 
 
+class ExpectedArgs(collections.namedtuple("ExpectedArgs", "raw per_decade nosmooth")):
+    """the three options of the expected values; the fields are the keywords of the jd2* and the keys of the json's `args` (`_asdict`)"""
+    __slots__ = ()
+
+    @classmethod
+    def parsed(cls, op):
+        """of a namespace with the options of add_options, unchecked"""
+        return cls(op.raw, op.perdecade, op.nosmooth)
+
+
 def check_perdecade(per_decade):
     """-> the groups per decade as an integer; ValueError unless it is one at or above 1"""
     if isinstance(per_decade, bool) or not isinstance(per_decade, (int, np.integer)) or per_decade < 1:
         raise ValueError("perdecade must be an integer at or above 1, got %r" % (per_decade,))
     return int(per_decade)
+
+
+def check_exp_args(raw=False, per_decade=10, nosmooth=False):
+    """-> ExpectedArgs of the three, checked by check_perdecade"""
+    return ExpectedArgs(bool(raw), check_perdecade(per_decade), bool(nosmooth))
+
+
+def options_of(bal=None, exp=None, **options):
+    """the two records of a *_chrom -> (BalanceArgs, ExpectedArgs): those given, or made of their fields among the keywords"""
+    if bal is None:
+        bal = check_args(**{k: options.pop(k) for k in BalanceArgs._fields if k in options})
+    if exp is None:
+        exp = check_exp_args(**{k: options.pop(k) for k in ExpectedArgs._fields if k in options})
+    if options:
+        raise TypeError("unexpected keywords %s" % ", ".join(sorted(options)))
+    return bal, exp
 
 
 def group_bounds(nd, per_decade):
@@ -136,57 +162,52 @@ def oe_matrix(mat, wr, expected):
     return np.asarray(mat, np.float64) * np.outer(wr, wr) / e
 
 
-def expected_chrom(ch, chrom, res, cut=0, ignore_diags=2, min_nnz=10, min_count=0, mad_max=5, tol=1e-5, max_iters=200, raw=False,
-                   per_decade=10, nosmooth=False, region=None, chunk=CHUNK):
-    """One chromosome on the device: `ch` has the mat_*, bal_* and exp_* methods of api.Chromosome; region = (chrom, start, end) or None
+Expected = collections.namedtuple("Expected", "nd n_used n_pairs cnt_sum val_sum expected groups")
+
+
+def expected_state(ch, st, bal, exp):
+    """The sums per diagonal of the state `st` of balance.balanced_state (with `exp.raw`: of the counts over its mask), the expected
+    values of them, set on the device -> Expected.  `bal`: BalanceArgs, `exp`: ExpectedArgs."""
+    nd, n_used = ch.exp_diagonals(valid=st.mask, balanced=False) if exp.raw else ch.exp_diagonals()
+    n_pairs, cnt_sum, val_sum = ch.exp_diagonals_get(0, nd)
+    expected, groups = expected_of(n_pairs, val_sum, bal.ignore_diags, exp.per_decade, exp.nosmooth)
+    ch.exp_set(expected)
+    return Expected(nd, n_used, n_pairs, cnt_sum, val_sum, expected, groups)
+
+
+def expected_chrom(ch, chrom, res, cut=0, region=None, chunk=CHUNK, **options):
+    """One chromosome on the device: `ch` has the mat_*, bal_* and exp_* methods of api.Chromosome; region = (chrom, start, end) or None;
+    `options`: the records bal= and exp= (options_of), or their fields as keywords
     -> dict(expected: text, ps: text, cells: text, stats: the json's entry, matrix: text or None)"""
+    bal, exp = options_of(**options)
     try:
-        n_cells = ch.mat_cells(res, cut=cut, fold=True)[0]
-        b0, nb, _ = ch.bal_marginals(ignore_diags)
-        sum_, nnz = ch.bal_marginals_get(0, nb)
-        valid = valid_bins(sum_, nnz, min_nnz, min_count, mad_max)
-        if raw:
-            iters, converged, var, scale = 0, False, float("nan"), float("nan")
-            ew = np.where(valid, 1.0, np.nan)
-            nd, n_used = ch.exp_diagonals(valid=valid, balanced=False)
-        else:
-            iters, converged, var, scale = ch.bal_iterate(valid, max_iters=max_iters, tol=tol)
-            ew = ch.bal_weights(0, nb)
-            nd, n_used = ch.exp_diagonals()
-        n_pairs, cnt_sum, val_sum = ch.exp_diagonals_get(0, nd)
-        exp, groups = expected_of(n_pairs, val_sum, ignore_diags, per_decade, nosmooth)
-        ch.exp_set(exp)
-        cells = []
-        for first in range(0, int(n_cells), int(chunk)):
-            k = min(int(chunk), int(n_cells) - first)
-            bx, by, cnt = ch.mat_cells_get(first, k)
-            val = raw_values(bx, by, cnt, b0, ew) if raw else ch.bal_cells_get(first, k)
-            cells.append(format_cells(chrom, res, bx, by, cnt, val, ch.exp_cells_get(first, k)))
+        st = balanced_state(ch, res, cut, bal, exp.raw)
+        ew = np.where(st.mask, 1.0, np.nan) if exp.raw else ch.bal_weights(0, st.nb)
+        ex = expected_state(ch, st, bal, exp)
+        cells, first = [], 0
+        for bx, by, cnt in cell_chunks(ch, st.n_cells, chunk):
+            val = raw_values(bx, by, cnt, st.b0, ew) if exp.raw else ch.bal_cells_get(first, len(bx))
+            cells.append(format_cells(chrom, res, bx, by, cnt, val, ch.exp_cells_get(first, len(bx))))
+            first += len(bx)
         mat_text = None
         if region is not None:
             rb0, rn = region_bins(region[1], region[2], res)
             mat = ch.mat_window(res, rb0, rb0, rn, rn, cut=cut, mirror=True)[0]
-            mat_text = format_balanced_matrix(chrom, res, rb0, rb0, oe_matrix(mat, weights_over(b0, ew, rb0, rn), exp))
+            mat_text = format_balanced_matrix(chrom, res, rb0, rb0, oe_matrix(mat, weights_over(st.b0, ew, rb0, rn), ex.expected))
     finally:
         ch.mat_free()
-    if not raw and nb > 0 and not converged:
-        logger.warning("WARNING: %s did not converge in %d iterations (variance %s, tol %s)" % (chrom, iters, fmt(var), fmt(tol)))
-    stats = {"b0": int(b0), "nb": int(nb), "nd": int(nd), "n_used": int(n_used), "n_valid": int(np.count_nonzero(~np.isnan(ew))),
-             "iters": int(iters), "converged": bool(converged), "var": _num(var), "scale": _num(scale)}
-    return {"expected": format_expected(chrom, res, n_pairs, cnt_sum, val_sum, exp), "ps": format_ps(chrom, res, groups),
+    msg = not_converged(chrom, st, bal.tol, exp.raw)
+    if msg is not None:
+        logger.warning("WARNING: " + msg)
+    stats = dict(balance_stats(st), b0=int(st.b0), nb=int(st.nb), nd=int(ex.nd), n_used=int(ex.n_used), n_valid=int(np.count_nonzero(~np.isnan(ew))))
+    return {"expected": format_expected(chrom, res, ex.n_pairs, ex.cnt_sum, ex.val_sum, ex.expected), "ps": format_ps(chrom, res, ex.groups),
             "cells": "".join(cells), "stats": stats, "matrix": mat_text}
 
 
 def expected_outputs(per_chrom, args):
     """{suffix: text} of the files from {chrom: expected_chrom's dict}, and the json's content"""
-    names = sorted(per_chrom)
-    js = {"args": args, "chroms": {n: per_chrom[n]["stats"] for n in names}}
-    texts = {SUFFIXES[0]: "".join(per_chrom[n]["expected"] for n in names), SUFFIXES[1]: "".join(per_chrom[n]["ps"] for n in names),
-             SUFFIXES[2]: "".join(per_chrom[n]["cells"] for n in names), SUFFIXES[3]: json.dumps(js, indent=1, sort_keys=True) + "\n"}
-    mats = [per_chrom[n]["matrix"] for n in names if per_chrom[n]["matrix"] is not None]
-    if mats:
-        texts[SUFFIXES[4]] = mats[0]
-    return texts, js
+    return chrom_outputs(per_chrom, ((SUFFIXES[0], "expected"), (SUFFIXES[1], "ps"), (SUFFIXES[2], "cells")), SUFFIXES[3], {"args": args},
+                         SUFFIXES[4])
 
 
 def jd2expected(jd, fout, res=10000, cut=0, chroms=(), raw=False, per_decade=10, nosmooth=False, region=None, ignore_diags=2, min_nnz=10,
@@ -194,67 +215,51 @@ def jd2expected(jd, fout, res=10000, cut=0, chroms=(), raw=False, per_decade=10,
     """The expected values by distance and the O/E cells of every cis chromosome of `jd` -> `<fout>_expected.txt`, `<fout>_ps.txt`,
     `<fout>_oe_cells.txt`, `<fout>_expected.json` and, with `region`, `<fout>_oe_matrix.txt`; returns the json's content."""
     res, cut = check_res(res), int(cut)
-    ignore_diags, min_nnz, min_count, mad_max, tol, max_iters = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters)
-    per_decade = check_perdecade(per_decade)
-    rg = None if region is None else parse_region(region)
-    if rg is not None and not window_fits(rg, rg, res):
-        raise ValueError("the region needs more than %d bins a side or %d cells at -res %d; the smallest -res that fits is %d"
-                         % (matrix.WMAX, matrix.CELLS_MAX, res, matrix.smallest_res(rg, rg)))
-    recs = matrix._records(jd, chroms)
-    if rg is not None and rg[0] not in [c for c, _ in recs]:
-        raise ValueError("no cis .jd file of chromosome %s among those to process" % rg[0])
-    per_chrom = {}
-    for chrom, r in recs:
-        logger.info("expected contacts by distance of %s" % chrom)
-        with r.lock:
-            per_chrom[chrom] = expected_chrom(r.chrom, chrom, res, cut, ignore_diags, min_nnz, min_count, mad_max, tol, max_iters, bool(raw),
-                                              per_decade, bool(nosmooth), region=rg if rg is not None and rg[0] == chrom else None)
-    args = {"res": res, "cut": cut, "raw": bool(raw), "per_decade": per_decade, "nosmooth": bool(nosmooth), "ignore_diags": ignore_diags,
-            "min_nnz": min_nnz, "min_count": min_count, "mad_max": mad_max, "tol": tol, "max_iters": max_iters,
-            "region": None if rg is None else "%s:%d-%d" % rg}
+    bal, exp = check_args(ignore_diags, min_nnz, min_count, mad_max, tol, max_iters), check_exp_args(raw, per_decade, nosmooth)
+    rg, recs = region_records(jd, chroms, region, res, "process")
+    per_chrom = each_chrom(recs, logger, "expected contacts by distance of %s",
+                           lambda ch, chrom: expected_chrom(ch, chrom, res, cut, region=rg if rg is not None and rg[0] == chrom else None,
+                                                            bal=bal, exp=exp))
+    args = dict(bal._asdict(), res=res, cut=cut, region=None if rg is None else "%s:%d-%d" % rg, **exp._asdict())
     texts, js = expected_outputs(per_chrom, args)
     write_outputs(fout, texts)
     return js
+
+
+def add_options(ap):
+    """the three options of ExpectedArgs.parsed, then the six of balance.add_options"""
+    ap.add_argument("-raw", dest="raw", required=False, action="store_true", help="The raw counts over the valid bins, without balancing.")
+    ap.add_argument("-perdecade", dest="perdecade", required=False, default=10, type=int,
+                    help="Groups of diagonals per decade of distance the expected value is averaged over, default 10.")
+    ap.add_argument("-nosmooth", dest="nosmooth", required=False, action="store_true",
+                    help="The expected value of a diagonal is its own average, not its group's.")
+    balance.add_options(ap)
+
+
+def parsed_options(op):
+    """the nine keywords of a jd2* from a namespace with the options of add_options: the fields of the two records"""
+    return dict(BalanceArgs.parsed(op)._asdict(), **ExpectedArgs.parsed(op)._asdict())
 
 
 def help(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cloops_amd.expected",
                                  description="Expected contacts by distance (P(s)) and observed / expected cells on MI355X. "
                                              "For example: python -m cloops_amd.expected -d hic -o hic -res 10000")
-    ap.add_argument("-d", dest="d", required=True, type=str, help="The directory of cis .jd files.")
-    ap.add_argument("-o", dest="output", required=True, type=str, help="Output prefix.")
-    ap.add_argument("-res", dest="res", required=False, default=10000, type=int, help="Bin size in bp, default 10000.")
-    ap.add_argument("-cut", dest="cut", required=False, default=0, type=int, help="Distance cutoff to filter PETs, default 0.")
-    ap.add_argument("-c", dest="chroms", required=False, default="", type=str,
-                    help="Whether to process limited chroms, specify it as chr1,chr2,chr3, default is all.")
-    ap.add_argument("-raw", dest="raw", required=False, action="store_true",
-                    help="Expected values of the raw counts over the valid bins, without balancing.")
-    ap.add_argument("-perdecade", dest="perdecade", required=False, default=10, type=int,
-                    help="Groups of diagonals per decade of distance the expected value is averaged over, default 10.")
-    ap.add_argument("-nosmooth", dest="nosmooth", required=False, action="store_true",
-                    help="The expected value of a diagonal is its own average, not its group's.")
+    common(ap, 10000, chroms=True)
     ap.add_argument("-r", dest="region", required=False, default=None, type=str,
                     help="Also write the O/E matrix of this region, chrom:start-end, into <o>_oe_matrix.txt.")
-    ap.add_argument("-ignorediags", dest="ignorediags", required=False, default=2, type=int,
-                    help="Cells nearer the diagonal than this many bins take no part, default 2.")
-    ap.add_argument("-minnnz", dest="minnnz", required=False, default=10, type=int, help="A bin needs this many non-empty cells, default 10.")
-    ap.add_argument("-mincount", dest="mincount", required=False, default=0, type=int, help="A bin needs this many contacts, default 0.")
-    ap.add_argument("-mad", dest="mad", required=False, default=5.0, type=float,
-                    help="Bins whose log marginal lies more than this many median absolute deviations below the median are left out; "
-                         "0 switches the filter off. Default 5.")
-    ap.add_argument("-tol", dest="tol", required=False, default=1e-5, type=float, help="Variance of the marginals to stop at, default 1e-5.")
-    ap.add_argument("-maxiters", dest="maxiters", required=False, default=200, type=int, help="Most iterations, default 200.")
+    add_options(ap)
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     op = help(argv)
-    jd2expected(op.d, op.output, res=op.res, cut=op.cut, chroms=[] if op.chroms == "" else set(op.chroms.split(",")), raw=op.raw,
-                per_decade=op.perdecade, nosmooth=op.nosmooth, region=op.region, ignore_diags=op.ignorediags, min_nnz=op.minnnz,
-                min_count=op.mincount, mad_max=op.mad, tol=op.tol, max_iters=op.maxiters)
+    jd2expected(op.d, op.output, res=op.res, cut=op.cut, chroms=chroms_of(op), region=op.region, **parsed_options(op))
     return 0
 
 
 if __name__ == "__main__":
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     sys.exit(main())
+
+

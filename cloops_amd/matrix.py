@@ -213,6 +213,44 @@ def _records(jd, chroms=()):
     return [(chrom, CACHE.get(f)) for chrom, f in chrom_files(jd, chroms)]
 
 
+def region_records(jd, chroms, region, res, verb):
+    """-> (`region` as (chrom, start, end) or None, _records(jd, chroms)); ValueError for a region that is no window at `res`, or whose
+    chromosome is not among those records (`verb`: what the caller does to them)"""
+    rg = None if region is None else parse_region(region)
+    if rg is not None and not window_fits(rg, rg, res):
+        raise ValueError("the region needs more than %d bins a side or %d cells at -res %d; the smallest -res that fits is %d"
+                         % (WMAX, CELLS_MAX, res, smallest_res(rg, rg)))
+    recs = _records(jd, chroms)
+    if rg is not None and rg[0] not in [c for c, _ in recs]:
+        raise ValueError("no cis .jd file of chromosome %s among those to %s" % (rg[0], verb))
+    return rg, recs
+
+
+def each_chrom(recs, log, what, fn):
+    """{chrom: fn(the record's chromosome, chrom)} over the records of _records, each under its lock, after the line `what` % chrom
+    on the logger `log`"""
+    per_chrom = {}
+    for chrom, r in recs:
+        log.info(what % chrom)
+        with r.lock:
+            per_chrom[chrom] = fn(r.chrom, chrom)
+    return per_chrom
+
+
+def chrom_outputs(per_chrom, parts, json_suffix, js, matrix_suffix=None):
+    """{suffix: text} of a command's files from {chrom: dict of texts}: per (suffix, key) of `parts` the texts of that key joined in
+    name order, the json `js` (given "chroms": the "stats" of each) under `json_suffix`, and under `matrix_suffix` the "matrix" text of
+    the chromosome that has one; and the json's content"""
+    names = sorted(per_chrom)
+    js = dict(js, chroms={n: per_chrom[n]["stats"] for n in names})
+    texts = {suffix: "".join(per_chrom[n][key] for n in names) for suffix, key in parts}
+    texts[json_suffix] = json.dumps(js, indent=1, sort_keys=True) + "\n"
+    mats = [] if matrix_suffix is None else [per_chrom[n]["matrix"] for n in names if per_chrom[n]["matrix"] is not None]
+    if mats:
+        texts[matrix_suffix] = mats[0]
+    return texts, js
+
+
 def _one_record(jd, chrom):
     recs = _records(jd, {chrom})
     if len(recs) != 1:
@@ -249,11 +287,7 @@ def jd2cells(jd, fout, res=10000, cut=0, chroms=(), fold=True):
     """The non-empty cells of every cis chromosome of `jd` -> `<fout>_cells.txt` (bg2) and `<fout>_cells.json`; returns the json's
     content."""
     res, cut = check_res(res), int(cut)
-    per_chrom = {}
-    for chrom, r in _records(jd, chroms):
-        logger.info("contact-matrix cells of %s" % chrom)
-        with r.lock:
-            per_chrom[chrom] = chrom_cells(r.chrom, chrom, res, cut, bool(fold))
+    per_chrom = each_chrom(_records(jd, chroms), logger, "contact-matrix cells of %s", lambda ch, chrom: chrom_cells(ch, chrom, res, cut, bool(fold)))
     texts, js = cells_outputs(per_chrom, res, cut, bool(fold))
     write_outputs(fout, texts)
     return js
@@ -282,19 +316,28 @@ def jd2v4c(jd, fout, view, region=None, res=1000, cut=0, norm="none"):
     return js
 
 
+def common(p, res, chroms=False):
+    """-d -o -res -cut and, for a command over all chromosomes, -c; `res`: the command's default"""
+    p.add_argument("-d", dest="d", required=True, type=str, help="The directory of cis .jd files.")
+    p.add_argument("-o", dest="output", required=True, type=str, help="Output prefix.")
+    p.add_argument("-res", dest="res", required=False, default=res, type=int, help="Bin size in bp, default %d." % res)
+    p.add_argument("-cut", dest="cut", required=False, default=0, type=int, help="Distance cutoff to filter PETs, default 0.")
+    if chroms:
+        p.add_argument("-c", dest="chroms", required=False, default="", type=str,
+                       help="Whether to process limited chroms, specify it as chr1,chr2,chr3, default is all.")
+
+
+def chroms_of(op):
+    """the `chroms` of a jd2* from the -c of `common`"""
+    return [] if op.chroms == "" else set(op.chroms.split(","))
+
+
 def help(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cloops_amd.matrix",
                                  description="Contact matrices on MI355X. "
                                              "For example: python -m cloops_amd.matrix window -d hic -o hic -r chr21:20000000-21000000")
     sub = ap.add_subparsers(dest="cmd")
     sub.required = True
-
-    def common(p, res):
-        p.add_argument("-d", dest="d", required=True, type=str, help="The directory of cis .jd files.")
-        p.add_argument("-o", dest="output", required=True, type=str, help="Output prefix.")
-        p.add_argument("-res", dest="res", required=False, default=res, type=int, help="Bin size in bp, default %d." % res)
-        p.add_argument("-cut", dest="cut", required=False, default=0, type=int, help="Distance cutoff to filter PETs, default 0.")
-
     w = sub.add_parser("window", help="The dense contact matrix of a region, as text for a heatmap.")
     common(w, 5000)
     w.add_argument("-r", dest="region", required=True, type=str, help="The region of the rows, chrom:start-end.")
@@ -304,9 +347,7 @@ def help(argv=None):
                    help="Count every PET at its transposed cell too (default with one region).")
     w.add_argument("-plot", dest="plot", required=False, action="store_true", help="Draw the matrix into <o>_matrix.pdf.")
     c = sub.add_parser("cells", help="The non-empty cells of every chromosome, as bg2 text.")
-    common(c, 10000)
-    c.add_argument("-c", dest="chroms", required=False, default="", type=str,
-                   help="Whether to process limited chroms, specify it as chr1,chr2,chr3, default is all.")
+    common(c, 10000, chroms=True)
     c.add_argument("-nofold", dest="nofold", required=False, action="store_true",
                    help="Keep a PET with Y bin below X bin in its own cell instead of the upper triangle's.")
     v = sub.add_parser("v4c", help="The interaction profile of one viewpoint, as a bedGraph.")
@@ -324,7 +365,7 @@ def main(argv=None):
     if op.cmd == "window":
         jd2window(op.d, op.output, op.region, region2=op.region2, res=op.res, cut=op.cut, mirror=True if op.mirror else None, plot=op.plot)
     elif op.cmd == "cells":
-        jd2cells(op.d, op.output, res=op.res, cut=op.cut, chroms=[] if op.chroms == "" else set(op.chroms.split(",")), fold=not op.nofold)
+        jd2cells(op.d, op.output, res=op.res, cut=op.cut, chroms=chroms_of(op), fold=not op.nofold)
     else:
         jd2v4c(op.d, op.output, op.view, region=op.region, res=op.res, cut=op.cut, norm=op.norm)
     return 0

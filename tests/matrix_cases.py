@@ -93,6 +93,32 @@ class OracleChrom(object):
         self.cells = None
 
 
+class Recording(object):
+    """a stand-in chromosome that lists the calls made on it from outside as (name, args, keywords), an array written as its dtype's
+    kind and length (`b[5]`); `fail`: the method that raises instead of running"""
+
+    def __init__(self, inner, fail=None):
+        self.inner, self.fail, self.log = inner, fail, []
+
+    @staticmethod
+    def _plain(v):
+        if isinstance(v, np.ndarray):
+            return "%s[%s]" % (v.dtype.kind, ",".join(str(n) for n in v.shape))
+        return v.item() if isinstance(v, np.generic) else v
+
+    def __getattr__(self, name):
+        method = getattr(self.inner, name)
+        if not callable(method):
+            return method
+
+        def call(*args, **kw):
+            self.log.append((name, tuple(self._plain(a) for a in args), {k: self._plain(v) for k, v in kw.items()}))
+            if name == self.fail:
+                raise RuntimeError("%s fails" % name)
+            return method(*args, **kw)
+        return call
+
+
 # ---- data ------------------------------------------------------------------------------------------------------
 def twelve():
     """a hand-written example: twelve rows over the bins 0 .. 4 of 100 bp, one of them with Y < X, two duplicates"""

@@ -249,3 +249,36 @@ def test_the_stand_in_keeps_the_order_of_calls():
     ch.mat_cells(100, fold=True)
     with pytest.raises(RuntimeError):
         ch.bal_marginals_get()
+
+
+# ---- the walk down the device state, the options and the clean-up that the four commands share --------------------------------
+def test_the_calls_on_the_device_and_no_more():
+    ch = MC.Recording(BC.OracleChrom(*MC.twelve()))
+    balance.balance_chrom(ch, "chr1", 100, ignore_diags=2, min_nnz=1)
+    assert ch.log == [("mat_cells", (100,), {"cut": 0, "fold": True}), ("bal_marginals", (2,), {}), ("bal_marginals_get", (0, 5), {}),
+                      ("bal_iterate", ("b[5]",), {"max_iters": 200, "tol": 1e-5}), ("bal_weights", (0, 5), {}),
+                      ("mat_cells_get", (0, 10), {}), ("bal_cells_get", (0, 10), {}), ("mat_free", (), {})]
+    ch = MC.Recording(BC.OracleChrom(*MC.twelve()))
+    balance.balance_chrom(ch, "chr1", 100, ignore_diags=2, min_nnz=1, chunk=7, region=("chr1", 100, 400))
+    assert ch.log[5:] == [("mat_cells_get", (0, 7), {}), ("bal_cells_get", (0, 7), {}), ("mat_cells_get", (7, 3), {}), ("bal_cells_get", (7, 3), {}),
+                          ("mat_window", (100, 1, 1, 3, 3), {"cut": 0, "mirror": True}), ("mat_free", (), {})]
+
+
+def test_main_hands_every_option_on(standin, tmp_path):
+    out = os.path.join(str(tmp_path), "o")
+    kw = dict(res=100, cut=20, ignore_diags=1, min_nnz=1, min_count=1, mad_max=2.5, tol=1e-8, max_iters=30, region="chr1:100-400")
+    js = balance.jd2balance("jd", out + "k", chroms={"chr1", "chr2"}, **kw)
+    assert js["args"] == kw
+    assert balance.main(["-d", "jd", "-o", out + "m", "-res", "100", "-cut", "20", "-c", "chr1,chr2", "-ignorediags", "1", "-minnnz", "1",
+                         "-mincount", "1", "-mad", "2.5", "-tol", "1e-8", "-maxiters", "30", "-r", "chr1:100-400"]) == 0
+    assert _read(out + "m", balance.SUFFIXES) == _read(out + "k", balance.SUFFIXES)
+    assert balance.check_args(**{k: kw[k] for k in balance.BalanceArgs._fields})._asdict() == {k: kw[k] for k in balance.BalanceArgs._fields}
+
+
+@pytest.mark.parametrize("step", ["bal_marginals", "bal_iterate", "bal_weights", "mat_cells_get", "mat_window"])
+def test_a_failing_step_frees_the_cells_once_and_writes_nothing(step, standin, tmp_path):
+    standin["chr1"].chrom = ch = MC.Recording(standin["chr1"].chrom, fail=step)
+    with pytest.raises(RuntimeError):
+        balance.jd2balance("jd", os.path.join(str(tmp_path), "f"), region="chr1:100-400", **ARGS)
+    assert [c[0] for c in ch.log].count("mat_free") == 1 and ch.log[-1][0] == "mat_free" and ch.log[-2][0] == step
+    assert os.listdir(str(tmp_path)) == [] and standin["chr2"].chrom.calls == []

@@ -356,3 +356,38 @@ def test_the_stand_in_keeps_the_order_of_calls():
     ch.bal_marginals(2)
     with pytest.raises(RuntimeError):
         ch.eig_build()
+
+
+# ---- the walk down the device state, the options and the clean-up that the commands share -------------------------------------
+def test_the_calls_on_the_device_and_no_more():
+    head = [("mat_cells", (100,), {"cut": 0, "fold": True}), ("bal_marginals", (2,), {}), ("bal_marginals_get", (0, 5), {})]
+    tail = [("exp_diagonals_get", (0, 5), {}), ("exp_set", ("f[5]",), {}), ("exp_cells_get", (0, 7), {}), ("exp_cells_get", (7, 3), {}),
+            ("eig_build", (float("inf"), 5), {}), ("eig_iterate", (2,), {"max_iters": 1000, "tol": 1e-8}), ("eig_vectors", (0, 0, 5), {}),
+            ("eig_vectors", (1, 0, 5), {}), ("mat_free", (), {})]
+    ch = MC.Recording(CC.OracleChrom(*MC.twelve()))
+    compartments.compartments_chrom(ch, "chr1", 100, n_eigs=2, clip=100, ignore_diags=2, min_nnz=1, chunk=7)
+    assert ch.log == head + [("bal_iterate", ("b[5]",), {"max_iters": 200, "tol": 1e-5}), ("bal_weights", (0, 5), {}), ("exp_diagonals", (), {})] + tail
+    ch = MC.Recording(CC.OracleChrom(*MC.twelve()))
+    compartments.compartments_chrom(ch, "chr1", 100, n_eigs=2, clip=100, ignore_diags=2, min_nnz=1, chunk=7, raw=True)
+    assert ch.log == head + [("exp_diagonals", (), {"valid": "b[5]", "balanced": False})] + tail
+
+
+def test_main_hands_every_option_on(standin, tmp_path):
+    out = os.path.join(str(tmp_path), "o")
+    kw = dict(res=2000, cut=20, n_eigs=2, clip=95.0, eig_tol=1e-6, eig_iters=77, phase=None, raw=True, per_decade=4, nosmooth=True, ignore_diags=1,
+              min_nnz=3, min_count=1, mad_max=2.5, tol=1e-8, max_iters=30)
+    js = compartments.jd2compartments("jd", out + "k", chroms={"chr1", "chr2"}, **kw)
+    assert js["args"] == kw
+    assert compartments.main(["-d", "jd", "-o", out + "m", "-res", "2000", "-cut", "20", "-c", "chr1,chr2", "-neigs", "2", "-clip", "95", "-eigtol",
+                              "1e-6", "-eigiters", "77", "-raw", "-perdecade", "4", "-nosmooth", "-ignorediags", "1", "-minnnz", "3", "-mincount",
+                              "1", "-mad", "2.5", "-tol", "1e-8", "-maxiters", "30"]) == 0
+    assert _read(out + "m", compartments.SUFFIXES) == _read(out + "k", compartments.SUFFIXES)
+
+
+@pytest.mark.parametrize("step", ["bal_iterate", "bal_weights", "exp_set", "eig_build", "eig_vectors"])
+def test_a_failing_step_frees_the_cells_once_and_writes_nothing(step, standin, tmp_path):
+    standin["chr1"].chrom = ch = MC.Recording(standin["chr1"].chrom, fail=step)
+    with pytest.raises(RuntimeError):
+        compartments.jd2compartments("jd", os.path.join(str(tmp_path), "f"), res=2000, n_eigs=2)
+    assert [c[0] for c in ch.log].count("mat_free") == 1 and ch.log[-1][0] == "mat_free" and ch.log[-2][0] == step
+    assert os.listdir(str(tmp_path)) == [] and standin["chr2"].chrom.calls == []

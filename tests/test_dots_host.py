@@ -313,3 +313,49 @@ def test_gpu_cases_reach_their_edges():
     la = np.stack([ch.dot_lambdas_get(k) for k in range(4)])
     hist, nbey = ch.dot_hist(dots.default_edges(3))                          # a pixel beyond the last edge
     assert nbey > 0 and hist.sum() > 0 and np.nanmax(la) > 2.0 ** (2.0 / 3.0)
+
+
+# ---- the walk down the device state, the options and the clean-up that the commands share -------------------------------------
+def test_the_calls_on_the_device_and_no_more():
+    head = [("mat_cells", (100,), {"cut": 0, "fold": True}), ("bal_marginals", (2,), {}), ("bal_marginals_get", (0, 5), {})]
+    tail = [("exp_diagonals_get", (0, 5), {}), ("exp_set", ("f[5]",), {}), ("dot_lambdas", (2, 5, 4, 5), {}), ("dot_hist", ("f[40]",), {}),
+            ("dot_call", ("u[4,40]",), {}), ("dot_sig", (0, 0), {}), ("mat_free", (), {})]
+    ch = MC.Recording(DC.OracleChrom(*MC.twelve()))
+    dots.dots_chrom(ch, "chr1", 100, ignore_diags=2, min_nnz=1)
+    assert ch.log == head + [("bal_iterate", ("b[5]",), {"max_iters": 200, "tol": 1e-5}), ("exp_diagonals", (), {})] + tail   # no bal_weights
+    ch = MC.Recording(DC.OracleChrom(*MC.twelve()))
+    dots.dots_chrom(ch, "chr1", 100, ignore_diags=2, min_nnz=1, raw=True)
+    assert ch.log == head + [("exp_diagonals", (), {"valid": "b[5]", "balanced": False})] + tail
+
+
+def _two_records(monkeypatch, fail=None):
+    from cloops_amd import matrix
+    recs = [("chr1", FakeRecord(*MC.scattered(2, 3000, 60000, 20000))), ("chr7", FakeRecord(*MC.scattered(3, 200, 90000, 20000)))]
+    recs[0][1].chrom = MC.Recording(recs[0][1].chrom, fail=fail)
+    monkeypatch.setattr(matrix, "_records", lambda jd, chroms=(): [r for r in recs if not chroms or r[0] in chroms])
+    return recs
+
+
+def test_main_hands_every_option_on(tmp_path, monkeypatch):
+    _two_records(monkeypatch)
+    out = os.path.join(str(tmp_path), "o")
+    kw = dict(res=2000, cut=20, p=1, w=4, mindist=5, maxdist=60000, fdr=0.3, chunks=11, merge=7, minpix=2, enrich=[1.0, 1.25, 1.5, 1.75, 2.0],
+              raw=True, per_decade=4, nosmooth=True, ignore_diags=1, min_nnz=3, min_count=1, mad_max=2.5, tol=1e-8, max_iters=30)
+    js = dots.jd2dots("jd", out + "k", chroms={"chr1", "chr7"}, **kw)
+    assert js["args"] == kw
+    assert dots.main(["-d", "jd", "-o", out + "m", "-res", "2000", "-cut", "20", "-c", "chr1,chr7", "-p", "1", "-w", "4", "-mindist", "5", "-maxdist",
+                      "60000", "-fdr", "0.3", "-chunks", "11", "-merge", "7", "-minpix", "2", "-enrich", "1,1.25,1.5,1.75,2", "-raw", "-perdecade",
+                      "4", "-nosmooth", "-ignorediags", "1", "-minnnz", "3", "-mincount", "1", "-mad", "2.5", "-tol", "1e-8", "-maxiters", "30"]) == 0
+    for sfx in dots.SUFFIXES:
+        with open(out + "m" + sfx) as fm, open(out + "k" + sfx) as fk:
+            assert fm.read() == fk.read()
+
+
+@pytest.mark.parametrize("step", ["bal_iterate", "exp_diagonals", "exp_set", "dot_lambdas", "dot_sig"])
+def test_a_failing_step_frees_the_cells_once_and_writes_nothing(step, tmp_path, monkeypatch):
+    recs = _two_records(monkeypatch, fail=step)
+    with pytest.raises(RuntimeError):
+        dots.jd2dots("jd", os.path.join(str(tmp_path), "f"), res=2000, maxdist=60000)
+    log = recs[0][1].chrom.log
+    assert [c[0] for c in log].count("mat_free") == 1 and log[-1][0] == "mat_free" and log[-2][0] == step
+    assert os.listdir(str(tmp_path)) == [] and recs[1][1].chrom.calls == []

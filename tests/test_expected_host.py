@@ -321,3 +321,51 @@ def test_the_stand_in_keeps_the_order_of_calls():
         drop()
         with pytest.raises(RuntimeError):
             ch.exp_diagonals_get()
+
+
+# ---- the walk down the device state, the options and the clean-up that the commands share -------------------------------------
+CELLS = ("mat_cells", (100,), {"cut": 0, "fold": True})
+MARGINALS = [("bal_marginals", (2,), {}), ("bal_marginals_get", (0, 5), {})]
+ITERATE = ("bal_iterate", ("b[5]",), {"max_iters": 200, "tol": 1e-5})
+DIAGONALS = [("exp_diagonals_get", (0, 5), {}), ("exp_set", ("f[5]",), {})]
+
+
+def test_the_calls_on_the_device_and_no_more():
+    ch = MC.Recording(EC.OracleChrom(*MC.twelve()))
+    expected.expected_chrom(ch, "chr1", 100, ignore_diags=2, min_nnz=1)
+    assert ch.log == [CELLS] + MARGINALS + [ITERATE, ("bal_weights", (0, 5), {}), ("exp_diagonals", (), {})] + DIAGONALS + \
+        [("mat_cells_get", (0, 10), {}), ("bal_cells_get", (0, 10), {}), ("exp_cells_get", (0, 10), {}), ("mat_free", (), {})]
+    ch = MC.Recording(EC.OracleChrom(*MC.twelve()))
+    expected.expected_chrom(ch, "chr1", 100, ignore_diags=2, min_nnz=1, raw=True, chunk=7, region=("chr1", 100, 400))
+    assert ch.log == [CELLS] + MARGINALS + [("exp_diagonals", (), {"valid": "b[5]", "balanced": False})] + DIAGONALS + \
+        [("mat_cells_get", (0, 7), {}), ("exp_cells_get", (0, 7), {}), ("mat_cells_get", (7, 3), {}), ("exp_cells_get", (7, 3), {}),
+         ("mat_window", (100, 1, 1, 3, 3), {"cut": 0, "mirror": True}), ("mat_free", (), {})]
+
+
+def test_main_hands_every_option_on(standin, tmp_path):
+    out = os.path.join(str(tmp_path), "o")
+    kw = dict(res=100, cut=20, raw=True, per_decade=4, nosmooth=True, ignore_diags=1, min_nnz=1, min_count=1, mad_max=2.5, tol=1e-8, max_iters=30,
+              region="chr1:100-400")
+    js = expected.jd2expected("jd", out + "k", chroms={"chr1", "chr2"}, **kw)
+    assert js["args"] == kw
+    assert expected.main(["-d", "jd", "-o", out + "m", "-res", "100", "-cut", "20", "-c", "chr1,chr2", "-raw", "-perdecade", "4", "-nosmooth",
+                          "-ignorediags", "1", "-minnnz", "1", "-mincount", "1", "-mad", "2.5", "-tol", "1e-8", "-maxiters", "30", "-r",
+                          "chr1:100-400"]) == 0
+    assert _read(out + "m", expected.SUFFIXES) == _read(out + "k", expected.SUFFIXES)
+    # the records as keywords of the per-chromosome function, and as records
+    nine = {k: kw[k] for k in balance.BalanceArgs._fields + expected.ExpectedArgs._fields}
+    bal, exp = expected.options_of(**nine)
+    assert dict(bal._asdict(), **exp._asdict()) == nine and expected.options_of(bal=bal, exp=exp) == (bal, exp)
+    ch = standin["chr2"].chrom
+    assert expected.expected_chrom(ch, "chr2", 100, cut=20, **nine) == expected.expected_chrom(ch, "chr2", 100, cut=20, bal=bal, exp=exp)
+    with pytest.raises(TypeError):
+        expected.options_of(perdecade=4)
+
+
+@pytest.mark.parametrize("step", ["bal_iterate", "bal_weights", "exp_diagonals", "exp_set", "exp_cells_get"])
+def test_a_failing_step_frees_the_cells_once_and_writes_nothing(step, standin, tmp_path):
+    standin["chr1"].chrom = ch = MC.Recording(standin["chr1"].chrom, fail=step)
+    with pytest.raises(RuntimeError):
+        expected.jd2expected("jd", os.path.join(str(tmp_path), "f"), **ARGS)
+    assert [c[0] for c in ch.log].count("mat_free") == 1 and ch.log[-1][0] == "mat_free" and ch.log[-2][0] == step
+    assert os.listdir(str(tmp_path)) == [] and standin["chr2"].chrom.calls == []
