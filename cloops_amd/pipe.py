@@ -12,21 +12,23 @@ What differs is where the work happens:
   * `runDBSCAN` spreads chromosomes over the visible GPUs (one host thread per GPU) instead
     of joblib worker processes (pipe.py:117).
 """
+import contextlib
 import itertools
 import os
 import sys
 import threading
 import time
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 from . import api
 from . import _roctx
+from ._lib import DIST_LOGBINS
 from .cDBSCAN2 import cDBSCAN as DBSCAN          # pipe.py:42  (production variant)
 from .dist import lpt_assign
-from .ests import estIntSelCutFrag, estIntSelCutFrag_bounded
+from .ests import estIntSelCutFrag, estIntSelCutFrag_bounded, logbin, logbin_range
 
 #: clustering variant used by singleDBSCAN; "block" mirrors the alternative import at pipe.py:43
 DBSCAN_VARIANT = "v2"
@@ -491,20 +493,6 @@ def _single_arrays(f, eps, minPts, cut, device):
     return r.key, f, dataI, dataS, dis, dss, n_in
 
 
-def _boxes_classified(r, res):
-    """host part of pipe.py:78-102 on the K-row cluster table: (dataI boxes, dataS boxes) as
-    int32 [k,4] arrays (minX, maxX, minY, maxY) in ascending cluster id"""
-    b = res.boxes
-    K = len(b)
-    empty4 = np.zeros((0, 4), np.int32)
-    if K == 0:
-        return empty4, empty4
-    t = b.view(np.int32).reshape(K, 5)                     # rows {minX, maxX, minY, maxY, count}
-    ok = (t[:, 4] > 0) & (t[:, 0] != t[:, 1]) & (t[:, 2] != t[:, 3])      # pipe.py:83-85
-    inter = ok & (t[:, 1] < t[:, 2])                                       # pipe.py:97
-    return t[inter, :4], t[ok & ~inter, :4]              # copies (fancy index): the pinned view may be reused
-
-
 def _combine_steps(step_boxes, _hash_bits=None):
     """combineTwice (pipe.py:155-174) applied over all steps at once, on arrays: a box is kept
     in the step where it FIRST appears (duplicates inside one step are all kept, like the
@@ -569,7 +557,6 @@ def _select_kth(chroms, cut, loghist, ranks, allsum=None, pool=None, fine=None):
     locates the bin of a rank; the bin is then refined with 2048-bin histograms of (|d| - lo) >> shift summed over the
     chromosomes (and, with `allsum`, over the ranks) until single distances are resolved -- one refinement pass for
     bins up to 2048 distances wide (|d| < 2^18), two beyond."""
-    from .ests import logbin_range, logbin
     cum = np.cumsum(np.asarray(loghist, dtype=np.int64))
     out, cache = [], {}
     if fine is not None and fine[0] >= 1:
@@ -655,21 +642,279 @@ SWEEP_THREADS = 8
 #: Measured on the 200 M-PET mode-3 sweep: 0.212 s against 0.208 s -- the serial order (largest chromosome first) is worth more
 #: than the 2 ms of host time the 23 enqueues take, so it stays off.
 PARALLEL_ENQUEUE = False
-STEP_TRACE = None        # developer hook (tools/step_gap.py): a list -> (step, t of the last wait that returned, t of the next step's first enqueue)
-
-
-def _lib_logbins():
-    from ._lib import DIST_LOGBINS
-    return DIST_LOGBINS
+#: developer hook (tools/step_gap.py): a list -> marks (step, label, t) are appended to it.  Per step: "enqueue" (before the largest
+#: chromosome's), "waited" (once per chromosome, as its wait returns), "collected", "reduced", "stats" and, after an estimate, "cut"
+STEP_TRACE = None
 
 #: |2**cut - nearest integer| below which runSweepFast re-derives the cut from the distance lists (ests.py:57 truncates) even
 #: when the error bound of ests.estIntSelCutFrag_bounded would settle it (a floor under that bound)
 CUT_RECHECK_MARGIN = 1e-6
 
 
+def _trace(step_no, label):
+    if STEP_TRACE is not None:
+        STEP_TRACE.append((step_no, label, time.perf_counter()))
+
+
+def _log_no_inter(log, ep, m):
+    if log:                                                   # pipe.py:251-255
+        log("ERROR: no inter-ligation PETs detected for eps %s minPts %s,can't model the distance cutoff,continue anyway" % (ep, m))
+
+
+def _final_cut(cuts, max_cut):
+    """pipe.py:276-280: the largest or the smallest of the positive cuts of a sweep"""
+    pos = [c for c in cuts if c > 0]
+    if not pos:
+        # np.min([]) raises in the reference; keep that behaviour observable
+        raise ValueError("zero-size array to reduction operation minimum which has no identity")
+    return int(np.max(pos)) if max_cut else int(np.min(pos))
+
+
+class _StepStats(object):
+    """The statistics of one sweep step.  The xshift aside, every field is a sum: over the chromosomes of this rank (`add`), then
+    over the ranks (`over_ranks`).  What crosses the ranks is ONE float64 vector, and its layout is stated here and nowhere else in the package
+    (bench.py times an all-reduce of its length): the integers, then the floats,
+
+        integers   [0:4]  n_inter, n_self, n_in, n_chroms
+                   [4:6]  n_all (inter, self)      [6:8]  n_pos (inter, self)
+                   [8 : 8 + DIST_LOGBINS]  loghist      then FINE_BINS words: fine
+        floats     [0:2]  sumx      [2:4]  sumxx      [4]  xshift      [5]  1 on a rank that reports an xshift, else 0
+
+    n_inter / n_self: inter- and self-ligation boxes; n_in: PETs that entered DBSCAN; n_chroms: chromosomes with an inter-ligation
+    box.  Only those chromosomes count from n_all on (runDBSCAN skips the others entirely, pipe.py:121-122): n_all / n_pos / sumx /
+    sumxx per group (x = log2|d| - xshift) and the self group's loghist / fine as cl_dist_summary makes them."""
+    FINE_BINS = 2048
+    __slots__ = ("n_inter", "n_self", "n_in", "n_chroms", "n_all", "n_pos", "loghist", "fine", "sumx", "sumxx", "xshift")
+
+    def __init__(self):
+        self.n_inter = self.n_self = self.n_in = self.n_chroms = 0
+        self.n_all, self.n_pos, self.sumx, self.sumxx = [0, 0], [0, 0], [0.0, 0.0], [0.0, 0.0]
+        self.loghist = np.zeros(DIST_LOGBINS, dtype=np.int64)
+        self.fine = np.zeros(self.FINE_BINS, dtype=np.int64)
+        self.xshift = 0.0
+
+    def add(self, n_inter, n_self, n_in, s):
+        """one chromosome's step_result() and last_n_in() -> whether the chromosome counts (it has an inter-ligation box)"""
+        self.n_self += n_self
+        self.n_in += n_in
+        if n_inter == 0:
+            return False
+        self.n_inter += n_inter
+        self.n_chroms += 1
+        for g in (0, 1):
+            self.n_all[g] += s["n_all"][g]
+            self.n_pos[g] += s["n_pos"][g]
+            self.sumx[g] += s["sumx"][g]
+            self.sumxx[g] += s["sumxx"][g]
+        self.loghist += s["loghist"]                          # (integer histograms: exact in any order)
+        if s.get("fine") is not None:
+            self.fine += s["fine"]
+        self.xshift = s["xshift"]
+        return True
+
+    def pack(self):
+        """-> (integers int64, floats float64) in the layout above"""
+        ints = np.concatenate([np.asarray([self.n_inter, self.n_self, self.n_in, self.n_chroms] + self.n_all + self.n_pos, dtype=np.int64),
+                               self.loghist, self.fine])
+        return ints, np.asarray(self.sumx + self.sumxx + [self.xshift, 1.0 if self.n_chroms else 0.0], dtype=np.float64)
+
+    @classmethod
+    def unpack(cls, ints, floats):
+        """the record of packed (and summed) vectors; its histograms and float sums are views of them"""
+        t = cls.__new__(cls)
+        t.n_inter, t.n_self, t.n_in, t.n_chroms = (int(v) for v in ints[:4])
+        t.n_all, t.n_pos = [int(ints[4]), int(ints[5])], [int(ints[6]), int(ints[7])]
+        t.loghist, t.fine = ints[8:8 + DIST_LOGBINS], ints[8 + DIST_LOGBINS:]
+        t.sumx, t.sumxx = floats[0:2], floats[2:4]
+        # xshift is a constant of the library, the same on every rank that has one: the sum over the ranks divided by the number
+        # of ranks that reported (a rank without a counted chromosome reports 0 and counts as 0)
+        t.xshift = float(floats[4]) / max(float(floats[5]), 1.0)
+        return t
+
+    def over_ranks(self, allsum, step_no):
+        """-> the genome-wide record: with `allsum` ONE exchange, the counts riding as float64 next to the sums (every count and
+        every sum of counts stays far below 2^53, so they come back exact); without it this rank's record is the genome's and
+        nothing is packed, exchanged or converted"""
+        if allsum is None:
+            _trace(step_no, "reduced")
+            return self
+        ints, floats = self.pack()
+        _trace(step_no, "reduced")
+        both = allsum(np.concatenate([ints.astype(np.float64), floats]))
+        return self.unpack(np.rint(both[:len(ints)]).astype(np.int64), both[len(ints):])
+
+
 class _DataI(dict):
     """runSweepFast's candidate tables; `.gathered` = what `device_consumer` returned"""
     gathered = None
+
+
+#: one (eps, minPts) step of a sweep: its number, the cut it filters with and where its summary counts distances exactly
+_Step = namedtuple("_Step", "no eps minPts cut fine_lo")
+
+
+@contextlib.contextmanager
+def _sweep_hold(fs, res_all, eps, minPts):
+    """One sweep's hold on its handles -> live = [(f, resident)] of the non-empty chromosomes, in file order.  The candidate
+    buffer, the layout and the sort index of a handle are state of ONE sweep: a second sweep over the same residents waits (locks
+    taken in one global order, so two sweeps over overlapping sets cannot deadlock)."""
+    live = [(f, r) for f, r in zip(fs, res_all) if len(r)]
+    held = sorted({id(r): r for _, r in live}.values(), key=id)
+    for r in held:
+        r.sweep_lock.acquire()
+    try:
+        # (a synchronous call on a handle -- cluster(), sig_counts() -- holds its r.lock: no stream is swapped under one)
+        for r in held:
+            r.lock.acquire()
+        try:
+            STREAMS.rebalance([(r.chrom, len(r)) for _, r in live])
+        finally:
+            for r in held:
+                r.lock.release()
+        for f, r in live:
+            r.chrom.cand_reset()
+            # the region query of the first run at an eps serves the later runs at that eps (their minPts are smaller: the
+            # reference sorts them descending, pipe.py:316-320) -- its counts have to tell `count >= m` for every m of the list
+            # (cl_sweep_plan: with several eps the q index pays from the first sort on and, if the values share a divisor, one fine
+            #  sort serves all of them; the counts of an eps are bracketed for the whole minPts list)
+            r.chrom.sweep_plan(eps, minPts)
+        yield live
+    finally:
+        for f, r in live:
+            # the announced minPts list belongs to this sweep: a later one-off run on the handle serves its own minPts only
+            try:
+                r.chrom.sweep_plan([], [])
+            except Exception:
+                pass
+        for r in held:
+            r.sweep_lock.release()
+
+
+def _enqueue_step(step, by_size, variant, pool):
+    """The step's run of every chromosome enqueued, in the order of `by_size` (largest first).  Chromosomes are independent inside
+    a step and the handles share the device's streams: the kernels of different chromosomes overlap on the GPU.  A handle's r.lock
+    is held from here until _collect_step has taken its result."""
+    def enqueue(fr):
+        f, r = fr
+        if fr is by_size[0]:
+            _trace(step.no, "enqueue")
+        r.lock.acquire()
+        try:
+            r.chrom.step_async(variant, step.eps, step.minPts, step.cut, step.no, step.fine_lo)
+        except Exception as e:
+            r.lock.release()
+            return e
+        return None
+
+    errs = _pmap(pool if PARALLEL_ENQUEUE else None, enqueue, by_size)
+    if any(e is not None for e in errs):
+        # a failed enqueue must not leave the other chromosomes locked with a run in flight
+        for (f, r), e in zip(by_size, errs):
+            if e is None:
+                try:
+                    r.chrom.wait()
+                except Exception:
+                    pass
+                r.lock.release()
+        raise [e for e in errs if e is not None][0]
+
+
+def _collect_step(step, live, pool, probe, appended):
+    """The step's results summed over this rank's chromosomes -> (_StepStats, the residents that count: those with an inter-ligation
+    box); `appended` (f -> inter-ligation boxes appended on the device so far) grows by them.  A run carries its own tail on the
+    device: the table classified (pipe.py:83-97), its inter-ligation boxes appended to the chromosome's candidate buffer under this
+    step's number, the distance statistics reduced -- everything is on the host with the run's completion."""
+    def collect(fr):
+        f, r = fr
+        try:
+            res = r.chrom.wait()
+            _trace(step.no, "waited")
+            if probe is not None:
+                probe(f, step.eps, step.minPts, step.cut, res)
+            n_inter, n_self, s = r.chrom.step_result()
+            n_in = r.chrom.last_n_in()
+        finally:
+            r.lock.release()
+        return f, r, n_inter, n_self, n_in, s
+
+    tot, used = _StepStats(), []
+    # (results are taken in file order AS THEY ARRIVE: the sums of the chromosomes that finished early are done while the others
+    #  still run, behind the step's last wait only that chromosome's share is left.  Not pool.map: when one result raises, its
+    #  iterator cancels the calls that have not started, and their chromosomes would stay locked with a run in flight)
+    futs = [] if pool is None else [pool.submit(collect, fr) for fr in live][::-1]        # (popped from the end: a result is let go once summed)
+    for f, r, n_inter, n_self, n_in, s in (map(collect, live) if pool is None else (futs.pop().result() for _ in live)):
+        if tot.add(n_inter, n_self, n_in, s):
+            appended[f] = appended.get(f, 0) + n_inter
+            used.append(r)
+    _trace(step.no, "collected")
+    return tot, used
+
+
+def _estimate_cut(step, tot, used, st, variant, allsum, pool, plot, log):
+    """pipe.py:251-267 on the genome-wide statistics `tot` of a step (`used`: this rank's chromosomes that count in them) ->
+    (cut_2, frags, fine_lo of the next step), or None where the reference estimates nothing: no inter-ligation PETs anywhere, or
+    one of the two distance groups is empty.  Notes on how the cut was settled, and the curves of a plot, go into `st`."""
+    if tot.n_chroms == 0:
+        _log_no_inter(log, step.eps, step.minPts)
+        return None
+    if not (tot.n_all[0] > 0 and tot.n_all[1] > 0):           # pipe.py:256-259
+        return None
+    if tot.n_pos[0] == 0 or tot.n_pos[1] == 0:
+        raise ValueError("cannot convert float NaN to integer")      # what int(2 ** nan) raises in ests.py:57
+    n1 = tot.n_pos[1]
+    med = _select_kth(used, step.cut, tot.loghist, sorted({(n1 - 1) // 2, n1 // 2}), allsum, pool,
+                      fine=(step.fine_lo, tot.fine) if step.fine_lo >= 1 else None)
+    # the next step's summary also counts the distances around this median exactly (the median moves little from step to step):
+    # lower edge of the log bin 1024 below it, so that the ranks below it are known
+    fine_lo = logbin_range(logbin(max(1, med[0] - 1024)))[0]
+    # the cut from sum x and sum x^2 (x = log2|d| - xshift), with the range that the reduction's rounding leaves for the
+    # reference's int(2 ** cut) (ests.estIntSelCutFrag_bounded, DESIGN.md section 4, K7 / K10)
+    cut_2, frags, (rc_lo, rc_hi), margin = estIntSelCutFrag_bounded(tot.n_all, tot.n_pos, tot.sumx, tot.sumxx, tot.xshift,
+                                                                    (med[0], med[-1]), n_parts=tot.n_chroms)
+    if rc_lo != rc_hi or margin < CUT_RECHECK_MARGIN:
+        if allsum is None:
+            # 2**cut may sit on either side of an integer within the error of the statistics: settle it the reference's way, from
+            # the distance lists with numpy's own sums (rare -- a group of (nearly) equal distances, or 2**cut within ~1e-6 of an
+            # integer; one extra run per chromosome with labels on the host)
+            parts = [_cluster_arrays(r, step.eps, step.minPts, step.cut, variant) for r in used]
+            cut_2, frags = estIntSelCutFrag(np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts]))
+            st["cut_rechecked"] = True
+        else:
+            # several ranks: the lists are spread over them -- keep the statistics' cut, inside the bound
+            st["cut_range"] = (int(rc_lo), int(rc_hi))
+            if log and rc_lo != rc_hi:
+                log("WARNING: the distance statistics of eps=%s,minPts=%s bound the cutoff only to [%s, %s]" % (step.eps, step.minPts, rc_lo, rc_hi))
+    if plot is not None:
+        # pipe.py:261-267: the picture of this step's two distance groups with the estimated cut drawn in; the handles still hold
+        # the step's runs (a re-check above repeated them with the same parameters)
+        t_plot0 = time.perf_counter()
+        st["kde"] = _step_kde(used, step.cut, tot.n_pos, tot.sumx, tot.sumxx, tot.xshift, pool)
+        _plot_step(st["kde"], cut_2, "%s_eps%s_minPts%s_disCutoff" % (plot, step.eps, step.minPts), log)
+        st["plot_s"] = time.perf_counter() - t_plot0
+    if log:
+        log("Estimated inter-ligation and self-ligation distance cutoff as %s for eps=%s,minPts=%s" % (cut_2, step.eps, step.minPts))
+    return cut_2, frags, fine_lo
+
+
+def _finish_sweep(live, appended, final_cut, pool, finish_device, device_consumer):
+    """combineTwice over all steps (pipe.py:257,275), then filterClusterByDis (pipe.py:130-143, floor division): on the device, per
+    chromosome; only the surviving boxes cross PCIe -> _DataI"""
+    def finish(fr):
+        f, r = fr
+        with r.lock:
+            if finish_device:
+                ptr, k = r.chrom.cand_finish_device(final_cut)
+                return r.key, {"f": f, "boxes": None, "dev_rows": ptr, "n_rows": k}
+            b = r.chrom.cand_finish(final_cut, appended[f])
+        return r.key, {"f": f, "boxes": b}                    # int32 [k, 4] rows (minX, maxX, minY, maxY), append order
+
+    # key order = first appearance over the steps, file order inside a step: what combineTwice's dict inserts
+    # (pipe.py:155-174) and runStat later walks -- `appended` was filled in exactly that order
+    res_of = dict(live)
+    dataI = _DataI(_pmap(pool, finish, [(f, res_of[f]) for f in appended]))
+    if finish_device and device_consumer is not None:
+        dataI.gathered = device_consumer(dataI)               # (residents pinned, sweep locks held: the pointers are alive)
+    return dataI
 
 
 def runSweepFast(fs, eps, minPts, cut=0, max_cut=False, log=None, variant=None, allsum=None, probe=None, forced_cuts=None, finish_device=False,
@@ -682,8 +927,8 @@ def runSweepFast(fs, eps, minPts, cut=0, max_cut=False, log=None, variant=None, 
 
     `allsum` (optional): element-wise global sum of a small numpy array over all ranks
     (cloops_amd.dist.make_allsum) -- with it every rank passes ITS chromosomes as `fs` and the
-    chained cut is estimated from the genome-wide statistics; the per-step exchange is a few
-    hundred bytes (6 sums, 2 squared deviations, 4-8 histograms of 256 bins).
+    chained cut is estimated from the genome-wide statistics; the per-step exchange is one
+    vector (_StepStats) and, where the median needs them, the histograms of its refinement.
 
     `probe` (optional): called as probe(f, eps, minPts, cut_in, result) for every completed run (bench.py reads
     the HIP-event kernel timings of profiled handles through it).
@@ -711,240 +956,41 @@ def runSweepFast(fs, eps, minPts, cut=0, max_cut=False, log=None, variant=None, 
     variant = variant or DBSCAN_VARIANT
     if plot is not None and allsum is not None:
         raise ValueError("runSweepFast: plot needs the whole genome on one rank (it cannot be combined with allsum)")
-    gsum = allsum if allsum is not None else (lambda a: a)
-    devs = _devices()
-    with CACHE.pinned(fs, devs) as res_all:
-        return _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gsum, probe, forced_cuts, finish_device, device_consumer,
-                           plot)
-
-
-def _sweep_fast(fs, res_all, eps, minPts, cut, max_cut, log, variant, allsum, gsum, probe=None, forced_cuts=None, finish_device=False,
-                device_consumer=None, plot=None):
-    if plot is not None and allsum is not None:
-        raise ValueError("runSweepFast: plot needs the whole genome on one rank (it cannot be combined with allsum)")
-    cuts = [cut]
-    steps = []
-    live = [(f, r) for f, r in zip(fs, res_all) if len(r)]
-    by_size = sorted(live, key=lambda fr: -len(fr[1]))   # enqueue order: largest first (results are collected in file order)
-    appended = {}                                        # f -> inter-ligation boxes appended on the device so far
-    pool = ThreadPoolExecutor(max_workers=SWEEP_THREADS) if len(live) > 1 else None
-    # the candidate buffer, the layout and the sort index of a handle are state of ONE sweep: a second sweep over the same
-    # residents waits (locks taken in one global order, so two sweeps over overlapping sets cannot deadlock)
-    held = sorted({id(r): r for _, r in live}.values(), key=id)
-    for r in held:
-        r.sweep_lock.acquire()
-    try:
-        # (a synchronous call on a handle -- cluster(), sig_counts() -- holds its r.lock: no stream is swapped under one)
-        for r in held:
-            r.lock.acquire()
-        try:
-            STREAMS.rebalance([(r.chrom, len(r)) for _, r in live])
-        finally:
-            for r in held:
-                r.lock.release()
-        for f, r in live:
-            r.chrom.cand_reset()
-            # the region query of the first run at an eps serves the later runs at that eps (their minPts are smaller: the
-            # reference sorts them descending, pipe.py:316-320) -- its counts have to tell `count >= m` for every m of the list
-            # (cl_sweep_plan: with several eps the q index pays from the first sort on and, if the values share a divisor, one fine
-            #  sort serves all of them; the counts of an eps are bracketed for the whole minPts list)
-            r.chrom.sweep_plan(eps, minPts)
-        step_no = 0
-        # where the summary should look for the next median (see _select_kth).  The first step has no earlier median to go by:
-        # it counts the distances 1 .. 2048 exactly (self-ligation distances are a few hundred bp: ests.py's cut model) and falls
-        # back to the refinement passes if the median lies beyond
-        fine_lo = 1
-        for ep in eps:
-            for m in minPts:
-                step_cut = cut
-                this_step = step_no
-                step_no += 1
-                t_step0 = time.perf_counter()
-                # one roctx range per step, from the enqueue to this rank's statistics on the host (rocprofv3 --marker-trace)
-                rng = _roctx.range_("cloops sweep step %d: eps %d minPts %d cut %d" % (this_step, ep, m, step_cut))
-                rng.__enter__()
-
-                # chromosomes are independent inside a step: enqueue them all (each handle has its own
-                # streams), then collect -- the kernels of different chromosomes overlap on the GPU
-                # and the host-side collection runs on the pool
-                def enqueue(fr):
-                    f, r = fr
-                    if STEP_TRACE is not None and fr is by_size[0]:
-                        STEP_TRACE.append((this_step, "enqueue", time.perf_counter()))
-                    r.lock.acquire()
-                    try:
-                        r.chrom.step_async(variant, ep, m, step_cut, this_step, fine_lo)
-                    except Exception as e:
-                        r.lock.release()
-                        return e
-                    return None
-
-                errs = _pmap(pool if PARALLEL_ENQUEUE else None, enqueue, by_size)
-                if any(e is not None for e in errs):
-                    # a failed enqueue must not leave the other chromosomes locked with a run in flight
-                    for (f, r), e in zip(by_size, errs):
-                        if e is None:
-                            try:
-                                r.chrom.wait()
-                            except Exception:
-                                pass
-                            r.lock.release()
-                    rng.__exit__(None, None, None)
-                    raise [e for e in errs if e is not None][0]
-
-                def collect(fr):
-                    f, r = fr
-                    try:
-                        res = r.chrom.wait()
-                        if STEP_TRACE is not None:
-                            STEP_TRACE.append((this_step, "waited", time.perf_counter()))
-                        if probe is not None:
-                            probe(f, ep, m, step_cut, res)
-                        # the run carried its own tail on the device: the table classified (pipe.py:83-97), its
-                        # inter-ligation boxes appended to the chromosome's candidate buffer under this step's number,
-                        # the distance statistics reduced -- everything is on the host with the run's completion
-                        nI, nS, s1 = r.chrom.step_result()
-                        n_in = r.chrom.last_n_in()
-                    finally:
-                        r.lock.release()
-                    return f, r, nI, nS, n_in, s1
-
-                used = []
-                nI_tot = nS = n_in = 0
-                tot = {"n_all": [0, 0], "n_pos": [0, 0], "sumx": [0.0, 0.0], "sumxx": [0.0, 0.0]}
-                loghist = np.zeros(_lib_logbins(), dtype=np.int64)
-                fine = np.zeros(2048, dtype=np.int64)
-                xshift = 0.0
-                # (results are taken in file order AS THEY ARRIVE: the sums of the chromosomes that finished early are done while
-                #  the others still run -- behind the step's last wait only that chromosome's share is left)
-                for f, r, nI, ndS, nin, s1 in (pool.map(collect, live) if (pool is not None and len(live) > 1) else map(collect, live)):
-                    nS += ndS
-                    n_in += nin
-                    if nI == 0:                               # runDBSCAN skips such chromosomes entirely (pipe.py:121-122)
-                        continue
-                    nI_tot += nI
-                    appended[f] = appended.get(f, 0) + nI
-                    used.append(r)
-                    for gg in (0, 1):
-                        for kk in ("n_all", "n_pos", "sumx", "sumxx"):
-                            tot[kk][gg] += s1[kk][gg]
-                    loghist += s1["loghist"]                  # (integer histograms: exact in any order)
-                    if s1.get("fine") is not None:
-                        fine += s1["fine"]
-                    xshift = s1["xshift"]
-                if STEP_TRACE is not None:
-                    STEP_TRACE.append((this_step, "collected", time.perf_counter()))
-                # the genome-wide statistics: everything is additive over chromosomes and ranks -- two small exchanges per
-                # step (one integer vector, one float vector), then the histograms of the median's refinement
-                gi = np.concatenate([np.asarray([nI_tot, nS, n_in, len(used)] + tot["n_all"] + tot["n_pos"], dtype=np.int64), loghist, fine])
-                gf = np.asarray(tot["sumx"] + tot["sumxx"] + [xshift if used else 0.0, 1.0 if used else 0.0], dtype=np.float64)
-                if STEP_TRACE is not None:
-                    STEP_TRACE.append((this_step, "reduced", time.perf_counter()))
-                if allsum is not None:
-                    # ONE exchange per step: the counts ride as float64 next to the sums (every count and every sum of counts
-                    # stays far below 2^53, so they come back exact)
-                    both = gsum(np.concatenate([gi.astype(np.float64), gf]))
-                    gi, gf = np.rint(both[:len(gi)]).astype(np.int64), both[len(gi):]
-                g, loghist, fine = gi[:4], gi[8:8 + len(loghist)], gi[8 + len(loghist):]
-                st = {"eps": ep, "minPts": m, "cut_in": int(cut), "n_inter": int(g[0]), "n_self": int(g[1]), "n_in": int(g[2])}
-                steps.append(st)
-                st["wall_s"] = time.perf_counter() - t_step0   # enqueue .. statistics of this rank on the host (+ the exchange); the cut follows
-                rng.__exit__(None, None, None)
-                if STEP_TRACE is not None:
-                    STEP_TRACE.append((this_step, "stats", time.perf_counter()))
-                if int(g[3]) == 0:                            # pipe.py:251-255
-                    if log:
-                        log("ERROR: no inter-ligation PETs detected for eps %s minPts %s,can't model the distance cutoff,continue anyway" % (ep, m))
-                    if forced_cuts is not None and forced_cuts[this_step] is not None:
-                        cut = int(forced_cuts[this_step])
-                        cuts.append(cut)
-                        st["cut_out"] = cut
-                    continue
-                xshift = float(gf[4]) / max(float(gf[5]), 1.0)            # the library constant (ranks without a chromosome report 0)
-                tot = {"n_all": [int(gi[4]), int(gi[5])], "n_pos": [int(gi[6]), int(gi[7])]}
-                if tot["n_all"][0] > 0 and tot["n_all"][1] > 0:      # pipe.py:256-259
-                    if tot["n_pos"][0] == 0 or tot["n_pos"][1] == 0:
-                        raise ValueError("cannot convert float NaN to integer")      # what int(2 ** nan) raises in ests.py:57
-                    n1 = tot["n_pos"][1]
-                    med = _select_kth(used, cut, loghist, sorted({(n1 - 1) // 2, n1 // 2}), allsum, pool,
-                                      fine=(fine_lo, fine) if fine_lo >= 1 else None)
-                    # the next step's summary also counts the distances around this median exactly (the median moves little
-                    # from step to step): lower edge of the log bin 1024 below it, so that the ranks below it are known
-                    from .ests import logbin, logbin_range
-                    fine_lo = logbin_range(logbin(max(1, med[0] - 1024)))[0]
-                    # the cut from sum x and sum x^2 (x = log2|d| - xshift), with the range that the reduction's rounding
-                    # leaves for the reference's int(2 ** cut) (ests.estIntSelCutFrag_bounded)
-                    cut_2, frags, (rc_lo, rc_hi), margin = estIntSelCutFrag_bounded(tot["n_all"], tot["n_pos"], gf[0:2], gf[2:4], xshift,
-                                                                                    (med[0], med[-1]), n_parts=int(g[3]))
-                    if rc_lo != rc_hi or margin < CUT_RECHECK_MARGIN:
-                        if allsum is None:
-                            # 2**cut may sit on either side of an integer within the error of the statistics: settle it the
-                            # reference's way, from the distance lists with numpy's own sums (rare -- a group of (nearly) equal
-                            # distances, or 2**cut within ~1e-6 of an integer; one extra run per chromosome with labels on the host)
-                            parts = [_cluster_arrays(r, ep, m, step_cut, variant) for r in used]
-                            cut_2, frags = estIntSelCutFrag(np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts]))
-                            st["cut_rechecked"] = True
-                        else:
-                            # several ranks: the lists are spread over them -- keep the statistics' cut, inside the bound
-                            st["cut_range"] = (int(rc_lo), int(rc_hi))
-                            if log and rc_lo != rc_hi:
-                                log("WARNING: the distance statistics of eps=%s,minPts=%s bound the cutoff only to [%s, %s]" % (ep, m, rc_lo, rc_hi))
-                    if plot is not None:
-                        # pipe.py:261-267: the picture of this step's two distance groups with the estimated cut drawn in; the
-                        # handles still hold the step's runs (a re-check above repeated them with the same parameters)
-                        t_plot0 = time.perf_counter()
-                        st["kde"] = _step_kde(used, step_cut, tot["n_pos"], gf[0:2], gf[2:4], xshift, pool)
-                        _plot_step(st["kde"], cut_2, "%s_eps%s_minPts%s_disCutoff" % (plot, ep, m), log)
-                        st["plot_s"] = time.perf_counter() - t_plot0
-                    if log:
-                        log("Estimated inter-ligation and self-ligation distance cutoff as %s for eps=%s,minPts=%s" % (cut_2, ep, m))
-                    if forced_cuts is not None and forced_cuts[this_step] is not None:
-                        cut_2 = int(forced_cuts[this_step])
-                    st["cut_out"] = int(cut_2)
-                    st["frags"] = int(frags)
-                    cuts.append(cut_2)
-                    cut = cut_2                               # pipe.py:274
-                    if STEP_TRACE is not None:
-                        STEP_TRACE.append((this_step, "cut", time.perf_counter()))
-                elif forced_cuts is not None and forced_cuts[this_step] is not None:
-                    cut = int(forced_cuts[this_step])
-                    cuts.append(cut)
-                    st["cut_out"] = cut
-        pos = [c for c in cuts if c > 0]
-        if pos:
-            cut = int(np.max(pos)) if max_cut else int(np.min(pos))     # pipe.py:276-280
-        else:
-            raise ValueError("zero-size array to reduction operation minimum which has no identity")
-        # combineTwice over all steps (pipe.py:257,275), then filterClusterByDis (pipe.py:130-143, floor division): on the
-        # device, per chromosome; only the surviving boxes cross PCIe
-        final_cut = cut
-
-        def finish(fr):
-            f, r = fr
-            with r.lock:
-                if finish_device:
-                    ptr, k = r.chrom.cand_finish_device(final_cut)
-                    return r.key, {"f": f, "boxes": None, "dev_rows": ptr, "n_rows": k}
-                b = r.chrom.cand_finish(final_cut, appended[f])
-            return r.key, {"f": f, "boxes": b}                # int32 [k, 4] rows (minX, maxX, minY, maxY), append order
-
-        # key order = first appearance over the steps, file order inside a step: what combineTwice's dict inserts
-        # (pipe.py:155-174) and runStat later walks -- `appended` was filled in exactly that order
-        res_of = dict(live)
-        dataI = _DataI(_pmap(pool, finish, [(f, res_of[f]) for f in appended]))
-        if finish_device and device_consumer is not None:
-            dataI.gathered = device_consumer(dataI)           # (residents pinned, sweep locks held: the pointers are alive)
-    finally:
-        if pool is not None:
-            pool.shutdown(wait=True)
-        for f, r in live:
-            # the announced minPts list belongs to this sweep: a later one-off run on the handle serves its own minPts only
-            try:
-                r.chrom.sweep_plan([], [])
-            except Exception:
-                pass
-        for r in held:
-            r.sweep_lock.release()
+    cuts, steps = [cut], []
+    appended = {}                                             # f -> inter-ligation boxes appended on the device so far
+    # where a step's summary should look for the median (see _select_kth).  The first step has no earlier median to go by: it
+    # counts the distances 1 .. 2048 exactly (self-ligation distances are a few hundred bp: ests.py's cut model) and falls back
+    # to the refinement passes if the median lies beyond
+    fine_lo = 1
+    with CACHE.pinned(fs, _devices()) as res_all, _sweep_hold(fs, res_all, eps, minPts) as live, \
+            (ThreadPoolExecutor(max_workers=SWEEP_THREADS) if len(live) > 1 else contextlib.nullcontext()) as pool:
+        by_size = sorted(live, key=lambda fr: -len(fr[1]))    # enqueue order: largest first (results are collected in file order)
+        for ep, m in itertools.product(eps, minPts):
+            step = _Step(len(steps), ep, m, cut, fine_lo)
+            t_step0 = time.perf_counter()
+            # one roctx range per step, from the enqueue to this rank's statistics on the host (rocprofv3 --marker-trace); wall_s
+            # covers the same: enqueue .. statistics of this rank on the host (+ the exchange); the cut follows
+            with _roctx.range_("cloops sweep step %d: eps %d minPts %d cut %d" % (step.no, ep, m, cut)):
+                _enqueue_step(step, by_size, variant, pool)
+                local, used = _collect_step(step, live, pool, probe, appended)
+                tot = local.over_ranks(allsum, step.no)
+                st = {"eps": ep, "minPts": m, "cut_in": int(cut), "n_inter": tot.n_inter, "n_self": tot.n_self, "n_in": tot.n_in,
+                      "wall_s": time.perf_counter() - t_step0}
+            steps.append(st)
+            _trace(step.no, "stats")
+            est = _estimate_cut(step, tot, used, st, variant, allsum, pool, plot, log)
+            # a forced cut replaces what the step estimated -- or did not estimate -- as the cut it hands on
+            forced = forced_cuts[step.no] if forced_cuts is not None else None
+            if est is not None or forced is not None:
+                cut = int(forced) if forced is not None else est[0]         # pipe.py:274
+                st["cut_out"] = int(cut)
+                cuts.append(cut)
+            if est is not None:
+                st["frags"] = int(est[1])
+                fine_lo = est[2]
+                _trace(step.no, "cut")
+        cut = _final_cut(cuts, max_cut)
+        dataI = _finish_sweep(live, appended, cut, pool, finish_device, device_consumer)
     return dataI, cut, cuts, steps
 
 
@@ -974,9 +1020,8 @@ def runSweep(fs, eps, minPts, cut=0, cpu=1, max_cut=False, log=None):
             st = {"eps": ep, "minPts": m, "cut_in": int(cut), "n_inter": sum(len(v["records"]) for v in dataI_2.values()),
                   "n_self": nS, "n_in": n_in}
             steps.append(st)
-            if len(dataI_2) == 0:                         # pipe.py:251-255
-                if log:
-                    log("ERROR: no inter-ligation PETs detected for eps %s minPts %s,can't model the distance cutoff,continue anyway" % (ep, m))
+            if len(dataI_2) == 0:
+                _log_no_inter(log, ep, m)
                 continue
             dis_2 = np.concatenate(dis_2) if dis_2 else np.zeros(0)
             dss_2 = np.concatenate(dss_2) if dss_2 else np.zeros(0)
@@ -991,12 +1036,7 @@ def runSweep(fs, eps, minPts, cut=0, cpu=1, max_cut=False, log=None):
                 cuts.append(cut_2)
                 cut = cut_2                               # pipe.py:274
                 dataI = combineTwice(dataI, dataI_2)
-    pos = [c for c in cuts if c > 0]
-    if pos:
-        cut = int(np.max(pos)) if max_cut else int(np.min(pos))     # pipe.py:276-280
-    else:
-        # np.min([]) raises in the reference; keep that behaviour observable
-        raise ValueError("zero-size array to reduction operation minimum which has no identity")
+    cut = _final_cut(cuts, max_cut)
     dataI = filterClusterByDis(dataI, cut)
     return dataI, cut, cuts, steps
 

@@ -9,12 +9,14 @@ Reference lines restated here:
 import ctypes
 import os
 import subprocess
+import threading
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libcloops_oracle.so")
 _lib = None
+_load_lock = threading.Lock()
 
 VARIANTS = {"v1": 1, "v2": 2, "block": 3}
 
@@ -29,18 +31,21 @@ def build(force=False):
 
 def _load():
     global _lib
-    if _lib is None:
-        build()
-        lib = ctypes.CDLL(_SO)
-        i64p = ctypes.POINTER(ctypes.c_int64)
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        for name in ("cl_oracle_v1", "cl_oracle_v2", "cl_oracle_block"):
-            fn = getattr(lib, name)
-            fn.argtypes = [i64p, i64p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, i32p]
-            fn.restype = ctypes.c_int
-        lib.cl_oracle_neighbor_counts.argtypes = [i64p, i64p, ctypes.c_int64, ctypes.c_int64, i32p]
-        lib.cl_oracle_neighbor_counts.restype = ctypes.c_int
-        _lib = lib
+    # the first callers can be the threads of a pool (the stand-in chromosomes of a sweep): one of them builds and loads, the
+    # others wait -- a stale library rebuilt by several threads at once was opened half written ("file too short")
+    with _load_lock:
+        if _lib is None:
+            build()
+            lib = ctypes.CDLL(_SO)
+            i64p = ctypes.POINTER(ctypes.c_int64)
+            i32p = ctypes.POINTER(ctypes.c_int32)
+            for name in ("cl_oracle_v1", "cl_oracle_v2", "cl_oracle_block"):
+                fn = getattr(lib, name)
+                fn.argtypes = [i64p, i64p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, i32p]
+                fn.restype = ctypes.c_int
+            lib.cl_oracle_neighbor_counts.argtypes = [i64p, i64p, ctypes.c_int64, ctypes.c_int64, i32p]
+            lib.cl_oracle_neighbor_counts.restype = ctypes.c_int
+            _lib = lib
     return _lib
 
 

@@ -299,3 +299,126 @@ def test_device_tables_are_consumed_under_the_sweeps_locks(monkeypatch, tmp_path
         assert not any(pipe.CACHE.get(f).sweep_lock.locked() for f in fs)
     finally:
         pipe.CACHE.clear()
+
+
+# ---- the sweep driver's stages: the exchange vector, forced cuts without an estimate, a failing wait, the orders ----
+def test_exchange_vector_layout(monkeypatch):
+    """what a rank hands to `allsum`: per step ONE float64 vector of 8 + DIST_LOGBINS + 2048 + 6 words -- counts, n_all, n_pos, loghist,
+    fine, then sumx, sumxx, xshift and the ranks reporting one -- equal, position by position, to the sums of the chromosomes'
+    step_result() values (bench.py times an all-reduce of this length); every other call is a refinement histogram of the median"""
+    from cloops_amd import _lib
+    from cloops_amd.synth import synth_chrom
+    results = []
+
+    class Keeping(fake_backend.FakeChromosome):
+        def step_result(self):
+            out = fake_backend.FakeChromosome.step_result(self)
+            results.append((self._step[0], self.n, out[0], out[1], {k: np.copy(v) for k, v in out[2].items()}, self.last_n_in()))
+            return out
+    monkeypatch.setattr(api, "Chromosome", Keeping)
+    monkeypatch.setattr(api, "device_count", lambda: 1)
+    pipe.CACHE.clear()
+    fs = [pipe.CACHE.put_arrays("k%d-k%d" % (k, k), *synth_chrom(600 + k, 200000, 900 + k)) for k in range(2)]
+    sent = []
+
+    def allsum(a):
+        sent.append(a.copy())
+        return a.copy()
+    try:
+        _, _, _, steps = pipe.runSweepFast(fs, [800, 1200], [4, 3], cut=0, allsum=allsum)
+    finally:
+        pipe.CACHE.clear()
+    L, F = _lib.DIST_LOGBINS, 2048
+    vecs = [a for a in sent if len(a) == 8 + L + F + 6]
+    assert len(vecs) == len(steps) == 4
+    assert all(a.dtype == np.int64 and a.shape == (F,) for a in sent if len(a) != 8 + L + F + 6)      # the median's refinement
+    for k, v in enumerate(vecs):
+        assert v.dtype == np.float64 and v.ndim == 1
+        mine = sorted((r for r in results if r[0] == k), key=lambda r: r[1])                       # file order
+        counted = [r for r in mine if r[2] > 0]
+        assert len(mine) == 2 and len(counted) == 2, "both chromosomes must count for the sums to mean something"
+        assert list(v[0:4]) == [sum(r[2] for r in mine), sum(r[3] for r in mine), sum(r[5] for r in mine), len(counted)]
+        for g in (0, 1):
+            assert v[4 + g] == sum(r[4]["n_all"][g] for r in counted) and v[6 + g] == sum(r[4]["n_pos"][g] for r in counted)
+            assert v[8 + L + F + g] == counted[0][4]["sumx"][g] + counted[1][4]["sumx"][g]
+            assert v[8 + L + F + 2 + g] == counted[0][4]["sumxx"][g] + counted[1][4]["sumxx"][g]
+        assert np.array_equal(v[8:8 + L], counted[0][4]["loghist"] + counted[1][4]["loghist"])
+        assert np.array_equal(v[8 + L:8 + L + F], counted[0][4]["fine"] + counted[1][4]["fine"])
+        assert v[8 + L:8 + L + F].sum() > 0
+        assert v[8 + L + F + 4] == counted[-1][4]["xshift"] and v[8 + L + F + 5] == 1.0
+        assert (steps[k]["n_inter"], steps[k]["n_self"], steps[k]["n_in"]) == tuple(int(x) for x in v[0:3])
+
+
+def test_forced_cuts_on_steps_without_an_estimate(monkeypatch):
+    """a forced cut also replaces what a step could NOT estimate: step 0 finds no cluster (the "no inter-ligation PETs" branch), step 1
+    finds one inter-ligation blob and no self-ligation PET (one distance group empty).  Without forced cuts such a sweep has no
+    positive cut and ends in the reference's ValueError"""
+    monkeypatch.setattr(api, "Chromosome", fake_backend.FakeChromosome)
+    monkeypatch.setattr(api, "device_count", lambda: 1)
+    pipe.CACHE.clear()
+    rng = np.random.RandomState(5)
+    f = pipe.CACHE.put_arrays("chrA-chrA", 100000 + rng.randint(0, 300, 5), 600000 + rng.randint(0, 300, 5))
+    log = []
+    try:
+        with pytest.raises(ValueError, match="zero-size array to reduction operation minimum which has no identity"):
+            pipe.runSweepFast([f], [1000], [8, 5], cut=0)
+        dataI, cut, cuts, steps = pipe.runSweepFast([f], [1000], [8, 5], cut=0, forced_cuts=[3000, 7000], log=log.append)
+    finally:
+        pipe.CACHE.clear()
+    assert cuts == [0, 3000, 7000] and cut == 3000
+    assert [s["cut_in"] for s in steps] == [0, 3000] and [s["cut_out"] for s in steps] == [3000, 7000]
+    assert not any("frags" in s for s in steps)
+    assert [s["n_inter"] for s in steps] == [0, 1]
+    assert list(dataI) == [("chrA", "chrA")] and len(dataI[("chrA", "chrA")]["boxes"]) == 1
+    assert len(log) == 1 and log[0].startswith("ERROR: no inter-ligation PETs detected for eps 1000 minPts 8")
+
+
+class _Watched(fake_backend.FakeChromosome):
+    """records the order of the enqueues and every sweep_plan; the wait of the chromosome of `boom` PETs raises"""
+    order, plans, boom = [], [], None
+
+    def step_async(self, variant, eps, minPts, cut, step, fine_lo=-1):
+        type(self).order.append((step, self.n))
+        return fake_backend.FakeChromosome.step_async(self, variant, eps, minPts, cut, step, fine_lo)
+
+    def wait(self, copy=False):
+        if self.n == type(self).boom:
+            self._pending.pop(0)
+            raise RuntimeError("boom")
+        return fake_backend.FakeChromosome.wait(self, copy)
+
+    def sweep_plan(self, eps_list, min_pts_list):
+        type(self).plans.append((self.n, list(eps_list), list(min_pts_list)))
+
+
+@pytest.fixture()
+def five_watched(monkeypatch):
+    from cloops_amd.synth import synth_chrom
+    monkeypatch.setattr(api, "Chromosome", _Watched)
+    monkeypatch.setattr(api, "device_count", lambda: 1)
+    _Watched.order, _Watched.plans, _Watched.boom = [], [], None
+    pipe.CACHE.clear()
+    yield [pipe.CACHE.put_arrays("k%d-k%d" % (k, k), *synth_chrom(400 + k, 200000, 70 + k)) for k in range(5)]
+    pipe.CACHE.clear()
+
+
+def test_failed_wait_releases_every_lock(five_watched):
+    """the wait of the third of five chromosomes raises: runSweepFast raises that error, and no handle stays locked, pinned, with a
+    run pending or with the sweep's minPts list announced"""
+    fs = five_watched
+    _Watched.boom = 402
+    with pytest.raises(RuntimeError, match="boom"):
+        pipe.runSweepFast(fs, [800], [4, 3], cut=0)
+    for f in fs:
+        r = pipe.CACHE.get(f)
+        assert not r.lock.locked() and not r.sweep_lock.locked() and r.pins == 0
+        assert not getattr(r.chrom, "_pending", [])
+        assert [p[1:] for p in _Watched.plans if p[0] == r.chrom.n] == [([800], [4, 3]), ([], [])]
+
+
+def test_enqueue_is_largest_first_and_keys_in_file_order(five_watched):
+    fs = five_watched
+    dataI, cut, cuts, steps = pipe.runSweepFast(fs, [800], [4, 3], cut=0)
+    assert _Watched.order == [(s, n) for s in range(len(steps)) for n in (404, 403, 402, 401, 400)]
+    keys = [pipe.CACHE.get(f).key for f in fs]
+    assert len(dataI) > 1 and list(dataI) == [k for k in keys if k in dataI]

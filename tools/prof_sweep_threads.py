@@ -24,10 +24,9 @@ def wrap(obj, name):
                 acc[name] += dt; cnt[name] += 1
     setattr(obj, name, w)
 
-for nm in ("wait", "cluster_async", "dist_stats", "dist_sqdev", "dist_hist"):
+for nm in ("wait", "step_async", "step_result", "cand_finish", "dist_bin_hist"):
     wrap(api.Chromosome, nm)
-for nm in ("_boxes_classified", "_combine_steps", "_select_kth"):
-    wrap(pipe, nm)
+wrap(pipe, "_select_kth")
 fs = []
 for name, X, Y in synth_genome(n_total, cfg=mode):
     fs.append(pipe.CACHE.put_arrays("%s-%s" % (name, name), X, Y))
