@@ -48,6 +48,7 @@ CL_DOT_WMAX = 16             # largest half-width of the donut's footprint
 CL_DOT_CHUNKS_MAX = 64       # chunks of la of a cl_dot_hist
 CL_DOT_CMAX = 4095           # counts at or above it share the histogram's last column
 CL_DOT_BAND_MAX = 134217728  # 2^27 entries nb (dmax + 4 w) of the value band of cl_dot_lambdas
+CL_SAD_CLASSES_MAX = 64      # classes of a cl_sad_sums
 
 
 class ClBox(ctypes.Structure):
@@ -172,6 +173,9 @@ PROTOTYPES = {
     "cl_dot_call": (_int, [_vp, _vp, _i64p]),
     "cl_dot_sig_get": (_int, [_vp, _i64, _i64, _vp]),
     "cl_dot_free": (_int, [_vp]),
+    "cl_sad_sums": (_int, [_vp, _vp, _i64, _i32, _i64, _i64, _i64p, _i64p, _i64p]),
+    "cl_sad_get": (_int, [_vp, _vp, _vp, _vp]),
+    "cl_sad_free": (_int, [_vp]),
     "cl_conv_create": (_int, [_int, _vp, _i32, _i64, _i64, _vpp]),
     "cl_conv_feed": (_int, [_vp, _vp, _i64, _i32, _i64p, _i64p, _i64p]),
     "cl_conv_render": (_int, [_vp, _vp, _i64, _i64p]),

@@ -1086,6 +1086,40 @@ class Chromosome(_Handle):
         _lib.check(self._lib.cl_dot_free(self._h))
         self._dot_bins = self._dot_nd = self._dot_chunks = self._dot_sig = 0
 
+    def sad_sums(self, cls, n_cls, lo, hi):
+        """K30: the saddle tables of the matrix of the last exp_set.  cls: the class of every bin (int [nb]; -1: the bin takes no part,
+        else 0 <= cls < n_cls <= CL_SAD_CLASSES_MAX); the band max(ignore_diags, 1) <= lo <= hi <= nb.  Over the pairs i < j of valid
+        classed bins with lo <= j - i < hi, per (class of i, class of j): their number, their cells and the sum of the cells' O/E, kept
+        for sad_get.  Refused when a diagonal of the band with valid pairs has no finite positive expected value -> (n_binned: the
+        valid bins with a class, n_pairs, n_in: the totals of the pairs and of the cells)  (cl_sad_sums)"""
+        cls = np.asarray(cls)
+        nb, n_cls = getattr(self, "_bal_bins", 0), int(n_cls)
+        if cls.ndim != 1 or len(cls) != nb or (cls.size and cls.dtype.kind not in "iu"):
+            raise ValueError("sad_sums: the classes need one integer per bin (%d), got %s of shape %s" % (nb, cls.dtype, cls.shape))
+        if not 1 <= n_cls <= _lib.CL_SAD_CLASSES_MAX:
+            raise ValueError("sad_sums: n_cls must lie in [1, %d], got %d" % (_lib.CL_SAD_CLASSES_MAX, n_cls))
+        if cls.size and (int(cls.min()) < -1 or int(cls.max()) >= n_cls):
+            raise ValueError("sad_sums: a class outside [-1, %d)" % n_cls)
+        k = np.ascontiguousarray(cls, dtype=np.int32)
+        nbin, npair, nin = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._lib.cl_sad_sums(self._h, _vp(k) if nb else None, nb, n_cls, int(lo), int(hi), ctypes.byref(nbin), ctypes.byref(npair),
+                                         ctypes.byref(nin)))
+        self._sad_cls = n_cls
+        return int(nbin.value), int(npair.value), int(nin.value)
+
+    def sad_get(self):
+        """the tables of the last sad_sums -> (sum float64, pairs int64, cells int64), each [n_cls, n_cls]: row = the class of the
+        lower bin, column = the class of the upper bin  (cl_sad_get)"""
+        n = getattr(self, "_sad_cls", 0) or 1                                # (no tables: the library refuses before it writes)
+        s, p, c = np.zeros((n, n), np.float64), np.zeros((n, n), np.int64), np.zeros((n, n), np.int64)
+        _lib.check(self._lib.cl_sad_get(self._h, _vp(s), _vp(p), _vp(c)))
+        return s, p, c
+
+    def sad_free(self):
+        """releases the tables and the device scratch of the sad_* calls; everything up to the expected values stays  (cl_sad_free)"""
+        _lib.check(self._lib.cl_sad_free(self._h))
+        self._sad_cls = 0
+
     def neighbor_counts(self, eps, cut=0):
         out = np.full(self.n, -1, dtype=np.int32)
         _lib.check(self._lib.cl_neighbor_counts(self._h, int(eps), int(cut), out.ctypes.data_as(ctypes.c_void_p)))

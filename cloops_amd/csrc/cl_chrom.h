@@ -11,7 +11,7 @@
 //                   fresh by run_begin() at the start of every run, read by nobody after the enqueue (the developer build's
 //                   cl_debug_time_lists aside).  finish_enqueue() commits the record to the slot in one assignment once the run is
 //                   completely enqueued; nothing else writes a slot's record (finish_wait() clears the destination it has served).
-//   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K29
+//   Base, Counts, Fine, Kde, Sig, Cand and K12 .. K30
 //                   state that outlives a run: one struct each, the buffers together with the flags that say what they hold, and
 //                   one invalidate() where several flags fall together.
 // What reports on the LAST run (last_k2_mode, dbg_g / dbg_nm, refused_labelled, the slots' records) stays in the handle: callers
@@ -415,6 +415,20 @@ struct cl_chrom {
             long long dmin = 0, dmax = 0, n_sig = 0;
         } st;
     } dt;
+    // K30 (k_saddle.hip): the effective class of every bin (-1: invalid or without a class), the per-tile class counts of the pair
+    // counts and their exclusive sums, the per-chunk tables of the sums (fp64 sums, then cell counts), the three folded tables; the
+    // tables of the last cl_sad_sums on the host, where cl_sad_get reads them.  Kept from cl_sad_sums to the next one, cl_sad_free,
+    // anything that releases or rebuilds K26's state (exp_release, cl_exp_diagonals, cl_exp_set) or destruction
+    struct Sad {
+        DevBuf cls, th, tb, part, out;
+        struct State {
+            bool ready = false;
+            int n_cls = 0;
+            long long lo = 0, hi = 0, n_binned = 0, n_pairs = 0, n_in = 0;
+            std::vector<double> sum;
+            std::vector<long long> pairs, cells;
+        } st;
+    } sd;
     bool k7_classified = false;       // k7_cls matches the last completed run
     hipStream_t copy_stream = nullptr, aux_stream = nullptr;
     int copy_mode = 0;                // 0: the D2H copies of a run go through copy_stream, 1: they are issued in `stream` (caller's stream),
@@ -492,7 +506,8 @@ const int* k7_hist_for(cl_chrom* c, int cut);
 K7Src k7_src(cl_chrom* c, const cl_chrom::Held& r, cl_chrom::Slot& sl, int cut, int M, const int* dM);
 int finish_enqueue(cl_chrom* c, const RunRequest& req, int n_strips, const int* d_M);
 // A unit drops its buffers and its state by assigning a fresh struct, and with them what was made from them: K25's marginals and
-// weights belong to K24's cells, K26's diagonals to K25's marginals and weights, K27's matrix and K29's lambdas to K26's expected values.  Called by
+// weights belong to K24's cells, K26's diagonals to K25's marginals and weights, K27's matrix, K29's lambdas and K30's tables to K26's
+// expected values.  Called by
 // the units' entry points; the handle's destruction needs none of them
 static inline void track_release(cl_chrom* c) { c->tk = cl_chrom::Track(); }
 static inline void cov_release(cl_chrom* c) { c->cv = cl_chrom::Cov(); }
@@ -501,7 +516,8 @@ static inline void dom_release(cl_chrom* c) { c->dm = cl_chrom::Dom(); }
 static inline void kdis_release(cl_chrom* c) { c->kd = cl_chrom::Kdis(); }
 static inline void eig_release(cl_chrom* c) { c->eg = cl_chrom::Eig(); }
 static inline void dot_release(cl_chrom* c) { c->dt = cl_chrom::Dot(); }
-static inline void exp_release(cl_chrom* c) { eig_release(c); dot_release(c); c->ex = cl_chrom::Exp(); }
+static inline void sad_release(cl_chrom* c) { c->sd = cl_chrom::Sad(); }
+static inline void exp_release(cl_chrom* c) { eig_release(c); dot_release(c); sad_release(c); c->ex = cl_chrom::Exp(); }
 static inline void bal_release(cl_chrom* c) { exp_release(c); c->bl = cl_chrom::Bal(); }
 static inline void scc_release(cl_chrom* c) { c->sc = cl_chrom::Scc(); }
 static inline void mat_release(cl_chrom* c) { c->mx = cl_chrom::Mat(); bal_release(c); scc_release(c); }

@@ -269,6 +269,7 @@ extern "C" int cl_exp_diagonals(cl_chrom* c, const uint32_t* valid, int32_t bala
     HIP_TRY(hipSetDevice(c->device));
     eig_release(c);                                                                  // (K27's matrix was made of the earlier diagonals)
     dot_release(c);                                                                  // (... and K29's lambdas)
+    sad_release(c);                                                                  // (... and K30's tables)
     c->ex.st = cl_chrom::Exp::State();                                               // (the earlier state's buffers are written from here on; every K26 call ends synchronised)
     rc = exp_diagonals(c, valid, balanced, st);
     if (rc != CL_OK) {
@@ -302,6 +303,7 @@ extern "C" int cl_exp_set(cl_chrom* c, const double* expected, int64_t count)
     if (count > 0 && !expected) return fail(CL_ERR_ARG, "cl_exp_set: bad arguments");
     eig_release(c);                                                             // (K27's matrix was made of the earlier expected values)
     dot_release(c);                                                             // (... and K29's lambdas)
+    sad_release(c);                                                             // (... and K30's tables)
     if (count > 0) {
         HIP_TRY(hipSetDevice(c->device));
         c->ex.st.expected = false;

@@ -809,6 +809,47 @@ int cl_dot_sig_get(cl_chrom* c, int64_t first, int64_t count, int64_t* cell_inde
 int cl_dot_free(cl_chrom* c);
 
 /*
+ * Saddle tables (K30): how strongly the map segregates by a per-bin class -- the sums that `cooltools saddle` is made of: the bins are
+ * sorted into classes (quantiles of a compartment track), and every pair of classes gets the number of its bin pairs, the number of
+ * its cells and the sum of their O/E.  The reference has no counterpart, so these definitions are the specification
+ * (tests/saddle_cases.py restates them in numpy); the track, the class edges, the symmetrising, the strength, the texts and the files
+ * stay on the host (cloops_amd/saddle.py).
+ *
+ * Input: the state after cl_mat_cells(fold = 1), cl_bal_marginals, cl_exp_diagonals (either mode) and cl_exp_set: the cells (bx, by,
+ * cnt), the bins b0 .. b0 + nb - 1, K26's validity of a bin and its w, ign = ignore_diags and expected[d].  From the caller: cls[nb]
+ * (int32), the class of every bin: -1 means the bin takes no part, otherwise 0 <= cls[i] < n_cls; n_cls, 1 <= n_cls <=
+ * CL_SAD_CLASSES_MAX; and a band lo <= d < hi with max(ign, 1) <= lo <= hi <= nb: the main diagonal never takes part.
+ * The pair set P: all (i, j) with 0 <= i < j < nb, lo <= j - i < hi, both bins valid and both classes >= 0.
+ * Three n_cls x n_cls tables, row-major, a the class of the lower bin and b the class of the upper bin:
+ *   pairs[a][b] (int64) = the number of (i, j) in P with cls[i] = a and cls[j] = b; pairs without a cell count too;
+ *   cells[a][b] (int64) = the number of cells whose bin pair is in P with those classes;
+ *   sum[a][b] (fp64)    = the sum of K26's O/E over those cells, ((w[bx] cnt) w[by]) / expected[by - bx] in that order of operations;
+ *                         a pair without a cell adds 0.
+ * As cl_eig_build does, cl_sad_sums refuses an expected[d] that is NaN, infinite or <= 0 on a diagonal lo <= d < hi that holds at
+ * least one valid pair, on the host before any launch: the host picks hi so that there is none.
+ * The terms of an entry of `sum` are added in an order that depends on the cells, nb, cls, lo and hi alone -- neither on the device's
+ * CU count nor on timing: two calls with the same input give the same bytes.  No fp64 atomics.
+ *
+ * cl_sad_sums -- count == nb -> *n_binned (the valid bins with a class), *n_pairs (the total of pairs), *n_in (the total of cells).
+ * The pair counts cost nb n_cls look-ups (differences of per-class prefix counts), not nb (hi - lo); the sums stream the cells once
+ * in the order they lie.
+ * cl_sad_get -- the three tables, n_cls * n_cls entries each.
+ * cl_sad_free -- releases the state (cells and the K25-K26 state stay).  The next cl_sad_sums, cl_exp_set, cl_exp_diagonals,
+ * cl_exp_free and everything that releases K26's state release it as well.  K27's and K29's state and K30's do not touch each other.
+ *
+ * The calls are synchronous on the handle's stream.  nb == 0 is not an error: lo = hi = 0 and the totals are all zero; lo == hi is
+ * not an error: the tables are all zero.  Errors: CL_ERR_ARG, found on the host before any launch, scalar outputs zeroed and the
+ * earlier state left usable, for a NULL handle or NULL outputs, any call before cl_exp_set, count != nb, a class outside [-1, n_cls),
+ * n_cls out of range, a band outside the rule above, the rule on the expected values, cl_sad_get before cl_sad_sums, or runs in
+ * flight.
+ */
+#define CL_SAD_CLASSES_MAX 64
+int cl_sad_sums(cl_chrom* c, const int32_t* cls, int64_t count, int32_t n_cls, int64_t lo, int64_t hi, int64_t* n_binned, int64_t* n_pairs,
+                int64_t* n_in);
+int cl_sad_get(cl_chrom* c, double* sum, int64_t* pairs, int64_t* cells);
+int cl_sad_free(cl_chrom* c);
+
+/*
  * Pairs files to BEDPE (K15): the per-line loops of scripts/hicpropairs2bedpe (pairs2bedpe, :9-35) and
  * scripts/juicerLong2bedpe.py (long2bedpe, :10-32), one chunk of input text at a time.  A converter is not tied to a
  * chromosome: it is a handle of its own.
